@@ -10,7 +10,11 @@ parity mode is timed next to it and reported as `exact_mode`).  Prints ONE JSON 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Besides the headline the line carries (outside the timed region, short runs):
+A plain run sets up, warms up, times ONE region of exactly `--steps` steps, counts the rays of the frames after it (`value` divides
+them) and prints the line.  --dump-outputs DIR writes what the last timed step computed (denoised.npy, shadow_mask.npy) first.
+
+With --full, besides the headline the line carries (outside the timed region, short runs): the same region repeated until >= 5 s are
+timed (`timed_repeats`, `ms_per_step_median`), per-kernel HIP-event times (`stages`), the other arithmetic mode (`exact_mode`), and
   passes       N = 1: BASELINE configs[2], [3] and the passes of [4] on one GPU — AO 4 spp, half-res reflections, DDGI 16x8x16x256, the
                whole hybrid frame at 1080p and at 4K: ms, Mrays/s, frames/s and, per kernel, the HIP-event time and the fraction of the
                8 TB/s HBM roofline its ALGORITHMIC bytes (SURVEY.md §8d) amount to;
@@ -65,8 +69,11 @@ def parse():
     ap.add_argument("--obj", default=None, help="Wavefront OBJ (+MTL) to render instead of the procedural scene (hybrid_rendering_amd/assets.py)")
     ap.add_argument("--ring", type=int, default=8, help="distinct camera positions cycled through")
     ap.add_argument("--exact", type=int, default=0, help="1: time the bit-for-bit parity arithmetic as the headline instead of the tolerance mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-passes", action="store_true", help="skip the `passes` / `hybrid_4k` blocks (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: repeated timed regions, per-kernel times and roofline, the other "
+                    "arithmetic mode, the `passes` / `hybrid_4k` blocks, the CPU baseline, the `comm` block of N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-passes", action="store_true", help="with --full: skip the `passes` / `hybrid_4k` blocks (profiling runs)")
     ap.add_argument("--cpu-frames", type=int, default=4)
     return ap.parse_args()
 
@@ -326,7 +333,7 @@ def run(args, torch, dist, rank, world, local_rank):
         if world > 1:
             dist.barrier()
 
-    def timed_run(tiled, steps, warmup, min_total_s=5.0):
+    def timed_run(tiled, steps, warmup):
         def step(k):
             fi = cycle[k % len(cycle)]
             fi.num_frames = k
@@ -365,21 +372,23 @@ def run(args, torch, dist, rank, world, local_rank):
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 el = float(t.item())
             return el
-        # A region of K steps of a ~0.2 ms frame lasts a few ms: too short for a driver that samples GPU activity every few seconds, and one
-        # host hiccup is a large share of it.  The region is therefore repeated until >= 5 s have been timed in total (round 6; round 5: 1 s —
-        # the driver's activity sampler, five samples over the 22 s run, still saw an idle GPU in every one) — same K steps each, same brackets — and the
-        # MEDIAN region is reported (`timed_repeats`, VERDICT r3 #5d); one region if K steps already take that long.
-        els = [region(warmup)]
-        n_rep = 1 if min_total_s <= 0 else int(min(2500, max(1, math.ceil(min_total_s / max(els[0], 1e-6)))))
+        timed_run.region = region
+        return region(warmup), step      # ONE region of exactly `steps` steps
+
+    def repeat_regions(region, first, k_first, steps, min_total_s=5.0):
+        """--full: a region of K steps of a ~0.2 ms frame lasts a few ms and one host hiccup is a large share of it, so the same region (same K
+        steps, same brackets) is repeated until >= 5 s have been timed in total and the MEDIAN region is reported beside the headline
+        (`timed_repeats`, VERDICT r3 #5d); one region if K steps already take that long"""
+        els = [first]
+        n_rep = int(min(2500, max(1, math.ceil(min_total_s / max(first, 1e-6)))))
         if world > 1:   # every rank repeats the same number of times
             t = torch.tensor([n_rep], dtype=torch.int64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             n_rep = int(t.item())
         for r in range(1, n_rep):
-            els.append(region(warmup + r * steps))
-        el = float(np.median(els))
-        timed_run.last = {"timed_repeats": len(els), "timed_region_ms": [round(e * 1e3, 3) for e in els][:16], "timed_total_ms": round(sum(els) * 1e3, 2)}
-        return el, step
+            els.append(region(k_first + r * steps))
+        return {"timed_repeats": len(els), "timed_region_ms": [round(e * 1e3, 3) for e in els][:16], "timed_total_ms": round(sum(els) * 1e3, 2),
+                "ms_per_step_median": round(float(np.median(els)) / steps * 1e3, 4)}
 
     # ------------------------------------------------------------------------------------------------ the timed region (headline)
     stage("headline")
@@ -387,23 +396,44 @@ def run(args, torch, dist, rank, world, local_rank):
     tiled.params.exact = exact
     shadows = tiled.pass_
     b0, b1 = tiled.b0, tiled.b1
+    # the GPU leaves its idle clocks before the timed pass warms up: a scratch pass (its own history, no collectives) renders the frame cycle
+    # for 0.3 s.  The timed pass's state, and so what its last step computes, does not depend on it; without it the first region after a
+    # short warm-up runs ~0.7 % slower than the regions after it.
+    spin = hr.RayTracedShadows(ctx, W, H)
+    spin.params.exact = exact
+    t0, k = time.perf_counter(), 0
+    while time.perf_counter() - t0 < 0.3:
+        for _ in range(8):
+            fi = cycle[k % len(cycle)]
+            fi.num_frames = k
+            spin.render(scene, fi)
+            k += 1
+        torch.cuda.synchronize()
+    spin.close()
     elapsed, step = timed_run(tiled, args.steps, args.warmup)
-    timing = dict(timed_run.last)
-    stage("per_kernel")
+    if args.dump_outputs and rank == 0:
+        stage("dump_outputs")
+        dump_outputs(args.dump_outputs, torch, hr, tiled)
+    timing = {}
+    if args.full:
+        stage("repeats")
+        timing = repeat_regions(timed_run.region, elapsed, args.warmup, args.steps)
+    stage("ray_count")
 
-    # ---- per-kernel HIP events on the launch stream, right AFTER the timed region (same stream, same frame cycle: 12 event records per
-    # ~0.2 ms frame inside it cost 18 % of the throughput; the per-kernel averages agree within 1.5 % either way, and rocprofv3 agrees
-    # with both — DESIGN.md §5), plus ray counts
+    # ---- ray counts of the frames after the timed region (`value` divides them); --full: per-kernel HIP events on the launch stream on the same
+    # frames (same stream, same frame cycle: 12 event records per ~0.2 ms frame inside the timed region cost 18 % of the throughput; the per-kernel
+    # averages agree within 1.5 % either way, and rocprofv3 agrees with both — DESIGN.md §5)
     acc = {}
     rays_total, n_prof = 0, min(args.steps, 60)
     k0 = args.warmup + args.steps
-    shadows.set_profiling(True)
+    shadows.set_profiling(args.full)
     for k in range(k0, k0 + n_prof):
         step(k)
         rays_total += shadows.ray_count()
-        for name, ms, nbytes in shadows.stage_times():
-            a = acc.setdefault(name, [0.0, nbytes])
-            a[0] += ms / n_prof
+        if args.full:
+            for name, ms, nbytes in shadows.stage_times():
+                a = acc.setdefault(name, [0.0, nbytes])
+                a[0] += ms / n_prof
     shadows.set_profiling(False)
     rays_per_frame = rays_total / n_prof
     if world > 1:
@@ -417,6 +447,37 @@ def run(args, torch, dist, rank, world, local_rank):
             tot += counter.ray_count()
         rays_per_frame = tot / 8
         counter.close()
+    px = W * (b1 - b0)
+    total_rays = rays_per_frame * args.steps * world
+    if world > 1:
+        t = torch.tensor([rays_per_frame], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        total_rays = float(t.item()) * args.steps
+    ms_per_step = elapsed / args.steps * 1e3
+    value = total_rays / elapsed / 1e6
+    out = {
+        "metric": "shadow Mrays/s over the fully denoised frame (1 spp trace + SVGF temporal + 4x a-trous)",
+        "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{W}x{H} {scene_name} ({sd.n_tris} tris) ray-traced shadows 1spp + SVGF denoise"
+                               + (f", {world}x the pixels of 1920x1080 (same view), row-tiled into {world} cost-balanced bands" if world > 1 else ""),
+                   "math": ("exact=1: every stage image bit-identical to the oracle" if exact else
+                            "exact=0 (shipping mode): masks / ray counts bit-exact, fp16 images within tolerance (tests/test_gpu_tolerance.py)"),
+                   "trace_launch_order": "blockIdx" if os.environ.get("HR_TILE_ORDER") == "0" else "heaviest tiles of the last frame first (csrc/tile_order.h)",
+                   "rays_per_frame_per_gpu": int(rays_per_frame), "pixels_per_gpu": px, "bvh_nodes": int(scene.info.n_nodes)},
+        "timing_note": "ms_per_step = one timed region of exactly `steps` steps (barrier + synchronize on both sides)"
+                       + ("; ms_per_step_median = the median of `timed_repeats` such regions, repeated until >= 5 s are timed in total" if args.full else ""),
+        "denoised_frames_per_s": round(args.steps / elapsed, 2),                  # frames of W x H (the whole tiled frame)
+        "denoised_1080p_equiv_per_s": round(W * H / (args.width * args.height) * args.steps / elapsed, 2),
+    }
+    if not args.full:
+        stage("done")
+        return out
+
+    # ---- --full: everything below is reported next to the headline, never part of it
+    out.update(timing)
+    stage("per_kernel")
     stages = {n: dict(ms=v[0], bytes=v[1]) for n, v in acc.items()}
     # instrumented trace (node visits / triangle tests) on a few frames of the cycle
     # (VERDICT r4 #1a) the counts `frac` divides are those of the TIMED kernel: occluder cache ON, in the state the previous frame of the
@@ -434,7 +495,6 @@ def run(args, torch, dist, rank, world, local_rank):
         step(kk)
     nodes_per_ray, tris_per_ray = nn / max(nr, 1), nt / max(nr, 1)
     walk_nodes_per_ray, walk_tris_per_ray = wn / max(wr, 1), wt / max(wr, 1)
-    px = W * (b1 - b0)
     trace_bytes = px * 12.125 + rays_per_frame * (nodes_per_ray * NODE_BYTES + tris_per_ray * TRI_BYTES)
     walk_bytes = px * 12.125 + rays_per_frame * (walk_nodes_per_ray * NODE_BYTES + walk_tris_per_ray * TRI_BYTES)
     if "ray_trace" in stages:
@@ -449,13 +509,6 @@ def run(args, torch, dist, rank, world, local_rank):
         s.update(classify(prof, kern, s["ms"], s["bytes"], gather=(n == "ray_trace")))
         s["GBps"] = s["bytes"] / (s["ms"] * 1e-3) / 1e9 if s["ms"] > 0 else 0.0
 
-    total_rays = rays_per_frame * args.steps * world
-    if world > 1:
-        t = torch.tensor([rays_per_frame], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        total_rays = float(t.item()) * args.steps
-    ms_per_step = elapsed / args.steps * 1e3
-    value = total_rays / elapsed / 1e6
     comm_info = None
     if world > 1:
         # what the driver's SCALE record needs to tell compute from communication: how many ranks RCCL really saw, the band cut, and
@@ -466,24 +519,9 @@ def run(args, torch, dist, rank, world, local_rank):
         dist.all_reduce(ex, op=dist.ReduceOp.MAX)
         comm_info = bench_report.comm_block(dist.get_backend(), seen.item(), bounds, tiled.history_rows, ex.item(), W)
     dom = max(stages.items(), key=lambda kv: kv[1]["ms"])
-    out = {
-        "metric": "shadow Mrays/s over the fully denoised frame (1 spp trace + SVGF temporal + 4x a-trous)",
-        "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{W}x{H} {scene_name} ({sd.n_tris} tris) ray-traced shadows 1spp + SVGF denoise"
-                               + (f", {world}x the pixels of 1920x1080 (same view), row-tiled into {world} cost-balanced bands" if world > 1 else ""),
-                   "math": ("exact=1: every stage image bit-identical to the oracle" if exact else
-                            "exact=0 (shipping mode): masks / ray counts bit-exact, fp16 images within tolerance (tests/test_gpu_tolerance.py)"),
-                   "trace_launch_order": "blockIdx" if os.environ.get("HR_TILE_ORDER") == "0" else "heaviest tiles of the last frame first (csrc/tile_order.h)",
-                   "rays_per_frame_per_gpu": int(rays_per_frame), "pixels_per_gpu": px, "bvh_nodes": int(scene.info.n_nodes),
-                   "nodes_per_ray": round(nodes_per_ray, 2), "tris_per_ray": round(tris_per_ray, 2),
-                   "nodes_per_ray_full_walk": round(walk_nodes_per_ray, 2), "tris_per_ray_full_walk": round(walk_tris_per_ray, 2)},
-        "timed_repeats": timing["timed_repeats"], "timed_region_ms": timing["timed_region_ms"], "timed_total_ms": timing["timed_total_ms"],
-        "timing_note": "ms_per_step = MEDIAN over `timed_repeats` timed regions of exactly `steps` steps each (barrier + synchronize on both sides of every region; "
-                       "repeated until >= 5 s are timed in total)",
-        "denoised_frames_per_s": round(args.steps / elapsed, 2),                  # frames of W x H (the whole tiled frame)
-        "denoised_1080p_equiv_per_s": round(W * H / (args.width * args.height) * args.steps / elapsed, 2),
+    out["config"].update({"nodes_per_ray": round(nodes_per_ray, 2), "tris_per_ray": round(tris_per_ray, 2),
+                          "nodes_per_ray_full_walk": round(walk_nodes_per_ray, 2), "tris_per_ray_full_walk": round(walk_tris_per_ray, 2)})
+    out.update({
         "trace_only_Mrays_per_s": round(rays_per_frame / (stages["ray_trace"]["ms"] * 1e-3) / 1e6, 2) if "ray_trace" in stages else None,
         "roofline": {"kernel": dom[0], "kernel_name": dom[1].get("kernel"), "bound": dom[1].get("bound") or "latency", "achieved": round(dom[1]["GBps"], 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": dom[1]["frac"], "traffic": dom[1].get("traffic"), "traffic_lo": dom[1].get("traffic_lo"), "dram_frac": dom[1].get("dram_frac"),
@@ -509,7 +547,7 @@ def run(args, torch, dist, rank, world, local_rank):
                              "counts of the cache-less walk; the ~17 MB BVH is served by L2 / Infinity Cache, so dram_frac (counter traffic) is the HBM-side figure; the operative roof of "
                              "this kernel is VALU issue: valu_frac = valu_issue_frac x lane_utilisation (= binding_frac)"},
         "stages": {n: {k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items()} for n, s in stages.items()},
-    }
+    })
     if comm_info:
         out["comm"] = comm_info
 
@@ -518,8 +556,8 @@ def run(args, torch, dist, rank, world, local_rank):
     other.params.exact = 1 - exact
     stage("other_mode")
     PARTIAL.update(out)
-    el2, _ = timed_run(other, max(20, args.steps // 4), 10, min_total_s=0.0)
     n2 = max(20, args.steps // 4)
+    el2, _ = timed_run(other, n2, 10)
     out["tolerance_mode" if exact else "exact_mode"] = {"ms_per_step": round(el2 / n2 * 1e3, 4), "value": round(total_rays / args.steps * n2 / el2 / 1e6, 2), "unit": "Mrays/s",
                                                         "steps": n2, "note": "hr_shadows_params.exact = %d on the same frames" % (1 - exact)}
     other.wait_exchange()
@@ -574,6 +612,17 @@ def run(args, torch, dist, rank, world, local_rank):
         PARTIAL.update(out)
     stage("done")
     return out
+
+
+def dump_outputs(d, torch, hr, tiled):
+    """--dump-outputs: what a caller of the timed path receives after its last step — the pass's result (hr_shadows_output(HR_OUTPUT_ATROUS), RG16F,
+    as float32) and its ray-trace output (the bit-packed R32_UINT visibility mask, one float64 per 32-bit word: exact); with N > 1 the rows of this
+    rank's band.  ~17 MB at 1920x1080."""
+    os.makedirs(d, exist_ok=True)
+    denoised = tiled.band_output().float().cpu().numpy()
+    mask = tiled.pass_.output(hr.OUTPUT_RAY_TRACE).cpu().numpy().view(np.uint32).astype(np.float64)
+    np.save(os.path.join(d, "denoised.npy"), denoised)
+    np.save(os.path.join(d, "shadow_mask.npy"), mask)
 
 
 def passes_block(torch, hr, HybridFrame, ctx, scene, sd, prof, exact):

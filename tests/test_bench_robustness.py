@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,7 +97,7 @@ def test_gpu_two_ranks_on_one_gpu_report_comm_error():
     # set short, and BOTH endings are accepted — the refusal (local fallback numbers) and the watchdog (the line as far as it is known)
     env = dict(os.environ, HR_DIST_BACKEND="nccl", HR_FORCE_DEVICE="0", HR_BENCH_TIMEOUT_S="90")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29732",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-passes", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-passes", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=400)
     d = _last_json(out.stdout)
     assert d["comm"]["error"], d
@@ -106,10 +107,11 @@ def test_gpu_two_ranks_on_one_gpu_report_comm_error():
 
 @pytest.mark.gpu
 def test_gpu_bench_line_as_the_driver_runs_it():
-    """the driver's own command (BENCH_rNN: `python3 bench.py --gpus 1 --steps 20 --warmup 5`): the LAST stdout line is one JSON object < 7000 bytes
-    with the contract's fields, a live `roofline` and a `cpu_baseline`; the full record sits in bench_detail.json"""
+    """`bench.py --gpus 1 --steps 20 --warmup 5 --full`: the LAST stdout line is one JSON object < 7000 bytes with the contract's fields, a live
+    `roofline` and a `cpu_baseline`; the full record sits in bench_detail.json"""
     env = dict(os.environ, HR_BENCH_CPU_SECONDS="2", HR_BENCH_TEST_C_STDOUT="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], capture_output=True, text=True, env=env, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], capture_output=True, text=True, env=env,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     # stdout is the line and nothing else: what libraries write through C stdio (RCCL's banner sits in libc's buffer until the process exits,
     # i.e. AFTER the line) goes to stderr (bench.isolate_stdout)
@@ -128,6 +130,34 @@ def test_gpu_bench_line_as_the_driver_runs_it():
     assert set(d["passes"]["4k"]) == {"shadows", "ao", "reflections", "ddgi"}
     detail = json.load(open(os.path.join(ROOT, "bench_detail.json")))
     assert detail["value"] == d["value"] and "kernels" in detail["passes"]["ao"]
+
+
+@pytest.mark.gpu
+def test_gpu_plain_bench_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """a plain run (no --full) times ONE region of exactly `steps` steps and carries none of the --full blocks; --dump-outputs writes what the last
+    timed step computed as float arrays (<= 64 MB in all), identical from run to run with the same arguments"""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = _last_json(out.stdout)
+        assert line["steps"] == 30 and line["warmup"] == 5 and line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0, line
+        assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        # value = rays per frame x steps / elapsed and ms_per_step = elapsed / steps: the same region
+        assert abs(line["value"] * line["ms_per_step"] * 1e3 / line["config"]["rays_per_frame_per_gpu"] - 1.0) < 2e-3, line
+        for k in ("roofline", "cpu_baseline", "passes", "exact_mode", "stages", "timed_repeats"):
+            assert k not in line, k
+        arrs = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert set(arrs) == {"denoised.npy", "shadow_mask.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        runs.append(arrs)
+    den = runs[0]["denoised.npy"]
+    assert den.shape == (1080, 1920, 2) and np.isfinite(den).all() and 0.02 < den[..., 0].mean() < 0.98
+    assert runs[0]["shadow_mask.npy"].any()
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
 
 
 def test_an_eight_gpu_line_keeps_the_fields_the_scale_record_needs():

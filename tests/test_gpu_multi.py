@@ -64,7 +64,7 @@ def test_cpp_tiled_frame_uses_rccl_with_two_devices():
 
 @needs_two
 def test_bench_two_gpus_reports_ranks_and_comm_times():
-    j, out = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"], timeout=1500)
+    j, out = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"], timeout=1500)
     assert j["n_gpus"] == 2 and j["comm"]["ranks_seen"] == 2 and j["comm"]["backend"] == "nccl", j.get("comm")
     assert j["comm"]["exchange_us_per_frame"] > 0 and len(j["comm"]["band_bounds"]) == 3
     assert "passes_error" not in j, j["passes_error"]
@@ -77,7 +77,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     `comm` block and of the hybrid_4k block — what the driver's --gpus N launch executes with RCCL"""
     if _n_devices() < 1:
         pytest.skip("no GPU")
-    j, out = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"], timeout=1500,
+    j, out = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"], timeout=1500,
                      env=dict(HR_DIST_BACKEND="gloo", HR_FORCE_DEVICE="0"))
     assert j["n_gpus"] == 2 and j["comm"]["ranks_seen"] == 2 and j["comm"]["backend"] == "gloo"
     assert len(j["comm"]["band_bounds"]) == 3 and j["comm"]["exchange_us_per_frame"] > 0
@@ -91,7 +91,7 @@ def test_bench_two_ranks_forked_hybrid_frame_gloo():
     fall-back to the serial frame) and give the same ray counts as the serial one"""
     if _n_devices() < 1:
         pytest.skip("no GPU")
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline"]
     jf, _ = _launch(args, timeout=1500, env=dict(HR_DIST_BACKEND="gloo", HR_FORCE_DEVICE="0", HR_FRAME_FORKED="1"))
     assert "passes_error" not in jf, jf["passes_error"]
     assert jf["hybrid_4k"]["forked_streams"] is True and "forked_error" not in jf["hybrid_4k"], jf["hybrid_4k"]

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/pmc_sets
 if [ "$1" != "--" ] && [ -n "$1" ]; then OUT=$1; shift; fi
 [ "$1" == "--" ] && shift
 CMD=("$@")
-[ ${#CMD[@]} -eq 0 ] && CMD=(python $R/bench.py --steps 3 --warmup 1)
+[ ${#CMD[@]} -eq 0 ] && CMD=(python $R/bench.py --steps 3 --warmup 1 --full)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 i=0

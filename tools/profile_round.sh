@@ -1,6 +1,6 @@
 #!/bin/bash
 # Produces the files of a profiles/<name>/ directory on the GPU box (under gpurun_out/<name>/):
-#   bench.json                   the JSON line of an un-profiled bench.py run (default flags)
+#   bench.json                   the JSON line of an un-profiled bench.py --full run
 #   kernel_stats.csv             rocprofv3 --kernel-trace --stats of the headline command (bench.py --no-passes --no-cpu-baseline)
 #   frame_kernel_stats[_4k].csv  the same for every pass of the hybrid frame (tools/passbench.py, tolerance mode) at 1920x1080 / 3840x2160
 #   pmc_summary[_4k].json        per-kernel average FETCH_SIZE / WRITE_SIZE (KB) per launch, one --pmc pass each, over the passbench run
@@ -15,7 +15,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH=(python $R/bench.py --steps 100 --warmup 20 --exact $EXACT)
 if [ -z "$SKIP_BENCH" ]; then
-    python $R/bench.py --exact $EXACT 2>/dev/null | tail -1 > $OUT/bench.json          # the compact stdout line (what the driver parses)
+    python $R/bench.py --exact $EXACT --full 2>/dev/null | tail -1 > $OUT/bench.json   # the compact stdout line
     cp $R/bench_detail.json $OUT/bench_detail.json 2>/dev/null                          # the full record (per-kernel blocks, notes)
     rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- "${BENCH[@]}" --no-cpu-baseline --no-passes > /dev/null 2> $OUT/kt.err
     cp $(find $OUT/kt -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv
