@@ -19,7 +19,7 @@ HR_DEV f3 spherical_fibonacci(float i, float n)
     const float a   = i * PHI_M1;
     const float phi = 2.0f * HR_M_PI * (a - floorf(a));
     const float ct  = 1.0f - (2.0f * i + 1.0f) * __fdiv_rn(1.0f, n);
-    const float st  = hr_sqrt(clamp1(1.0f - ct * ct, 0.0f, 1.0f));
+    const float st  = hr_sqrt(glsl_clamp(1.0f - ct * ct, 0.0f, 1.0f));
     float s, c;
     det_sincos(phi, s, c);
     return mk3(c * st, s * st, ct);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_EU) void k_ddgi_t
             if (false)
 #endif
             {
-                const f3 F   = fresnel_schlick_roughness(max2(dot3(s.N, Wo), 0.0f), F0, s.roughness);
+                const f3 F   = fresnel_schlick_roughness(glsl_max(dot3(s.N, Wo), 0.0f), F0, s.roughness);
                 const f3 kD  = scale3(sub3(one3(), F), 1.0f - s.metallic);
                 const f3 irr = sample_irradiance(a.d, s.P, s.N, Wo, a.prev_irr, a.prev_depth);
                 Lo = add3(Lo, mul3(mul3(scale3(kD, a.gi_intensity), c_diffuse), irr));
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64) void k_ddgi_shade(DDGIWaveArgs w)
             P1 = ds.P1; P2 = ds.P2; flags = 1u;
             if (a.infinite_bounces == 1)
             {
-                const f3 F   = fresnel_schlick_roughness(max2(dot3(s.N, Wo), 0.0f), F0, s.roughness);
+                const f3 F   = fresnel_schlick_roughness(glsl_max(dot3(s.N, Wo), 0.0f), F0, s.roughness);
                 const f3 kD  = scale3(sub3(one3(), F), 1.0f - s.metallic);
                 const f3 irr = sample_irradiance(a.d, s.P, s.N, Wo, a.prev_irr, a.prev_depth);
                 I = mul3(mul3(scale3(kD, a.gi_intensity), c_diffuse), irr);
@@ -380,7 +380,7 @@ __global__ void k_ddgi_probe_update(DDGIUpdateArgs a)
         for (int i = threadIdx.x; i < num; i += blockDim.x)
         {
             const uint2 q = a.dirdist[(size_t)probe * R + offset + i];
-            float dist = min2(a.d.max_distance, h2f_hi(q.y) - 0.01f);
+            float dist = glsl_min(a.d.max_distance, h2f_hi(q.y) - 0.01f);   // a NaN distance gives max_distance, as in the shader
             if (dist == -1.0f) dist = a.d.max_distance;
             s_dd[i] = make_float4(h2f_lo(q.x), h2f_hi(q.x), h2f_lo(q.y), dist);
             const uint2 c = a.radiance[(size_t)probe * R + offset + i];
@@ -397,8 +397,10 @@ __global__ void k_ddgi_probe_update(DDGIUpdateArgs a)
                 float w;
                 if (SHARP50) { const float b2 = dp * dp, b4 = b2 * b2, b8 = b4 * b4, b16 = b8 * b8, b32 = b16 * b16; w = ((1.0f * b2) * b16) * b32; }
                 else w = det_pow_auto(dp, a.d.depth_sharpness);
-                w = w >= 0.00000001f ? w : 0.0f;
-                r0 += dd.w * w; r1 += (dd.w * dd.w) * w; total_w += w;
+                // a ray under the weight threshold is SKIPPED (gi_probe_update.glsl: if (weight >= FLT_EPS)): select the products, not the
+                // weight, so that 0 * inf cannot put a NaN into the sum (r0 starts at +0 and never becomes -0, so adding +0 equals skipping)
+                const bool on = w >= 0.00000001f;
+                r0 += on ? dd.w * w : 0.0f; r1 += on ? (dd.w * dd.w) * w : 0.0f; total_w += on ? w : 0.0f;
             };
             int r = 0;
             for (; r + 4 <= num; r += 4) { one_ray(r); one_ray(r + 1); one_ray(r + 2); one_ray(r + 3); }   // four rays' LDS reads in flight together
@@ -409,8 +411,9 @@ __global__ void k_ddgi_probe_update(DDGIUpdateArgs a)
             auto one_ray = [&](int r) {
                 const float4 dd = s_dd[r], c = s_rad[r];
                 float dp = __builtin_fmaxf(0.0f, dot3(texel_dir, mk3(dd.x, dd.y, dd.z)));
-                dp = dp >= 0.00000001f ? dp : 0.0f;
-                r0 += c.x * dp; r1 += c.y * dp; r2 += c.z * dp; total_w += dp;
+                // skip, not zero-weight: an inf radiance ray facing away from the texel must not give inf * 0 = NaN (see the depth branch)
+                const bool on = dp >= 0.00000001f;
+                r0 += on ? c.x * dp : 0.0f; r1 += on ? c.y * dp : 0.0f; r2 += on ? c.z * dp : 0.0f; total_w += on ? dp : 0.0f;
             };
             int r = 0;
             for (; r + 4 <= num; r += 4) { one_ray(r); one_ray(r + 1); one_ray(r + 2); one_ray(r + 3); }

@@ -183,7 +183,9 @@ HR_DEV f3 sample_irradiance_pass(const DDGIU& d, f3 P, f3 N, f3 Wo, const AtlasR
     const float iw = fm::rcp(sum_w);
     f3 net = mk3(sum.x * iw, sum.y * iw, sum.z * iw);
     net.x = (net.x != net.x) ? 0.5f : net.x; net.y = (net.y != net.y) ? 0.5f : net.y; net.z = (net.z != net.z) ? 0.5f : net.z;
-    redo = noted || (2e-7f * max_nt > 1e-3f * sum_w);
+    // a sum that is not finite was driven by an inf / NaN atlas texel (HDR radiance: 0 * inf in a bilinear or trilinear weight): whether the
+    // reference gets inf, NaN -> 0.5 or a finite value there depends on which weights are exactly 0 in ITS arithmetic, so the parity gather decides
+    redo = noted || (2e-7f * max_nt > 1e-3f * sum_w) || !__builtin_isfinite(sum.x + sum.y + sum.z);
 #ifdef HR_DEBUG_DDGI_PIXEL
     if (dbg) printf("[ddgi dbg] P %.9g %.9g %.9g base %d %d %d alpha %.9g %.9g %.9g net %.9g %.9g %.9g redo %d\n", P.x, P.y, P.z, bx, by, bz, alpha.x, alpha.y, alpha.z, net.x, net.y, net.z, (int)redo);
 #endif

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_deferred(DeferredArgs a)
     {
         const f3    I   = neg3(Wo);
         const f3    R   = sub3(I, scale3(N, 2.0f * dot3(N, I)));
-        const float ndv = max2(dot3(N, Wo), 0.0f);
+        const float ndv = glsl_max(dot3(N, Wo), 0.0f);
         const f3    F   = fresnel_schlick_roughness(ndv, F0, roughness);
         const f3    kD  = scale3(sub3(one3(), F), 1.0f - metallic);
         f3 irradiance;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k_deferred(DeferredArgs a)
             f3 col = mk3(0.0f, 0.0f, 0.0f);
 #pragma unroll
             for (int k = 0; k < 9; k++) col = add3(col, scale3(mk3(a.sh9[k][0], a.sh9[k][1], a.sh9[k][2]), c[k]));
-            col = mk3(max2(0.0f, col.x), max2(0.0f, col.y), max2(0.0f, col.z));
+            col = mk3(glsl_max(0.0f, col.x), glsl_max(0.0f, col.y), glsl_max(0.0f, col.z));
             irradiance = div3s(col, Pi);
         }
         const f3 diffuse = mul3(irradiance, c_diffuse);

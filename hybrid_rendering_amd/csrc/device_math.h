@@ -38,6 +38,13 @@ HR_DEV f3 normalize3(f3 a)
 HR_DEV float min2(float a, float b) { return a < b ? a : b; }
 HR_DEV float max2(float a, float b) { return a > b ? a : b; }
 HR_DEV float clamp1(float x, float lo, float hi) { return min2(max2(x, lo), hi); }
+// The GLSL specification's formulas (min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x): min2 / max2 above take the reversed comparison,
+// which agrees on finite non-zero operands but returns the other operand on a NaN and -0 for min(+0, -0).  Sites that restate a shader's
+// min / max / clamp where a NaN or a signed zero can reach them use these (the oracle's glsl_min / glsl_max).  min2 / max2 stay as they are:
+// traverse.h's slab tests rely on their NaN behaviour.
+HR_DEV float glsl_min(float x, float y) { return y < x ? y : x; }
+HR_DEV float glsl_max(float x, float y) { return x < y ? y : x; }
+HR_DEV float glsl_clamp(float x, float lo, float hi) { return glsl_min(glsl_max(x, lo), hi); }
 HR_DEV float mix1(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 HR_DEV float fract1(float x) { return x - floorf(x); }
 HR_DEV float step1(float edge, float x) { return x < edge ? 0.0f : 1.0f; }
@@ -177,6 +184,9 @@ HR_DEV float det_log(float x)
 HR_DEV float det_pow(float x, float y)
 {
     if (x <= 0.0f) return 0.0f;
+    // det_log reads the bits of x: a NaN (whose sign and payload are unspecified) or +inf must not reach it.  As IEEE pow: NaN stays
+    // NaN, +inf^y is +inf for y > 0 (0 for y < 0, 1 for y == 0)
+    if (!(x < INFINITY)) return (x != x || y > 0.0f) ? x : (y < 0.0f ? 0.0f : 1.0f);
     return det_exp(y * det_log(x));
 }
 
@@ -251,7 +261,7 @@ HR_DEV f3 world_pos_from_depth(float u, float v, float ndc_depth, const float* _
 }
 
 // common.glsl:141-144
-HR_DEV float luminance(f3 rgb) { return max2(dot3(rgb, mk3(0.299f, 0.587f, 0.114f)), 0.0001f); }
+HR_DEV float luminance(f3 rgb) { return glsl_max(dot3(rgb, mk3(0.299f, 0.587f, 0.114f)), 0.0001f); }
 
 // bnd_sampler.glsl:4-24.  int(clamp(unorm8 * 256, 0, 255)) is the identity on 0..255
 // (tests/test_oracle_kat.py::test_unorm8_identity), so the byte is used directly.

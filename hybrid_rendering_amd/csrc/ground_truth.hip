@@ -29,8 +29,6 @@ struct GTArgs
 };
 
 #define GT_MAX_DEPTH 32
-// GLSL max(x, y) = (x < y) ? y : x: keeps a NaN first argument (the indirect path can produce 0/0), unlike max2
-HR_DEV float glsl_max(float x, float y) { return (x < y) ? y : x; }
 // brdf.glsl:96-112
 HR_DEV f3 sample_specular_ggx_lobe(f3 n, float alpha, float xi_x, float xi_y)
 {
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
             const float ps  = __fdiv_rn(D_ggx(NdotH, alpha) * NdotH, glsl_max(HR_EPSILON, 4.0f * VdotH));
             const float pdf = mix1(pd, ps, 0.5f);
             const f3    brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
-            const float cos_theta = clamp1(dot3(s.N, Wi), 0.0f, 1.0f);
+            const float cos_theta = glsl_clamp(dot3(s.N, Wi), 0.0f, 1.0f);
             const f3    tb = mul3(T, scale3(brdf, cos_theta));
             f3 Tn = mk3(__fdiv_rn(tb.x, pdf), __fdiv_rn(tb.y, pdf), __fdiv_rn(tb.z, pdf));
             const float probability = glsl_max(Tn.x, glsl_max(Tn.y, Tn.z));
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
         }
         f3 L = adds[depth];
         for (int k = depth - 1; k >= 0; k--) L = add3(adds[k], L);
-        const f3 clamped = mk3(L.x < 1.0f ? L.x : 1.0f, L.y < 1.0f ? L.y : 1.0f, L.z < 1.0f ? L.z : 1.0f); // RADIANCE_CLAMP_COLOR
+        const f3 clamped = mk3(glsl_min(L.x, 1.0f), glsl_min(L.y, 1.0f), glsl_min(L.z, 1.0f)); // RADIANCE_CLAMP_COLOR
         f3 out = clamped;
         const size_t i = (size_t)y * a.w + x;
         if (a.num_frames != 0u)

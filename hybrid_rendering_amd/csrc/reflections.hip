@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
             if (a.sample_gi == 1)
             {
                 const f3    R   = reflect3(neg3(hWo), s.N);
-                const float ndv = max2(dot3(s.N, hWo), 0.0f);
+                const float ndv = glsl_max(dot3(s.N, hWo), 0.0f);
                 const f3    F   = fresnel_schlick_roughness(ndv, F0, s.roughness);
                 hkD             = scale3(sub3(one3(), F), 1.0f - s.metallic);
                 const f3    pre = a.env.prefiltered_fetch(R, s.roughness * 4.0f);
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
             color = add3(hLo, add3(mul3(hkD, diffuse), hspec));
         }
     }
-    if (geom) a.out[o] = make_uint2(pack_h2(min2(color.x, 0.7f), min2(color.y, 0.7f)), pack_h2(min2(color.z, 0.7f), ray_length));
+    if (geom) a.out[o] = make_uint2(pack_h2(glsl_min(color.x, 0.7f), glsl_min(color.y, 0.7f)), pack_h2(glsl_min(color.z, 0.7f), ray_length));
     HR_DIV(div_flush(dvp, g_div_refl); div_flush(dvs, g_div_refl + 8);)
     for (int o2 = 32; o2 > 0; o2 >>= 1) rays += __shfl_down(rays, o2);
     if (lane == 0) a.ray_slots[tile] = rays;
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_refl_temporal(ReflTemporalArgs a)
             ImgR16F none { nullptr, 0, 0, 0 };
             const bool success = reproject<false, true, true, ImgRGBA16F>(in, a.hist, a.hist_moments, none, hc, hm, hl);
             if (a.apron_flag && in.apron_miss && y >= a.band_y0 && y < a.band_y1) atomicOr(a.apron_flag, 1u);   // rare (motion beyond the history apron of a row band)
-            hl = min2(32.0f, success ? hl + 1.0f : 1.0f);
+            hl = glsl_min(32.0f, success ? hl + 1.0f : 1.0f);
             f3 history = mk3(hc[0], hc[1], hc[2]);
             if (success)
             {
@@ -303,23 +303,23 @@ __global__ __launch_bounds__(256) void k_refl_temporal(ReflTemporalArgs a)
                     }
                 const f3 mean = div3s(s1, 289.0f);
                 const f3 var  = sub3(div3s(s2, 289.0f), mul3(mean, mean));
-                const f3 sd   = mk3(hr_sqrt(max2(var.x, 0.0f)), hr_sqrt(max2(var.y, 0.0f)), hr_sqrt(max2(var.z, 0.0f)));
+                const f3 sd   = mk3(hr_sqrt(glsl_max(var.x, 0.0f)), hr_sqrt(glsl_max(var.y, 0.0f)), hr_sqrt(glsl_max(var.z, 0.0f)));
                 const f3 amin = sub3(mean, sd), amax = add3(mean, sd);
                 // clip_aabb (:111-129)
                 const f3 center = scale3(add3(amax, amin), 0.5f);
                 const f3 extent = add3(scale3(sub3(amax, amin), 0.5f), mk3(0.001f, 0.001f, 0.001f));
                 const f3 cv     = sub3(history, center);
-                const float mx  = max2(max2(fabsf(__fdiv_rn(cv.x, extent.x)), fabsf(__fdiv_rn(cv.y, extent.y))), fabsf(__fdiv_rn(cv.z, extent.z)));
+                const float mx  = glsl_max(glsl_max(fabsf(__fdiv_rn(cv.x, extent.x)), fabsf(__fdiv_rn(cv.y, extent.y))), fabsf(__fdiv_rn(cv.z, extent.z)));
                 if (mx > 1.0f) history = add3(center, div3s(cv, mx));
             }
             const float max_acc = a.moving ? 8.0f : hl;
-            const float al = success ? max2(a.alpha, __fdiv_rn(1.0f, max_acc)) : 1.0f;
-            const float am = success ? max2(a.moments_alpha, __fdiv_rn(1.0f, max_acc)) : 1.0f;
+            const float al = success ? glsl_max(a.alpha, __fdiv_rn(1.0f, max_acc)) : 1.0f;
+            const float am = success ? glsl_max(a.moments_alpha, __fdiv_rn(1.0f, max_acc)) : 1.0f;
             m0 = luminance(color);
             m1 = m0 * m0;
             m0 = mix1(hm[0], m0, am);
             m1 = mix1(hm[1], m1, am);
-            r3 = max2(0.0f, m1 - m0 * m0);
+            r3 = glsl_max(0.0f, m1 - m0 * m0);
             const f3 acc = mix3(history, color, al);
             r0 = acc.x; r1 = acc.y; r2 = acc.z;
         }
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void k_refl_atrous(ReflAtrousArgs a)
             const f3    cn = oct_decode(h2f_lo(g2.x), h2f_hi(g2.x));
             const float center_depth = h2f_hi(g3.y);
             // one denominator, many numerators: share the denominator half of the correctly rounded divisions (device_math.h)
-            const DivBy phi_c = div_prepare(a.phi_color * hr_sqrt(max2(0.0f, 1e-10f + var))), by_sigma = div_prepare(a.sigma_depth);
+            const DivBy phi_c = div_prepare(a.phi_color * hr_sqrt(glsl_max(0.0f, 1e-10f + var))), by_sigma = div_prepare(a.sigma_depth);
             float sum_w = 1.0f, s0 = cc.x, s1 = cc.y, s2 = cc.z, s3 = h2f_hi(c.y);
             if (RADIUS == 1)
             {
@@ -399,9 +399,9 @@ __global__ __launch_bounds__(256) void k_refl_atrous(ReflAtrousArgs a)
                     const float sl = luminance(sc);
                     const f3    sn = oct_decode(h2f_lo(t_g2[t].x), h2f_hi(t_g2[t].x));
                     const float wZ = det_exp(div_by(-fabsf(center_depth - h2f_hi(t_g3[t].y)), by_sigma));
-                    const float wN = pow_phi_normal(clamp1(dot3(cn, sn), 0.0f, 1.0f), a.phi_normal);
+                    const float wN = pow_phi_normal(glsl_clamp(dot3(cn, sn), 0.0f, 1.0f), a.phi_normal);
                     const float wL = div_by(fabsf(center_luma - sl), phi_c);
-                    w8[t] = det_exp((0.0f - max2(wL, 0.0f)) - max2(wZ, 0.0f)) * wN;
+                    w8[t] = det_exp((0.0f - glsl_max(wL, 0.0f)) - glsl_max(wZ, 0.0f)) * wN;
                 }
 #pragma unroll
                 for (int t = 0; t < 8; t++)
@@ -431,9 +431,9 @@ __global__ __launch_bounds__(256) void k_refl_atrous(ReflAtrousArgs a)
                     const float sl = luminance(sc);
                     const f3    sn = oct_decode(h2f_lo(q2.x), h2f_hi(q2.x));
                     const float wZ = det_exp(div_by(-fabsf(center_depth - h2f_hi(q3.y)), by_sigma));
-                    const float wN = pow_phi_normal(clamp1(dot3(cn, sn), 0.0f, 1.0f), a.phi_normal);
+                    const float wN = pow_phi_normal(glsl_clamp(dot3(cn, sn), 0.0f, 1.0f), a.phi_normal);
                     const float wL = div_by(fabsf(center_luma - sl), phi_c);
-                    const float w  = det_exp((0.0f - max2(wL, 0.0f)) - max2(wZ, 0.0f)) * wN;
+                    const float w  = det_exp((0.0f - glsl_max(wL, 0.0f)) - glsl_max(wZ, 0.0f)) * wN;
                     const float wc = w * (kx * ky);
                     sum_w += wc;
                     s0 += wc * sc.x; s1 += wc * sc.y; s2 += wc * sc.z;

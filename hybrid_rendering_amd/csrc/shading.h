@@ -87,12 +87,12 @@ HR_DEV float D_ggx(float ndoth, float alpha)
 {
     const float a2 = alpha * alpha;
     const float denom = (ndoth * ndoth) * (a2 - 1.0f) + 1.0f;
-    return __fdiv_rn(a2, max2(HR_EPSILON, (HR_M_PI * denom * denom)));
+    return __fdiv_rn(a2, glsl_max(HR_EPSILON, (HR_M_PI * denom * denom)));
 }
 HR_DEV float G1_schlick_ggx(float roughness, float ndotv)
 {
     const float k = __fdiv_rn((roughness + 1.0f) * (roughness + 1.0f), 8.0f);
-    return __fdiv_rn(ndotv, max2(HR_EPSILON, (ndotv * (1.0f - k) + k)));
+    return __fdiv_rn(ndotv, glsl_max(HR_EPSILON, (ndotv * (1.0f - k) + k)));
 }
 HR_DEV float G_schlick_ggx(float ndotl, float ndotv, float roughness) { return G1_schlick_ggx(roughness, ndotl) * G1_schlick_ggx(roughness, ndotv); }
 HR_DEV f3 F_schlick(f3 f0, float vdoth)
@@ -104,11 +104,11 @@ HR_DEV f3 evaluate_specular_brdf(float roughness, f3 F, float ndoth, float ndotl
 {
     const float alpha = roughness * roughness;
     const f3    num   = scale3(scale3(F, D_ggx(ndoth, alpha)), G_schlick_ggx(ndotl, ndotv, roughness));
-    return div3s(num, max2(HR_EPSILON, (4.0f * ndotl * ndotv)));
+    return div3s(num, glsl_max(HR_EPSILON, (4.0f * ndotl * ndotv)));
 }
 HR_DEV f3 evaluate_uber_brdf(f3 diffuse_color, float roughness, f3 N, f3 F0, f3 Wo, f3 Wh, f3 Wi)
 {
-    const float NdotL = max2(dot3(N, Wi), 0.0f), NdotV = max2(dot3(N, Wo), 0.0f), NdotH = max2(dot3(N, Wh), 0.0f), VdotH = max2(dot3(Wi, Wh), 0.0f);
+    const float NdotL = glsl_max(dot3(N, Wi), 0.0f), NdotV = glsl_max(dot3(N, Wo), 0.0f), NdotH = glsl_max(dot3(N, Wh), 0.0f), VdotH = glsl_max(dot3(Wi, Wh), 0.0f);
     const f3 F        = F_schlick(F0, VdotH);
     const f3 specular = evaluate_specular_brdf(roughness, F, NdotH, NdotL, NdotV);
     const f3 diffuse  = div3s(diffuse_color, HR_M_PI);
@@ -117,15 +117,15 @@ HR_DEV f3 evaluate_uber_brdf(f3 diffuse_color, float roughness, f3 N, f3 F0, f3 
 HR_DEV f3 fresnel_schlick_roughness(float cos_theta, f3 F0, float roughness)
 {
     const float r1 = 1.0f - roughness;
-    const f3    m  = mk3(max2(r1, F0.x), max2(r1, F0.y), max2(r1, F0.z));
-    const float p  = det_powi(max2(1.0f - cos_theta, 0.0f), 5);
+    const f3    m  = mk3(glsl_max(r1, F0.x), glsl_max(r1, F0.y), glsl_max(r1, F0.z));
+    const float p  = det_powi(glsl_max(1.0f - cos_theta, 0.0f), 5);
     return add3(F0, scale3(sub3(m, F0), p));
 }
 // brdf.glsl:8-32
 HR_DEV f3 sample_cosine_lobe_n(f3 n, float rx, float ry)
 {
-    rx = max2(0.00001f, rx);
-    ry = max2(0.00001f, ry);
+    rx = glsl_max(0.00001f, rx);
+    ry = glsl_max(0.00001f, ry);
     const float phi = 2.0f * HR_M_PI * ry;
     const float ct = hr_sqrt(rx), st = hr_sqrt(1.0f - rx);
     float s, c;
@@ -274,8 +274,8 @@ HR_DEV IrrCell irradiance_cell(const DDGIU& d, const IrrDiv& D, f3 P, f3 N)
     c.by = clampi((int)__fdiv_rn(P.y - g0.y, gs.y), 0, d.probe_counts[1] - 1);
     c.bz = clampi((int)__fdiv_rn(P.z - g0.z, gs.z), 0, d.probe_counts[2] - 1);
     const f3 base_pos = grid_coord_to_position(d, c.bx, c.by, c.bz);
-    c.alpha = mk3(clamp1(__fdiv_rn(P.x - base_pos.x, gs.x), 0.0f, 1.0f), clamp1(__fdiv_rn(P.y - base_pos.y, gs.y), 0.0f, 1.0f),
-                  clamp1(__fdiv_rn(P.z - base_pos.z, gs.z), 0.0f, 1.0f));
+    c.alpha = mk3(glsl_clamp(__fdiv_rn(P.x - base_pos.x, gs.x), 0.0f, 1.0f), glsl_clamp(__fdiv_rn(P.y - base_pos.y, gs.y), 0.0f, 1.0f),
+                  glsl_clamp(__fdiv_rn(P.z - base_pos.z, gs.z), 0.0f, 1.0f));
     texture_coord_in_cell(normalize3(N), D.iw, D.ih, D.irr_in, d.irradiance_probe_side_length, c.icx, c.icy);
     return c;
 }
@@ -294,7 +294,7 @@ HR_DEV IrrTerm irradiance_probe_term(const DDGIU& d, const IrrDiv& D, f3 P, f3 N
     float weight = 1.0f;
     {
         const f3    tdp = normalize3(sub3(probe_pos, P));
-        const float t   = max2(0.0001f, (dot3(tdp, N) + 1.0f) * 0.5f);
+        const float t   = glsl_max(0.0001f, (dot3(tdp, N) + 1.0f) * 0.5f);
         weight          = weight * (t * t + 0.2f);
     }
     if (d.visibility_test == 1)
@@ -304,12 +304,12 @@ HR_DEV IrrTerm irradiance_probe_term(const DDGIU& d, const IrrDiv& D, f3 P, f3 N
         const float dist = len3(probe_to_point);
         atlas_bilinear_rg(depth, u, v, mean, m2);
         const float variance = fabsf(mean * mean - m2);
-        const float dm  = max2(dist - mean, 0.0f);
+        const float dm  = glsl_max(dist - mean, 0.0f);
         float che = __fdiv_rn(variance, variance + dm * dm);
-        che       = max2(che * che * che, 0.0f);
+        che       = glsl_max(che * che * che, 0.0f);
         weight    = weight * ((dist <= mean) ? 1.0f : che);
     }
-    weight = max2(0.000001f, weight);
+    weight = glsl_max(0.000001f, weight);
     float u, v;
     texture_coord_of_cell(c.icx, c.icy, col, cz, D.iw, D.ih, D.irr_in, d.irradiance_probe_side_length, u, v);
     f3 probe_irr = atlas_bilinear_rgb(irradiance, u, v);
@@ -536,7 +536,7 @@ HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
     if (s.materials)
     {
         const float* m = s.materials + (size_t)mat * 8;
-        o.albedo = mk3(m[0], m[1], m[2]); o.metallic = m[3]; o.roughness = max2(m[4], 0.1f);
+        o.albedo = mk3(m[0], m[1], m[2]); o.metallic = m[3]; o.roughness = glsl_max(m[4], 0.1f);
     }
     else { o.albedo = mk3(0.8f, 0.8f, 0.8f); o.metallic = 0.0f; o.roughness = 0.5f; }
     if (s.mat_tex)
@@ -551,7 +551,7 @@ HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
         }
         float c[4];
         if (mt[0] >= 0) { sample_texture(s, mt[0], tu, tv, c); o.albedo = mk3(c[0], c[1], c[2]); }
-        if (mt[2] >= 0) { sample_texture(s, mt[2], tu, tv, c); o.roughness = max2(c[mt[4] & 3], 0.1f); }
+        if (mt[2] >= 0) { sample_texture(s, mt[2], tu, tv, c); o.roughness = glsl_max(c[mt[4] & 3], 0.1f); }
         if (mt[3] >= 0) { sample_texture(s, mt[3], tu, tv, c); o.metallic = c[mt[5] & 3]; }
         if (mt[1] >= 0)
         {
@@ -588,7 +588,7 @@ HR_DEV void fetch_light_hard(const hr_light& L, f3 Wo, f3 P, f3 N, f3& Li, f3& W
         else attenuation = __fdiv_rn(smoothstep1(L.data3[1], L.data3[2], dot3(Wi, ldir)), dist * dist);
     }
     Wh          = normalize3(add3(Wo, Wi));
-    attenuation = attenuation * clamp1(dot3(N, Wi), 0.0f, 1.0f);
+    attenuation = attenuation * glsl_clamp(dot3(N, Wi), 0.0f, 1.0f);
 }
 
 // (shared by the shadow pass and the ground-truth path tracer)
@@ -628,7 +628,7 @@ HR_DEV void fetch_light_shadow(const hr_light& L, f3 P, f3 N, float rx, float ry
         float aa    = smoothstep1(L.data3[1], L.data3[2], dot3(Wi, ldir));
         attenuation = __fdiv_rn(aa, t_max * t_max);
     }
-    attenuation = attenuation * clamp1(dot3(N, Wi), 0.0f, 1.0f);
+    attenuation = attenuation * glsl_clamp(dot3(N, Wi), 0.0f, 1.0f);
 }
 
 struct TraceCtx

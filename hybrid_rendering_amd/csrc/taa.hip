@@ -27,8 +27,8 @@ HR_DEV f4 add4(f4 a, f4 b) { f4 r; r.x = a.x + b.x; r.y = a.y + b.y; r.z = a.z +
 HR_DEV f4 sub4(f4 a, f4 b) { f4 r; r.x = a.x - b.x; r.y = a.y - b.y; r.z = a.z - b.z; r.w = a.w - b.w; return r; }
 HR_DEV f4 scale4(f4 a, float s) { f4 r; r.x = a.x * s; r.y = a.y * s; r.z = a.z * s; r.w = a.w * s; return r; }
 HR_DEV f4 div4s(f4 a, float s) { f4 r; r.x = __fdiv_rn(a.x, s); r.y = __fdiv_rn(a.y, s); r.z = __fdiv_rn(a.z, s); r.w = __fdiv_rn(a.w, s); return r; }
-HR_DEV f4 min4(f4 a, f4 b) { f4 r; r.x = min2(a.x, b.x); r.y = min2(a.y, b.y); r.z = min2(a.z, b.z); r.w = min2(a.w, b.w); return r; }
-HR_DEV f4 max4(f4 a, f4 b) { f4 r; r.x = max2(a.x, b.x); r.y = max2(a.y, b.y); r.z = max2(a.z, b.z); r.w = max2(a.w, b.w); return r; }
+HR_DEV f4 min4(f4 a, f4 b) { f4 r; r.x = glsl_min(a.x, b.x); r.y = glsl_min(a.y, b.y); r.z = glsl_min(a.z, b.z); r.w = glsl_min(a.w, b.w); return r; }
+HR_DEV f4 max4(f4 a, f4 b) { f4 r; r.x = glsl_max(a.x, b.x); r.y = glsl_max(a.y, b.y); r.z = glsl_max(a.z, b.z); r.w = glsl_max(a.w, b.w); return r; }
 HR_DEV f4 mix4(f4 a, f4 b, float t) { return add4(scale4(a, 1.0f - t), scale4(b, t)); }
 
 HR_DEV f4 bilinear(const TexRGBA& t, float u, float v)
@@ -85,7 +85,7 @@ struct ToneMapArgs
 HR_DEV float aces_film(float x) // tone_map.frag:36-44
 {
     const float num = x * (2.51f * x + 0.03f), den = x * (2.43f * x + 0.59f) + 0.14f;
-    return clamp1(__fdiv_rn(num, den), 0.0f, 1.0f);
+    return glsl_clamp(__fdiv_rn(num, den), 0.0f, 1.0f);
 }
 __global__ __launch_bounds__(256) void k_tone_map(ToneMapArgs a)
 {
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_taa(TAAArgs a)
     cavg = scale4(add4(cavg, cavg5), 0.5f);
     texel1 = clip_aabb(cmin, cmax, min4(max4(cavg, cmin), cmax), texel1);
     const float lum0 = luminance(mk3(texel0.x, texel0.y, texel0.z)), lum1 = luminance(mk3(texel1.x, texel1.y, texel1.z));
-    const float unbiased_diff = __fdiv_rn(fabsf(lum0 - lum1), max2(lum0, max2(lum1, 0.2f)));
+    const float unbiased_diff = __fdiv_rn(fabsf(lum0 - lum1), glsl_max(lum0, glsl_max(lum1, 0.2f)));
     const float uw = 1.0f - unbiased_diff, uw2 = uw * uw;
     const float k_feedback = mix1(a.feedback_min, a.feedback_max, uw2);
     if (a.sharpen == 1)
@@ -167,8 +167,8 @@ __global__ __launch_bounds__(256) void k_taa(TAAArgs a)
     for (int c = 0; c < 3; c++)
     {
         float b = mix1(t0[c], t1[c], k_feedback);
-        b       = __fdiv_rn(b, max2(1.0f - b, 0.00000001f));
-        o[c]    = clamp1(b, 0.0f, 1.0f);
+        b       = __fdiv_rn(b, glsl_max(1.0f - b, 0.00000001f));
+        o[c]    = glsl_clamp(b, 0.0f, 1.0f);
     }
     a.out[(size_t)y * a.w + x] = make_uint2(pack_h2(o[0], o[1]), pack_h2(o[2], 1.0f));
 }

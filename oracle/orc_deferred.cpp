@@ -77,7 +77,7 @@ void orc_deferred_shade(const void* ubo_, int w, int h, const uint8_t* gb1, cons
             {   // indirect lighting
                 const vec3 I  = -Wo;
                 const vec3 Rr = I - N * (2.0f * dot(N, I)); // reflect(-Wo, N)
-                const float ndv = fmax2(dot(N, Wo), 0.0f);
+                const float ndv = glsl_max(dot(N, Wo), 0.0f);
                 vec3 F  = fresnel_schlick_roughness(ndv, F0, roughness);
                 vec3 kD = (v3(1.0f, 1.0f, 1.0f) - F) * (1.0f - metallic);
                 vec3 irradiance;
@@ -99,7 +99,7 @@ void orc_deferred_shade(const void* ubo_, int w, int h, const uint8_t* gb1, cons
                     c[4] *= CosineA2; c[5] *= CosineA2; c[6] *= CosineA2; c[7] *= CosineA2; c[8] *= CosineA2;
                     vec3 col = v3(0, 0, 0);
                     for (int k = 0; k < 9; k++) col = col + v3(sh9[k * 4], sh9[k * 4 + 1], sh9[k * 4 + 2]) * c[k];
-                    col = v3(fmax2(0.0f, col.x), fmax2(0.0f, col.y), fmax2(0.0f, col.z));
+                    col = v3(glsl_max(0.0f, col.x), glsl_max(0.0f, col.y), glsl_max(0.0f, col.z));
                     irradiance = col / Pi;
                 }
                 vec3 diffuse = irradiance * c_diffuse;

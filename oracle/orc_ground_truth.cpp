@@ -19,9 +19,6 @@ void fetch_light_properties_shadow(const Light& light, vec3 P, vec3 N, float rx,
 
 extern "C" {
 
-// GLSL max(x, y) = (x < y) ? y : x  — keeps a NaN first argument, unlike fmax2 (the indirect path can produce 0/0)
-static inline float glsl_max(float x, float y) { return (x < y) ? y : x; }
-
 // brdf.glsl:96-112 sample_specular_ggx_lobe
 static inline vec3 sample_specular_ggx_lobe(vec3 n, float alpha, float xi_x, float xi_y)
 {
@@ -135,7 +132,7 @@ void orc_ground_truth_render_ex(const void* scene_, const void* ubo_, const uint
                 const float ps  = (D_ggx(NdotH, alpha) * NdotH) / glsl_max(ORC_EPSILON, 4.0f * VdotH);
                 const float pdf = mixf(pd, ps, 0.5f);
                 const vec3  brdf = evaluate_uber_brdf(c_diffuse, roughness, sh.N, F0, Wo, Wh, Wi);
-                const float cos_theta = clampf(dot(sh.N, Wi), 0.0f, 1.0f);
+                const float cos_theta = glsl_clamp(dot(sh.N, Wi), 0.0f, 1.0f);
                 vec3 Tn = (T * (brdf * cos_theta)) / pdf;
                 const float probability = glsl_max(Tn.x, glsl_max(Tn.y, Tn.z));
                 if (next_float(rng) > probability) break;
@@ -145,7 +142,7 @@ void orc_ground_truth_render_ex(const void* scene_, const void* ubo_, const uint
             // unwind: L_k = adds[k] + L_{k+1}
             vec3 L = adds[depth];
             for (int k = depth - 1; k >= 0; k--) L = adds[k] + L;
-            const vec3 clamped = v3(fmin2(L.x, 1.0f), fmin2(L.y, 1.0f), fmin2(L.z, 1.0f)); // RADIANCE_CLAMP_COLOR (common.glsl:19)
+            const vec3 clamped = v3(glsl_min(L.x, 1.0f), glsl_min(L.y, 1.0f), glsl_min(L.z, 1.0f)); // RADIANCE_CLAMP_COLOR (common.glsl:19)
             vec3 out = clamped;
             const size_t o4 = ((size_t)y * w + x) * 4;
             if (num_frames != 0)

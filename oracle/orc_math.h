@@ -105,6 +105,17 @@ static inline vec3  normalize(vec3 a)
 static inline float fmin2(float a, float b) { return a < b ? a : b; }
 static inline float fmax2(float a, float b) { return a > b ? a : b; }
 static inline float clampf(float x, float lo, float hi) { return fmin2(fmax2(x, lo), hi); }
+// The GLSL specification's formulas (GLSL 4.60 §8.3): min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x, clamp(x, lo, hi) =
+// min(max(x, lo), hi).  fmin2 / fmax2 above take the reversed comparison: the two agree on every finite non-zero operand pair, but on a
+// NaN operand the spec order returns the FIRST argument (fmin2 / fmax2 the second) and min(+0, -0) is +0 (fmin2: -0).  They are used
+// where HDR radiance can bring a NaN or a signed zero: the DDGI, reflections, TAA, tone map, deferred and ground-truth restatements and
+// orc_shading.h (plus luminance below and the shadow pass's light attenuation, which shares the light code).  The shadows / AO temporal,
+// a-trous and upsample stages, smoothstep, the G-buffer synthesis and unorm8 conversions keep fmin2 / fmax2 / clampf: their inputs are
+// bounded and finite (visibility, AO, G-buffer channels), and the kernels they are compared with keep min2 / max2 there.
+// (refshim/glsl.h binds the spec formulas for the reference's shaders.)
+static inline float glsl_min(float x, float y) { return y < x ? y : x; }
+static inline float glsl_max(float x, float y) { return x < y ? y : x; }
+static inline float glsl_clamp(float x, float lo, float hi) { return glsl_min(glsl_max(x, lo), hi); }
 static inline float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 static inline vec3  mix3(vec3 a, vec3 b, float t) { return a * (1.0f - t) + b * t; }
 static inline float fractf(float x) { return x - std::floor(x); }
@@ -188,6 +199,9 @@ static inline float det_log(float x)
 static inline float det_pow(float x, float y)
 {
     if (x <= 0.0f) return 0.0f;
+    // det_log reads the bits of x: a NaN (whose sign and payload are unspecified) or +inf must not reach it.  As IEEE pow: NaN stays
+    // NaN, +inf^y is +inf for y > 0 (0 for y < 0, 1 for y == 0)
+    if (!(x < INFINITY)) return (x != x || y > 0.0f) ? x : (y < 0.0f ? 0.0f : 1.0f);
     return det_exp(y * det_log(x));
 }
 
@@ -251,7 +265,7 @@ static inline vec3 world_position_from_depth(float u, float v, float ndc_depth, 
 // common.glsl:141-144
 static inline float luminance(vec3 rgb)
 {
-    return fmax2(dot(rgb, v3(0.299f, 0.587f, 0.114f)), 0.0001f);
+    return glsl_max(dot(rgb, v3(0.299f, 0.587f, 0.114f)), 0.0001f);
 }
 
 // common.glsl:160-165

@@ -127,7 +127,7 @@ void orc_reflections_ray_trace(const void* scene_, const void* ubo_, const void*
                     if (prm->sample_gi == 1)
                     {
                         const vec3 R  = reflect3(-hWo, sh.N);
-                        float ndv     = fmax2(dot(sh.N, hWo), 0.0f);
+                        float ndv     = glsl_max(dot(sh.N, hWo), 0.0f);
                         vec3  F       = fresnel_schlick_roughness(ndv, F0, sh.roughness);
                         vec3  kD      = (v3(1.0f, 1.0f, 1.0f) - F) * (1.0f - sh.metallic);
                         vec3  pre     = env.prefiltered_fetch(R, sh.roughness * 4.0f);
@@ -140,7 +140,7 @@ void orc_reflections_ray_trace(const void* scene_, const void* ubo_, const void*
                     ray_length = 0.001f + hit.t;
                 }
             }
-            o[0] = f32_to_f16(fmin2(color.x, 0.7f)); o[1] = f32_to_f16(fmin2(color.y, 0.7f)); o[2] = f32_to_f16(fmin2(color.z, 0.7f));
+            o[0] = f32_to_f16(glsl_min(color.x, 0.7f)); o[1] = f32_to_f16(glsl_min(color.y, 0.7f)); o[2] = f32_to_f16(glsl_min(color.z, 0.7f));
             o[3] = f32_to_f16(ray_length);
         }
     if (rays_out) *rays_out = rays;
@@ -184,7 +184,7 @@ void orc_reflections_temporal(const void* ubo_, int w, int h, const uint16_t* in
                         ri.view_proj_inverse = &ubo.view_proj_inverse;
                         ri.gb2 = g2; ri.gb3 = g3; ri.pgb2 = pg2; ri.pgb3 = pg3; ri.pdepth = pd; ri.w = w; ri.h = h;
                         bool success = reproject<false, true, true, 4>(ri, hc, &hm, nullptr, hcol, hmom, &hlen);
-                        hlen = fmin2(32.0f, success ? hlen + 1.0f : 1.0f);
+                        hlen = glsl_min(32.0f, success ? hlen + 1.0f : 1.0f);
                         vec3 history_color = v3(hcol[0], hcol[1], hcol[2]);
                         if (success)
                         {
@@ -200,23 +200,23 @@ void orc_reflections_temporal(const void* ubo_, int w, int h, const uint16_t* in
                             const float wgt = 289.0f;
                             vec3 mean = m1 / wgt;
                             vec3 var  = (m2 / wgt) - (mean * mean);
-                            vec3 sd   = v3(std::sqrt(fmax2(var.x, 0.0f)), std::sqrt(fmax2(var.y, 0.0f)), std::sqrt(fmax2(var.z, 0.0f)));
+                            vec3 sd   = v3(std::sqrt(glsl_max(var.x, 0.0f)), std::sqrt(glsl_max(var.y, 0.0f)), std::sqrt(glsl_max(var.z, 0.0f)));
                             vec3 amin = mean - sd, amax = mean + sd;
                             // clip_aabb
                             vec3 center = 0.5f * (amax + amin);
                             vec3 extent = 0.5f * (amax - amin) + v3(0.001f, 0.001f, 0.001f);
                             vec3 cv  = history_color - center;
                             vec3 cvc = v3(std::fabs(cv.x / extent.x), std::fabs(cv.y / extent.y), std::fabs(cv.z / extent.z));
-                            float mx = fmax2(fmax2(cvc.x, cvc.y), cvc.z);
+                            float mx = glsl_max(glsl_max(cvc.x, cvc.y), cvc.z);
                             if (mx > 1.0f) history_color = center + cv / mx;
                         }
                         const float max_acc = moving ? 8.0f : hlen;
-                        const float a  = success ? fmax2(alpha, 1.0f / max_acc) : 1.0f;
-                        const float am = success ? fmax2(moments_alpha, 1.0f / max_acc) : 1.0f;
+                        const float a  = success ? glsl_max(alpha, 1.0f / max_acc) : 1.0f;
+                        const float am = success ? glsl_max(moments_alpha, 1.0f / max_acc) : 1.0f;
                         float mo0 = luminance(color), mo1 = mo0 * mo0;
                         mo0 = mixf(hmom[0], mo0, am);
                         mo1 = mixf(hmom[1], mo1, am);
-                        const float variance = fmax2(0.0f, mo1 - mo0 * mo0);
+                        const float variance = glsl_max(0.0f, mo1 - mo0 * mo0);
                         vec3 acc = mix3(history_color, color, a);
                         omom[0] = mo0; omom[1] = mo1; omom[2] = hlen; omom[3] = 0.0f;
                         orad[0] = acc.x; orad[1] = acc.y; orad[2] = acc.z; orad[3] = variance;
@@ -263,7 +263,7 @@ void orc_reflections_atrous(int w, int h, const uint16_t* in_color, const float*
                     const float d = depth[(size_t)y * w + x], roughness = g3.fetch(x, y, 0);
                     if (d == 1.0f) { for (int c = 0; c < 4; c++) out.store(x, y, c, 0.0f); continue; }
                     if (roughness < 0.05f || (approximate_with_ddgi == 1 && roughness > 0.75f)) { for (int c = 0; c < 4; c++) out.store(x, y, c, cc[c]); continue; }
-                    const float phi_c = phi_color * std::sqrt(fmax2(0.0f, 1e-10f + var));
+                    const float phi_c = phi_color * std::sqrt(glsl_max(0.0f, 1e-10f + var));
                     float sum_w = 1.0f, sum[4] = { cc[0], cc[1], cc[2], cc[3] };
                     for (int yy = -radius; yy <= radius; yy++)
                         for (int xx = -radius; xx <= radius; xx++)
@@ -278,9 +278,9 @@ void orc_reflections_atrous(int w, int h, const uint16_t* in_color, const float*
                                 const vec3  sn = octohedral_to_direction(g2.fetch(px, py, 0), g2.fetch(px, py, 1));
                                 const float sdp = g3.fetch(px, py, 3);
                                 const float wZ = det_exp(-std::fabs(center_depth - sdp) / sigma_depth);
-                                const float wN = det_pow_auto(clampf(dot(cn, sn), 0.0f, 1.0f), phi_normal);
+                                const float wN = det_pow_auto(glsl_clamp(dot(cn, sn), 0.0f, 1.0f), phi_normal);
                                 const float wL = std::fabs(center_luma - sl) / phi_c;
-                                const float wgt = det_exp((0.0f - fmax2(wL, 0.0f)) - fmax2(wZ, 0.0f)) * wN;
+                                const float wgt = det_exp((0.0f - glsl_max(wL, 0.0f)) - glsl_max(wZ, 0.0f)) * wN;
                                 const float wc  = wgt * kernel;
                                 sum_w += wc;
                                 sum[0] += wc * sc[0]; sum[1] += wc * sc[1]; sum[2] += wc * sc[2];

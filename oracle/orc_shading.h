@@ -76,12 +76,12 @@ static inline float D_ggx(float ndoth, float alpha)
 {
     float a2 = alpha * alpha;
     float denom = (ndoth * ndoth) * (a2 - 1.0f) + 1.0f;
-    return a2 / fmax2(ORC_EPSILON, (ORC_M_PI * denom * denom));
+    return a2 / glsl_max(ORC_EPSILON, (ORC_M_PI * denom * denom));
 }
 static inline float G1_schlick_ggx(float roughness, float ndotv)
 {
     float k = ((roughness + 1.0f) * (roughness + 1.0f)) / 8.0f;
-    return ndotv / fmax2(ORC_EPSILON, (ndotv * (1.0f - k) + k));
+    return ndotv / glsl_max(ORC_EPSILON, (ndotv * (1.0f - k) + k));
 }
 static inline float G_schlick_ggx(float ndotl, float ndotv, float roughness) { return G1_schlick_ggx(roughness, ndotl) * G1_schlick_ggx(roughness, ndotv); }
 static inline vec3  F_schlick(vec3 f0, float vdoth)
@@ -93,11 +93,11 @@ static inline vec3 evaluate_specular_brdf(float roughness, vec3 F, float ndoth, 
 {
     float alpha = roughness * roughness;
     vec3  num   = (D_ggx(ndoth, alpha) * F) * G_schlick_ggx(ndotl, ndotv, roughness);
-    return num / fmax2(ORC_EPSILON, (4.0f * ndotl * ndotv));
+    return num / glsl_max(ORC_EPSILON, (4.0f * ndotl * ndotv));
 }
 static inline vec3 evaluate_uber_brdf(vec3 diffuse_color, float roughness, vec3 N, vec3 F0, vec3 Wo, vec3 Wh, vec3 Wi)
 {
-    float NdotL = fmax2(dot(N, Wi), 0.0f), NdotV = fmax2(dot(N, Wo), 0.0f), NdotH = fmax2(dot(N, Wh), 0.0f), VdotH = fmax2(dot(Wi, Wh), 0.0f);
+    float NdotL = glsl_max(dot(N, Wi), 0.0f), NdotV = glsl_max(dot(N, Wo), 0.0f), NdotH = glsl_max(dot(N, Wh), 0.0f), VdotH = glsl_max(dot(Wi, Wh), 0.0f);
     vec3  F        = F_schlick(F0, VdotH);
     vec3  specular = evaluate_specular_brdf(roughness, F, NdotH, NdotL, NdotV);
     vec3  diffuse  = diffuse_color / ORC_M_PI;
@@ -106,8 +106,8 @@ static inline vec3 evaluate_uber_brdf(vec3 diffuse_color, float roughness, vec3 
 static inline vec3 fresnel_schlick_roughness(float cos_theta, vec3 F0, float roughness)
 {
     float r1 = 1.0f - roughness;
-    vec3  m  = v3(fmax2(r1, F0.x), fmax2(r1, F0.y), fmax2(r1, F0.z));
-    float p  = det_powi(fmax2(1.0f - cos_theta, 0.0f), 5);
+    vec3  m  = v3(glsl_max(r1, F0.x), glsl_max(r1, F0.y), glsl_max(r1, F0.z));
+    float p  = det_powi(glsl_max(1.0f - cos_theta, 0.0f), 5);
     return F0 + (m - F0) * p;
 }
 vec3 sample_cosine_lobe(vec3 n, float rx, float ry); // orc_ao.cpp (brdf.glsl:20-32)
@@ -208,7 +208,7 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
     vec3 base_pos = grid_coord_to_position(d, bx, by, bz);
     vec3 sum_irr = v3(0, 0, 0);
     float sum_w = 0.0f;
-    vec3 alpha = v3(clampf((P.x - base_pos.x) / gs.x, 0.0f, 1.0f), clampf((P.y - base_pos.y) / gs.y, 0.0f, 1.0f), clampf((P.z - base_pos.z) / gs.z, 0.0f, 1.0f));
+    vec3 alpha = v3(glsl_clamp((P.x - base_pos.x) / gs.x, 0.0f, 1.0f), glsl_clamp((P.y - base_pos.y) / gs.y, 0.0f, 1.0f), glsl_clamp((P.z - base_pos.z) / gs.z, 0.0f, 1.0f));
     for (int i = 0; i < 8; ++i)
     {
         int ox = i & 1, oy = (i >> 1) & 1, oz = (i >> 2) & 1;
@@ -221,7 +221,7 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
         float weight = 1.0f;
         {
             vec3  tdp = normalize(probe_pos - P);
-            float t   = fmax2(0.0001f, (dot(tdp, N) + 1.0f) * 0.5f);
+            float t   = glsl_max(0.0001f, (dot(tdp, N) + 1.0f) * 0.5f);
             weight    = weight * (t * t + 0.2f);
         }
         if (d.visibility_test == 1)
@@ -231,12 +231,12 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
             vec3  temp = atlas_bilinear<2>(depth, d.depth_texture_width, d.depth_texture_height, tc.x, tc.y);
             float mean = temp.x;
             float variance = std::fabs(temp.x * temp.x - temp.y);
-            float dm  = fmax2(dist - mean, 0.0f);
+            float dm  = glsl_max(dist - mean, 0.0f);
             float che = variance / (variance + dm * dm);
-            che       = fmax2(che * che * che, 0.0f);
+            che       = glsl_max(che * che * che, 0.0f);
             weight    = weight * ((dist <= mean) ? 1.0f : che);
         }
-        weight = fmax2(0.000001f, weight);
+        weight = glsl_max(0.000001f, weight);
         vec2 tc = texture_coord_from_direction(normalize(N), p, d.irradiance_texture_width, d.irradiance_texture_height, d.irradiance_probe_side_length);
         vec3 probe_irr = atlas_bilinear<4>(irradiance, d.irradiance_texture_width, d.irradiance_texture_height, tc.x, tc.y);
         const float crush = 0.2f;
@@ -328,7 +328,7 @@ static inline SurfaceHit surface_at(const Scene& s, const Hit& h)
     if (!s.materials.empty())
     {
         const float* m = &s.materials[(size_t)mat * 8];
-        o.albedo = v3(m[0], m[1], m[2]); o.metallic = m[3]; o.roughness = fmax2(m[4], 0.1f);
+        o.albedo = v3(m[0], m[1], m[2]); o.metallic = m[3]; o.roughness = glsl_max(m[4], 0.1f);
     }
     else { o.albedo = v3(0.8f, 0.8f, 0.8f); o.metallic = 0.0f; o.roughness = 0.5f; }
     if (!s.mat_tex.empty())
@@ -343,7 +343,7 @@ static inline SurfaceHit surface_at(const Scene& s, const Hit& h)
             tv = (qu[1] * b0 + qu[3] * b1) + qu[5] * b2;
         }
         if (mt[0] >= 0) { vec4 c = sample_texture(s.textures[mt[0]], tu, tv); o.albedo = v3(c.x, c.y, c.z); }
-        if (mt[2] >= 0) o.roughness = fmax2(comp4(sample_texture(s.textures[mt[2]], tu, tv), mt[4]), 0.1f);
+        if (mt[2] >= 0) o.roughness = glsl_max(comp4(sample_texture(s.textures[mt[2]], tu, tv), mt[4]), 0.1f);
         if (mt[3] >= 0) o.metallic = comp4(sample_texture(s.textures[mt[3]], tu, tv), mt[5]);
         if (mt[1] >= 0)
         {
@@ -385,7 +385,7 @@ static inline void fetch_light_hard(const Light& L, vec3 Wo, vec3 P, vec3 N, vec
         }
     }
     *Wh          = normalize(Wo + *Wi);
-    *attenuation = *attenuation * clampf(dot(N, *Wi), 0.0f, 1.0f);
+    *attenuation = *attenuation * glsl_clamp(dot(N, *Wi), 0.0f, 1.0f);
 }
 
 // direct_lighting (lighting.glsl:117-196): RAY_TRACING always; T = throughput; sky = SAMPLE_SKY_LIGHT

@@ -54,7 +54,7 @@ void fetch_light_properties_shadow(const Light& light, vec3 P, vec3 N, float rx,
         float light_distance    = *t_max;
         *attenuation            = angle_attenuation / (light_distance * light_distance);
     }
-    *attenuation = *attenuation * clampf(dot(N, *Wi), 0.0f, 1.0f);
+    *attenuation = *attenuation * glsl_clamp(dot(N, *Wi), 0.0f, 1.0f);
 }
 
 } // namespace orc

@@ -18,8 +18,8 @@ inline V4 add(V4 a, V4 b) { return V4 { a.x + b.x, a.y + b.y, a.z + b.z, a.w + b
 inline V4 sub(V4 a, V4 b) { return V4 { a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w }; }
 inline V4 scale(V4 a, float s) { return V4 { a.x * s, a.y * s, a.z * s, a.w * s }; }
 inline V4 divs(V4 a, float s) { return V4 { a.x / s, a.y / s, a.z / s, a.w / s }; }
-inline V4 vmin(V4 a, V4 b) { return V4 { fmin2(a.x, b.x), fmin2(a.y, b.y), fmin2(a.z, b.z), fmin2(a.w, b.w) }; }
-inline V4 vmax(V4 a, V4 b) { return V4 { fmax2(a.x, b.x), fmax2(a.y, b.y), fmax2(a.z, b.z), fmax2(a.w, b.w) }; }
+inline V4 vmin(V4 a, V4 b) { return V4 { glsl_min(a.x, b.x), glsl_min(a.y, b.y), glsl_min(a.z, b.z), glsl_min(a.w, b.w) }; }
+inline V4 vmax(V4 a, V4 b) { return V4 { glsl_max(a.x, b.x), glsl_max(a.y, b.y), glsl_max(a.z, b.z), glsl_max(a.w, b.w) }; }
 
 struct Tex4 // RGBA16F
 {
@@ -56,7 +56,7 @@ struct Tex1 // R32F
     }
 };
 
-inline float lum(V4 c) { return fmax2((c.x * 0.299f + c.y * 0.587f) + c.z * 0.114f, 0.0001f); } // common.glsl:141-144
+inline float lum(V4 c) { return glsl_max((c.x * 0.299f + c.y * 0.587f) + c.z * 0.114f, 0.0001f); } // common.glsl:141-144
 
 // taa.comp:123-151, the non-optimised variant
 inline V4 clip_aabb(V4 aabb_min, V4 aabb_max, V4 p, V4 q)
@@ -151,7 +151,7 @@ void orc_taa_resolve(int w, int h, const uint16_t* color, const uint16_t* prev, 
             cavg = scale(add(cavg, cavg5), 0.5f);
             texel1 = clip_aabb(cmin, cmax, vmin(vmax(cavg, cmin), cmax), texel1);
             const float lum0 = lum(texel0), lum1 = lum(texel1);
-            const float unbiased_diff = std::fabs(lum0 - lum1) / fmax2(lum0, fmax2(lum1, 0.2f));
+            const float unbiased_diff = std::fabs(lum0 - lum1) / glsl_max(lum0, glsl_max(lum1, 0.2f));
             const float uw = 1.0f - unbiased_diff, uw2 = uw * uw;
             const float k_feedback = mixf(feedback_min, feedback_max, uw2);
             if (sharpen == 1)
@@ -170,8 +170,8 @@ void orc_taa_resolve(int w, int h, const uint16_t* color, const uint16_t* prev, 
             for (int c = 0; c < 3; c++)
             {
                 float b = mixf(t0[c], t1[c], k_feedback);
-                b = b / fmax2(1.0f - b, 0.00000001f);
-                o[c] = f32_to_f16(clampf(b, 0.0f, 1.0f));
+                b = b / glsl_max(1.0f - b, 0.00000001f);
+                o[c] = f32_to_f16(glsl_clamp(b, 0.0f, 1.0f));
             }
             o[3] = f32_to_f16(1.0f);
         }
@@ -195,7 +195,7 @@ void orc_tone_map(int w, int h, const uint16_t* color, int single_channel, float
                 for (int k = 0; k < 3; k++)
                 {
                     const float v = in[k];
-                    const float aces = clampf((v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f), 0.0f, 1.0f);
+                    const float aces = glsl_clamp((v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f), 0.0f, 1.0f);
                     rgb[k] = det_pow_auto(aces, 1.0f / 2.2f);
                 }
             }

@@ -144,3 +144,27 @@ def fuzz_config(seed: int, trial: int, hard: bool = False):
     for c in fuzz_configs(seed, trial + 1, hard):
         pass
     return c
+
+
+def _is_nan_bits(b):
+    """NaN test on fp16 (uint16) or fp32 (uint32) bit patterns: exponent all ones and a non-zero mantissa, whatever the sign."""
+    if b.dtype == np.uint16:
+        return ((b & 0x7c00) == 0x7c00) & ((b & 0x03ff) != 0)
+    return ((b & 0x7f800000) == 0x7f800000) & ((b & 0x007fffff) != 0)
+
+
+def assert_bits_equal_nan(got, ref, what):
+    """got / ref: uint16 (fp16) or uint32 (fp32) bit patterns.  Bit-identical, except that two NaNs count as equal whatever their sign and
+    payload (GLSL and HIP leave a NaN's payload unspecified).  +0 / -0, +-inf and every finite value must match bit for bit."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.dtype == ref.dtype and got.dtype in (np.uint16, np.uint32), (what, got.dtype, ref.dtype)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    both_nan = _is_nan_bits(got) & _is_nan_bits(ref)
+    bad = (got != ref) & ~both_nan
+    if bad.any():
+        fl = np.float16 if got.dtype == np.uint16 else np.float32
+        w = np.argwhere(bad)[:8]
+        idx = tuple(w.T)
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} values differ (NaN == NaN); first (index): {w.tolist()} "
+                             f"got {got[idx].view(fl).tolist()} ({[hex(int(v)) for v in got[idx]]}) "
+                             f"ref {ref[idx].view(fl).tolist()} ({[hex(int(v)) for v in ref[idx]]})")

@@ -1,0 +1,358 @@
+"""GPU stage tests at the HDR edge: the HIP passes against the oracle on the crafted non-finite inputs of tests/nonfinite_cases.py (the oracle
+is pinned to the reference's shaders on the same inputs by tests/test_ref_shaders_nonfinite.py).  The inputs are injected through the
+passes' writable views: the DDGI ray images after ray_trace(), the atlases the probe update reads (current_read) and the ones
+sample_probe_grid() and the reflections read.  Exact mode (params.exact = 1) is bit-identical with NaN == NaN (helpers.assert_bits_equal_nan);
+in tolerance mode the DDGI atlases stay bit-exact (the contract) and the sampled image answers to the non-finite clause of the image rule
+(docs/TOLERANCE.md, test_gpu_tolerance.compare16(nonfinite=True))."""
+import numpy as np
+import pytest
+
+import helpers
+import nonfinite_cases as nc
+from hybrid_rendering_amd import synth, synth_env
+
+pytestmark = pytest.mark.gpu
+
+
+def _put(view, bits):
+    """copy fp16 bit patterns into a pass-owned image view (same element count, contiguous)"""
+    import torch
+    src = torch.from_numpy(np.ascontiguousarray(bits)).view(torch.float16).reshape(view.shape).cuda()
+    view.copy_(src)
+
+
+@pytest.mark.parametrize("exact", [1, 0])
+def test_ddgi_probe_update_and_sample_on_hdr_inputs(oracle, hr, ctx, exact):
+    """k_ddgi_probe_update on +inf / 65504 / NaN radiance rays and inf / NaN / miss distances (first frame), then on inf / NaN texels of the
+    previous atlases (hysteresis); k_ddgi_sample / the fast gather on atlases with inf and NaN irradiance and overflowed depth moments"""
+    import torch
+    import test_gpu_tolerance as T
+    from hybrid_rendering_amd import api_gi
+    from oracle import pyoracle_ddgi as od
+    name, w, h = "sponza_small", 64, 48
+    sd = helpers.scene_data(name)
+    osc, gsc = oracle.Scene(sd), hr.Scene(ctx, sd)
+    lo, hi = sd.bounds()
+    ddgi = synth_env.ddgi_uniforms(lo, hi, probe_counts=(3, 2, 2), rays_per_probe=48, normal_bias=0.1)
+    sky = synth_env.sky_cubemap(8)
+    env = api_gi.environment(torch.from_numpy(sky).cuda().view(torch.float16))
+    frames = helpers.make_frames(oracle, osc, name, w, h, 2, 1.0)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    gp = api_gi.DDGI(ctx, w, h, ddgi)
+    gp.params.exact = exact
+    rad, dd = nc.probe_rays(ddgi)
+    pirr, pdep = nc.prev_atlases(ddgi)
+    rng = np.random.RandomState(3)
+    try:
+        for f in range(2):
+            fr = frames[f]
+            fi = hr.frame_inputs(helpers.to_cuda(fr["gb"]), None, fr["ubo"], f, f & 1, sob_d, sr_d)
+            gp.set_orientation(synth_env.random_orientation(rng))
+            gp.ray_trace(gsc, fi, env)
+            _put(gp.image(gp.IMG_RADIANCE), rad)
+            _put(gp.image(gp.IMG_DIRDIST), dd)
+            if f:
+                ci, cd = gp.current_read()
+                _put(ci, pirr)
+                _put(cd, pdep)
+            gp.probe_update()
+            torch.cuda.synchronize()
+            first = f == 0
+            oi = od.border_update(ddgi, False, od.probe_update(ddgi, False, first, rad, dd, pirr))
+            odp = od.border_update(ddgi, True, od.probe_update(ddgi, True, first, rad, dd, pdep))
+            wi, wd = gp.current_write()
+            # the atlases are bit-exact in both modes (the probe update has one kernel)
+            helpers.assert_bits_equal_nan(helpers.bits16(wi), oi, f"frame {f}: irradiance atlas")
+            helpers.assert_bits_equal_nan(helpers.bits16(wd), odp, f"frame {f}: depth atlas")
+            n_nan, n_inf = int(np.isnan(nc.f16(oi)).sum()), int(np.isinf(nc.f16(oi)).sum())
+            assert n_nan > 0 and n_inf > 0 and np.isfinite(nc.f16(oi)).mean() > 0.9, (n_nan, n_inf)
+            # the probe-grid sample on poisoned atlases
+            sirr, sdep = nc.poison_atlases(ddgi, oi, odp)
+            _put(wi, sirr)
+            _put(wd, sdep)
+            gp.sample_probe_grid(fi)
+            torch.cuda.synchronize()
+            ref = od.sample_probe_grid(fr["ubo"], ddgi, fr["gb"]["depth"], fr["gb"]["gb2"], gp.params.gi_intensity, sirr, sdep)
+            got = helpers.bits16(gp.output())
+            rv = nc.f16(ref[..., :3])
+            assert (~np.isfinite(rv)).any() and np.isfinite(rv).any()
+            if exact:
+                helpers.assert_bits_equal_nan(got, ref, f"frame {f}: sampled irradiance")
+            else:
+                T.compare16(got, ref, f"frame {f}: sampled irradiance (tolerance mode)", nonfinite=True)
+            gp.end_frame()
+    finally:
+        gp.close()
+        gsc.close()
+
+
+@pytest.mark.parametrize("approx", [1, 0])
+def test_reflections_on_inf_irradiance_and_metallic_hits(oracle, hr, ctx, approx):
+    """the reflections' trace kernel on metallic = 1 hits (kD = 0) with +inf irradiance probes: the hit's indirect term is 0 * inf = NaN and
+    the stored min(color, 0.7) keeps it (GLSL formula order); then the temporal and a-trous stages carry the NaN texels — exact mode,
+    every stage image against the oracle"""
+    import torch
+    from hybrid_rendering_amd import api_gi, api_reflections
+    from oracle import pyoracle_reflections as orf
+    W, H = 48, 32
+    sd = nc.metallic_scene(helpers.scene_data("sponza_small"))
+    osc, gsc = oracle.Scene(sd), hr.Scene(ctx, sd)
+    lo, hi = sd.bounds()
+    ddgi = synth_env.ddgi_uniforms(lo, hi, probe_counts=(3, 2, 3), rays_per_probe=32, normal_bias=0.1)
+    sky = synth_env.sky_cubemap(8)
+    pre, lut = synth_env.prefiltered_chain(sky, 4), synth_env.brdf_lut(8)
+    env_np = dict(sky=sky, prefiltered=pre, pre_size=8, pre_levels=4, lut=lut)
+    f16 = lambda a: torch.from_numpy(a).cuda().view(torch.float16)
+    env = api_gi.environment(f16(sky), f16(pre), 8, 4, f16(lut))
+    frames = helpers.make_frames(oracle, osc, "sponza_small", W, H, 1, 1.0)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    g_ddgi = api_gi.DDGI(ctx, W, H, ddgi)
+    gp = api_reflections.RayTracedReflections(ctx, W, H, 0)
+    gp.params.approximate_with_ddgi = approx
+    gp.params.exact = 1
+    op = orf.ReflectionsPass(W, H, approximate_with_ddgi=bool(approx))
+    try:
+        fr = frames[0]
+        cur = fr["gb"]
+        fi = hr.frame_inputs(helpers.to_cuda(cur), helpers.to_cuda(cur), fr["ubo"], 0, False, sob_d, sr_d, cur_full=helpers.to_cuda(cur))
+        g_ddgi.render(gsc, fi, env, synth_env.random_orientation(np.random.RandomState(1)))
+        irr, dep = nc.inf_atlases(ddgi)
+        ci, cd = g_ddgi.current_read()
+        _put(ci, irr)
+        _put(cd, dep)
+        torch.cuda.synchronize()
+        op.render(osc, fr["ubo"], ddgi, cur, cur, sob, sr, 0, env_np, irr, dep, camera_delta=(0.0, 0.0, 0.0), ping_pong=False)
+        gp.set_camera_delta((0.0, 0.0, 0.0))
+        gp.render(gsc, fi, env, g_ddgi)
+        torch.cuda.synchronize()
+        st = op.stages
+        tv = nc.f16(st["trace"][..., :3])
+        assert np.isnan(tv).any() and np.isfinite(tv).any(), "the oracle's trace image must hold NaN hit colours"
+        helpers.assert_bits_equal_nan(helpers.bits16(gp.image(gp.IMG_TRACE)), st["trace"], "trace image")
+        helpers.assert_bits_equal_nan(helpers.bits16(gp.image(gp.IMG_COLOR0)), st["temporal"], "temporal colour")
+        helpers.assert_bits_equal_nan(helpers.bits16(gp.image(gp.IMG_MOMENTS0)), st["moments"], "moments")
+        helpers.assert_bits_equal_nan(helpers.bits16(gp.output(hr.OUTPUT_ATROUS)), st["atrous"][-1], "a-trous output")
+    finally:
+        gp.close()
+        g_ddgi.close()
+        gsc.close()
+
+
+def _check(got, ref, what, exact, **rule):
+    import test_gpu_tolerance as T
+    if exact:
+        helpers.assert_bits_equal_nan(got, ref, what)
+    else:
+        T.compare16(got, ref, what + " (tolerance mode)", nonfinite=True, **rule)
+
+
+@pytest.mark.parametrize("exact,stages", [(1, "all"), (0, "trace_temporal"),
+                                          pytest.param(0, "atrous", marks=pytest.mark.xfail(strict=True, reason=
+                                              "known: the tolerance-mode a-trous kernels (denoise_fast.hip) take max(variance, 0) with the IEEE "
+                                              "v_max, which drops a NaN variance that the reference keeps (841 texels of channel 3); open"))])
+def test_reflections_tolerance_mode_on_nan_hits(oracle, hr, ctx, exact, stages):
+    """the reflections pass in both modes on the NaN hit colours of test_reflections_on_inf_irradiance_and_metallic_hits: the trace image
+    is bit-exact in both (the contract), the denoised images answer to the non-finite clause of the image rule in tolerance mode"""
+    import torch
+    import test_gpu_tolerance as T
+    from hybrid_rendering_amd import api_gi, api_reflections
+    from oracle import pyoracle_reflections as orf
+    W, H = 48, 32
+    sd = nc.metallic_scene(helpers.scene_data("sponza_small"))
+    osc, gsc = oracle.Scene(sd), hr.Scene(ctx, sd)
+    lo, hi = sd.bounds()
+    ddgi = synth_env.ddgi_uniforms(lo, hi, probe_counts=(3, 2, 3), rays_per_probe=32, normal_bias=0.1)
+    sky = synth_env.sky_cubemap(8)
+    pre, lut = synth_env.prefiltered_chain(sky, 4), synth_env.brdf_lut(8)
+    env_np = dict(sky=sky, prefiltered=pre, pre_size=8, pre_levels=4, lut=lut)
+    f16 = lambda a: torch.from_numpy(a).cuda().view(torch.float16)
+    env = api_gi.environment(f16(sky), f16(pre), 8, 4, f16(lut))
+    frames = helpers.make_frames(oracle, osc, "sponza_small", W, H, 1, 1.0)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    g_ddgi = api_gi.DDGI(ctx, W, H, ddgi)
+    gp = api_reflections.RayTracedReflections(ctx, W, H, 0)
+    gp.params.exact = exact
+    op = orf.ReflectionsPass(W, H)
+    try:
+        fr = frames[0]
+        cur = fr["gb"]
+        fi = hr.frame_inputs(helpers.to_cuda(cur), helpers.to_cuda(cur), fr["ubo"], 0, False, sob_d, sr_d, cur_full=helpers.to_cuda(cur))
+        g_ddgi.render(gsc, fi, env, synth_env.random_orientation(np.random.RandomState(1)))
+        irr, dep = nc.inf_atlases(ddgi)
+        ci, cd = g_ddgi.current_read()
+        _put(ci, irr)
+        _put(cd, dep)
+        torch.cuda.synchronize()
+        op.render(osc, fr["ubo"], ddgi, cur, cur, sob, sr, 0, env_np, irr, dep, camera_delta=(0.0, 0.0, 0.0), ping_pong=False)
+        gp.set_camera_delta((0.0, 0.0, 0.0))
+        gp.render(gsc, fi, env, g_ddgi)
+        torch.cuda.synchronize()
+        st = op.stages
+        assert np.isnan(nc.f16(st["trace"][..., :3])).any() and np.isnan(nc.f16(st["atrous"][-1][..., :3])).any()
+        helpers.assert_bits_equal_nan(helpers.bits16(gp.image(gp.IMG_TRACE)), st["trace"], "trace image")
+        if stages != "atrous":
+            _check(helpers.bits16(gp.image(gp.IMG_COLOR0)), st["temporal"], "temporal colour", exact, variance_channels=(3,), outlier_pixels=T.REFL_OUTLIERS)
+            _check(helpers.bits16(gp.image(gp.IMG_MOMENTS0)), st["moments"], "moments", exact, variance_channels=(1,), outlier_pixels=T.REFL_OUTLIERS)
+        if stages != "trace_temporal":
+            _check(helpers.bits16(gp.output(hr.OUTPUT_ATROUS)), st["atrous"][-1], "a-trous output", exact, variance_channels=(3,), outlier_pixels=T.REFL_OUTLIERS)
+    finally:
+        gp.close()
+        g_ddgi.close()
+        gsc.close()
+
+
+def test_deferred_taa_and_tone_map_on_hdr_inputs(oracle, hr, ctx):
+    """the deferred composite with NaN / inf / >= 1e4 GI and reflections images, TAA over two frames of HDR colour with NaN, and the tone
+    map (fp32 and RGBA8: a NaN channel stores 0, as a UNORM8 conversion does) against the oracle.  These passes have one arithmetic mode."""
+    import torch
+    from hybrid_rendering_amd import api_deferred, api_gi, api_post
+    from oracle import pyoracle_deferred as odf, pyoracle_post as opost
+    W, H = 48, 32
+    sd = helpers.scene_data("sponza_small")
+    osc = oracle.Scene(sd)
+    frames = helpers.make_frames(oracle, osc, "sponza_small", W, H, 2, 0.5, "point")
+    sky = synth_env.sky_cubemap(16)
+    pre, lut, sh9 = synth_env.prefiltered_chain(sky, 5), synth_env.brdf_lut(16), synth_env.sh9_from_cubemap(sky)
+    env_np = dict(sky=sky, prefiltered=pre, pre_size=16, pre_levels=5, lut=lut)
+    f16 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda().view(torch.float16)
+    env = api_gi.environment(f16(sky), f16(pre), 16, 5, f16(lut))
+    sob, sr = synth.blue_noise_tables()
+    gi, refl = nc.hdr_colour(H, W, seed=10), nc.hdr_colour(H, W, seed=12)
+    g = api_deferred.DeferredShading(ctx, W, H)
+    g.set_sh9(sh9)
+    t = api_post.TemporalAA(ctx, W, H)
+    o = opost.TAAPass(W, H)
+    try:
+        fr = frames[0]
+        fi = hr.frame_inputs(helpers.to_cuda(fr["gb"]), None, fr["ubo"], 0, 0, torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda())
+        for flags in (12, 8, 4):
+            g.params.use_ray_traced_shadows = g.params.use_ray_traced_ao = 0
+            g.params.use_ray_traced_reflections, g.params.use_ddgi = (flags >> 2) & 1, (flags >> 3) & 1
+            g.render(fi, env, reflections=f16(refl), gi=f16(gi))
+            torch.cuda.synchronize()
+            ref = odf.shade(fr["ubo"], fr["gb"], None, None, refl, gi, flags, sh9, env_np)
+            helpers.assert_bits_equal_nan(helpers.bits16(g.output()), ref, f"deferred flags {flags}")
+            rv = nc.f16(ref[..., :3])
+            assert (~np.isfinite(rv)).any() and np.isfinite(rv).mean() > 0.9, flags
+        for k in range(2):
+            col = nc.hdr_colour(H, W, seed=8 + k)
+            o.reset = (k == 0)
+            t.params.reset = int(k == 0)
+            assert np.array_equal(o.update(k).view(np.uint32), t.update(k).view(np.uint32))
+            o.render(col, frames[k]["gb"], k & 1)
+            t.render(f16(col.view(np.float16)), helpers.to_cuda(frames[k]["gb"]), k & 1)
+            torch.cuda.synchronize()
+            helpers.assert_bits_equal_nan(helpers.bits16(t.output(k & 1)), o.output(k & 1), f"TAA frame {k}")
+        taa = o.output(1)
+        assert np.isnan(nc.f16(taa)).any() and (nc.f16(taa) == 1.0).any()
+        for img in (taa, nc.hdr_colour(H, W, seed=9)):
+            for single, exposure in ((False, 1.0), (True, 1.0), (False, 0.37)):
+                ref = opost.tone_map(img, single, exposure)
+                fo, bo = api_post.tone_map(ctx, f16(img.view(np.float16)), single, exposure)
+                torch.cuda.synchronize()
+                helpers.assert_bits_equal_nan(fo.cpu().numpy().view(np.uint32), ref.view(np.uint32), f"tone map single={single} exposure={exposure}")
+                with np.errstate(invalid="ignore"):
+                    q = np.floor(np.clip(np.nan_to_num(ref, nan=0.0), 0.0, 1.0) * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
+                assert np.array_equal(bo.cpu().numpy(), q), f"tone map RGBA8 single={single} exposure={exposure}"
+        assert np.isnan(opost.tone_map(taa, True, 1.0)).any()     # the RGBA8 check above met NaN channels
+    finally:
+        g.close()
+        t.close()
+
+
+@pytest.mark.parametrize("approx", [1, 0])
+def test_hdr_sequence_end_to_end(oracle, hr, ctx, approx):
+    """Four frames of sponza_small with infinite bounces on, a point light of intensity 1e11 a few units above the floor, an HDR sky with
+    +inf and 60000 texels and metallic = 1 materials, through DDGI -> reflections -> deferred composite -> TAA -> tone map, exact mode.
+    Some probe rays' radiance overflows to +inf and others land in [6e4, 65504]; the atlases' inf then feeds the next frame's rays
+    (0 * inf = NaN on the metallic hits), so NaN and inf run through every stage.  Every stage image against the oracle's."""
+    import torch
+    from hybrid_rendering_amd import api_deferred, api_gi, api_post, api_reflections
+    from oracle import pyoracle_ddgi as od, pyoracle_deferred as odf, pyoracle_post as opost, pyoracle_reflections as orf
+    W, H, n = 64, 48, 4
+    sd = nc.hdr_sequence_scene(helpers.scene_data("sponza_small"))
+    osc, gsc = oracle.Scene(sd), hr.Scene(ctx, sd)
+    light = nc.hdr_point_light(1.0e11)
+    cams = helpers.cameras("sponza_small", W / H, n, 0.5)
+    lo, hi = sd.bounds()
+    ddgi = synth_env.ddgi_uniforms(lo, hi, probe_counts=(4, 3, 3), rays_per_probe=32, normal_bias=0.1)
+    sky = nc.hdr_sky(8)
+    fin_sky = synth_env.sky_cubemap(8)
+    pre, lut, sh9 = synth_env.prefiltered_chain(fin_sky, 4), synth_env.brdf_lut(8), synth_env.sh9_from_cubemap(fin_sky)
+    env_np = dict(sky=sky, prefiltered=pre, pre_size=8, pre_levels=4, lut=lut)
+    f16 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda().view(torch.float16)
+    env = api_gi.environment(f16(sky), f16(pre), 8, 4, f16(lut))
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    g_gi, g_rf = api_gi.DDGI(ctx, W, H, ddgi), api_reflections.RayTracedReflections(ctx, W, H, 0)
+    g_df, g_taa = api_deferred.DeferredShading(ctx, W, H), api_post.TemporalAA(ctx, W, H)
+    g_df.set_sh9(sh9)
+    g_df.params.use_ray_traced_shadows = g_df.params.use_ray_traced_ao = 0
+    g_df.params.use_ray_traced_reflections = g_df.params.use_ddgi = 1
+    g_gi.params.exact = g_rf.params.exact = 1
+    g_rf.params.approximate_with_ddgi = approx
+    o_gi, o_rf, o_taa = od.DDGIPass(ddgi), orf.ReflectionsPass(W, H, approximate_with_ddgi=bool(approx)), opost.TAAPass(W, H)
+    assert g_gi.params.infinite_bounces and o_gi.p["infinite_bounces"]
+    rng = np.random.RandomState(3)
+    seen = dict(rad_inf=False, rad_nan=False, rad_near_max=False, irr_nan=False, refl_nan=False, shade_nonfinite=False, taa_nan=False)
+    ping = False
+    try:
+        prev_gb = None
+        for f in range(n):
+            ubo = synth.make_ubo(cams[f], cams[f - 1] if f else None, light)
+            gb = osc.gbuffer(ubo, W, H)
+            pgb = prev_gb if prev_gb is not None else gb
+            orient = synth_env.random_orientation(rng)
+            cd = (0.0, 0.0, 0.0) if f == 0 else (-0.5, 0.0, 0.0)
+            # ---- oracle
+            o_gi.render(osc, ubo, gb, sky, orient, f)
+            irr, dep = o_gi.current_read()
+            o_rf.render(osc, ubo, ddgi, gb, pgb, sob, sr, f, env_np, irr, dep, camera_delta=cd, ping_pong=ping)
+            shade = odf.shade(ubo, gb, None, None, o_rf.stages["output"], o_gi.stages["output"], 12, sh9, env_np)
+            o_taa.reset = (f == 0)
+            o_taa.update(f)
+            o_taa.render(shade, gb, f & 1)
+            tm = opost.tone_map(o_taa.output(f & 1))
+            # ---- GPU
+            gb_d, pgb_d = helpers.to_cuda(gb), helpers.to_cuda(pgb)
+            fi = hr.frame_inputs(gb_d, pgb_d, ubo, f, ping, sob_d, sr_d, cur_full=gb_d)
+            g_gi.render(gsc, fi, env, orient)
+            g_rf.set_camera_delta(cd)
+            g_rf.render(gsc, fi, env, g_gi)
+            g_df.render(fi, env, reflections=g_rf.output(hr.OUTPUT_UPSAMPLE), gi=g_gi.output())
+            g_taa.params.reset = int(f == 0)
+            g_taa.update(f)
+            g_taa.render(g_df.output(), gb_d, f & 1)
+            tf, tb = api_post.tone_map(ctx, g_taa.output(f & 1))
+            torch.cuda.synchronize()
+            st, rs = o_gi.stages, o_rf.stages
+            eq = helpers.assert_bits_equal_nan
+            eq(helpers.bits16(g_gi.image(g_gi.IMG_RADIANCE)).reshape(st["radiance"].shape), st["radiance"], f"frame {f}: DDGI radiance")
+            eq(helpers.bits16(g_gi.image(g_gi.IMG_DIRDIST)).reshape(st["direction_distance"].shape), st["direction_distance"], f"frame {f}: DDGI direction / distance")
+            ci, cdp = g_gi.current_read()
+            eq(helpers.bits16(ci), st["irradiance"], f"frame {f}: irradiance atlas")
+            eq(helpers.bits16(cdp), st["depth"], f"frame {f}: depth atlas")
+            eq(helpers.bits16(g_gi.output()), st["output"], f"frame {f}: DDGI sample")
+            eq(helpers.bits16(g_rf.image(g_rf.IMG_TRACE)), rs["trace"], f"frame {f}: reflections trace")
+            eq(helpers.bits16(g_rf.image(g_rf.IMG_COLOR1 if ping else g_rf.IMG_COLOR0)), rs["temporal"], f"frame {f}: reflections temporal")
+            eq(helpers.bits16(g_rf.image(g_rf.IMG_MOMENTS1 if ping else g_rf.IMG_MOMENTS0)), rs["moments"], f"frame {f}: reflections moments")
+            eq(helpers.bits16(g_rf.output(hr.OUTPUT_UPSAMPLE)), rs["output"], f"frame {f}: reflections output")
+            eq(helpers.bits16(g_df.output()), shade, f"frame {f}: deferred composite")
+            eq(helpers.bits16(g_taa.output(f & 1)), o_taa.output(f & 1), f"frame {f}: TAA")
+            eq(tf.cpu().numpy().view(np.uint32), tm.view(np.uint32), f"frame {f}: tone map")
+            r = nc.f16(st["radiance"][..., :3])
+            seen["rad_inf"] |= bool(np.isinf(r).any())
+            seen["rad_nan"] |= bool(np.isnan(r).any())
+            seen["rad_near_max"] |= bool(((r >= 6.0e4) & np.isfinite(r)).any())
+            seen["irr_nan"] |= bool(np.isnan(nc.f16(st["irradiance"])).any())
+            seen["refl_nan"] |= bool(np.isnan(nc.f16(rs["output"][..., :3])).any())
+            seen["shade_nonfinite"] |= bool((~np.isfinite(nc.f16(shade[..., :3]))).any())
+            seen["taa_nan"] |= bool(np.isnan(nc.f16(o_taa.output(f & 1))).any())
+            prev_gb = gb
+            ping = not ping
+        assert all(seen.values()), seen     # not vacuous: the oracle's images really hold inf, NaN and near-max values
+    finally:
+        g_gi.close(); g_rf.close(); g_df.close(); g_taa.close(); gsc.close()

@@ -60,30 +60,48 @@ OUTLIER_ABS = 2.0 ** -5
 
 
 def compare16(got, ref, what, rel_l2=1e-3, ulps=2, frac=0.999, abs_floor=OUTPUT_FLOOR, exclude=None, variance_channels=(), variance_floor=VARIANCE_FLOOR,
-              cap_ulps=None, cap_abs=None, outlier_pixels=None, outlier_scale=1):
+              cap_ulps=None, cap_abs=None, outlier_pixels=None, outlier_scale=1, nonfinite=False):
     """got / ref: uint16 fp16 bit patterns, ALL channels of the image.  abs_floor: differences below it count as equal (OUTPUT_FLOOR for every image;
     INTERMEDIATE_FLOOR for intermediate images whose small values are differences of nearly equal numbers, e.g. variance = m2 - m1^2).  exclude: bool [H, W] of texels
     left out of the per-texel bound (neighbourhoods of tiles whose classification differs — a discrete decision; they stay in the L2
     bound).  variance_channels: channels that carry a variance estimate (shadows .y, reflections .a): they descend from
     `m2 - m1^2` / `E[x^2] - E[x]^2`, a difference of nearly equal numbers, so their rule is "2 fp16 ulp OR |diff| <= variance_floor"
     — the quantity the next a-trous iteration reads them for is phi * sqrt(variance) (shadows_denoise_atrous.comp:65-88), on which
-    a 1e-4 absolute slip is far below the 2-ulp bound of the filtered channel; the L2 bounds cover them like every other channel."""
+    a 1e-4 absolute slip is far below the 2-ulp bound of the filtered channel; the L2 bounds cover them like every other channel.
+    nonfinite (opt-in, docs/TOLERANCE.md "Non-finite images"): the NaN texel sets must be identical; +-inf is ordered by _key like every
+    other value (65504 vs +inf is 1 ulp, 60000 vs +inf far beyond the cap); absolute differences, the hard cap's absolute arm and the L2
+    bounds are taken over the texels finite in both images.  Without it every texel must be finite."""
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
     outlier_pixels = OUTLIER_PIXELS if outlier_pixels is None else outlier_pixels
     g, r = got.view(np.float16).astype(np.float64), ref.view(np.float16).astype(np.float64)
-    assert np.isfinite(g).all(), f"{what}: non-finite values"
+    gv, rv = g, r      # the values as stored, for the messages
+    if nonfinite:
+        gn, rn = np.isnan(g), np.isnan(r)
+        if not np.array_equal(gn, rn):
+            w = np.argwhere(gn != rn)
+            raise AssertionError(f"{what}: NaN texel sets differ in {len(w)} texels; first (y, x, ...): {w[:6].tolist()} "
+                                 f"got {g[tuple(w[:6].T)].tolist()} ref {r[tuple(w[:6].T)].tolist()}")
+        both = np.isfinite(g) & np.isfinite(r)
+        # the ordered keys of NaN texels are meaningless: both NaN counts as equal (0 ulp); the float values of texels that are not
+        # finite in both images leave the absolute and L2 terms (their ulp distance through _key still binds: inf vs 60000 fails the cap)
+        got = np.where(gn, ref, got).astype(got.dtype)
+        g, r = np.where(both, g, 0.0), np.where(both, r, 0.0)
+        absd = np.where(both, 0.0, np.inf)     # + |g - r| below: the absolute arms never pass a texel that is not finite in both
+    else:
+        assert np.isfinite(g).all(), f"{what}: non-finite values"
+        absd = 0.0
     num, den = np.sqrt(((g - r) ** 2).sum()), np.sqrt((r ** 2).sum())
     rl2 = num / den if den > 0 else num
-    ok = (np.abs(_key(got) - _key(ref)) <= ulps) | (np.abs(g - r) <= abs_floor)
+    ok = (np.abs(_key(got) - _key(ref)) <= ulps) | (absd + np.abs(g - r) <= abs_floor)
     for c in variance_channels:
-        ok[..., c] |= np.abs(g - r)[..., c] <= variance_floor
+        ok[..., c] |= (absd + np.abs(g - r))[..., c] <= variance_floor
     if exclude is not None:
         ex = exclude if ok.ndim == 2 else exclude[..., None]
         ok = ok | ex
     # hard caps: no texel may be arbitrarily wrong
     cap_ulps = CAP_ULPS if cap_ulps is None else cap_ulps
     cap_abs = max(CAP_ABS if cap_abs is None else cap_abs, abs_floor)
-    ulp_d, abs_d = np.abs(_key(got) - _key(ref)), np.abs(g - r)
+    ulp_d, abs_d = np.abs(_key(got) - _key(ref)), absd + np.abs(g - r)
     capped = (ulp_d <= cap_ulps) | (abs_d <= cap_abs)
     for c in variance_channels:
         capped[..., c] |= abs_d[..., c] <= max(cap_abs, variance_floor)
@@ -108,7 +126,7 @@ def compare16(got, ref, what, rel_l2=1e-3, ulps=2, frac=0.999, abs_floor=OUTPUT_
     elif not outside.all():
         w = np.argwhere(~outside)
         raise AssertionError(f"{what}: {len(w)} texels beyond the hard cap ({cap_ulps} fp16 ulp or {cap_abs:.2e}); worst {int(ulp_d[~outside].max())} ulp / {abs_d[~outside].max():.3e}; "
-                             f"first (y, x, ...): {w[:6].tolist()} got {g[tuple(w[:6].T)].tolist()} ref {r[tuple(w[:6].T)].tolist()}")
+                             f"first (y, x, ...): {w[:6].tolist()} got {gv[tuple(w[:6].T)].tolist()} ref {rv[tuple(w[:6].T)].tolist()}")
     if exb is not None and exb.any():
         # inside the neighbourhood of a flipped tile: bounded by the value range of the channel (a copied / cleared tile swaps values, it does not invent them)
         rng = (r.max(axis=tuple(range(r.ndim - 1)) if r.ndim == 3 else None) - r.min(axis=tuple(range(r.ndim - 1)) if r.ndim == 3 else None)) + cap_abs
@@ -116,7 +134,7 @@ def compare16(got, ref, what, rel_l2=1e-3, ulps=2, frac=0.999, abs_floor=OUTPUT_
         assert not over.any(), f"{what}: {int(over.sum())} texels next to a flipped tile differ by more than the channel's value range (max {abs_d[exb].max():.3e})"
     f = ok.mean()
     bad = np.argwhere(~ok)
-    where = f"; first offenders (y, x, ...): {bad[:6].tolist()} got {g[tuple(bad[:6].T)].tolist()} ref {r[tuple(bad[:6].T)].tolist()}" if len(bad) else ""
+    where = f"; first offenders (y, x, ...): {bad[:6].tolist()} got {gv[tuple(bad[:6].T)].tolist()} ref {rv[tuple(bad[:6].T)].tolist()}" if len(bad) else ""
     sel = ok if exclude is None else (ok & ~(exclude if ok.ndim == 2 else np.broadcast_to(exclude[..., None], ok.shape)))
     rl2_in = np.sqrt(((g - r)[sel] ** 2).sum()) / max(np.sqrt((r[sel] ** 2).sum()), 1e-30)
     assert rl2_in <= rel_l2, f"{what}: relative L2 error over the texels inside the ulp bound {rl2_in:.2e} > {rel_l2:.0e}"

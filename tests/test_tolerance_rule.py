@@ -98,3 +98,36 @@ def test_fuzz_sequences_name_the_recorded_draws():
             (8088, 159): ("sponza_small", 177, 136, "default", 2), (555, 66): ("sponza_small", 336, 138, "spot", 1), (31337, 206): ("sponza_small", 181, 159, "spot", 1)}
     for k, c in got.items():
         assert (c["name"], c["W"], c["H"], c["light"], c["scale"]) == want[k], (k, c)
+
+
+def test_nonfinite_clause():
+    """docs/TOLERANCE.md "Non-finite images": opt-in.  The default still refuses any non-finite texel; with nonfinite=True the NaN sets must
+    be identical, +-inf is ordered by the fp16 ulp key (65504 vs +inf is 1 ulp, accepted; 60000 vs +inf is far beyond the cap) and the
+    absolute / L2 terms are taken over the texels finite in both images"""
+    ref = _image()
+    ref[0, 0, 0], ref[1, 1, 1], ref[2, 2, 2], ref[3, 3, 0] = np.inf, np.nan, np.float16(65504.0), -np.inf
+    with pytest.raises(AssertionError, match="non-finite"):
+        T.compare16(_bits(ref.copy()), _bits(ref), "inf / NaN under the default rule")
+    T.compare16(_bits(ref.copy()), _bits(ref), "identical with inf / NaN", nonfinite=True)
+    got = ref.copy()
+    got[1, 1, 1] = np.float16(-np.nan)     # another NaN: same set
+    step = np.random.RandomState(2).choice([-1, 0, 1], size=ref.shape)
+    fin = np.isfinite(ref)
+    gb = np.where(fin & (np.abs(ref) < 60000), (_bits(got).astype(np.int32) + step), _bits(got)).astype(np.uint16)
+    T.compare16(gb, _bits(ref), "one ulp on the finite texels", nonfinite=True)
+    knife = ref.copy()
+    knife[0, 0, 0] = np.float16(65504.0)   # the reference's +inf came out one rounding short: 1 ulp
+    T.compare16(_bits(knife), _bits(ref), "65504 vs +inf", nonfinite=True)
+    far = ref.copy()
+    far[0, 0, 0] = np.float16(60000.0)
+    with pytest.raises(AssertionError, match="hard cap"):
+        T.compare16(_bits(far), _bits(ref), "60000 vs +inf", nonfinite=True)
+    for y, x, c, v in ((1, 1, 1, 0.3), (5, 5, 0, np.nan)):
+        bad = ref.copy()
+        bad[y, x, c] = v
+        with pytest.raises(AssertionError, match="NaN texel sets"):
+            T.compare16(_bits(bad), _bits(ref), "NaN set differs", nonfinite=True)
+    sign = ref.copy()
+    sign[3, 3, 0] = np.inf
+    with pytest.raises(AssertionError, match="hard cap"):
+        T.compare16(_bits(sign), _bits(ref), "+inf vs -inf", nonfinite=True)
