@@ -5,6 +5,7 @@
 #include <memory>
 #include <new>
 #include "traverse.h"
+#include "selftest.h"
 #include <cstring>
 
 using namespace hr;
@@ -273,24 +274,60 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a)
     a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
 }
 
+// the modes of hr_selftest_math / hr_selftest_math_sweep (include/hr_api_post.h); the tests' CPU mirror restates each
+HR_DEV void selftest_eval(int which, const float v[8], const SelftestParams& P, float r[SELFTEST_MAX_OUT])
+{
+    const float x = v[0], y = v[1], z = v[2];
+#pragma unroll
+    for (int k = 0; k < SELFTEST_MAX_OUT; k++) r[k] = 0.0f;
+    switch (which)
+    {
+        case 0: det_sincos(x, r[0], r[1]); break;
+        case 1: r[0] = det_exp(x); break;
+        case 2: r[0] = det_log(x); break;
+        case 3: r[0] = det_pow_auto(x, y); break;
+        case 4: r[0] = (float)f2h(x); r[1] = h2f(f2h(x)); break;
+        case 5: { f3 o = oct_decode(x, y); r[0] = o.x; r[1] = o.y; r[2] = o.z; break; }
+        case 6: oct_encode(mk3(x, y, z), r[0], r[1]); break;
+        case 7: r[0] = hr_sqrt(x); r[1] = __fdiv_rn(1.0f, x); break;
+        case 8: r[0] = __fdiv_rn(x, y); break;
+        case 9:
+        {
+            const DivBy D = div_prepare(y);
+            r[0] = div_by(x, D);
+            r[1] = div_by_inrange(x, D);
+            r[2] = div_by_if(z != 0.0f, x, D);
+            break;
+        }
+        case 10: r[0] = glsl_min(x, y); r[1] = glsl_max(x, y); r[2] = glsl_clamp(x, y, z); break;
+        case 11: r[0] = min2(x, y); r[1] = max2(x, y); r[2] = clamp1(x, y, z); break;
+        case 12: r[0] = mix1(x, y, z); r[1] = smoothstep1(x, y, z); r[2] = step1(x, y); r[3] = fract1(x); break;
+        case 13: r[0] = det_powi(x, (y >= 0.0f && y <= 64.0f) ? (int)y : 0); r[1] = det_pow(x, y); break;
+        case 14: { f3 o = world_pos_from_depth(x, y, z, P.m); r[0] = o.x; r[1] = o.y; r[2] = o.z; break; }
+        case 15: r[0] = (float)(int)x; break;   // v_cvt_i32_f32 out of range (no oracle: the tests record what gfx950 does)
+        default: break;
+    }
+}
+
 __global__ void k_selftest_math(int which, long long n, const float* in, float* out)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float x = in[i * 3], y = in[i * 3 + 1], z = in[i * 3 + 2];
-    float       r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
-    switch (which)
-    {
-        case 0: det_sincos(x, r0, r1); break;
-        case 1: r0 = det_exp(x); break;
-        case 2: r0 = det_log(x); break;
-        case 3: r0 = det_pow_auto(x, y); break;
-        case 4: r0 = (float)f2h(x); r1 = h2f(f2h(x)); break;
-        case 5: { f3 v = oct_decode(x, y); r0 = v.x; r1 = v.y; r2 = v.z; break; }
-        case 6: oct_encode(mk3(x, y, z), r0, r1); break;
-        default: break;
-    }
-    out[i * 3] = r0; out[i * 3 + 1] = r1; out[i * 3 + 2] = r2;
+    float v[8] = { in[i * 3], in[i * 3 + 1], in[i * 3 + 2], 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    SelftestParams P = {};
+    float r[SELFTEST_MAX_OUT];
+    selftest_eval(which, v, P, r);
+    out[i * 3] = r[0]; out[i * 3 + 1] = r[1]; out[i * 3 + 2] = r[2];
+}
+
+__global__ void k_selftest_math_sweep(int which, int gen, long long first, long long n, const float* in, SelftestParams P, int nout, float* out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v[8], r[SELFTEST_MAX_OUT];
+    selftest_inputs(gen, i, first, in, P, v);
+    selftest_eval(which, v, P, r);
+    selftest_store(i, n, nout, r, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -301,6 +338,19 @@ hr_status hr_selftest_math(int32_t which, int64_t n, const float* in, float* out
     HR_CHECK_ARG(n >= 0 && (n == 0 || (in && out)));
     if (n == 0) return HR_OK;
     hipLaunchKernelGGL(k_selftest_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)which, (long long)n, in, out);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+hr_status hr_selftest_math_sweep(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out, void* stream)
+{
+    HR_CHECK_ARG(n >= 0 && params && nout >= 1 && nout <= SELFTEST_MAX_OUT && gen >= SELFTEST_GEN_ARRAY && gen <= SELFTEST_GEN_DIV);
+    HR_CHECK_ARG(n == 0 || (out && (gen != SELFTEST_GEN_ARRAY || in)));
+    if (n == 0) return HR_OK;
+    SelftestParams P;
+    std::memcpy(&P, params, sizeof(P));
+    hipLaunchKernelGGL(k_selftest_math_sweep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)which, (int)gen, (long long)first,
+                       (long long)n, in, P, (int)nout, out);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }

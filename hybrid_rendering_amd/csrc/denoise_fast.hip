@@ -22,6 +22,7 @@
 #include "tile_order.h"
 #include "exact_predicates.h"   // before any contract(fast): the knife-edge fallbacks keep the parity kernels' arithmetic
 #include "ddgi_sample_fast.h"
+#include "selftest.h"
 
 #pragma clang fp contract(fast)
 
@@ -1779,3 +1780,82 @@ void launch_upsample_fast(const UpsampleArgs& a, hipStream_t st)
 }
 
 } // namespace hr
+
+// ---- self test of this translation unit's arithmetic (hr_selftest_fast_math, include/hr_api_post.h) --------------------------------
+// Compiled here, under the contract(fast) pragma above, so that the parity helpers (fm::*_rn, exact::*) are checked where the tolerance
+// kernels use them: their claim is that contraction stays off inside them whatever the surrounding code allows.
+namespace hr {
+
+HR_DEV void selftest_fast_eval(int which, const float v[8], const SelftestParams& P, float r[SELFTEST_MAX_OUT])
+{
+    const float x = v[0], y = v[1], z = v[2];
+#pragma unroll
+    for (int k = 0; k < SELFTEST_MAX_OUT; k++) r[k] = 0.0f;
+    const int w = (int)P.w, h = (int)P.h;
+    switch (which)
+    {
+        case 0: r[0] = fm::rcp(x); r[1] = fm::rsq(x); r[2] = fm::sqrt1(x); r[3] = fm::rcp_nr(x); break;
+        case 1: r[0] = fm::expf_(x); r[1] = fm::log2f_(x); r[2] = fm::exp2f_(x); break;
+        case 2: r[0] = fm::powf_(x, y); break;
+        case 3: { const uint32_t p = fm::pack2(x, y); r[0] = (float)(p & 0xffffu); r[1] = (float)(p >> 16); break; }
+        case 4:
+        {
+            const uint32_t p = (uint32_t)f2h(x) | ((uint32_t)f2h(y) << 16);
+            const f3 a = fm::oct_raw(p), b = fm::oct_unit(p);
+            r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = b.x; r[4] = b.y; r[5] = b.z;
+            break;
+        }
+        case 5: r[0] = fm::mix_rn(x, y, z); r[1] = fm::var_rn(x, y); r[2] = fm::mad_rn(x, y, z); r[3] = fm::mul_rn(x, y); r[4] = fm::cheb_variance_rn(x, y); break;
+        case 6: r[0] = fm::bilerp_rn(v[0], v[1], v[2], v[3], v[4], v[5]); break;
+        case 7:
+        {
+            const DivBy Dw = div_prepare(v[5]), Dh = div_prepare(v[6]);
+            fm::atlas_coord_rn(v[0], v[1], (int)v[2], (int)v[3], (int)v[4], v[5], v[6], Dw, Dh, r[0], r[1]);
+            break;
+        }
+        case 8: r[0] = fm::div_rn(x, y); r[1] = (float)fm::tap_texel(x, y, z, v[3]); break;
+        case 9:
+        {
+            const int px = (int)x, py = (int)y;
+            r[0] = exact::tap_valid(P.m, px, py, w, h, z, __float_as_uint(v[3]), __float_as_uint(v[4]), P.cur_id, px, py, __float_as_uint(v[5]),
+                                    __float_as_uint(v[6]), v[7]) ? 1.0f : 0.0f;
+            break;
+        }
+        case 10: exact::virtual_point(P.m, P.m2, mk3(P.cam[0], P.cam[1], P.cam[2]), (int)x, (int)y, w, h, z, v[3], r[0], r[1]); break;
+        case 11:
+        {
+            f3 Pw, N, Wo;
+            exact::pixel_inputs(P.m, P.cam, (int)x, (int)y, w, h, z, __float_as_uint(v[3]), Pw, N, Wo);
+            r[0] = Pw.x; r[1] = Pw.y; r[2] = Pw.z; r[3] = N.x; r[4] = N.y; r[5] = N.z; r[6] = Wo.x; r[7] = Wo.y; r[8] = Wo.z;
+            break;
+        }
+        default: break;
+    }
+}
+
+__global__ void kf_selftest_fast_math(int which, int gen, long long first, long long n, const float* in, SelftestParams P, int nout, float* out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v[8], r[SELFTEST_MAX_OUT];
+    selftest_inputs(gen, i, first, in, P, v);
+    selftest_fast_eval(which, v, P, r);
+    selftest_store(i, n, nout, r, out);
+}
+
+} // namespace hr
+
+extern "C" hr_status hr_selftest_fast_math(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out,
+                                           void* stream)
+{
+    using namespace hr;
+    HR_CHECK_ARG(n >= 0 && params && nout >= 1 && nout <= SELFTEST_MAX_OUT && gen >= SELFTEST_GEN_ARRAY && gen <= SELFTEST_GEN_DIV);
+    HR_CHECK_ARG(n == 0 || (out && (gen != SELFTEST_GEN_ARRAY || in)));
+    if (n == 0) return HR_OK;
+    SelftestParams P;
+    std::memcpy(&P, params, sizeof(P));
+    hipLaunchKernelGGL(kf_selftest_fast_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)which, (int)gen, (long long)first,
+                       (long long)n, in, P, (int)nout, out);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}

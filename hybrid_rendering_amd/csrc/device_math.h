@@ -87,12 +87,14 @@ HR_DEV uint32_t pack_h2(float a, float b) { return (uint32_t)f2h(a) | ((uint32_t
 HR_DEV void det_sincos(float x, float& s, float& c)
 {
     float kf = floorf(x * 0.636619772367581f + 0.5f);
-    int   k  = (int)kf;
     float r  = ((x - kf * 1.5703125f) - kf * 4.837512969970703125e-4f) - kf * 7.54978995489188e-8f;
     float z  = r * r;
     float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
     float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
-    int   q  = k & 3;
+    // quadrant = kf mod 4 in float arithmetic (exact for every integral kf), not (int)kf & 3: past |x| ~ 3.4e9 (int)kf overflows, and
+    // gfx950's v_cvt_i32_f32 saturates where x86 returns INT_MIN.  inf / NaN: quadrant 0 (the results are NaN either way)
+    const float kq = kf - 4.0f * floorf(kf * 0.25f);
+    int   q  = kq == kq ? (int)kq : 0;
     float sv = (q & 1) ? cp : sp;
     float cv = (q & 1) ? sp : cp;
     s = (q & 2) ? -sv : sv;
@@ -133,27 +135,22 @@ HR_DEV DivBy div_prepare(float d)
     D.fast = d >= 1e-6f && d <= 1e6f;
     return D;
 }
-HR_DEV float div_by(float n, const DivBy& D)
-{
-    const float an = fabsf(n);
-    if (D.fast && (n == 0.0f || (an >= 1e-12f && an <= 3e5f)))
-    {
-        const float q0 = n * D.r1;
-        const float e1 = hr_fma(-D.d, q0, n);
-        const float q1 = hr_fma(e1, D.r1, q0);
-        const float e2 = hr_fma(-D.d, q1, n);
-        return hr_fma(e2, D.r1, q1);
-    }
-    return __fdiv_rn(n, D.d);
-}
-// div_by without its range tests: the CALLER guarantees D.fast and n == 0 or 1e-12 <= |n| <= 3e5 (a NaN comes back a NaN either way)
+// div_by without its range tests: the CALLER guarantees D.fast and n == 0 or 1e-12 <= |n| <= 3e5 (a NaN comes back a NaN either way).
+// d > 0 there, so the quotient has the sign of n: the FMA sequence alone returns +0 for n = -0 (e1 = (-d)(-0) + -0 = +0; the compiler's
+// expansion restores the sign in v_div_fixup) — found by tests/test_gpu_device_math.py::test_div_by_fallback_edges
 HR_DEV float div_by_inrange(float n, const DivBy& D)
 {
     const float q0 = n * D.r1;
     const float e1 = hr_fma(-D.d, q0, n);
     const float q1 = hr_fma(e1, D.r1, q0);
     const float e2 = hr_fma(-D.d, q1, n);
-    return hr_fma(e2, D.r1, q1);
+    return __builtin_copysignf(hr_fma(e2, D.r1, q1), n);
+}
+HR_DEV float div_by(float n, const DivBy& D)
+{
+    const float an = fabsf(n);
+    if (D.fast && (n == 0.0f || (an >= 1e-12f && an <= 3e5f))) return div_by_inrange(n, D);
+    return __fdiv_rn(n, D.d);
 }
 // ... behind a flag the caller established once for all its numerators (wave-uniform where the denominator is): no per-quotient range branches
 HR_DEV float div_by_if(bool inrange, float n, const DivBy& D) { return inrange ? div_by_inrange(n, D) : __fdiv_rn(n, D.d); }
@@ -161,6 +158,7 @@ HR_DEV float div_by_if(bool inrange, float n, const DivBy& D) { return inrange ?
 HR_DEV float det_log(float x)
 {
     if (x <= 0.0f) return -1.0e30f;
+    if (!(x < INFINITY)) return x;   // log(+inf) = +inf, a NaN stays a NaN (the bit manipulation below would make finite values of both)
     uint32_t u = __float_as_uint(x);
     int      e = (int)(u >> 23) - 126;
     float    m = __uint_as_float((u & 0x007fffffu) | 0x3f000000u);

@@ -5,10 +5,15 @@
 // and forbids fused multiply-adds; it made every denoise kernel VALU-bound at 10-35% of the HBM roofline.
 // north_star asks for bit-exactness only of the visibility masks and a stated fp32 tolerance for the fp16 images, so the
 // shipping mode computes with the hardware's transcendental unit:
-//   x / y      -> x * v_rcp_f32(y)           (1 ulp)          sqrt -> v_sqrt_f32 (1 ulp), 1/sqrt -> v_rsq_f32 (1 ulp)
-//   exp(x)     -> v_exp_f32(x * log2 e)      (1 ulp)          pow(x, p) -> v_exp_f32(p * v_log_f32(x))
+//   x / y      -> x * v_rcp_f32(y)                            sqrt -> v_sqrt_f32, 1/sqrt -> v_rsq_f32
+//   exp(x)     -> v_exp_f32(x * log2 e)                       pow(x, p) -> v_exp_f32(p * v_log_f32(x))
 //   a * b + c  -> v_fma_f32 (the file is compiled with fp-contract fast), sums re-associated where it saves work
-// Accuracy: a few fp32 ulp per stage — three orders of magnitude below the fp16 ulp (2^-11) the images are stored with;
+// Measured on gfx950 (tests/test_gpu_device_math.py pins each bound), in ulp of the correctly rounded result: rcp 0.89, rsq 0.86, sqrt 0.93
+// (fp16 range and 1e-6 .. 1e6), rcp_nr 0.5 (correctly rounded there), exp2 0.77 on [-125, 0]; exp(x) up to 62 ulp on [-87, 0] — at x = -87
+// rounding x * log2 e costs up to ~44 ulp and log2 e's own fp32 rounding ~20; log2 within 1.9e-6 absolute and pow within 5.3e-6 relative over fp16 bases.  The hardware
+// flushes subnormal INPUTS of rcp / rsq / sqrt / log2 to zero (rcp(1e-40) = inf, log2(1e-40) = -inf), and rcp_nr(0) / rcp_nr(inf) are NaN.
+// Accuracy: a few fp32 ulp per stage (~60 where an exp argument is large) — two to three orders of magnitude below the fp16 ulp
+// (2^-11) the images are stored with;
 // tests/test_gpu_tolerance.py holds the stated bound (rel-L2 <= 1e-3 per image, <= 2 fp16 ulp on >= 99.9 % of the texels —
 // the rest are discrete decisions, e.g. a reprojection validity test on a knife edge, flipped by an fp32 ulp).
 #pragma once

@@ -101,6 +101,14 @@ hr_status hr_tone_map(hr_ctx* ctx, const hr_image_view* color, int32_t single_ch
  * 4 fp32->fp16 bits (as float of the uint16)  5 oct_decode(x,y)->(nx,ny,nz)  6 oct_encode(x,y,z)->(ex,ey).
  * in: device [n][3] floats, out: device [n][3] floats. */
 hr_status hr_selftest_math(int32_t which, int64_t n, const float* in, float* out, void* stream);
+/* The same modes and more (7 sqrt, 1/x  8 x/y  9 div_by family  10 glsl_min/max/clamp  11 min2/max2/clamp1  12 mix/smoothstep/step/fract
+ * 13 powi, pow  14 world_pos_from_depth  15 (int)x), with inputs from `in` ([n][8], gen 0) or from the index first + i (gen 1: fp32 bits, 2: fp16
+ * pair, 3: denominator x numerator grid); params: host, 80 floats (matrices, constants); out: device [nout][n] floats.  hr_selftest_fast_math
+ * evaluates the tolerance-mode helpers (fast_math.h, exact_predicates.h) in their own translation unit.  Test infrastructure. */
+hr_status hr_selftest_math_sweep(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out,
+                                 void* stream);
+hr_status hr_selftest_fast_math(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out,
+                                void* stream);
 
 #ifdef __cplusplus
 }

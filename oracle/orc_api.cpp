@@ -2,6 +2,8 @@
 #include "orc_api.h"
 #include "orc_bvh.h"
 #include "orc_common.h"
+#include "orc_reproject.h"
+#include <atomic>
 
 using namespace orc;
 
@@ -262,5 +264,213 @@ void orc_world_position_from_depth(float u, float v, float depth, const float* v
     for (int i = 0; i < 16; i++) m.m[i] = view_proj_inverse[i];
     vec3 p = world_position_from_depth(u, v, depth, m);
     out3[0] = p.x; out3[1] = p.y; out3[2] = p.z;
+}
+}
+
+// ---- self-test mirror (hr_selftest_math_sweep / hr_selftest_fast_math, include/hr_api_post.h) ----------------------
+// The same modes, the same index-generated inputs and the same planar outputs as the device self test, on arrays and in
+// parallel, so that sweeps over all 2^32 fp32 patterns can be checked chunk by chunk without moving inputs through Python.
+namespace {
+
+struct SelftestParams
+{
+    float    m[16], m2[16], cam[3], y, z, w, h, cur_id;
+    uint32_t d_first;
+    int32_t  n_num;
+    float    num[32];
+    float    pad[6];
+};
+static_assert(sizeof(SelftestParams) == 80 * 4, "SelftestParams layout");
+constexpr int MAX_OUT = 9;
+
+float random_numerator(uint64_t j)
+{
+    uint64_t z = j * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 29)) * 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 32;
+    const uint32_t lo = 0x2b8cbcccu, hi = 0x48927c00u;   // bits of 1e-12f and 3e5f
+    const uint32_t b  = lo + (uint32_t)((z & 0xffffffffull) % (uint64_t)(hi - lo + 1u));
+    return u2f(b | ((uint32_t)(z >> 63) << 31));
+}
+
+void inputs(int gen, int64_t i, int64_t first, const float* in, const SelftestParams& P, float v[8])
+{
+    for (int k = 0; k < 8; k++) v[k] = 0.0f;
+    const uint64_t j = (uint64_t)(first + i);
+    if (gen == 0)
+    {
+        for (int k = 0; k < 8; k++) v[k] = in[i * 8 + k];
+        return;
+    }
+    v[1] = P.y;
+    v[2] = P.z;
+    if (gen == 1) v[0] = u2f((uint32_t)j);
+    else if (gen == 2)
+    {
+        v[0] = f16_to_f32((uint16_t)(j & 0xffffu));
+        v[1] = f16_to_f32((uint16_t)((j >> 16) & 0xffffu));
+    }
+    else if (gen == 3)
+    {
+        const uint64_t nn = (uint64_t)(P.n_num > 0 ? P.n_num : 1);
+        const float    t  = P.num[j % nn];
+        v[0] = t != t ? random_numerator(j) : t;
+        v[1] = u2f(P.d_first + (uint32_t)(j / nn));
+    }
+}
+
+mat4 to_mat4(const float* m)
+{
+    mat4 r;
+    for (int k = 0; k < 16; k++) r.m[k] = m[k];
+    return r;
+}
+
+// tu 0: device_math.h (api.hip), every mode has a definition here.  tu 1: denoise_fast.hip; modes 0-2 and 4 are the hardware's
+// approximations (rcp, rsq, exp, log, oct_unit): their accuracy is measured against float64 by the tests, they have no oracle here.
+bool eval(int tu, int which, const float v[8], const SelftestParams& P, float r[MAX_OUT])
+{
+    const float x = v[0], y = v[1], z = v[2];
+    for (int k = 0; k < MAX_OUT; k++) r[k] = 0.0f;
+    if (tu == 0)
+    {
+        switch (which)
+        {
+            case 0: det_sincos(x, &r[0], &r[1]); return true;
+            case 1: r[0] = det_exp(x); return true;
+            case 2: r[0] = det_log(x); return true;
+            case 3: r[0] = det_pow_auto(x, y); return true;
+            case 4: r[0] = (float)f32_to_f16(x); r[1] = f16_to_f32(f32_to_f16(x)); return true;
+            case 5: { vec3 o = octohedral_to_direction(x, y); r[0] = o.x; r[1] = o.y; r[2] = o.z; return true; }
+            case 6: { vec2 o = direction_to_octohedral(v3(x, y, z)); r[0] = o.x; r[1] = o.y; return true; }
+            case 7: r[0] = std::sqrt(x); r[1] = 1.0f / x; return true;
+            case 8: r[0] = x / y; return true;
+            case 9: r[0] = r[1] = r[2] = x / y; return true;   // div_by, div_by_inrange, div_by_if: correctly rounded (inrange: in its domain)
+            case 10: r[0] = glsl_min(x, y); r[1] = glsl_max(x, y); r[2] = glsl_clamp(x, y, z); return true;
+            case 11: r[0] = fmin2(x, y); r[1] = fmax2(x, y); r[2] = clampf(x, y, z); return true;
+            case 12: r[0] = mixf(x, y, z); r[1] = smoothstepf(x, y, z); r[2] = stepf(x, y); r[3] = fractf(x); return true;
+            case 13: r[0] = det_powi(x, (y >= 0.0f && y <= 64.0f) ? (int)y : 0); r[1] = det_pow(x, y); return true;
+            case 14: { vec3 o = world_position_from_depth(x, y, z, to_mat4(P.m)); r[0] = o.x; r[1] = o.y; r[2] = o.z; return true; }
+            default: return false;
+        }
+    }
+    const int w = (int)P.w, h = (int)P.h;
+    switch (which)
+    {
+        case 3: r[0] = (float)f32_to_f16(x); r[1] = (float)f32_to_f16(y); return true;
+        case 5: r[0] = mixf(x, y, z); r[1] = x - y * y; r[2] = x * y + z; r[3] = x * y; r[4] = std::fabs(x * x - y); return true;
+        case 6: r[0] = mixf(mixf(v[0], v[1], v[4]), mixf(v[2], v[3], v[4]), v[5]); return true;
+        case 7:
+        {
+            // gi_common.glsl texture_coord_from_direction, then the bilinear set-up's texel coordinate u * size - 0.5
+            const float tw = v[5], th = v[6], side = (float)(int)v[4], pwb = side + 2.0f;
+            const float zx = (x + 1.0f) * 0.5f, zy = (y + 1.0f) * 0.5f;
+            const float u = ((float)(int)v[2] * pwb + 2.0f) / tw + (zx * side) / tw, vv = ((float)(int)v[3] * pwb + 2.0f) / th + (zy * side) / th;
+            r[0] = u * tw - 0.5f;
+            r[1] = vv * th - 0.5f;
+            return true;
+        }
+        case 8: r[0] = x / y; r[1] = (float)(int)std::floor((x + y * z) * v[3]); return true;
+        case 9:
+        {
+            const int   px = (int)x, py = (int)y;
+            const mat4  M  = to_mat4(P.m);
+            const float tu = ((float)px + 0.5f) / (float)w, tv = ((float)py + 0.5f) / (float)h;
+            const uint32_t c2x = f2u(v[3]), c2y = f2u(v[4]), q2x = f2u(v[5]), q3y = f2u(v[6]);
+            const vec3  cn = octohedral_to_direction(f16_to_f32(c2x & 0xffffu), f16_to_f32(c2x >> 16));
+            const vec3  cp = world_position_from_depth(tu, tv, z, M);
+            const vec3  hn = octohedral_to_direction(f16_to_f32(q2x & 0xffffu), f16_to_f32(q2x >> 16));
+            const vec3  hp = world_position_from_depth(tu + f16_to_f32(c2y & 0xffffu), tv + f16_to_f32(c2y >> 16), v[7], M);
+            r[0] = is_reprojection_valid(px, py, cp, hp, cn, hn, P.cur_id, f16_to_f32(q3y & 0xffffu), w, h) ? 1.0f : 0.0f;
+            return true;
+        }
+        case 10:
+        {
+            const vec2 o = virtual_point_reprojection((int)x, (int)y, w, h, z, v[3], v3(P.cam[0], P.cam[1], P.cam[2]), to_mat4(P.m), to_mat4(P.m2));
+            r[0] = o.x; r[1] = o.y;
+            return true;
+        }
+        case 11:
+        {
+            const float tu = ((float)(int)x + 0.5f) / (float)w, tv = ((float)(int)y + 0.5f) / (float)h;
+            const vec3  Pw = world_position_from_depth(tu, tv, z, to_mat4(P.m));
+            const uint32_t g2x = f2u(v[3]);
+            const vec3  N  = octohedral_to_direction(f16_to_f32(g2x & 0xffffu), f16_to_f32(g2x >> 16));
+            const vec3  Wo = normalize(v3(P.cam[0], P.cam[1], P.cam[2]) - Pw);
+            r[0] = Pw.x; r[1] = Pw.y; r[2] = Pw.z; r[3] = N.x; r[4] = N.y; r[5] = N.z; r[6] = Wo.x; r[7] = Wo.y; r[8] = Wo.z;
+            return true;
+        }
+        default: return false;
+    }
+}
+
+// planes that hold fp16 bit patterns (as floats): any two fp16 NaNs are equal there
+bool half_plane(int tu, int which, int k) { return (tu == 0 && which == 4 && k == 0) || (tu == 1 && which == 3); }
+
+bool same(float a, float b, bool half)
+{
+    if (f2u(a) == f2u(b) || (a != a && b != b)) return true;
+    if (!half || !(a >= 0.0f && a < 65536.0f && b >= 0.0f && b < 65536.0f)) return false;
+    const uint32_t ha = (uint32_t)a, hb = (uint32_t)b;
+    return a == (float)ha && b == (float)hb && (ha & 0x7c00u) == 0x7c00u && (hb & 0x7c00u) == 0x7c00u && (ha & 0x3ffu) && (hb & 0x3ffu);
+}
+
+} // namespace
+
+extern "C" {
+
+// out: [nout][n] floats.  Returns 0, or -1 for a mode without a definition here / bad arguments.
+int orc_selftest_math(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, float* out)
+{
+    if (nout < 1 || nout > MAX_OUT || n < 0 || (gen == 0 && !in) || gen < 0 || gen > 3) return -1;
+    SelftestParams P;
+    std::memcpy(&P, params, sizeof(P));
+    {
+        float v[8], r[MAX_OUT];
+        inputs(1, 0, 0, nullptr, P, v);
+        if (!eval(tu, which, v, P, r)) return -1;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++)
+    {
+        float v[8], r[MAX_OUT];
+        inputs(gen, i, first, in, P, v);
+        eval(tu, which, v, P, r);
+        for (int k = 0; k < nout; k++) out[(size_t)k * n + i] = r[k];
+    }
+    return 0;
+}
+
+// Compares the device's planar outputs of one chunk with the mirror, NaN == NaN (tests/helpers.assert_bits_equal_nan).  Returns the number of
+// mismatching elements (or -1); the first max_report of them (in no particular order) go to report_out as chunk-relative indices.
+int64_t orc_selftest_compare(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, const float* gpu_out,
+                             int64_t max_report, int64_t* report_out)
+{
+    if (nout < 1 || nout > MAX_OUT || n < 0 || (gen == 0 && !in) || gen < 0 || gen > 3) return -1;
+    SelftestParams P;
+    std::memcpy(&P, params, sizeof(P));
+    {
+        float v[8], r[MAX_OUT];
+        inputs(1, 0, 0, nullptr, P, v);
+        if (!eval(tu, which, v, P, r)) return -1;
+    }
+    int64_t              bad = 0;
+    std::atomic<int64_t> slot { 0 };
+#pragma omp parallel for schedule(static) reduction(+ : bad)
+    for (int64_t i = 0; i < n; i++)
+    {
+        float v[8], r[MAX_OUT];
+        inputs(gen, i, first, in, P, v);
+        eval(tu, which, v, P, r);
+        bool ok = true;
+        for (int k = 0; k < nout; k++) ok = ok && same(r[k], gpu_out[(size_t)k * n + i], half_plane(tu, which, k));
+        if (!ok)
+        {
+            bad++;
+            const int64_t s = slot.fetch_add(1);
+            if (s < max_report) report_out[s] = i;
+        }
+    }
+    return bad;
 }
 }

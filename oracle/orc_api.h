@@ -112,4 +112,9 @@ void     orc_oct_decode(float ex, float ey, float* out3);
 void     orc_oct_encode(const float* n3, float* out2);
 float    orc_sample_blue_noise(int x, int y, int sample_index, int dim, const uint8_t* sobol, const uint8_t* scrambling_ranking);
 void     orc_world_position_from_depth(float u, float v, float depth, const float* view_proj_inverse, float* out3);
+
+// ---- self-test mirror of hr_selftest_math_sweep (tu 0) / hr_selftest_fast_math (tu 1): same modes, inputs, planar outputs ----
+int     orc_selftest_math(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, float* out);
+int64_t orc_selftest_compare(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, const float* gpu_out,
+                             int64_t max_report, int64_t* report_out);
 }

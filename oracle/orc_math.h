@@ -142,14 +142,16 @@ static inline void det_sincos(float x, float* s_out, float* c_out)
 {
     // quadrant reduction: k = round(x * 2/pi)
     float kf = std::floor(x * 0.636619772367581f + 0.5f);
-    int   k  = (int)kf;
     // Cody-Waite with pi/2 split in three parts
     float r = ((x - kf * 1.5703125f) - kf * 4.837512969970703125e-4f) - kf * 7.54978995489188e-8f;
     float z = r * r;
     float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
     float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
     float s, c;
-    switch (k & 3)
+    // quadrant = kf mod 4 in float arithmetic (exact for every integral kf), not (int)kf & 3: past |x| ~ 3.4e9 (int)kf overflows (x86:
+    // INT_MIN, gfx950: saturated).  inf / NaN: quadrant 0 (the results are NaN either way)
+    const float kq = kf - 4.0f * std::floor(kf * 0.25f);
+    switch (kq == kq ? (int)kq : 0)
     {
         case 0: s = sp; c = cp; break;
         case 1: s = cp; c = -sp; break;
@@ -176,6 +178,7 @@ static inline float det_log(float x)
 {
     // x > 0, normal.  Returns natural log.
     if (x <= 0.0f) return -1.0e30f;
+    if (!(x < INFINITY)) return x;   // log(+inf) = +inf, a NaN stays a NaN (the bit manipulation below would make finite values of both)
     uint32_t u = f2u(x);
     int      e = (int)(u >> 23) - 126;             // x = m * 2^e, m in [0.5,1)
     float    m = u2f((u & 0x007fffffu) | 0x3f000000u);

@@ -88,7 +88,62 @@ def lib():
         _lib.orc_pow.restype = C.c_float
         _lib.orc_pow.argtypes = [C.c_float, C.c_float]
         _lib.orc_sample_blue_noise.restype = C.c_float
+        _lib.orc_selftest_math.restype = C.c_int
+        _lib.orc_selftest_math.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.orc_selftest_compare.restype = C.c_int64
+        _lib.orc_selftest_compare.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_int64, C.c_void_p]
     return _lib
+
+
+# ---- self-test mirror (orc_selftest_math / orc_selftest_compare; the device side is hr_selftest_math_sweep / hr_selftest_fast_math) ----
+GEN_ARRAY, GEN_BITS, GEN_HALF2, GEN_DIV = 0, 1, 2, 3
+TU_DEVICE_MATH, TU_FAST = 0, 1
+
+
+def selftest_params(m=None, m2=None, cam=(0.0, 0.0, 0.0), y=0.0, z=0.0, w=0, h=0, cur_id=0.0, d_first=0, num=()):
+    """The 80-float parameter block of the self test (SelftestParams in csrc/selftest.h and orc_api.cpp)."""
+    p = np.zeros(80, np.float32)
+    if m is not None:
+        p[0:16] = np.asarray(m, np.float32).reshape(16)
+    if m2 is not None:
+        p[16:32] = np.asarray(m2, np.float32).reshape(16)
+    p[32:35] = cam
+    p[35], p[36], p[37], p[38], p[39] = y, z, w, h, cur_id
+    p[40:41].view(np.uint32)[0] = np.uint32(d_first)
+    num = np.asarray(num, np.float32)
+    assert len(num) <= 32
+    p[41:42].view(np.int32)[0] = len(num)
+    p[42:42 + len(num)] = num
+    return p
+
+
+def selftest_math(tu, which, n, inp=None, gen=GEN_ARRAY, first=0, params=None, nout=3):
+    """[nout][n] float32 outputs of the mirror; inp: [n][8] float32 for gen 0"""
+    params = selftest_params() if params is None else np.ascontiguousarray(params, np.float32)
+    if inp is not None:
+        inp = np.ascontiguousarray(inp, np.float32)
+        assert inp.shape == (n, 8)
+    out = np.empty((nout, n), np.float32)
+    st = lib().orc_selftest_math(tu, which, gen, first, n, None if inp is None else inp.ctypes.data, params.ctypes.data, nout, out.ctypes.data)
+    assert st == 0, (tu, which)
+    return out
+
+
+def selftest_compare(tu, which, gen, first, n, gpu_out, params=None, inp=None, max_report=16):
+    """(number of mismatching elements, up to max_report sorted chunk-relative indices); gpu_out: a C-contiguous [nout][n] float32 array"""
+    params = selftest_params() if params is None else np.ascontiguousarray(params, np.float32)
+    gpu_out = np.asarray(gpu_out)
+    assert gpu_out.dtype == np.float32 and gpu_out.flags["C_CONTIGUOUS"] and gpu_out.shape[-1] == n
+    nout = 1 if gpu_out.ndim == 1 else gpu_out.shape[0]
+    if inp is not None:
+        inp = np.ascontiguousarray(inp, np.float32)
+        assert inp.shape == (n, 8)
+    rep = np.zeros(max(max_report, 1), np.int64)
+    bad = lib().orc_selftest_compare(tu, which, gen, first, n, None if inp is None else inp.ctypes.data, params.ctypes.data, nout,
+                                     gpu_out.ctypes.data, max_report, rep.ctypes.data)
+    assert bad >= 0, (tu, which)
+    return int(bad), np.sort(rep[:min(bad, max_report)])
 
 
 def _p(a, t):
