@@ -95,7 +95,7 @@ ABI_SYMBOLS = [
     "hr_scene_destroy", "hr_trace_any_hit", "hr_trace_closest_hit", "hr_gbuffer_raycast", "hr_shadows_default_params", "hr_shadows_create",
     "hr_shadows_render", "hr_shadows_output", "hr_shadows_reset_history", "hr_shadows_destroy", "hr_shadows_ray_trace", "hr_shadows_denoise", "hr_shadows_temporal",
     "hr_shadows_atrous_iteration", "hr_shadows_upsample", "hr_shadows_image", "hr_shadows_history_apron_exceeded", "hr_shadows_set_profiling", "hr_shadows_get_stage_times",
-    "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
+    "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_bvh_child_boxes", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
     "hr_selftest_math_sweep", "hr_selftest_fast_math",
 ]
 
@@ -311,6 +311,23 @@ def bvh_selfcheck(verts, samples_per_triangle: int = 12) -> int:
     L.hr_bvh_selfcheck.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     _check(L.hr_bvh_selfcheck(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.c_int32(samples_per_triangle), C.byref(bad)), "hr_bvh_selfcheck")
     return int(bad.value)
+
+
+CHILD_BOX_DTYPE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("step", np.float32, 3), ("node", np.int32), ("slot", np.int32), ("depth", np.int32), ("is_leaf", np.int32)])
+
+
+def bvh_child_boxes(verts) -> np.ndarray:
+    """Host-only: the de-quantised child boxes of the BVH hr_scene_create would build over ``verts`` [n,3,3], as the traversal's box
+    test sees them — a structured array (CHILD_BOX_DTYPE): lo, hi, the node's quantisation step per axis, node, slot, depth, is_leaf."""
+    v = np.ascontiguousarray(verts, np.float32)
+    L = lib()
+    L.hr_bvh_child_boxes.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    n = C.c_int64(0)
+    _check(L.hr_bvh_child_boxes(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), None, C.c_int64(0), C.byref(n)), "hr_bvh_child_boxes")
+    out = np.zeros(int(n.value), CHILD_BOX_DTYPE)
+    _check(L.hr_bvh_child_boxes(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.c_void_p(out.ctypes.data), C.c_int64(len(out)), C.byref(n)), "hr_bvh_child_boxes")
+    assert int(n.value) == len(out)
+    return out
 
 
 def gbuffer_mip(g, level, stream=None):

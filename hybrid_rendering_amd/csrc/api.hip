@@ -7,6 +7,7 @@
 #include "traverse.h"
 #include "selftest.h"
 #include <cstring>
+#include <cmath>
 
 using namespace hr;
 
@@ -465,6 +466,54 @@ hr_status hr_bvh_selfcheck(const float* positions, int32_t n_tris, int32_t sampl
     catch (const std::exception& e)
     {
         set_last_error(std::string("hr_bvh_selfcheck: ") + e.what());
+        return HR_ERR_UNSUPPORTED;
+    }
+}
+
+// Host-only: the child boxes of the same BVH, de-quantised the way the traversal does it (origin + q * 2^(e-127), one fma per plane).
+hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes)
+{
+    HR_CHECK_ARG(n_boxes && n_tris >= 0 && capacity >= 0 && (out || capacity == 0) && (positions || n_tris == 0));
+    try
+    {
+        BuiltBVH b;
+        build_bvh8(positions, n_tris, b);
+        std::vector<int> depth(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
+        int64_t n = 0;
+        for (size_t j = 0; j < b.nodes.size(); j++)
+        {
+            const Node8& nd = b.nodes[j];
+            const int n_internal = nd.counts & 15, n_children = nd.counts >> 4;
+            for (int c = 0; c < n_internal; c++) depth[(size_t)nd.child_base + c] = depth[j] + 1;
+            const uint8_t e[3] = { nd.ex, nd.ey, nd.ez };
+            const float   o[3] = { nd.ox, nd.oy, nd.oz };
+            for (int c = 0; c < n_children; c++, n++)
+            {
+                if (n >= capacity) continue;
+                hr_child_box& r = out[n];
+                for (int a = 0; a < 3; a++)
+                {
+                    const uint32_t bits = (uint32_t)e[a] << 23;
+                    float step;
+                    std::memcpy(&step, &bits, 4);
+                    r.step[a] = step;
+                    r.lo[a] = std::fma((float)nd.qlo[a][c], step, o[a]);
+                    r.hi[a] = std::fma((float)nd.qhi[a][c], step, o[a]);
+                }
+                r.node = (int32_t)j; r.slot = c; r.depth = depth[j]; r.is_leaf = c >= n_internal ? 1 : 0;
+            }
+        }
+        *n_boxes = n;
+        return HR_OK;
+    }
+    catch (const std::bad_alloc&)
+    {
+        set_last_error("hr_bvh_child_boxes: host allocation failed");
+        return HR_ERR_OUT_OF_MEMORY;
+    }
+    catch (const std::exception& e)
+    {
+        set_last_error(std::string("hr_bvh_child_boxes: ") + e.what());
         return HR_ERR_UNSUPPORTED;
     }
 }

@@ -264,6 +264,12 @@ struct hr_scene
     double        top_area_at_build = 0.0;        // sum of the top-level nodes' half areas when it was built: the re-build trigger compares against it
     int           top_rebuilds = 0;
     std::vector<uint32_t> inst_dirty;             // per instance: its matrix changed in the update being enqueued
+    // The uploads of an update are asynchronous copies out of the host mirrors above (inst_host, inst_dirty, the top-level staging vectors):
+    // `uploads_done` is recorded behind them, and the next call that rewrites a mirror waits for it first (instances.hip wait_uploads)
+    hipEvent_t    uploads_done = nullptr;
+    bool          uploads_pending = false;
+    ~hr_scene() { if (uploads_done) (void)hipEventDestroy(uploads_done); }
+    int           max_rel_depth = 0;              // deepest node below an instance root (a fresh top level must leave room for it)
     std::vector<int32_t>  level_offsets;          // level_nodes[level_offsets[d] .. level_offsets[d + 1]): the nodes of depth d
     std::vector<uint32_t> inst_mesh;              // per instance: mesh index
     std::vector<hr::InstanceRec> inst_host;       // host copy of inst_records (matrices of the last update)

@@ -506,6 +506,29 @@ hr_status upload_top_level(hr_scene* s, hipStream_t st)
     return HR_OK;
 }
 
+// Before a host mirror that an earlier call's asynchronous copy may still read is rewritten: wait for those copies (only for them — the
+// event sits right behind the copies, in front of the update's kernels).
+hr_status wait_uploads(hr_scene* s)
+{
+    if (s->uploads_pending)
+    {
+        HR_HIP(hipEventSynchronize(s->uploads_done));
+        s->uploads_pending = false;
+    }
+    return HR_OK;
+}
+hr_status mark_uploads(hr_scene* s, hipStream_t st)
+{
+    if (!s->uploads_done) HR_HIP(hipEventCreateWithFlags(&s->uploads_done, hipEventDisableTiming));
+    HR_HIP(hipEventRecord(s->uploads_done, st));
+    s->uploads_pending = true;
+    return HR_OK;
+}
+
+// a fresh top level is adopted only if the walk's per-lane stack can hold the deepest path through it (traverse.h LaneStack drops pushes
+// beyond kMaxTraversalDepth silently); otherwise the standing one is kept — answers never depend on which top level is in place
+bool top_level_fits(const hr_scene* s, const TopLevel& tl) { return tl.max_depth + s->max_rel_depth + 1 < kMaxTraversalDepth; }
+
 hr_status update_impl(hr_scene* s, const float* matrices, hipStream_t st, bool all_dirty)
 {
     const int m = s->n_instances;
@@ -513,21 +536,24 @@ hr_status update_impl(hr_scene* s, const float* matrices, hipStream_t st, bool a
     {
         if (!finite16(matrices + (size_t)i * 16)) { set_last_error("hr_scene_update_instances: model_matrices[" + std::to_string(i) + "] is not finite"); return HR_ERR_INVALID_ARG; }
     }
-    // which instances moved: their subtrees are refitted, the others stand
-    s->inst_dirty.resize((size_t)m);
+    // which instances moved: their subtrees are refitted, the others stand.  Nothing of the scene is written before it is known that this call
+    // uploads at all, and then only after the copies of the previous call have left the host mirrors (two updates may be enqueued back to back)
+    std::vector<uint32_t> dirty_now((size_t)m);
     bool any = false;
     for (int i = 0; i < m; i++)
     {
         const bool d = all_dirty || std::memcmp(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64) != 0;
-        s->inst_dirty[(size_t)i] = d ? 1u : 0u;
+        dirty_now[(size_t)i] = d ? 1u : 0u;
         any = any || d;
-        std::memcpy(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64);
     }
     if (!any) return HR_OK;
     HR_HIP(hipSetDevice(s->ctx->device));
-    // the records are small (80 B per instance); the copies are ordered on `st` and read the scene's own host arrays, which live until the next update
-    HR_HIP(hipMemcpyAsync(s->inst_records.p, s->inst_host.data(), (size_t)m * sizeof(InstanceRec), hipMemcpyHostToDevice, st));
-    HR_HIP(hipMemcpyAsync(s->inst_dirty_dev.p, s->inst_dirty.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+    {
+        const hr_status ws = wait_uploads(s);
+        if (ws != HR_OK) return ws;
+    }
+    s->inst_dirty.swap(dirty_now);
+    for (int i = 0; i < m; i++) std::memcpy(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64);
     instance_boxes(s);
     {
         const double dx = (double)s->grid_hi[0] - s->grid_lo[0], dy = (double)s->grid_hi[1] - s->grid_lo[1], dz = (double)s->grid_hi[2] - s->grid_lo[2];
@@ -544,7 +570,7 @@ hr_status update_impl(hr_scene* s, const float* matrices, hipStream_t st, bool a
     {
         TopLevel tl;
         build_top_level(s, tl);
-        if (top_level_area(s, &tl) < 0.9 * top_level_area(s))   // only if the fresh one IS better (instances that merely spread out gain nothing)
+        if (top_level_fits(s, tl) && top_level_area(s, &tl) < 0.9 * top_level_area(s))   // only if the fresh one IS better (instances that merely spread out gain nothing)
         {
             adopt_top_level(s, tl);
             const hr_status us = upload_top_level(s, st);
@@ -552,9 +578,16 @@ hr_status update_impl(hr_scene* s, const float* matrices, hipStream_t st, bool a
             s->top_rebuilds++;
             all_dirty = true;
             for (int i = 0; i < m; i++) s->inst_dirty[(size_t)i] = 1u;
-            HR_HIP(hipMemcpyAsync(s->inst_dirty_dev.p, s->inst_dirty.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         }
         else s->top_area_at_build = top_level_area(s);   // the spread is the new normal
+    }
+    // the records are small (80 B per instance); the copies are ordered on `st` and read the scene's own host arrays, which stand until the
+    // next call has waited for `uploads_done`
+    HR_HIP(hipMemcpyAsync(s->inst_records.p, s->inst_host.data(), (size_t)m * sizeof(InstanceRec), hipMemcpyHostToDevice, st));
+    HR_HIP(hipMemcpyAsync(s->inst_dirty_dev.p, s->inst_dirty.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+    {
+        const hr_status ms = mark_uploads(s, st);
+        if (ms != HR_OK) return ms;
     }
     const uint32_t* dirty = (const uint32_t*)s->inst_dirty_dev.p;
     hipLaunchKernelGGL(k_instances_reset_bounds, dim3(cdiv(m, 256)), dim3(256), 0, st, (uint32_t*)s->bounds_bits.p, dirty, m);
@@ -716,7 +749,8 @@ hr_status create_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** 
     {
         TopLevel tl;
         build_top_level(s, tl);
-        if (tl.max_depth + max_rel + 1 >= kMaxTraversalDepth) { set_last_error("hr_scene_create_instanced: BVH depth exceeds the traversal stack"); return HR_ERR_UNSUPPORTED; }
+        s->max_rel_depth = max_rel;
+        if (!top_level_fits(s, tl)) { set_last_error("hr_scene_create_instanced: BVH depth exceeds the traversal stack"); return HR_ERR_UNSUPPORTED; }
         adopt_top_level(s, tl);
     }
     std::memcpy(nodes.data(), s->top_nodes_host.data(), (size_t)s->top_cap * sizeof(Node8));
@@ -874,6 +908,11 @@ hr_status hr_scene_rebuild_top_level(hr_scene* scene, void* stream)
     HR_HIP(hipSetDevice(scene->ctx->device));
     TopLevel tl;
     build_top_level(scene, tl);
+    if (!top_level_fits(scene, tl)) return HR_OK;   // too deep for the traversal stack: the standing top level stays
+    {
+        const hr_status ws = wait_uploads(scene);   // adopt_top_level rewrites the staging vectors an earlier upload may still read
+        if (ws != HR_OK) return ws;
+    }
     adopt_top_level(scene, tl);
     const hr_status us = upload_top_level(scene, st);
     if (us != HR_OK) return us;

@@ -219,8 +219,9 @@ typedef struct
  * the instances' matrices.  Errors as hr_scene_create; HR_ERR_INVALID_ARG also for mesh_idx >= n_meshes or a non-finite matrix. */
 hr_status hr_scene_create_instanced(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out);
 /* model_matrices: HOST [n_instances][16] column-major (copied before the call returns).  Enqueues on `stream`: matrix upload, vertex
- * transform, bottom-up refit; no host synchronisation.  Passes rendered on the same stream afterwards see the new geometry; per-scene
- * caches of the passes (AO entry-node table) notice the change.  HR_ERR_INVALID_ARG for a scene from hr_scene_create. */
+ * transform, bottom-up refit.  The host waits only until the small uploads of the PREVIOUS update / top-level re-build have left the scene's staging
+ * memory, never for the work: updates may be enqueued back to back and take effect in order.  Passes rendered on the same stream afterwards see the
+ * new geometry; per-scene caches of the passes (AO entry-node table) notice the change.  HR_ERR_INVALID_ARG for a scene from hr_scene_create. */
 hr_status hr_scene_update_instances(hr_scene* scene, const float* model_matrices, void* stream);
 int32_t   hr_scene_instance_count(const hr_scene* scene);   /* 0 for a scene from hr_scene_create */
 /* The top level over the instance roots (host SAH over the instances' boxes, 8-wide) is re-built by hr_scene_update_instances on its own when the

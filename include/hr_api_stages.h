@@ -182,6 +182,16 @@ hr_status hr_hybrid_frame_join(hr_hybrid_frame* f, void* stream);
 /* HR_FRAME_GRAPH bookkeeping: graphs instantiated (1 in steady state) and in-place updates (one per later frame) */
 hr_status hr_hybrid_frame_graph_stats(hr_hybrid_frame* f, int32_t* instantiations, int32_t* updates);
 hr_status hr_hybrid_frame_destroy(hr_hybrid_frame* f);
+/* Host only, beside hr_bvh_build_info / hr_bvh_selfcheck (hr_api.h): the child boxes of the same BVH as the traversal
+ * sees them — per non-empty child slot the de-quantised box origin + q * 2^(e-127) (one fp32 fma per plane, the planes the walk's slab test is built on), the node's quantisation step per
+ * axis, node index, slot, depth of the node (root = 0) and whether the slot is a leaf.  Writes min(*n_boxes, capacity) records to
+ * `out` (may be NULL with capacity 0 to ask for the count).  For tests that aim rays at box faces, edges and corners. */
+typedef struct
+{
+    float   lo[3], hi[3], step[3];
+    int32_t node, slot, depth, is_leaf;
+} hr_child_box;
+hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes);
 
 #ifdef __cplusplus
 }
