@@ -107,6 +107,8 @@ int main()
         hr::Context ctx(0);
         hr::Scene scene(ctx, d);                                   // per-mesh topologies built once, one subtree per instance
         if (scene.instance_count() != I) return 5;
+        hr::Scene shared_scene(ctx, d, hr::Scene::SharedInstances());   // the same desc with ONE tree per mesh, walked on two levels
+        if (!shared_scene.is_shared() || scene.is_shared()) return 6;
 
         const float eye[3] = { 50, 50, 235 }, f = 1.0f / std::tan(40.0f * 3.14159265f / 360.0f), n = 1.0f, fa = 1000.0f;
         float view[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -eye[0], -eye[1], -eye[2], 1 };
@@ -136,10 +138,11 @@ int main()
         frame.inputs.sobol = (const uint8_t*)sobol;
         frame.inputs.scrambling_ranking = (const uint8_t*)sr;
 
-        hr::RayTracedShadows shadows(ctx, W, H, hr::RAY_TRACE_SCALE_FULL_RES), shadows_flat(ctx, W, H, hr::RAY_TRACE_SCALE_FULL_RES);
+        hr::RayTracedShadows shadows(ctx, W, H, hr::RAY_TRACE_SCALE_FULL_RES), shadows_flat(ctx, W, H, hr::RAY_TRACE_SCALE_FULL_RES), shadows_shared(ctx, W, H, hr::RAY_TRACE_SCALE_FULL_RES);
+        shadows_shared.set_current_output(hr::RayTracedShadows::OUTPUT_RAY_TRACE);
         shadows.set_current_output(hr::RayTracedShadows::OUTPUT_RAY_TRACE);
         shadows_flat.set_current_output(hr::RayTracedShadows::OUTPUT_RAY_TRACE);
-        int    same = 0;
+        int    same = 0, same_shared = 0;
         size_t lit_first = 0, lit_last = 0;
         for (uint32_t i = 0; i < 4; i++)
         {
@@ -164,12 +167,20 @@ int main()
             hr::Frame ff = frame;
             ff.scene = &flat_scene;
             shadows_flat.render(nullptr, ff);
+            shared_scene.update_instances(mats, nullptr);           // O(instances): matrices, inverses and the top level only
+            hr::Frame fs = frame;
+            fs.scene = &shared_scene;
+            shadows_shared.render(nullptr, fs);
             HIP_OK(hipDeviceSynchronize());
             hr::ImageView ma = shadows.output_ds(), mb = shadows_flat.output_ds();
             std::vector<uint32_t> wa((size_t)ma.width * ma.height), wb(wa.size());
             HIP_OK(hipMemcpy(wa.data(), ma.data, wa.size() * 4, hipMemcpyDeviceToHost));
             HIP_OK(hipMemcpy(wb.data(), mb.data, wb.size() * 4, hipMemcpyDeviceToHost));
             same += wa == wb ? 1 : 0;
+            hr::ImageView mc = shadows_shared.output_ds();
+            std::vector<uint32_t> wc(wa.size());
+            HIP_OK(hipMemcpy(wc.data(), mc.data, wc.size() * 4, hipMemcpyDeviceToHost));
+            same_shared += wa == wc ? 1 : 0;
             size_t lit = 0;
             for (uint32_t wv : wa) lit += (size_t)__builtin_popcount(wv);
             if (i == 0) lit_first = lit;
@@ -177,7 +188,8 @@ int main()
         }
         std::printf("instanced scene: %d instances of %d meshes, %dx%d, 4 frames with a moving instance: %d of 4 masks equal the flattened scene's; lit pixels %zu -> %zu\n",
                     I, 2, W, H, same, lit_first, lit_last);
-        return (same == 4 && lit_first != lit_last && lit_last > 1000) ? 0 : 1;
+        std::printf("shared instanced scene (one BVH per mesh, two-level walk): %d of 4 masks equal the private-copy scene's\n", same_shared);
+        return (same == 4 && same_shared == 4 && lit_first != lit_last && lit_last > 1000) ? 0 : 1;
     }
     catch (const hr::Error& e)
     {

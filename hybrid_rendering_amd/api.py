@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "hr_shadows_atrous_iteration", "hr_shadows_upsample", "hr_shadows_image", "hr_shadows_history_apron_exceeded", "hr_shadows_set_profiling", "hr_shadows_get_stage_times",
     "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_bvh_child_boxes", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
     "hr_selftest_math_sweep", "hr_selftest_fast_math",
+    "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint",
 ]
 
 _lib = None
@@ -251,33 +252,53 @@ class Scene:
         return dict(gb1=gb1, gb2=gb2, gb3=gb3, depth=depth)
 
 
+def _instanced_desc(isd):
+    """(hr_instanced_scene_desc, the host arrays it points into) of a synth.InstancedSceneData"""
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    keep, meshes = [], (hr_mesh_desc * len(isd.meshes))()
+    for k, m in enumerate(isd.meshes):
+        arrs = [f32(m.verts), f32(m.normals), np.ascontiguousarray(m.tri_material, np.uint32), f32(m.uvs), f32(m.tangents)]
+        keep.append(arrs)
+        meshes[k] = hr_mesh_desc(*[(a.ctypes.data if a is not None else None) for a in arrs], m.n_tris)
+    inst = (hr_instance * len(isd.instances))()
+    for i, (mat, mesh_idx, mesh_id) in enumerate(isd.instances):
+        inst[i].model_matrix[:] = [float(v) for v in np.asarray(mat, np.float32).reshape(16)]
+        inst[i].mesh_idx, inst[i].mesh_id = int(mesh_idx), int(mesh_id)
+    mats = np.ascontiguousarray(isd.materials, np.float32)
+    d = hr_instanced_scene_desc(meshes, len(isd.meshes), inst, len(isd.instances), mats.ctypes.data, len(mats), None, None, 0)
+    if isd.material_textures is not None:
+        mt = np.ascontiguousarray(isd.material_textures, np.int32)
+        tex = [np.ascontiguousarray(t, np.uint8) for t in isd.textures]
+        arr = (hr_texture * len(tex))(*[hr_texture(t.ctypes.data, t.shape[1], t.shape[0]) for t in tex])
+        keep += [mt, tex, arr]
+        d.material_textures, d.textures, d.n_textures = mt.ctypes.data, C.cast(arr, C.c_void_p), len(tex)
+    return d, [keep, meshes, inst, mats]
+
+
+def instanced_scene_footprint(isd, shared: bool):
+    """hr_instanced_scene_footprint (host only): (status, hr_scene_info) of the scene either kind would build for ``isd`` — status 0, or
+    5 (HR_ERR_UNSUPPORTED) with the sizes filled in when that kind cannot hold it"""
+    d, keep = _instanced_desc(isd)
+    info = hr_scene_info()
+    st = lib().hr_instanced_scene_footprint(C.byref(d), C.c_int32(1 if shared else 0), C.byref(info))
+    del keep
+    return int(st), info
+
+
 class InstancedScene(Scene):
     """dw::RayTracedScene as the reference holds it — meshes + instances — with the per-frame update of main.cpp:74 (build_tlas):
-    hr_scene_create_instanced / hr_scene_update_instances.  ``isd``: synth.InstancedSceneData.  Every pass takes it like a Scene."""
+    hr_scene_create_instanced / hr_scene_update_instances.  ``isd``: synth.InstancedSceneData.  Every pass takes it like a Scene.
+    ``shared=True``: hr_scene_create_instanced_shared — one BVH per mesh, walked on two levels; same answers, O(meshes + instances) memory;
+    queries, the G-buffer synthesiser and the shadows pass take it, the other passes raise HRError (HR_ERR_UNSUPPORTED)."""
 
-    def __init__(self, ctx: Context, isd):
-        self.ctx, self.isd = ctx, isd
-        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-        keep, meshes = [], (hr_mesh_desc * len(isd.meshes))()
-        for k, m in enumerate(isd.meshes):
-            arrs = [f32(m.verts), f32(m.normals), np.ascontiguousarray(m.tri_material, np.uint32), f32(m.uvs), f32(m.tangents)]
-            keep.append(arrs)
-            meshes[k] = hr_mesh_desc(*[(a.ctypes.data if a is not None else None) for a in arrs], m.n_tris)
-        inst = (hr_instance * len(isd.instances))()
-        for i, (mat, mesh_idx, mesh_id) in enumerate(isd.instances):
-            inst[i].model_matrix[:] = [float(v) for v in np.asarray(mat, np.float32).reshape(16)]
-            inst[i].mesh_idx, inst[i].mesh_id = int(mesh_idx), int(mesh_id)
-        mats = np.ascontiguousarray(isd.materials, np.float32)
-        d = hr_instanced_scene_desc(meshes, len(isd.meshes), inst, len(isd.instances), mats.ctypes.data, len(mats), None, None, 0)
-        if isd.material_textures is not None:
-            mt = np.ascontiguousarray(isd.material_textures, np.int32)
-            tex = [np.ascontiguousarray(t, np.uint8) for t in isd.textures]
-            arr = (hr_texture * len(tex))(*[hr_texture(t.ctypes.data, t.shape[1], t.shape[0]) for t in tex])
-            keep += [mt, tex, arr]
-            d.material_textures, d.textures, d.n_textures = mt.ctypes.data, C.cast(arr, C.c_void_p), len(tex)
-        self._keep = [keep, meshes, inst, mats]
+    def __init__(self, ctx: Context, isd, shared: bool = False):
+        self.ctx, self.isd, self.shared = ctx, isd, bool(shared)
+        d, self._keep = _instanced_desc(isd)
         self.h = C.c_void_p()
-        _check(lib().hr_scene_create_instanced(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced")
+        if shared:
+            _check(lib().hr_scene_create_instanced_shared(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced_shared")
+        else:
+            _check(lib().hr_scene_create_instanced(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced")
         self.info = hr_scene_info()
         self.refresh_info()
 

@@ -536,6 +536,7 @@ hr_status hr_ao_ray_count(hr_ao* p, uint64_t* rays)
 hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_ao_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && in && prm && prm->spp >= 1 && prm->spp <= p->max_spp);
+    HR_REJECT_SHARED(scene, "hr_ao_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
@@ -800,6 +801,7 @@ hr_status hr_ao_render(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* i
 {
     HR_SCOPED_SAMPLE("Ambient Occlusion");
     HR_CHECK_ARG(p && scene && in && prm);
+    HR_REJECT_SHARED(scene, "hr_ao_render");
     HR_HIP(hipSetDevice(p->ctx->device));
     p->prof.begin_frame();
     p->last_denoise = prm->denoise != 0;

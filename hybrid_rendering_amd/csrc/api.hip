@@ -5,6 +5,7 @@
 #include <memory>
 #include <new>
 #include "traverse.h"
+#include "traverse2.h"
 #include "selftest.h"
 #include <cstring>
 #include <cmath>
@@ -271,6 +272,164 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a)
     a.gb2[i] = make_uint2(pack_h2(ox, oy), pack_h2(px - cx, py - cy));
     const float mesh_id = a.tri_mesh_id ? (float)a.tri_mesh_id[hit.prim] : 0.0f;
     a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2(mesh_id, clip.z));
+    const float dd = __fdiv_rn(clip.z, clip.w);
+    a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
+}
+
+// ---- shared instanced scenes (instances_shared.hip): the same queries through the two-level walk (traverse2.h), kernels of their own ----------------
+__global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, const float* rays, uint8_t* out, unsigned long long* stats)
+{
+    __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
+    const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long i    = (long long)blockIdx.x * 256 + threadIdx.x;
+    uint32_t        nn = 0, nt = 0;
+    if (i < n)
+    {
+        const float4 a = ((const float4*)rays)[i * 2], b = ((const float4*)rays)[i * 2 + 1];
+        out[i] = trace2<true, true>(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, &nn, &nt).prim == 0 ? 1 : 0;
+    }
+    if (stats)
+    {
+        for (int o = 32; o > 0; o >>= 1) { nn += __shfl_down(nn, o); nt += __shfl_down(nt, o); }
+        if (lane == 0)
+        {
+            atomicAdd(stats + 0, (unsigned long long)nn);
+            atomicAdd(stats + 1, (unsigned long long)nt);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_closest_hit_batch2(Scene2 sc, long long n, const float* rays, float* out_tuv, int32_t* out_prim)
+{
+    __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
+    const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long i    = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = ((const float4*)rays)[i * 2], b = ((const float4*)rays)[i * 2 + 1];
+    const Hit2 h = trace_closest2(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane);
+    out_tuv[i * 3 + 0] = h.t;
+    out_tuv[i * 3 + 1] = h.u;
+    out_tuv[i * 3 + 2] = h.v;
+    out_prim[i]        = h.prim;
+}
+
+// k_gbuffer_raycast over a shared scene: the hit triangle's world vertices and normals are what k_instances_transform would have stored
+// (model_matrix * (p, 1); mat3(model_matrix) * n), computed at the hit from the mesh's object-space arrays through the instance record
+struct GBufArgs2
+{
+    GBufArgs        g;               // nodes / tris / normals / verts / tri_material / tri_mesh_id unused
+    Scene2          sc;
+    const float*    mesh_positions;
+    const float*    mesh_normals;    // or null
+    const uint32_t* mesh_material;   // or null
+};
+
+HR_DEV f3 gb2_normal_at(const float* wn, const float* wv, bool has_normals, float b0, float b1, float b2)
+{
+    if (has_normals) return mk3(wn[0] * b0 + wn[3] * b1 + wn[6] * b2, wn[1] * b0 + wn[4] * b1 + wn[7] * b2, wn[2] * b0 + wn[5] * b1 + wn[8] * b2);
+    f3 v0 = mk3(wv[0], wv[1], wv[2]), v1 = mk3(wv[3], wv[4], wv[5]), v2 = mk3(wv[6], wv[7], wv[8]);
+    return normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
+}
+
+HR_DEV bool gb2_plane_bary(const float* wv, f3 o, f3 d, float& b0, float& b1, float& b2)
+{
+    f3 v0 = mk3(wv[0], wv[1], wv[2]), v1 = mk3(wv[3], wv[4], wv[5]), v2 = mk3(wv[6], wv[7], wv[8]);
+    f3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
+    f3 n  = cross3(e1, e2);
+    float dn = dot3(n, d);
+    if (dn == 0.0f) return false;
+    float tt = __fdiv_rn(dot3(n, sub3(v0, o)), dn);
+    f3    pp = sub3(add3(o, scale3(d, tt)), v0);
+    float d11 = dot3(e1, e1), d12 = dot3(e1, e2), d22 = dot3(e2, e2), p1 = dot3(pp, e1), p2 = dot3(pp, e2);
+    float den = d11 * d22 - d12 * d12;
+    if (den == 0.0f) return false;
+    b1 = __fdiv_rn(d22 * p1 - d12 * p2, den);
+    b2 = __fdiv_rn(d11 * p2 - d12 * p1, den);
+    b0 = 1.0f - b1 - b2;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2)
+{
+    __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
+    const GBufArgs& a = a2.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tiles_x = (a.w + 7) / 8, tiles_y = (a.h + 7) / 8;
+    const int tile = blockIdx.x * 4 + wave;
+    if (tile >= tiles_x * tiles_y) return;
+    const int x = (tile % tiles_x) * 8 + (lane & 7), y = (tile / tiles_x) * 8 + (lane >> 3);
+    if (x >= a.w || y >= a.h) return;
+    const size_t i   = (size_t)y * a.w + x;
+    const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
+    const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
+    const Hit2   hit = trace_closest2(a2.sc, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
+    if (hit.prim < 0)
+    {
+        a.gb1[i]   = 0u;
+        a.gb2[i]   = make_uint2(0u, 0u);
+        a.gb3[i]   = make_uint2(0u, pack_h2(0.0f, -1.0f));
+        a.depth[i] = 1.0f;
+        return;
+    }
+    const InstanceShared& rec = a2.sc.inst[hit.inst];
+    const size_t q = (size_t)rec.mesh_tri_base + hit.local;
+    float wv[9], wn[9];
+    {
+        const float* p = a2.mesh_positions + q * 9;
+#pragma unroll
+        for (int v = 0; v < 3; v++)
+        {
+            const f4 w = mul_m4(rec.m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
+            wv[v * 3] = w.x; wv[v * 3 + 1] = w.y; wv[v * 3 + 2] = w.z;
+        }
+        if (a2.mesh_normals)
+        {
+            const float* n = a2.mesh_normals + q * 9;
+#pragma unroll
+            for (int v = 0; v < 3; v++)
+            {
+                const float nx = n[v * 3], ny = n[v * 3 + 1], nz = n[v * 3 + 2];
+                wn[v * 3]     = (rec.m[0] * nx + rec.m[4] * ny) + rec.m[8] * nz;
+                wn[v * 3 + 1] = (rec.m[1] * nx + rec.m[5] * ny) + rec.m[9] * nz;
+                wn[v * 3 + 2] = (rec.m[2] * nx + rec.m[6] * ny) + rec.m[10] * nz;
+            }
+        }
+    }
+    const bool has_normals = a2.mesh_normals != nullptr;
+    const f3 P     = add3(cam, scale3(d, hit.t));
+    const f4 clip  = mul_m4(a.vp, P.x, P.y, P.z, 1.0f);
+    const f4 pclip = mul_m4(a.pvp, P.x, P.y, P.z, 1.0f);
+    const float b0 = 1.0f - hit.u - hit.v;
+    const f3 nI    = gb2_normal_at(wn, wv, has_normals, b0, hit.u, hit.v);
+    f3       n     = normalize3(nI);
+    if (dot3(n, d) > 0.0f) n = neg3(n);
+    float curvature = 0.0f;
+    if (has_normals)
+    {
+        float c0, c1, c2;
+        f3    dxv = mk3(0, 0, 0), dyv = mk3(0, 0, 0);
+        if (gb2_plane_bary(wv, cam, gb_pixel_dir(a, (float)x + 1.5f, (float)y + 0.5f), c0, c1, c2)) dxv = sub3(gb2_normal_at(wn, wv, true, c0, c1, c2), nI);
+        if (gb2_plane_bary(wv, cam, gb_pixel_dir(a, (float)x + 0.5f, (float)y + 1.5f), c0, c1, c2)) dyv = sub3(gb2_normal_at(wn, wv, true, c0, c1, c2), nI);
+        curvature = hr_sqrt(max2(dot3(dxv, dxv), dot3(dyv, dyv)));
+    }
+    float ox, oy;
+    oct_encode(n, ox, oy);
+    const float cx = __fdiv_rn(clip.x, clip.w) * 0.5f + 0.5f, cy = __fdiv_rn(clip.y, clip.w) * 0.5f + 0.5f;
+    const float px = __fdiv_rn(pclip.x, pclip.w) * 0.5f + 0.5f, py = __fdiv_rn(pclip.y, pclip.w) * 0.5f + 0.5f;
+    const uint32_t mat = a2.mesh_material ? a2.mesh_material[q] : 0u;
+    float albedo[3] = { 0.8f, 0.8f, 0.8f }, metallic = 0.0f, roughness = 0.5f;
+    if (a.materials)
+    {
+        const float* m = a.materials + (size_t)mat * 8;
+        albedo[0] = m[0]; albedo[1] = m[1]; albedo[2] = m[2]; metallic = m[3]; roughness = m[4];
+    }
+    uint32_t g1 = 0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) g1 |= (uint32_t)(clamp1(albedo[c], 0.0f, 1.0f) * 255.0f + 0.5f) << (8 * c);
+    g1 |= (uint32_t)(clamp1(metallic, 0.0f, 1.0f) * 255.0f + 0.5f) << 24;
+    a.gb1[i] = g1;
+    a.gb2[i] = make_uint2(pack_h2(ox, oy), pack_h2(px - cx, py - cy));
+    a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2((float)rec.mesh_id, clip.z));
     const float dd = __fdiv_rn(clip.z, clip.w);
     a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
 }
@@ -650,7 +809,7 @@ extern "C" hr_status hr_gbuffer_mip_nearest(const hr_gbuffer_level* src, const h
 hr_status hr_scene_get_info(const hr_scene* scene, hr_scene_info* info)
 {
     HR_CHECK_ARG(scene && info);
-    if (scene->n_instances > 0)
+    if (scene->n_instances > 0 && !scene->shared)   // a shared scene transforms no vertex: its bounds are the host's conservative ones
     {
         const hr_status s = instanced_scene_refresh_bounds(scene);   // the exact bounds of the last hr_scene_update_instances, read back on demand
         if (s != HR_OK) return s;
@@ -686,6 +845,13 @@ hr_status hr_trace_any_hit(const hr_scene* scene, int64_t n, const float* rays, 
 {
     HR_CHECK_ARG(scene && n >= 0 && (n == 0 || (rays && out)));
     if (n == 0) return HR_OK;
+    if (scene->shared)
+    {
+        const Scene2 sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
+        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sc, (long long)n, rays, out, (unsigned long long*)stats);
+        HR_HIP(hipGetLastError());
+        return HR_OK;
+    }
     hipLaunchKernelGGL(k_any_hit_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
                        (const TriGPU*)scene->tris.p, (long long)n, rays, out, (unsigned long long*)stats);
     HR_HIP(hipGetLastError());
@@ -696,6 +862,13 @@ hr_status hr_trace_closest_hit(const hr_scene* scene, int64_t n, const float* ra
 {
     HR_CHECK_ARG(scene && n >= 0 && (n == 0 || (rays && out_tuv && out_prim)));
     if (n == 0) return HR_OK;
+    if (scene->shared)
+    {
+        const Scene2 sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
+        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sc, (long long)n, rays, out_tuv, out_prim);
+        HR_HIP(hipGetLastError());
+        return HR_OK;
+    }
     hipLaunchKernelGGL(k_closest_hit_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
                        (const TriGPU*)scene->tris.p, (long long)n, rays, out_tuv, out_prim);
     HR_HIP(hipGetLastError());
@@ -718,6 +891,18 @@ hr_status hr_gbuffer_raycast(const hr_scene* scene, const hr_ubo* ubo, int32_t w
     a.w = w; a.h = h;
     a.gb1 = (uint32_t*)gb1; a.gb2 = (uint2*)gb2; a.gb3 = (uint2*)gb3; a.depth = depth;
     const int tiles = ((w + 7) / 8) * ((h + 7) / 8);
+    if (scene->shared)
+    {
+        GBufArgs2 a2;
+        a2.g = a;
+        a2.sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
+        a2.mesh_positions = (const float*)scene->mesh_positions.p;
+        a2.mesh_normals = scene->has_normals ? (const float*)scene->mesh_normals.p : nullptr;
+        a2.mesh_material = scene->has_material ? (const uint32_t*)scene->mesh_material.p : nullptr;
+        hipLaunchKernelGGL(k_gbuffer_raycast2, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2);
+        HR_HIP(hipGetLastError());
+        return HR_OK;
+    }
     hipLaunchKernelGGL(k_gbuffer_raycast, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
     HR_HIP(hipGetLastError());
     return HR_OK;

@@ -53,6 +53,25 @@ struct alignas(16) InstanceRec
 };
 static_assert(sizeof(InstanceRec) == 80, "InstanceRec must be 80 bytes");
 
+// One instance of a SHARED instanced scene (instances_shared.hip, traverse2.h): the mesh's object-space tree is stored once, the walk enters it
+// through `inv` and transforms the leaf triangles through `m` on the fly.  Records sit in the order of the top level's leaves.
+struct alignas(16) InstanceShared
+{
+    float    m[16];          // column-major object -> world
+    float    inv[9];         // column-major inverse of mat3(m) (host, double, rounded once)
+    float    inv_abs_row[3]; // per object axis k: sum_j |inv(k, j)|
+    float    extent;         // sum_j (|m(j, 3)| + sum_k |m(j, k)| max|p_k| over the mesh's bounds): the instance's world magnitude
+    uint32_t flags;          // bit 0: no object-space culling (the matrix has no safe inverse)
+    uint32_t first_tri;      // global index of the instance's first triangle
+    uint32_t mesh_tri_base;  // index of the mesh's first triangle in the concatenated per-mesh attribute arrays
+    uint32_t mesh_id;        // GB3.z of the instance's pixels
+    uint32_t n_tris;
+    uint32_t mesh_root;      // node index of the mesh tree's root
+    uint32_t instance;       // index in the scene desc
+    uint32_t pad[2];
+};
+static_assert(sizeof(InstanceShared) == 160, "InstanceShared must be 160 bytes");
+
 // deepest 8-wide tree the traversal's per-lane stack can walk (one entry per level, traverse.h LaneStack)
 constexpr int kMaxTraversalDepth = 64;
 

@@ -605,6 +605,7 @@ static void scene_shading(const hr_scene* scene, SceneShading& sh)
 hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_environment* env, const hr_ddgi_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && in && env && prm && env->sky && env->sky_size > 0);
+    HR_REJECT_SHARED(scene, "hr_ddgi_ray_trace");
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong
@@ -741,6 +742,7 @@ hr_status hr_ddgi_render(hr_ddgi* p, const hr_scene* scene, const hr_frame_input
 {
     HR_SCOPED_SAMPLE("DDGI");
     HR_CHECK_ARG(p && scene && in && env && prm);
+    HR_REJECT_SHARED(scene, "hr_ddgi_render");
     HR_HIP(hipSetDevice(p->ctx->device));
     p->prof.begin_frame();
     hr_status s;

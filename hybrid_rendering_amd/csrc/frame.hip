@@ -132,6 +132,7 @@ hr_status hr_hybrid_frame_destroy(hr_hybrid_frame* f)
 hr_status hr_hybrid_frame_render(hr_hybrid_frame* f, const hr_scene* scene, const hr_hybrid_frame_desc* d, hr_frame_mode mode, void* stream_)
 {
     HR_CHECK_ARG(f && scene && d);
+    if (f->ao || f->ddgi || f->reflections) HR_REJECT_SHARED(scene, "hr_hybrid_frame_render (AO / DDGI / reflections)");
     HR_CHECK_ARG((!f->shadows || (d->shadows_inputs && d->shadows_params)) && (!f->ao || (d->ao_inputs && d->ao_params)) &&
                  (!f->ddgi || (d->ddgi_inputs && d->ddgi_params && d->environment)) && (!f->reflections || (d->reflections_inputs && d->reflections_params)));
     hipStream_t main = (hipStream_t)stream_;

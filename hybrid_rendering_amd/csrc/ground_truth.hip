@@ -227,6 +227,7 @@ hr_status hr_ground_truth_get_stage_times(hr_ground_truth* p, hr_stage_times* ou
 hr_status hr_ground_truth_render(hr_ground_truth* p, const hr_scene* scene, const hr_ubo* ubo, const hr_environment* env, const hr_ground_truth_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && ubo && env && prm && env->sky && env->sky_size > 0);
+    HR_REJECT_SHARED(scene, "hr_ground_truth_render");
     HR_HIP(hipSetDevice(p->ctx->device));
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;

@@ -60,6 +60,21 @@ bool profiling_enabled(const hr_reflections* p);
 // instances.hip: brings info.bounds_* of an instanced scene up to date with its last update (synchronises the device when they lag)
 hr_status instanced_scene_refresh_bounds(const hr_scene* scene);
 
+// instances.hip, shared with instances_shared.hip: the binary SAH tree over instance boxes (full sweep along three axes) both kinds of top level
+// are collapsed from, the instances' conservative world boxes (fills inst_box, grid_lo / grid_hi), the upload fence of an update, and the depth
+// of the private-copy layout's deepest path for a host-only scene stub (n_instances, inst_host, inst_mesh, mesh_bounds, top_cap, max_rel_depth set)
+struct BinNode { float lo[3], hi[3]; int left, right, inst; };
+int       top_level_binary(std::vector<BinNode>& t, std::vector<int>& items, int n, const float* boxes);
+void      instanced_scene_boxes(hr_scene* s);
+hr_status instanced_scene_wait_uploads(hr_scene* s);
+hr_status instanced_scene_mark_uploads(hr_scene* s, hipStream_t st);
+int       private_copy_top_depth(hr_scene* stub, const std::vector<int>& mesh_depth_of_instance);
+bool      finite_matrix(const float* m);
+// instances_shared.hip.  HR_REJECT_SHARED: first statement (after the argument checks) of every pass that cannot walk a shared scene yet
+bool      reject_shared_scene(const hr_scene* s, const char* pass);
+#define HR_REJECT_SHARED(scene, pass) do { if (::hr::reject_shared_scene(scene, pass)) return HR_ERR_UNSUPPORTED; } while (0)
+hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild);
+
 struct DevBuf
 {
     void*  p     = nullptr;
@@ -276,5 +291,17 @@ struct hr_scene
     std::vector<float>    mesh_bounds;            // per mesh: object-space lo xyz, hi xyz
     float         grid_lo[3] = { 0, 0, 0 }, grid_hi[3] = { 0, 0, 0 };   // bounds a pass may read WITHOUT synchronising: exact for a flattened scene, the
                                                                          // host's conservative bounds (transformed mesh boxes) for an instanced one
+    // ---- shared instanced scenes (instances_shared.hip): `nodes` = [ top level, top_cap slots | mesh 0's tree | mesh 1's ... ], `tris` = the meshes'
+    // object-space references (prim = mesh-local triangle), inst_shared = one InstanceShared per top-level leaf
+    bool          shared = false;
+    hr::DevBuf    inst_shared;
+    std::vector<hr::InstanceShared> shared_host;  // upload staging, in leaf order
+    std::vector<int32_t>  shared_leaf_of;         // per instance: its leaf (= record) index
+    struct SharedTopNode { int n_internal, n_leaves, child_base, leaf_base, axis, depth; };
+    std::vector<SharedTopNode> shared_top;        // per used top-level slot
+    std::vector<int32_t>  shared_leaf_inst;       // per leaf: the instance
+    std::vector<float>    shared_mesh_absmax;     // per mesh: max |p_k| over its bounds, per axis
+    std::vector<uint32_t> shared_mesh_root;       // per mesh: node index of its root
+    int           shared_mesh_depth = 0;          // deepest mesh tree (levels below its root)
     mutable bool  bounds_stale = false;           // info.bounds_* lag the last update until hr_scene_get_info reads them back
 };

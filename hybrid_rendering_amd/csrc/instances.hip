@@ -287,7 +287,6 @@ struct TopLevel
     std::vector<int32_t> root_slot;   // per instance
     int                  used = 0, max_depth = 0;
 };
-struct BinNode { float lo[3], hi[3]; int left, right, inst; };
 
 inline double half_area(const float* lo, const float* hi)
 {
@@ -848,6 +847,22 @@ hr_status create_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** 
 
 } // namespace
 
+// hr_internal.h: what instances_shared.hip shares with this file
+int       hr::top_level_binary(std::vector<BinNode>& t, std::vector<int>& items, int n, const float* boxes) { return build_binary(t, items, 0, n, boxes, 0); }
+void      hr::instanced_scene_boxes(hr_scene* s) { instance_boxes(s); }
+hr_status hr::instanced_scene_wait_uploads(hr_scene* s) { return wait_uploads(s); }
+hr_status hr::instanced_scene_mark_uploads(hr_scene* s, hipStream_t st) { return mark_uploads(s, st); }
+bool      hr::finite_matrix(const float* m) { return finite16(m); }
+int       hr::private_copy_top_depth(hr_scene* stub, const std::vector<int>& mesh_depth_of_instance)
+{
+    instance_boxes(stub);
+    TopLevel tl;
+    build_top_level(stub, tl);
+    int d = 0;
+    for (int i = 0; i < stub->n_instances; i++) d = std::max(d, tl.depth[(size_t)tl.root_slot[(size_t)i]] + mesh_depth_of_instance[(size_t)i]);
+    return d;
+}
+
 // hr_scene_get_info of an instanced scene: the exact bounds of the last update, read back on demand (synchronises the device)
 hr_status hr::instanced_scene_refresh_bounds(const hr_scene* scene)
 {
@@ -894,6 +909,7 @@ hr_status hr_scene_update_instances(hr_scene* scene, const float* model_matrices
 {
     HR_CHECK_ARG(scene && model_matrices);
     if (scene->n_instances <= 0) { set_last_error("hr_scene_update_instances: not an instanced scene (hr_scene_create_instanced)"); return HR_ERR_INVALID_ARG; }
+    if (scene->shared) return shared_scene_update(scene, model_matrices, (hipStream_t)stream, false);
     return update_impl(scene, model_matrices, (hipStream_t)stream, false);
 }
 
@@ -905,6 +921,7 @@ hr_status hr_scene_rebuild_top_level(hr_scene* scene, void* stream)
     if (scene->n_instances <= 0) { set_last_error("hr_scene_rebuild_top_level: not an instanced scene"); return HR_ERR_INVALID_ARG; }
     if (scene->n_instances == 1) return HR_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (scene->shared) return shared_scene_update(scene, nullptr, st, true);
     HR_HIP(hipSetDevice(scene->ctx->device));
     TopLevel tl;
     build_top_level(scene, tl);

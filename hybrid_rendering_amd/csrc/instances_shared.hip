@@ -1,0 +1,598 @@
+// Shared instanced scenes: every mesh's object-space 8-wide BVH is stored ONCE and walked on two levels (traverse2.h) — the reference's own scene
+// model (scene_descriptor_set.glsl:30-34 Instance { mat4 model_matrix; uint mesh_idx; }, one BLAS per mesh, main.cpp:74 re-builds only the TLAS).
+// Memory, creation and update cost O(sum of meshes + instances), against O(instances x mesh) of hr_scene_create_instanced's private copies.
+//
+//   nodes:        [ top level, root = 0, top_cap = max(1, instances) slots | mesh 0's tree | mesh 1's tree | ... ]
+//   tris:         [ mesh 0's references | mesh 1's ... ]        object-space vertices, prim = mesh-local triangle index
+//   inst_shared:  one 160-byte InstanceShared per LEAF of the top level, in leaf order (a top-level leaf slot's meta byte is (1 << 5) | j and
+//                 the node's tri_base the record of its first leaf, so the walk's leaf mask names records directly)
+//
+// hr_scene_update_instances on such a scene is host work over the instances only: the inverse of every changed matrix (double), the instances'
+// conservative world boxes, a refit of the top level's boxes (or a fresh SAH top level when the standing one has degraded: the same trigger as
+// the private-copy kind), and two asynchronous copies — the top region of `nodes` and the records.  No vertex is transformed, no mesh node is
+// touched.  Answers are those of the private-copy kind and of a flattened scene bit for bit: see traverse2.h for what keeps them so.
+#include "hr_internal.h"
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+using namespace hr;
+
+namespace {
+
+hr_status validate_desc(const hr_instanced_scene_desc* d, const char* who)
+{
+    HR_CHECK_ARG(d && d->n_meshes > 0 && d->meshes && d->n_instances > 0 && d->instances);
+    for (int k = 0; k < d->n_meshes; k++) HR_CHECK_ARG(d->meshes[k].n_tris >= 0 && (d->meshes[k].positions || d->meshes[k].n_tris == 0));
+    for (int i = 0; i < d->n_instances; i++)
+    {
+        if (d->instances[i].mesh_idx >= (uint32_t)d->n_meshes) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].mesh_idx >= n_meshes"); return HR_ERR_INVALID_ARG; }
+        if (!finite_matrix(d->instances[i].model_matrix)) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].model_matrix is not finite"); return HR_ERR_INVALID_ARG; }
+    }
+    return HR_OK;
+}
+
+struct MeshTrees
+{
+    std::vector<BuiltBVH> blas;
+    std::vector<int>      depth;    // per mesh: deepest node below the root (root = 0)
+};
+
+void build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want_cells)
+{
+    mt.blas.resize((size_t)d->n_meshes);
+    mt.depth.assign((size_t)d->n_meshes, 0);
+    for (int k = 0; k < d->n_meshes; k++)
+    {
+        BuiltBVH& b = mt.blas[(size_t)k];
+        b.want_child_boxes = want_cells;
+        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, b);
+        std::vector<int> dep(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
+        for (size_t j = 0; j < b.nodes.size(); j++)
+            for (int c = 0; c < (b.nodes[j].counts & 15); c++)
+            {
+                dep[(size_t)b.nodes[j].child_base + c] = dep[j] + 1;
+                mt.depth[(size_t)k] = std::max(mt.depth[(size_t)k], dep[j] + 1);
+            }
+    }
+}
+
+// the host-side fields both kinds of instanced scene keep per instance and per mesh (what hr::instanced_scene_boxes reads)
+void fill_instances(hr_scene* s, const hr_instanced_scene_desc* d, const MeshTrees& mt)
+{
+    const int M = d->n_meshes, I = d->n_instances;
+    std::vector<uint32_t> mesh_tri_base((size_t)M + 1, 0u);
+    s->mesh_bounds.assign((size_t)M * 6, 0.0f);
+    for (int k = 0; k < M; k++)
+    {
+        mesh_tri_base[(size_t)k + 1] = mesh_tri_base[(size_t)k] + (uint32_t)d->meshes[k].n_tris;
+        for (int a = 0; a < 3; a++) { s->mesh_bounds[(size_t)k * 6 + a] = mt.blas[(size_t)k].lo[a]; s->mesh_bounds[(size_t)k * 6 + 3 + a] = mt.blas[(size_t)k].hi[a]; }
+        if (d->meshes[k].n_tris == 0) { s->mesh_bounds[(size_t)k * 6] = 1.0f; s->mesh_bounds[(size_t)k * 6 + 3] = 0.0f; }   // empty: lo > hi
+    }
+    s->n_instances = I;
+    s->inst_mesh.resize((size_t)I);
+    s->inst_host.resize((size_t)I);
+    uint64_t total = 0;
+    for (int i = 0; i < I; i++)
+    {
+        const uint32_t k = d->instances[i].mesh_idx;
+        s->inst_mesh[(size_t)i] = k;
+        InstanceRec& r = s->inst_host[(size_t)i];
+        std::memcpy(r.m, d->instances[i].model_matrix, 64);
+        r.first_tri = (uint32_t)total; r.mesh_tri_base = mesh_tri_base[k]; r.mesh_id = d->instances[i].mesh_id; r.n_tris = (uint32_t)d->meshes[k].n_tris;
+        total += (uint64_t)d->meshes[k].n_tris;
+    }
+}
+
+// ---- the top level: the binary SAH tree of instances.hip collapsed to 8-wide nodes whose leaves are instances --------------------------------------
+struct SharedTop
+{
+    std::vector<hr_scene::SharedTopNode> nodes;
+    std::vector<int32_t>                 leaf_inst;
+    int                                  max_depth = 0;
+};
+
+inline double half_area3(const float* lo, const float* hi)
+{
+    const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
+    return x * y + y * z + z * x;
+}
+
+void build_shared_top(const hr_scene* s, SharedTop& tl)
+{
+    const int I = s->n_instances;
+    tl.nodes.clear(); tl.leaf_inst.clear(); tl.max_depth = 0;
+    if (I == 1)
+    {
+        tl.nodes.push_back({ 0, 1, 0, 0, 0, 0 });
+        tl.leaf_inst.push_back(0);
+        return;
+    }
+    std::vector<BinNode> bin;
+    bin.reserve((size_t)I * 2);
+    std::vector<int> items((size_t)I);
+    for (int i = 0; i < I; i++) items[(size_t)i] = i;
+    const int root = top_level_binary(bin, items, I, s->inst_box.data());
+    struct Q { int bin, depth; };
+    std::vector<Q> queue { { root, 0 } };   // queue position = node slot
+    for (size_t qi = 0; qi < queue.size(); qi++)
+    {
+        const Q q = queue[qi];
+        // open the child of largest area until eight children stand (instance leaves cannot be opened)
+        int kids[8], nk = 2;
+        kids[0] = bin[(size_t)q.bin].left; kids[1] = bin[(size_t)q.bin].right;
+        while (nk < 8)
+        {
+            int    best = -1;
+            double ba = -1.0;
+            for (int c = 0; c < nk; c++)
+                if (bin[(size_t)kids[c]].inst < 0)
+                {
+                    const double ar = half_area3(bin[(size_t)kids[c]].lo, bin[(size_t)kids[c]].hi);
+                    if (ar > ba) { ba = ar; best = c; }
+                }
+            if (best < 0) break;
+            const int k = kids[best];
+            kids[best] = bin[(size_t)k].left; kids[nk++] = bin[(size_t)k].right;
+        }
+        const BinNode& me = bin[(size_t)q.bin];
+        int ax = 0;
+        if (me.hi[1] - me.lo[1] > me.hi[ax] - me.lo[ax]) ax = 1;
+        if (me.hi[2] - me.lo[2] > me.hi[ax] - me.lo[ax]) ax = 2;
+        int internal[8], ni = 0;
+        hr_scene::SharedTopNode n { 0, 0, (int)queue.size(), (int)tl.leaf_inst.size(), ax, q.depth };
+        for (int c = 0; c < nk; c++)
+            if (bin[(size_t)kids[c]].inst < 0) internal[ni++] = kids[c];
+            else { tl.leaf_inst.push_back(bin[(size_t)kids[c]].inst); n.n_leaves++; }
+        // internal children sorted along the node's longest axis: the walk's near-to-far / far-to-near hint (bvh.h)
+        std::stable_sort(internal, internal + ni, [&](int x, int y) { return (double)bin[(size_t)x].lo[ax] + bin[(size_t)x].hi[ax] < (double)bin[(size_t)y].lo[ax] + bin[(size_t)y].hi[ax]; });
+        n.n_internal = ni;
+        for (int c = 0; c < ni; c++) queue.push_back({ internal[c], q.depth + 1 });
+        if (ni) tl.max_depth = std::max(tl.max_depth, q.depth + 1);
+        tl.nodes.push_back(n);
+    }
+}
+
+uint8_t exponent_for_host(float extent)
+{
+    // smallest e with extent <= 255 * 2^(e - 127) (bvh_build.cpp exponent_for)
+    if (!(extent > 0.0f)) return 1;
+    int ex;
+    (void)std::frexp(extent / 255.0f, &ex);
+    int e = ex + 127;
+    if (e < 1) e = 1;
+    if (e > 254) e = 254;
+    while (e > 1 && std::ldexp(255.0, e - 1 - 127) >= (double)extent) e--;
+    while (e < 254 && std::ldexp(255.0, e - 127) < (double)extent) e++;
+    return (uint8_t)e;
+}
+
+// Boxes of a top level over the instances' current boxes, padded and quantised with the builder's rules (lo floored / hi ceiled).  Returns
+// the half-area sum of its nodes: what a re-build is judged by.
+double refit_shared_top(const hr_scene* s, const SharedTop& tl, float pad, std::vector<Node8>& out)
+{
+    const size_t n = tl.nodes.size();
+    out.assign((size_t)s->top_cap, Node8());
+    std::memset(out.data(), 0, out.size() * sizeof(Node8));
+    std::vector<float> box(n * 6);
+    double sum = 0.0;
+    for (size_t slot = n; slot-- > 0;)   // children sit behind their parent
+    {
+        const hr_scene::SharedTopNode& t = tl.nodes[slot];
+        const int nc = t.n_internal + t.n_leaves;
+        float clo[8][3], chi[8][3], lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+        for (int c = 0; c < nc; c++)
+        {
+            for (int k = 0; k < 3; k++)
+            {
+                if (c < t.n_internal) { clo[c][k] = box[((size_t)t.child_base + c) * 6 + k]; chi[c][k] = box[((size_t)t.child_base + c) * 6 + 3 + k]; }
+                else
+                {
+                    const float* b = &s->inst_box[(size_t)tl.leaf_inst[(size_t)t.leaf_base + (c - t.n_internal)] * 6];
+                    clo[c][k] = b[k] - pad; chi[c][k] = b[3 + k] + pad;
+                }
+                lo[k] = std::min(lo[k], clo[c][k]); hi[k] = std::max(hi[k], chi[c][k]);
+            }
+        }
+        for (int k = 0; k < 3; k++) { box[slot * 6 + k] = lo[k]; box[slot * 6 + 3 + k] = hi[k]; }
+        sum += half_area3(lo, hi);
+        Node8& nd = out[slot];
+        nd.ox = lo[0]; nd.oy = lo[1]; nd.oz = lo[2];
+        nd.ex = exponent_for_host(hi[0] - lo[0]); nd.ey = exponent_for_host(hi[1] - lo[1]); nd.ez = exponent_for_host(hi[2] - lo[2]);
+        nd.counts = (uint8_t)(t.n_internal | (nc << 4));
+        nd.child_base = (uint32_t)t.child_base;
+        nd.tri_base = (uint32_t)t.leaf_base;
+        const uint8_t eb[3] = { nd.ex, nd.ey, nd.ez };
+        for (int c = 0; c < nc; c++)
+        {
+            nd.meta[c] = c < t.n_internal ? (uint8_t)(0x10 | (c == 0 ? t.axis : 0)) : (uint8_t)((1 << 5) | (c - t.n_internal));
+            for (int k = 0; k < 3; k++)
+            {
+                const double sc = std::ldexp(1.0, (int)eb[k] - 127), o = (double)lo[k];
+                double l = std::floor(((double)clo[c][k] - o) / sc), h = std::ceil(((double)chi[c][k] - o) / sc);
+                if (!(l > 0.0)) l = 0.0;
+                if (l > 255.0) l = 255.0;
+                if (!(h < 255.0)) h = 255.0;
+                if (h < l) h = l;
+                nd.qlo[k][c] = (uint8_t)l; nd.qhi[k][c] = (uint8_t)h;
+            }
+        }
+        // a node without internal children keeps the sort axis out of slot 0's meta byte: a leaf's low bits are its offset
+    }
+    return sum;
+}
+
+// the deepest path of the two-level walk: one stack entry per level, plus the top level's entry parked at the instance boundary (traverse2.h)
+bool shared_top_fits(const hr_scene* s, const SharedTop& tl) { return tl.max_depth + s->shared_mesh_depth + 2 < kMaxTraversalDepth; }
+
+// one record: the matrix, its inverse (double, rounded once) and what the walk's slack needs (traverse2.h)
+void fill_record(const hr_scene* s, int i, InstanceShared& r)
+{
+    const InstanceRec& h = s->inst_host[(size_t)i];
+    const uint32_t     k = s->inst_mesh[(size_t)i];
+    std::memset(&r, 0, sizeof(r));
+    std::memcpy(r.m, h.m, 64);
+    r.first_tri = h.first_tri; r.mesh_tri_base = h.mesh_tri_base; r.mesh_id = h.mesh_id; r.n_tris = h.n_tris;
+    r.mesh_root = s->shared_mesh_root[k]; r.instance = (uint32_t)i;
+    double A[3][3];   // A[row][column]
+    for (int c = 0; c < 3; c++) for (int q = 0; q < 3; q++) A[q][c] = (double)h.m[c * 4 + q];
+    double C[3][3];   // inverse = adjugate / det
+    C[0][0] = A[1][1] * A[2][2] - A[1][2] * A[2][1]; C[0][1] = A[0][2] * A[2][1] - A[0][1] * A[2][2]; C[0][2] = A[0][1] * A[1][2] - A[0][2] * A[1][1];
+    C[1][0] = A[1][2] * A[2][0] - A[1][0] * A[2][2]; C[1][1] = A[0][0] * A[2][2] - A[0][2] * A[2][0]; C[1][2] = A[0][2] * A[1][0] - A[0][0] * A[1][2];
+    C[2][0] = A[1][0] * A[2][1] - A[1][1] * A[2][0]; C[2][1] = A[0][1] * A[2][0] - A[0][0] * A[2][1]; C[2][2] = A[0][0] * A[1][1] - A[0][1] * A[1][0];
+    const double det = A[0][0] * C[0][0] + A[0][1] * C[1][0] + A[0][2] * C[2][0];
+    bool   ok = det != 0.0 && std::isfinite(det);
+    double norm_a = 0.0, norm_i = 0.0, extent = 0.0;
+    const float* am = &s->shared_mesh_absmax[(size_t)k * 3];
+    for (int q = 0; q < 3; q++)
+    {
+        double ra = 0.0, ri = 0.0;
+        for (int c = 0; c < 3; c++)
+        {
+            const double v = ok ? C[q][c] / det : 0.0;
+            r.inv[c * 3 + q] = (float)v;
+            ok = ok && std::isfinite(r.inv[c * 3 + q]);
+            ra += std::fabs(A[q][c]); ri += std::fabs(v);
+            extent += std::fabs(A[q][c]) * (double)am[c];
+        }
+        r.inv_abs_row[q] = (float)(ri * (1.0 + 1e-6));
+        extent += std::fabs((double)h.m[12 + q]);
+        norm_a = std::max(norm_a, ra); norm_i = std::max(norm_i, ri);
+    }
+    r.extent = (float)(extent * (1.0 + 1e-6));
+    // beyond a condition number of 1e7 the fp32 inverse says little about where the ray is: walk the mesh without culling (slow, rare, correct)
+    ok = ok && std::isfinite(r.extent) && std::isfinite(r.inv_abs_row[0]) && std::isfinite(r.inv_abs_row[1]) && std::isfinite(r.inv_abs_row[2]) && norm_a * norm_i <= 1e7;
+    if (!ok)
+    {
+        for (int q = 0; q < 9; q++) r.inv[q] = 0.0f;
+        r.inv_abs_row[0] = r.inv_abs_row[1] = r.inv_abs_row[2] = 0.0f; r.extent = 0.0f;
+        r.flags = 1u;
+    }
+}
+
+void adopt_shared_top(hr_scene* s, const SharedTop& tl)
+{
+    s->shared_top = tl.nodes;
+    s->shared_leaf_inst = tl.leaf_inst;
+    s->shared_leaf_of.assign((size_t)s->n_instances, 0);
+    for (size_t l = 0; l < tl.leaf_inst.size(); l++) s->shared_leaf_of[(size_t)tl.leaf_inst[l]] = (int32_t)l;
+    s->info.max_depth = tl.max_depth + 1 + s->shared_mesh_depth;
+}
+
+float world_pad(const hr_scene* s)
+{
+    const double dx = (double)s->grid_hi[0] - s->grid_lo[0], dy = (double)s->grid_hi[1] - s->grid_lo[1], dz = (double)s->grid_hi[2] - s->grid_lo[2];
+    float pad = (float)(3e-5 * std::sqrt(dx * dx + dy * dy + dz * dz));   // bvh_build.cpp: well above the fp32 error of the triangle test
+    return pad > 0.0f ? pad : 1e-6f;
+}
+
+hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out)
+{
+    HR_CHECK_ARG(ctx && out);
+    hr_status st = validate_desc(d, "hr_scene_create_instanced_shared");
+    if (st != HR_OK) return st;
+    HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
+    const int M = d->n_meshes, I = d->n_instances;
+    bool all_normals = true, any_normals = false, all_mat = true, any_mat = false, all_uv = true, all_tan = true;
+    for (int k = 0; k < M; k++)
+    {
+        const hr_mesh_desc& me = d->meshes[k];
+        all_normals = all_normals && me.normals; any_normals = any_normals || me.normals;
+        all_mat = all_mat && me.tri_material; any_mat = any_mat || me.tri_material;
+        all_uv = all_uv && me.uvs; all_tan = all_tan && me.tangents;
+        if (me.tri_material)
+        {
+            if (!d->materials) { set_last_error("hr_scene_create_instanced_shared: tri_material given without materials"); return HR_ERR_INVALID_ARG; }
+            for (int i = 0; i < me.n_tris; i++)
+                if (me.tri_material[i] >= (uint32_t)d->n_materials) { set_last_error("hr_scene_create_instanced_shared: a tri_material entry >= n_materials"); return HR_ERR_INVALID_ARG; }
+        }
+    }
+    if (any_normals && !all_normals) { set_last_error("hr_scene_create_instanced_shared: vertex normals on some meshes only"); return HR_ERR_INVALID_ARG; }
+    if (any_mat && !all_mat) { set_last_error("hr_scene_create_instanced_shared: tri_material on some meshes only"); return HR_ERR_INVALID_ARG; }
+    HR_HIP(hipSetDevice(ctx->device));
+
+    MeshTrees mt;
+    build_mesh_trees(d, mt, false);
+    std::unique_ptr<hr_scene> guard(new hr_scene());
+    hr_scene* s = guard.get();
+    s->ctx = ctx; s->shared = true;
+    fill_instances(s, d, mt);
+    s->top_cap = std::max(1, I);
+    uint64_t n_nodes64 = (uint64_t)s->top_cap, n_refs64 = 0, n_tris64 = 0;
+    for (int k = 0; k < M; k++) { n_nodes64 += mt.blas[(size_t)k].nodes.size(); n_refs64 += mt.blas[(size_t)k].tris.size(); }
+    for (int i = 0; i < I; i++) n_tris64 += s->inst_host[(size_t)i].n_tris;
+    if (n_tris64 >= (1ull << 31) || n_refs64 >= (1ull << 31)) { set_last_error("hr_scene_create_instanced_shared: more than 2^31 triangles"); return HR_ERR_UNSUPPORTED; }
+    if (n_nodes64 >= (1ull << 23)) { set_last_error("hr_scene_create_instanced_shared: more than 2^23 BVH nodes"); return HR_ERR_UNSUPPORTED; }
+    const size_t n_nodes = (size_t)n_nodes64;
+    std::vector<Node8>  nodes(n_nodes);
+    std::vector<TriGPU> tris((size_t)n_refs64);
+    std::memset(nodes.data(), 0, n_nodes * sizeof(Node8));
+    s->shared_mesh_root.resize((size_t)M);
+    s->shared_mesh_absmax.assign((size_t)M * 3, 0.0f);
+    s->shared_mesh_depth = 0;
+    size_t node_at = (size_t)s->top_cap, ref_at = 0;
+    for (int k = 0; k < M; k++)
+    {
+        const BuiltBVH& b = mt.blas[(size_t)k];
+        s->shared_mesh_root[(size_t)k] = (uint32_t)node_at;
+        s->shared_mesh_depth = std::max(s->shared_mesh_depth, mt.depth[(size_t)k]);
+        if (d->meshes[k].n_tris > 0)
+            for (int a = 0; a < 3; a++) s->shared_mesh_absmax[(size_t)k * 3 + a] = std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]));
+        for (size_t j = 0; j < b.nodes.size(); j++)
+        {
+            Node8 n = b.nodes[j];
+            if (n.counts & 15) n.child_base += (uint32_t)node_at;
+            n.tri_base += (uint32_t)ref_at;
+            nodes[node_at + j] = n;
+        }
+        std::copy(b.tris.begin(), b.tris.end(), tris.begin() + ref_at);   // prim stays mesh-local
+        node_at += b.nodes.size(); ref_at += b.tris.size();
+    }
+    instanced_scene_boxes(s);
+    SharedTop tl;
+    build_shared_top(s, tl);
+    if (!shared_top_fits(s, tl)) { set_last_error("hr_scene_create_instanced_shared: top level + deepest mesh tree exceed the traversal stack"); return HR_ERR_UNSUPPORTED; }
+    adopt_shared_top(s, tl);
+
+    size_t mesh_tris = 0;
+    for (int k = 0; k < M; k++) mesh_tris += (size_t)d->meshes[k].n_tris;
+    std::vector<float>    mpos(mesh_tris * 9), mnor(all_normals ? mesh_tris * 9 : 0), muv(all_uv ? mesh_tris * 6 : 0), mtan(all_tan ? mesh_tris * 9 : 0);
+    std::vector<uint32_t> mmat(all_mat ? mesh_tris : 0);
+    {
+        size_t o = 0;
+        for (int k = 0; k < M; k++)
+        {
+            const hr_mesh_desc& me = d->meshes[k];
+            const size_t n = (size_t)me.n_tris;
+            if (n == 0) continue;
+            std::memcpy(&mpos[o * 9], me.positions, n * 36);
+            if (all_normals) std::memcpy(&mnor[o * 9], me.normals, n * 36);
+            if (all_mat) std::memcpy(&mmat[o], me.tri_material, n * 4);
+            if (all_uv) std::memcpy(&muv[o * 6], me.uvs, n * 24);
+            if (all_tan) std::memcpy(&mtan[o * 9], me.tangents, n * 36);
+            o += n;
+        }
+    }
+#define UP(buf, src, nbytes)                                                                     \
+    if ((st = s->buf.alloc(nbytes)) != HR_OK) return st;                                         \
+    if ((nbytes) > 0) { hipError_t e_ = hipMemcpy(s->buf.p, src, nbytes, hipMemcpyHostToDevice); \
+        if (e_ != hipSuccess) { set_last_error(std::string("hipMemcpy H2D failed: ") + hipGetErrorString(e_)); return HR_ERR_HIP; } }
+    UP(nodes, nodes.data(), n_nodes * sizeof(Node8))
+    UP(tris, tris.data(), tris.size() * sizeof(TriGPU))
+    UP(mesh_positions, mpos.data(), mesh_tris * 36)
+    UP(materials, d->materials, d->materials ? (size_t)d->n_materials * 32 : 0)
+    if (all_normals) { UP(mesh_normals, mnor.data(), mesh_tris * 36) s->has_normals = true; }
+    if (all_mat) { UP(mesh_material, mmat.data(), mesh_tris * 4) s->has_material = true; }
+    // textured materials: nothing that takes a shared scene today reads them (queries, G-buffer synthesiser, shadows); they are kept, per mesh
+    // like the other attributes, for the hit shading of the passes that follow (same checks and layout as hr_scene_create_instanced)
+    if (d->material_textures && d->materials && d->n_textures > 0 && d->textures)
+    {
+        std::vector<uint32_t> table;
+        std::vector<uint8_t>  texels;
+        for (int i = 0; i < d->n_textures; i++)
+        {
+            const hr_texture& t = d->textures[i];
+            if (!t.rgba8 || t.width <= 0 || t.height <= 0) { set_last_error("hr_scene_create_instanced_shared: empty texture"); return HR_ERR_INVALID_ARG; }
+            table.insert(table.end(), { (uint32_t)(texels.size() / 4), (uint32_t)t.width, (uint32_t)t.height, 0u });
+            texels.insert(texels.end(), t.rgba8, t.rgba8 + (size_t)t.width * t.height * 4);
+        }
+        for (int i = 0; i < d->n_materials * 4; i++)
+            if (d->material_textures[(i / 4) * 6 + (i % 4)] >= d->n_textures) { set_last_error("hr_scene_create_instanced_shared: material texture index out of range"); return HR_ERR_INVALID_ARG; }
+        UP(mat_tex, d->material_textures, (size_t)d->n_materials * 24)
+        UP(tex_table, table.data(), table.size() * 4)
+        UP(tex_data, texels.data(), texels.size())
+        if (all_uv) { UP(mesh_uvs, muv.data(), mesh_tris * 24) s->has_uvs = true; }
+        if (all_tan) { UP(mesh_tangents, mtan.data(), mesh_tris * 36) s->has_tangents = true; }
+        s->has_textures = true;
+    }
+#undef UP
+    s->has_mesh_id = true;
+    if ((st = s->inst_shared.alloc((size_t)I * sizeof(InstanceShared))) != HR_OK) return st;
+    s->n_materials = d->materials ? d->n_materials : 0;
+    { static std::atomic<uint64_t> next_uid { 1ull << 41 }; s->uid = next_uid.fetch_add(1); }   // disjoint from the other kinds' counters
+    if (const char* e = getenv("HR_TOP_LEVEL_REBUILD")) s->auto_rebuild = atoi(e) != 0;
+    s->info.n_tris     = (int32_t)n_tris64;
+    s->info.n_nodes    = (int32_t)n_nodes;
+    s->info.node_bytes = n_nodes * sizeof(Node8);
+    s->info.tri_bytes  = tris.size() * sizeof(TriGPU);
+    // first update: the instances' own matrices, then wait (creation is synchronous like hr_scene_create)
+    std::vector<float> mats((size_t)I * 16);
+    for (int i = 0; i < I; i++) std::memcpy(&mats[(size_t)i * 16], d->instances[i].model_matrix, 64);
+    s->top_area_at_build = -1.0;   // the first update records it
+    if ((st = shared_scene_update(s, mats.data(), nullptr, false)) != HR_OK) return st;
+    HR_HIP(hipStreamSynchronize(nullptr));
+    s->geometry_epoch = 0;
+    *out = guard.release();
+    return HR_OK;
+}
+
+hr_status footprint_impl(const hr_instanced_scene_desc* d, int32_t shared, hr_scene_info* info)
+{
+    HR_CHECK_ARG(info);
+    hr_status st = validate_desc(d, "hr_instanced_scene_footprint");
+    if (st != HR_OK) return st;
+    std::memset(info, 0, sizeof(*info));
+    MeshTrees mt;
+    build_mesh_trees(d, mt, false);
+    hr_scene stub;
+    fill_instances(&stub, d, mt);
+    const int I = d->n_instances, M = d->n_meshes;
+    uint64_t n_tris = 0, n_nodes = 0, n_refs = 0;
+    std::vector<int> inst_depth((size_t)I);
+    for (int i = 0; i < I; i++)
+    {
+        const BuiltBVH& b = mt.blas[stub.inst_mesh[(size_t)i]];
+        n_tris += stub.inst_host[(size_t)i].n_tris;
+        inst_depth[(size_t)i] = mt.depth[stub.inst_mesh[(size_t)i]];
+        stub.max_rel_depth = std::max(stub.max_rel_depth, inst_depth[(size_t)i]);
+        if (!shared) { n_nodes += b.nodes.size() - 1; n_refs += b.tris.size(); }
+    }
+    if (shared)
+    {
+        stub.top_cap = std::max(1, I);
+        for (int k = 0; k < M; k++) { n_nodes += mt.blas[(size_t)k].nodes.size(); n_refs += mt.blas[(size_t)k].tris.size(); stub.shared_mesh_depth = std::max(stub.shared_mesh_depth, mt.depth[(size_t)k]); }
+    }
+    else
+        stub.top_cap = I > 1 ? 2 * I : 1;
+    n_nodes += (uint64_t)stub.top_cap;
+    info->n_tris     = (int32_t)std::min<uint64_t>(n_tris, 0x7fffffffull);
+    info->n_nodes    = (int32_t)std::min<uint64_t>(n_nodes, 0x7fffffffull);
+    info->node_bytes = n_nodes * sizeof(Node8);
+    info->tri_bytes  = n_refs * sizeof(TriGPU);
+    const char* kind = shared ? "shared" : "private-copy";
+    if (n_tris >= (1ull << 31) || n_refs >= (shared ? (1ull << 31) : (1ull << 26)))
+    {
+        set_last_error(std::string("hr_instanced_scene_footprint: a ") + kind + " scene of this desc holds " + std::to_string(n_refs) + " triangle references (limit " + (shared ? "2^31" : "2^26") + ")");
+        return HR_ERR_UNSUPPORTED;
+    }
+    if (n_nodes >= (1ull << 23)) { set_last_error(std::string("hr_instanced_scene_footprint: more than 2^23 BVH nodes in a ") + kind + " scene"); return HR_ERR_UNSUPPORTED; }
+    bool fits;
+    if (shared)
+    {
+        instanced_scene_boxes(&stub);
+        SharedTop tl;
+        build_shared_top(&stub, tl);
+        info->max_depth = tl.max_depth + 1 + stub.shared_mesh_depth;
+        fits = shared_top_fits(&stub, tl);
+    }
+    else
+    {
+        info->max_depth = private_copy_top_depth(&stub, inst_depth);
+        fits = info->max_depth + 1 < kMaxTraversalDepth;
+    }
+    for (int a = 0; a < 3; a++) { info->bounds_lo[a] = stub.grid_lo[a]; info->bounds_hi[a] = stub.grid_hi[a]; }
+    info->box_pad = world_pad(&stub);
+    if (!fits) { set_last_error(std::string("hr_instanced_scene_footprint: BVH depth of a ") + kind + " scene exceeds the traversal stack"); return HR_ERR_UNSUPPORTED; }
+    return HR_OK;
+}
+
+} // namespace
+
+bool hr::reject_shared_scene(const hr_scene* s, const char* pass)
+{
+    if (!s || !s->shared) return false;
+    set_last_error(std::string(pass) + ": a shared instanced scene (hr_scene_create_instanced_shared) is not supported by this pass yet; use hr_scene_create_instanced");
+    return true;
+}
+
+// matrices == nullptr: the standing ones (force_rebuild: hr_scene_rebuild_top_level)
+hr_status hr::shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild)
+{
+    const int I = s->n_instances;
+    const bool first = s->top_area_at_build < 0.0;
+    bool any = first || force_rebuild;
+    if (matrices)
+        for (int i = 0; i < I; i++)
+        {
+            if (!finite_matrix(matrices + (size_t)i * 16)) { set_last_error("hr_scene_update_instances: model_matrices[" + std::to_string(i) + "] is not finite"); return HR_ERR_INVALID_ARG; }
+            any = any || std::memcmp(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64) != 0;
+        }
+    if (!any) return HR_OK;
+    HR_HIP(hipSetDevice(s->ctx->device));
+    {
+        const hr_status ws = instanced_scene_wait_uploads(s);   // the staging vectors below may still feed the previous call's copies
+        if (ws != HR_OK) return ws;
+    }
+    if (matrices)
+        for (int i = 0; i < I; i++) std::memcpy(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64);
+    instanced_scene_boxes(s);
+    s->info.box_pad = world_pad(s);
+    for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a]; s->info.bounds_hi[a] = s->grid_hi[a]; }   // conservative: no vertex is ever transformed here
+    SharedTop cur;
+    cur.nodes = s->shared_top; cur.leaf_inst = s->shared_leaf_inst;
+    double area = refit_shared_top(s, cur, s->info.box_pad, s->top_nodes_host);
+    // the top level is re-built when the instances have moved far enough for its boxes to overlap (instances.hip: the same trigger), or on demand
+    if (I > 1 && (force_rebuild || (!first && s->auto_rebuild && area > s->rebuild_ratio * s->top_area_at_build)))
+    {
+        SharedTop fresh;
+        build_shared_top(s, fresh);
+        if (shared_top_fits(s, fresh))   // checked on EVERY re-build: a deeper top level than the stack can hold is never adopted
+        {
+            std::vector<Node8> fresh_nodes;
+            const double fresh_area = refit_shared_top(s, fresh, s->info.box_pad, fresh_nodes);
+            if (force_rebuild || fresh_area < 0.9 * area)
+            {
+                adopt_shared_top(s, fresh);
+                s->top_nodes_host.swap(fresh_nodes);
+                s->top_rebuilds++;
+                area = fresh_area;
+            }
+        }
+        s->top_area_at_build = area;   // adopted: the fresh one's; otherwise the spread is the new normal
+    }
+    if (first) s->top_area_at_build = area;
+    s->shared_host.resize((size_t)I);
+    for (int i = 0; i < I; i++) fill_record(s, i, s->shared_host[(size_t)s->shared_leaf_of[(size_t)i]]);
+    HR_HIP(hipMemcpyAsync(s->nodes.p, s->top_nodes_host.data(), (size_t)s->top_cap * sizeof(Node8), hipMemcpyHostToDevice, st));
+    HR_HIP(hipMemcpyAsync(s->inst_shared.p, s->shared_host.data(), (size_t)I * sizeof(InstanceShared), hipMemcpyHostToDevice, st));
+    {
+        const hr_status ms = instanced_scene_mark_uploads(s, st);
+        if (ms != HR_OK) return ms;
+    }
+    s->geometry_epoch++;
+    return HR_OK;
+}
+
+extern "C" {
+
+hr_status hr_scene_create_instanced_shared(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out)
+{
+    try
+    {
+        return create_shared_impl(ctx, desc, out);
+    }
+    catch (const std::bad_alloc&)
+    {
+        set_last_error("hr_scene_create_instanced_shared: host allocation failed");
+        return HR_ERR_OUT_OF_MEMORY;
+    }
+    catch (const std::exception& e)
+    {
+        set_last_error(std::string("hr_scene_create_instanced_shared: ") + e.what());
+        return HR_ERR_UNSUPPORTED;
+    }
+}
+
+int32_t hr_scene_is_shared(const hr_scene* scene) { return scene && scene->shared ? 1 : 0; }
+
+hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info)
+{
+    try
+    {
+        return footprint_impl(desc, shared, info);
+    }
+    catch (const std::bad_alloc&)
+    {
+        set_last_error("hr_instanced_scene_footprint: host allocation failed");
+        return HR_ERR_OUT_OF_MEMORY;
+    }
+    catch (const std::exception& e)
+    {
+        set_last_error(std::string("hr_instanced_scene_footprint: ") + e.what());
+        return HR_ERR_UNSUPPORTED;
+    }
+}
+
+} // extern "C"

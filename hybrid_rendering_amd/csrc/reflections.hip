@@ -557,6 +557,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
                                    const hr_reflections_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && in && env && ddgi && prm && env->sky && env->sky_size > 0);
+    HR_REJECT_SHARED(scene, "hr_reflections_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
     hipStream_t st = (hipStream_t)stream_;
@@ -790,6 +791,7 @@ hr_status hr_reflections_render(hr_reflections* p, const hr_scene* scene, const 
 {
     HR_SCOPED_SAMPLE("Ray Traced Reflections");
     HR_CHECK_ARG(p && scene && in && env && ddgi && prm);
+    HR_REJECT_SHARED(scene, "hr_reflections_render");
     HR_HIP(hipSetDevice(p->ctx->device));
     p->prof.begin_frame();
     p->last_denoise = prm->denoise != 0;

@@ -8,6 +8,7 @@
 #include "hr_internal.h"
 #include "reproject.h"
 #include "traverse.h"
+#include "traverse2.h"
 #include "shading.h"
 #include "upsample.h"
 #include "pass_args.h"
@@ -160,6 +161,64 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             atomicAdd(a.stats + 0, (unsigned long long)nn);
             atomicAdd(a.stats + 1, (unsigned long long)nt);
             atomicAdd(a.stats + 2, (unsigned long long)wave_max);
+        }
+    }
+}
+
+// k_shadows_trace over a SHARED instanced scene (instances_shared.hip): the same pixel -> ray set-up, the two-level walk of traverse2.h.  The
+// occluder cache is off here (it stores an index into a world-space `tris`); the mask does not depend on it.  A kernel of its own, so that
+// k_shadows_trace compiles to what it did before.
+__global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_trace_shared(TraceArgs a, Scene2 sc)
+{
+    __shared__ uint32_t s_stack[TRACE_WAVES][HR_STACK_ENTRIES * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int launch_slot = blockIdx.x * TRACE_WAVES + wave;
+    if (launch_slot >= a.tiles_x * a.tiles_y) return;
+    const int slot = a.order ? (int)a.order[launch_slot] : launch_slot;
+    const int tx = slot % a.tiles_x, ty_local = slot / a.tiles_x, ty = ty_local + a.tile_y0;
+    unsigned long long t_begin = 0;
+    if (a.cost) t_begin = wall_clock64();
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    bool      lit = false, fired = false;
+    const int    kind = trace_lane_kind(x, y, a.w, a.h, a.y0, a.y1);
+    const size_t pix  = kind == 1 ? (size_t)y * a.w + x : (size_t)a.y0 * a.w;
+    const float    d_pre  = a.depth[pix];
+    const uint2    g2_pre = a.gb2[pix];
+    const uint32_t bn_pre = blue_noise_texel(x, y, a.sr);
+    if (kind)
+    {
+        const float d = kind == 1 ? d_pre : 0.0f;      // edge thread: out-of-image fetches read 0
+        if (d != 1.0f)
+        {
+            const float tu = __fdiv_rn((float)x + 0.5f, (float)a.w), tv = __fdiv_rn((float)y + 0.5f, (float)a.h);
+            const f3    P  = world_pos_from_depth(tu, tv, d, a.vpi);
+            const uint2 g2 = kind == 1 ? g2_pre : make_uint2(0u, 0u);
+            const f3    N  = oct_decode(h2f_lo(g2.x), h2f_hi(g2.x));
+            const f3    ro = add3(P, scale3(N, a.bias));
+            const float r0 = sample_blue_noise_t(bn_pre, (int)a.num_frames, 0, a.sobol);
+            const float r1 = sample_blue_noise_t(bn_pre, (int)a.num_frames, 1, a.sobol);
+            f3    Wi;
+            float t_max, att;
+            fetch_light_shadow(a.light, P, N, r0, r1, Wi, t_max, att);
+            if (att > 0.0f)
+            {
+                fired = true;
+                lit = !trace_any2(sc, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
+            }
+        }
+    }
+    const unsigned long long bits = __ballot(lit);
+    const unsigned long long fb   = __ballot(fired);
+    if (lane == 0)
+    {
+        const int my = ty * 2;
+        if (my * 4 >= a.y0 && my * 4 < a.y1) a.mask[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
+        if ((my + 1) * 4 >= a.y0 && (my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) a.mask[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
+        a.ray_slots[(size_t)ty * a.tiles_x + tx] = (uint16_t)__popcll(fb);
+        if (a.cost)
+        {
+            const unsigned long long ticks = wall_clock64() - t_begin;
+            a.cost[slot] = (uint16_t)(ticks > 65535ull ? 65535ull : ticks);
         }
     }
 }
@@ -745,6 +804,13 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     hr_status s = check_inputs(p, in, false);
     if (s != HR_OK) return s;
     HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
+    // the two-level walk has no instrumented or developer variants: statistics, timelines and the persistent-wave A/B kernel are refused for a
+    // shared instanced scene, before anything is enqueued or any state of the pass changes
+    if (scene->shared && (p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0))
+    {
+        set_last_error("hr_shadows_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
+        return HR_ERR_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     // clear_images() (ray_traced_shadows.cpp:938-968): first frame zeroes the feedback image and the
@@ -776,6 +842,17 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     if ((s = p->tile_order.flush(st)) != HR_OK) return s;   // last launch's costs, if no temporal stage took them along
     a.order = p->tile_order.order_arg(n_tiles); a.cost = p->tile_order.cost_arg(n_tiles);
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
+    if (scene->shared)
+    {
+        const Scene2 sc = { a.nodes, a.tris, (const InstanceShared*)scene->inst_shared.p };
+        a.occluder = nullptr;
+        int ev = p->prof.begin("ray_trace", st, px * 12 + px / 8);
+        hipLaunchKernelGGL(k_shadows_trace_shared, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, sc);
+        p->prof.end(ev, st);
+        HR_HIP(hipGetLastError());
+        if (a.cost && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;
+        return HR_OK;
+    }
     if (p->want_stats)
     {
         a.cost = nullptr;

@@ -64,6 +64,10 @@ public:
     // meshes + instances, as the reference's scene holds them (scene_descriptor_set.glsl:30-34); update_instances() every frame an instance
     // moved replaces main.cpp:74 build_tlas(cmd_buf)
     Scene(Context& ctx, const hr_instanced_scene_desc& desc) { check(hr_scene_create_instanced(ctx.handle(), &desc, &m_scene), "hr_scene_create_instanced"); }
+    // the shared kind (hr_scene_create_instanced_shared): one BVH per mesh walked on two levels — Scene(ctx, desc, hr::Scene::SharedInstances())
+    struct SharedInstances {};
+    Scene(Context& ctx, const hr_instanced_scene_desc& desc, SharedInstances) { check(hr_scene_create_instanced_shared(ctx.handle(), &desc, &m_scene), "hr_scene_create_instanced_shared"); }
+    bool     is_shared() const { return hr_scene_is_shared(m_scene) != 0; }
     void     update_instances(const float* model_matrices, Stream cmd_buf) { check(hr_scene_update_instances(m_scene, model_matrices, cmd_buf), "hr_scene_update_instances"); }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }
     uint64_t id() const { return hr_scene_id(m_scene); }   // dw::Scene::id()

@@ -16,6 +16,7 @@ def main():
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--shared", action="store_true", help="hr_scene_create_instanced_shared: one BVH per mesh, two-level walk")
     a = ap.parse_args()
     import torch
     from hybrid_rendering_amd import api as hr, synth
@@ -35,7 +36,7 @@ def main():
     isd = synth.InstancedSceneData(meshes=[building, cube, pyr], instances=instances(0), materials=building.materials)
     ctx = hr.Context(0)
     t0 = time.perf_counter()
-    g = hr.InstancedScene(ctx, isd)
+    g = hr.InstancedScene(ctx, isd, shared=True) if a.shared else hr.InstancedScene(ctx, isd)
     t_create = time.perf_counter() - t0
     mats = [synth.InstancedSceneData(isd.meshes, instances(f), isd.materials).matrices() for f in range(a.frames + 1)]
     for m in mats[:3]:
@@ -79,6 +80,8 @@ def main():
     res["shadow_trace_ms_refitted"] = round(out["refitted"][1]["ray_trace"], 4)
     res["shadow_trace_ms_rebuilt"] = round(out["rebuilt"][1]["ray_trace"], 4)
     res["masks_equal"] = True
+    if a.shared:
+        res["kind"] = "shared"
     print(json.dumps(res))
 
 
