@@ -98,6 +98,7 @@ ABI_SYMBOLS = [
     "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_bvh_child_boxes", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
     "hr_selftest_math_sweep", "hr_selftest_fast_math",
     "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint",
+    "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
 ]
 
 _lib = None
@@ -178,10 +179,12 @@ class Context:
 
 
 class Scene:
-    """Replaces dw::RayTracedScene: host triangles -> compressed 8-wide BVH in HBM."""
+    """Replaces dw::RayTracedScene: host triangles -> compressed 8-wide BVH in HBM.
+    ``deformable=True``: hr_scene_create_deformable — the same scene to every pass, built without spatial splits, whose vertices
+    ``update_vertices`` replaces on the GPU (the BVH is refitted; ``refit_cost`` / ``rebuild`` for when the refitted tree has gone bad)."""
 
-    def __init__(self, ctx: Context, sd):
-        self.ctx = ctx
+    def __init__(self, ctx: Context, sd, deformable: bool = False):
+        self.ctx, self.deformable = ctx, bool(deformable)
         self._keep = [np.ascontiguousarray(sd.verts, np.float32), None if sd.normals is None else np.ascontiguousarray(sd.normals, np.float32),
                       np.ascontiguousarray(sd.tri_material, np.uint32), np.ascontiguousarray(sd.tri_mesh_id, np.uint32),
                       np.ascontiguousarray(sd.materials, np.float32)]
@@ -197,7 +200,10 @@ class Scene:
             d.uvs, d.tangents = (uv.ctypes.data if uv is not None else None), (tg.ctypes.data if tg is not None else None)
             d.material_textures, d.textures, d.n_textures = mt.ctypes.data, arr, len(tex)
         self.h = C.c_void_p()
-        _check(lib().hr_scene_create(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create")
+        if deformable:
+            _check(lib().hr_scene_create_deformable(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_deformable")
+        else:
+            _check(lib().hr_scene_create(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create")
         self.info = hr_scene_info()
         _check(lib().hr_scene_get_info(self.h, C.byref(self.info)), "hr_scene_get_info")
 
@@ -221,6 +227,31 @@ class Scene:
     def refresh_info(self):
         _check(lib().hr_scene_get_info(self.h, C.byref(self.info)), "hr_scene_get_info")
         return self.info
+
+    def update_vertices(self, positions, normals=None, first_tri: int = 0, stream=None):
+        """hr_scene_update_vertices: ``positions`` (and ``normals``, None: keep) are cuda float32 tensors [n,3,3] for the original triangles
+        [first_tri, first_tri + n); enqueued on ``stream`` (default: torch's current stream), no host synchronisation"""
+        import torch
+        assert positions.is_cuda and positions.dtype == torch.float32 and positions.shape[1:] == (3, 3), "positions: cuda float32 [n,3,3]"
+        positions = positions.contiguous()
+        if normals is not None:
+            assert normals.is_cuda and normals.dtype == torch.float32 and normals.shape == positions.shape, "normals: cuda float32, the shape of positions"
+            normals = normals.contiguous()
+        L = lib()
+        L.hr_scene_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        _check(L.hr_scene_update_vertices(self.h, _ptr(positions), _ptr(normals), C.c_int32(first_tri), C.c_int32(positions.shape[0]), _stream_ptr(stream)),
+               "hr_scene_update_vertices")
+
+    def refit_cost(self) -> float:
+        """hr_scene_refit_cost: sum of the BVH nodes' half areas after the last update / as built (1.0: as built)"""
+        r = C.c_float(0.0)
+        _check(lib().hr_scene_refit_cost(self.h, C.byref(r)), "hr_scene_refit_cost")
+        return float(r.value)
+
+    def rebuild(self, stream=None):
+        """hr_scene_rebuild: the slow path — host build over the current vertices; synchronises"""
+        _check(lib().hr_scene_rebuild(self.h, _stream_ptr(stream)), "hr_scene_rebuild")
+        self.refresh_info()
 
     def any_hit(self, rays, stats=False, stream=None):
         """rays: cuda float32 [n,8] (origin, t_max, dir, t_min) -> uint8 [n] (1 = occluded)."""
@@ -316,11 +347,13 @@ class InstancedScene(Scene):
         _check(lib().hr_scene_update_instances(self.h, m.ctypes.data_as(C.POINTER(C.c_float)), _stream_ptr(stream)), "hr_scene_update_instances")
 
 
-def bvh_build_info(verts) -> hr_scene_info:
-    """Host-only BVH build (no GPU): the shape hr_scene_create would produce for triangles ``verts`` [n,3,3]."""
+def bvh_build_info(verts, deformable: bool = False) -> hr_scene_info:
+    """Host-only BVH build (no GPU): the shape hr_scene_create (``deformable``: hr_scene_create_deformable, no spatial splits) would produce
+    for triangles ``verts`` [n,3,3]."""
     v = np.ascontiguousarray(verts, np.float32)
     info = hr_scene_info()
-    _check(lib().hr_bvh_build_info(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.byref(info)), "hr_bvh_build_info")
+    fn, name = (lib().hr_bvh_build_info_deformable, "hr_bvh_build_info_deformable") if deformable else (lib().hr_bvh_build_info, "hr_bvh_build_info")
+    _check(fn(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.byref(info)), name)
     return info
 
 

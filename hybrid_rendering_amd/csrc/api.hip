@@ -572,17 +572,18 @@ hr_status hr_ctx_destroy(hr_ctx* ctx)
 
 int32_t hr_ctx_device(const hr_ctx* ctx) { return ctx ? ctx->device : -1; }
 
-static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out);
+
+static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable);
 
 // Host-only: build the 8-wide BVH of a triangle soup and report its shape (no device, no upload).  What hr_scene_create
 // would build for the same positions — lets an integrator (and the CPU test-suite) check depth / size limits up front.
-hr_status hr_bvh_build_info(const float* positions, int32_t n_tris, hr_scene_info* info)
+static hr_status build_info_impl(const float* positions, int32_t n_tris, hr_scene_info* info, bool spatial, const char* call)
 {
     HR_CHECK_ARG(info && n_tris >= 0 && (positions || n_tris == 0));
     try
     {
         BuiltBVH b;
-        build_bvh8(positions, n_tris, b);
+        build_bvh8(positions, n_tris, b, spatial);
         std::memset(info, 0, sizeof(*info));
         info->n_tris     = n_tris;
         info->n_nodes    = (int32_t)b.nodes.size();
@@ -595,15 +596,19 @@ hr_status hr_bvh_build_info(const float* positions, int32_t n_tris, hr_scene_inf
     }
     catch (const std::bad_alloc&)
     {
-        set_last_error("hr_bvh_build_info: host allocation failed");
+        set_last_error(std::string(call) + ": host allocation failed");
         return HR_ERR_OUT_OF_MEMORY;
     }
     catch (const std::exception& e)   // nothing else is expected; no exception may cross the C ABI
     {
-        set_last_error(std::string("hr_bvh_build_info: ") + e.what());
+        set_last_error(std::string(call) + ": " + e.what());
         return HR_ERR_UNSUPPORTED;
     }
 }
+
+hr_status hr_bvh_build_info(const float* positions, int32_t n_tris, hr_scene_info* info) { return build_info_impl(positions, n_tris, info, true, "hr_bvh_build_info"); }
+// the split-free tree hr_scene_create_deformable / hr_scene_rebuild build: tri_bytes = 48 x the finite triangles
+hr_status hr_bvh_build_info_deformable(const float* positions, int32_t n_tris, hr_scene_info* info) { return build_info_impl(positions, n_tris, info, false, "hr_bvh_build_info_deformable"); }
 
 // Host-only: builds the same BVH and checks that every triangle is found from every point of its surface (bvh.h
 // check_bvh8_coverage) — the invariant the spatial splits of the builder have to keep.
@@ -682,7 +687,7 @@ hr_status hr_scene_create(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out)
 {
     try
     {
-        return scene_create_impl(ctx, d, out);
+        return scene_create_impl(ctx, d, out, false);
     }
     catch (const std::bad_alloc&)
     {
@@ -696,7 +701,7 @@ hr_status hr_scene_create(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out)
     }
 }
 
-static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out)
+static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable)
 {
     HR_CHECK_ARG(ctx && d && out && d->n_tris >= 0 && (d->positions || d->n_tris == 0));
     HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
@@ -713,7 +718,7 @@ static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene
     }
     HR_HIP(hipSetDevice(ctx->device));
     BuiltBVH b;
-    build_bvh8(d->positions, d->n_tris, b);
+    build_bvh8(d->positions, d->n_tris, b, !deformable);
     if (b.nodes.size() >= (1u << 23))   // traversal stack entries hold child_base in 23 bits
     {
         set_last_error("hr_scene_create: more than 2^23 BVH nodes");
@@ -780,6 +785,7 @@ static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene
     s->info.tri_bytes   = b.tris.size() * sizeof(TriGPU);
     s->info.box_pad     = b.pad;
     for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a] = b.lo[a]; s->info.bounds_hi[a] = s->grid_hi[a] = b.hi[a]; }
+    if (deformable && (st = deformable_scene_adopt(s, b)) != HR_OK) return st;
     *out = guard.release();
     return HR_OK;
 }
@@ -812,6 +818,11 @@ hr_status hr_scene_get_info(const hr_scene* scene, hr_scene_info* info)
     if (scene->n_instances > 0 && !scene->shared)   // a shared scene transforms no vertex: its bounds are the host's conservative ones
     {
         const hr_status s = instanced_scene_refresh_bounds(scene);   // the exact bounds of the last hr_scene_update_instances, read back on demand
+        if (s != HR_OK) return s;
+    }
+    if (scene->deformable)
+    {
+        const hr_status s = deformable_scene_refresh_bounds(scene);   // the exact bounds of the last hr_scene_update_vertices
         if (s != HR_OK) return s;
     }
     *info = scene->info;
@@ -909,3 +920,5 @@ hr_status hr_gbuffer_raycast(const hr_scene* scene, const hr_ubo* ubo, int32_t w
 }
 
 } // extern "C"
+
+hr_status hr::scene_create_flat(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable) { return scene_create_impl(ctx, d, out, deformable); }

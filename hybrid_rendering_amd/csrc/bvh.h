@@ -91,7 +91,9 @@ struct BuiltBVH
 };
 
 // positions: [n][3][3].  Deterministic: the result does not depend on the number of builder threads (HR_BVH_THREADS, default min(hardware, 16)).
-void build_bvh8(const float* positions, int n_tris, BuiltBVH& out);
+// spatial = false (deformable scenes, deform.hip): no spatial splits and no early split clipping, whatever the developer switches say — every finite
+// triangle then has exactly one reference and a leaf's box is the bounds of its triangles plus the pad.
+void build_bvh8(const float* positions, int n_tris, BuiltBVH& out, bool spatial = true);
 
 // Host-side self-check (bvh_build.cpp): number of (triangle, sample point) pairs that reach no leaf holding the triangle — 0 for a
 // correct tree.

@@ -658,7 +658,7 @@ inline uint8_t exponent_for(float extent)
 
 } // namespace
 
-void build_bvh8(const float* positions, int n_tris, BuiltBVH& out)
+void build_bvh8(const float* positions, int n_tris, BuiltBVH& out, bool spatial)
 {
     out.nodes.clear();
     out.child_boxes.clear();
@@ -699,6 +699,7 @@ void build_bvh8(const float* positions, int n_tris, BuiltBVH& out)
     }
     double split_fraction = 0.0;
     if (const char* e = getenv("HR_BVH_SPLIT")) split_fraction = atof(e);
+    if (!spatial) split_fraction = 0.0;
     const float limit = split_fraction > 0.0 ? (float)(diag * split_fraction) : FLT_MAX;
     std::vector<Ref> refs;
     refs.reserve((size_t)n_tris + n_tris / 4);
@@ -729,6 +730,7 @@ void build_bvh8(const float* positions, int n_tris, BuiltBVH& out)
     B.bvh2_leaf = getenv("HR_BVH_GREEDY") ? kMaxLeaf : 1;
     if (const char* e = getenv("HR_BVH_SAH_DEPTH")) { const int v = atoi(e); if (v >= 0 && v < Builder::kSahDepth) B.sah_depth = v; }
     if (const char* e = getenv("HR_BVH_SBVH")) B.spatial = atoi(e) != 0;
+    if (!spatial) B.spatial = false;   // the caller's argument wins over the developer switch
     if (const char* e = getenv("HR_BVH_ALPHA")) B.alpha = atof(e);
     double budget_fraction = 0.3;
     if (const char* e = getenv("HR_BVH_BUDGET")) budget_fraction = atof(e);

@@ -74,6 +74,11 @@ bool      finite_matrix(const float* m);
 bool      reject_shared_scene(const hr_scene* s, const char* pass);
 #define HR_REJECT_SHARED(scene, pass) do { if (::hr::reject_shared_scene(scene, pass)) return HR_ERR_UNSUPPORTED; } while (0)
 hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild);
+// api.hip: hr_scene_create (deformable = false) and hr_scene_create_deformable (the builder runs without spatial splits, then deformable_scene_adopt)
+hr_status scene_create_flat(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable);
+// deform.hip: what a refit needs, for a scene that holds the uploaded tree `b`; the exact bounds of the last hr_scene_update_vertices, read back on demand
+hr_status deformable_scene_adopt(hr_scene* s, const BuiltBVH& b);
+hr_status deformable_scene_refresh_bounds(const hr_scene* scene);
 
 struct DevBuf
 {
@@ -303,5 +308,12 @@ struct hr_scene
     std::vector<float>    shared_mesh_absmax;     // per mesh: max |p_k| over its bounds, per axis
     std::vector<uint32_t> shared_mesh_root;       // per mesh: node index of its root
     int           shared_mesh_depth = 0;          // deepest mesh tree (levels below its root)
+    // ---- deformable scenes (deform.hip): a flat scene built without spatial splits; hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`
+    // and refits `nodes` through level_nodes / level_offsets / node_box (the arrays of the instanced scenes' refit)
+    bool          deformable = false;
+    hr::DevBuf    tri_ref, cost_partials;         // per original triangle: index of its one reference (-1: none); per refit workgroup: sum of its nodes' half areas
+    int           n_cost_partials = 0;
+    double        cost_at_build = 0.0, cost_ratio = 1.0;   // the sum of the slots when the tree was built / last ratio read back
+    bool          cost_stale = false;             // cost_ratio lags the last update until hr_scene_refit_cost reads the slots back
     mutable bool  bounds_stale = false;           // info.bounds_* lag the last update until hr_scene_get_info reads them back
 };

@@ -363,6 +363,86 @@ def cornell32() -> SceneData:
     return sc
 
 
+DEFORM_KINDS = ("wave", "twist", "collapse", "identity")
+
+
+def deform(sd: SceneData, frame: int, kind: str) -> SceneData:
+    """Frame ``frame`` of a deformation of ``sd`` (always computed from ``sd`` itself, frame 0 of every kind but "wave" is ``sd``): a new SceneData
+    with the same topology — triangle count and order, materials, mesh ids, uvs — for hr_scene_update_vertices and its tests.
+    "wave": a sine travelling along the longest axis, displacing along the shortest, amplitude max(a quarter of the shortest extent, 5 % of the
+    longest) — boxes left where they were would miss the surface; "twist": a rotation about the vertical axis through the centre that grows with
+    height and frame; "collapse": a growing share of triangles (15 % more per frame, picked by a hash of the index) shrinks towards its first
+    vertex, to a quarter of its size in the frame it is picked, to one point — exactly zero area — from the next; "identity": a copy.
+    Normals are the deformed faces' own (flat), the stored ones where a face has no area."""
+    assert kind in DEFORM_KINDS, kind
+    v = np.array(sd.verts, np.float32, copy=True)
+    n = v.shape[0]
+    lo, hi = (v.reshape(-1, 3).min(0), v.reshape(-1, 3).max(0)) if n else (np.zeros(3, np.float32), np.zeros(3, np.float32))
+    ext = (hi - lo).astype(np.float64)
+    if kind == "wave" and n:
+        j, k = int(np.argmax(ext)), int(np.argmin(ext))
+        if j == k:
+            k = (j + 1) % 3
+        amp = max(0.25 * ext[k], 0.05 * ext[j])
+        phase = 2.0 * np.pi * (2.0 * (v[..., j].astype(np.float64) - lo[j]) / max(ext[j], 1e-30) + 0.13 * frame)
+        v[..., k] = (v[..., k].astype(np.float64) + amp * np.sin(phase)).astype(np.float32)
+    elif kind == "twist" and n:
+        c = 0.5 * (lo.astype(np.float64) + hi)
+        ang = 0.15 * frame * (v[..., 1].astype(np.float64) - lo[1]) / max(ext[1], 1e-30)
+        x, z = v[..., 0].astype(np.float64) - c[0], v[..., 2].astype(np.float64) - c[2]
+        v[..., 0] = (c[0] + np.cos(ang) * x - np.sin(ang) * z).astype(np.float32)
+        v[..., 2] = (c[2] + np.sin(ang) * x + np.cos(ang) * z).astype(np.float32)
+    elif kind == "collapse" and n:
+        h = ((np.arange(n, dtype=np.uint64) * np.uint64(2654435761)) & np.uint64(0xffffffff)).astype(np.float64) / 4294967296.0
+        picked_at = np.floor(h / 0.15).astype(np.int64) + 1          # the first frame whose share min(1, 0.15 * frame) covers the triangle
+        age = frame - picked_at
+        quarter, point = age == 0, age >= 1
+        v0 = v[:, :1, :].copy()
+        v[quarter] = (v0[quarter] + np.float32(0.25) * (v[quarter] - v0[quarter])).astype(np.float32)
+        v[point] = np.broadcast_to(v0[point], v[point].shape)
+    nrm = np.array(sd.normals, np.float32, copy=True)
+    if n:
+        fn = np.cross(v[:, 1].astype(np.float64) - v[:, 0], v[:, 2].astype(np.float64) - v[:, 0])
+        ln = np.linalg.norm(fn, axis=1)
+        ok = ln > 1e-30
+        flip = np.sum(fn * nrm.mean(1), axis=1) < 0                   # keep the side the stored normals face
+        fn[flip] = -fn[flip]
+        nrm[ok] = (fn[ok] / ln[ok, None])[:, None, :].astype(np.float32)
+    return SceneData(v, nrm, sd.tri_material.copy(), sd.tri_mesh_id.copy(), sd.materials.copy(), f"{sd.name}:{kind}{frame}", dict(sd.meta),
+                     sd.uvs, sd.tangents, sd.material_textures, sd.textures)
+
+
+def heightfield(n: int = 64, size: float = 100.0, height: float = 12.0, seed: int = 11, strip: float = 0.0) -> SceneData:
+    """n x n cells (2 n^2 triangles) of a smooth random terrain over [0, size]^2.  ``strip`` > 0 adds that many long thin triangles per side
+    (fences across the whole field, 0.2 % of its width): input on which spatial splits pay, for tests that contrast the two builders."""
+    rng = np.random.default_rng(seed)
+    g = np.linspace(0.0, size, n + 1)
+    X, Z = np.meshgrid(g, g, indexing="ij")
+    Y = np.zeros_like(X)
+    for _ in range(6):
+        fx, fz, ph = rng.uniform(0.5, 4.0), rng.uniform(0.5, 4.0), rng.uniform(0, 6.28)
+        Y += rng.uniform(0.2, 1.0) * np.sin(2 * np.pi * (fx * X + fz * Z) / size + ph)
+    Y = (Y - Y.min()) / max(np.ptp(Y), 1e-9) * height
+    P = np.stack([X, Y, Z], -1).astype(np.float32)
+    a, b_, c, d = P[:-1, :-1], P[1:, :-1], P[1:, 1:], P[:-1, 1:]
+    tris = np.concatenate([np.stack([a, c, b_], -2).reshape(-1, 3, 3), np.stack([a, d, c], -2).reshape(-1, 3, 3)])
+    extra = []
+    for i in range(int(strip)):
+        t = size * (i + 0.5) / strip
+        w = 0.002 * size
+        extra += [[[t, 0.0, 0.0], [t + w, height * 2.0, size], [t, height * 2.0, size]], [[0.0, height * 2.0, t], [size, 0.0, t + w], [size, 0.0, t]]]
+    if extra:
+        tris = np.concatenate([tris, np.asarray(extra, np.float32)])
+    tris = np.ascontiguousarray(tris, np.float32)
+    fn = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]).astype(np.float64)
+    fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-30)
+    fn[fn[:, 1] < 0] *= -1.0
+    nrm = np.repeat(fn[:, None, :], 3, 1).astype(np.float32)
+    m = len(tris)
+    mats = np.asarray([[0.45, 0.55, 0.35, 0.0, 0.9, 0, 0, 0]], np.float32)
+    return SceneData(tris, nrm, np.zeros(m, np.uint32), np.zeros(m, np.uint32), mats, f"heightfield{n}")
+
+
 def sponza_like(detail: float = 1.0, seed: int = 1234, tier: str = "standard") -> SceneData:
     """Colonnaded two-storey atrium, open roof; ~262k triangles at detail=1.
 

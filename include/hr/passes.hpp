@@ -67,6 +67,13 @@ public:
     // the shared kind (hr_scene_create_instanced_shared): one BVH per mesh walked on two levels — Scene(ctx, desc, hr::Scene::SharedInstances())
     struct SharedInstances {};
     Scene(Context& ctx, const hr_instanced_scene_desc& desc, SharedInstances) { check(hr_scene_create_instanced_shared(ctx.handle(), &desc, &m_scene), "hr_scene_create_instanced_shared"); }
+    // a deforming mesh (hr_scene_create_deformable): Scene(ctx, desc, hr::Scene::Deformable()); update_vertices() every frame the vertices moved
+    // (device pointers, [n_tris][3][3] floats; normals may be null: keep), rebuild() when refit_cost() says the refitted tree has gone bad
+    struct Deformable {};
+    Scene(Context& ctx, const hr_scene_desc& desc, Deformable) { check(hr_scene_create_deformable(ctx.handle(), &desc, &m_scene), "hr_scene_create_deformable"); }
+    void     update_vertices(const float* positions, const float* normals, int32_t first_tri, int32_t n_tris, Stream cmd_buf) { check(hr_scene_update_vertices(m_scene, positions, normals, first_tri, n_tris, cmd_buf), "hr_scene_update_vertices"); }
+    float    refit_cost() const { float r = 1.0f; check(hr_scene_refit_cost(m_scene, &r), "hr_scene_refit_cost"); return r; }
+    void     rebuild(Stream cmd_buf) { check(hr_scene_rebuild(m_scene, cmd_buf), "hr_scene_rebuild"); }
     bool     is_shared() const { return hr_scene_is_shared(m_scene) != 0; }
     void     update_instances(const float* model_matrices, Stream cmd_buf) { check(hr_scene_update_instances(m_scene, model_matrices, cmd_buf), "hr_scene_update_instances"); }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }

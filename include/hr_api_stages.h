@@ -205,6 +205,14 @@ int32_t   hr_scene_is_shared(const hr_scene* scene);   /* 1 for a scene from hr_
  * for `desc` (shared != 0: the shared kind).  HR_ERR_UNSUPPORTED, with the sizes filled in, when that kind cannot hold it (private copies: >= 2^26
  * triangle references or >= 2^23 nodes); HR_ERR_INVALID_ARG as hr_scene_create_instanced. */
 hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info);
+/* ---- deformable scenes (added within revision 6): a flat scene, desc and errors as hr_scene_create, built without spatial splits.  update_vertices: `positions` / `normals` (NULL: keep) are DEVICE pointers, [n_tris][3][3] floats for the original triangles [first_tri, first_tri + n_tris); enqueued on `stream`, no host synchronisation; refits the BVH, answers equal a fresh scene's bit for bit.
+ * Non-finite vertices are the caller's responsibility, as at creation (a triangle that was not finite when the tree was built is never hit).  HR_ERR_INVALID_ARG for a plain or instanced scene, a range outside the scene, NULL positions.  refit_cost: sum of the nodes' half areas after the last update / as built (synchronises when it lags).
+ * rebuild: the slow path — synchronises, host build over the current vertices, new device arrays (re-capture graphs that hold the old ones); the caller decides when, nothing calls it.  hr_scene_get_info reads the exact bounds of the last update back. */
+hr_status hr_scene_create_deformable(hr_ctx* ctx, const hr_scene_desc* desc, hr_scene** out);
+hr_status hr_scene_update_vertices(hr_scene* scene, const float* positions, const float* normals, int32_t first_tri, int32_t n_tris, void* stream);
+hr_status hr_scene_refit_cost(const hr_scene* scene, float* ratio);
+hr_status hr_scene_rebuild(hr_scene* scene, void* stream);
+hr_status hr_bvh_build_info_deformable(const float* positions, int32_t n_tris, hr_scene_info* info);   /* host only: the shape of that split-free tree */
 
 #ifdef __cplusplus
 }
