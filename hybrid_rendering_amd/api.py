@@ -99,6 +99,7 @@ ABI_SYMBOLS = [
     "hr_selftest_math_sweep", "hr_selftest_fast_math",
     "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint",
     "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
+    "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",
 ]
 
 _lib = None
@@ -164,6 +165,10 @@ class hr_instance(C.Structure):
 class hr_instanced_scene_desc(C.Structure):
     _fields_ = [("meshes", C.POINTER(hr_mesh_desc)), ("n_meshes", C.c_int32), ("instances", C.POINTER(hr_instance)), ("n_instances", C.c_int32),
                 ("materials", C.c_void_p), ("n_materials", C.c_int32), ("material_textures", C.c_void_p), ("textures", C.c_void_p), ("n_textures", C.c_int32)]
+
+
+class hr_mesh_update(C.Structure):
+    _fields_ = [("mesh_idx", C.c_uint32), ("first_tri", C.c_int32), ("n_tris", C.c_int32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("bounds", C.c_void_p)]
 
 
 class Context:
@@ -320,13 +325,22 @@ class InstancedScene(Scene):
     """dw::RayTracedScene as the reference holds it — meshes + instances — with the per-frame update of main.cpp:74 (build_tlas):
     hr_scene_create_instanced / hr_scene_update_instances.  ``isd``: synth.InstancedSceneData.  Every pass takes it like a Scene.
     ``shared=True``: hr_scene_create_instanced_shared — one BVH per mesh, walked on two levels; same answers, O(meshes + instances) memory;
-    queries, the G-buffer synthesiser and the shadows pass take it, the other passes raise HRError (HR_ERR_UNSUPPORTED)."""
+    queries, the G-buffer synthesiser and the shadows pass take it, the other passes raise HRError (HR_ERR_UNSUPPORTED).
+    ``deformable=[...]`` (with ``shared=True``): hr_scene_create_instanced_shared_deformable — one flag per mesh; a flagged mesh is built without
+    spatial splits and ``update_meshes`` replaces its vertices on the GPU (``mesh_refit_cost`` for when its refitted tree has gone bad)."""
 
-    def __init__(self, ctx: Context, isd, shared: bool = False):
+    def __init__(self, ctx: Context, isd, shared: bool = False, deformable=None):
         self.ctx, self.isd, self.shared = ctx, isd, bool(shared)
         d, self._keep = _instanced_desc(isd)
         self.h = C.c_void_p()
-        if shared:
+        if deformable is not None:
+            assert shared, "deformable meshes live in a shared scene (shared=True)"
+            flags = np.ascontiguousarray(np.asarray(deformable).astype(bool), np.uint8)
+            assert flags.shape == (len(isd.meshes),), "deformable: one flag per mesh"
+            L = lib()
+            L.hr_scene_create_instanced_shared_deformable.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _check(L.hr_scene_create_instanced_shared_deformable(ctx.h, C.byref(d), C.c_void_p(flags.ctypes.data), C.byref(self.h)), "hr_scene_create_instanced_shared_deformable")
+        elif shared:
             _check(lib().hr_scene_create_instanced_shared(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced_shared")
         else:
             _check(lib().hr_scene_create_instanced(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced")
@@ -339,6 +353,52 @@ class InstancedScene(Scene):
     @property
     def top_level_rebuilds(self) -> int:
         return int(lib().hr_scene_top_level_rebuilds(self.h))
+
+    def update_meshes(self, updates, stream=None):
+        """hr_scene_update_meshes: ``updates`` is a list of (mesh_idx, positions) or dicts with keys mesh_idx, positions (cuda float32 [n,3,3],
+        object space), and optionally normals (cuda, the shape of positions; default: keep), first_tri (default 0) and bounds (host, (lo xyz, hi xyz)
+        of the WHOLE mesh after the update; default: measured on the GPU, which makes the call wait once).  Enqueued on ``stream``."""
+        import torch
+        arr, keep = (hr_mesh_update * max(1, len(updates)))(), []
+        for i, u in enumerate(updates):
+            if not isinstance(u, dict):
+                u = dict(mesh_idx=u[0], positions=u[1])
+            pos, nrm, bounds = u["positions"], u.get("normals"), u.get("bounds")
+            assert pos.is_cuda and pos.dtype == torch.float32 and pos.shape[1:] == (3, 3), "positions: cuda float32 [n,3,3]"
+            pos = pos.contiguous()
+            if nrm is not None:
+                assert nrm.is_cuda and nrm.dtype == torch.float32 and nrm.shape == pos.shape, "normals: cuda float32, the shape of positions"
+                nrm = nrm.contiguous()
+            if bounds is not None:
+                bounds = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float32).reshape(3) for b in bounds]), np.float32)
+            keep.append((pos, nrm, bounds))
+            arr[i] = hr_mesh_update(int(u["mesh_idx"]), int(u.get("first_tri", 0)), int(pos.shape[0]), pos.data_ptr() if pos.shape[0] else None,
+                                    nrm.data_ptr() if nrm is not None else None, bounds.ctypes.data if bounds is not None else None)
+        L = lib()
+        L.hr_scene_update_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        _check(L.hr_scene_update_meshes(self.h, C.cast(arr, C.c_void_p), C.c_int32(len(updates)), _stream_ptr(stream)), "hr_scene_update_meshes")
+        del keep
+
+    def mesh_refit_cost(self, mesh_idx: int) -> float:
+        """hr_scene_mesh_refit_cost: sum of mesh ``mesh_idx``'s BVH nodes' half areas after its last update / as built (synchronises); raises HRError
+        (HR_ERR_INVALID_ARG) when the bounds given with the last update do not contain the mesh"""
+        r = C.c_float(0.0)
+        L = lib()
+        L.hr_scene_mesh_refit_cost.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        _check(L.hr_scene_mesh_refit_cost(self.h, C.c_uint32(mesh_idx), C.byref(r)), "hr_scene_mesh_refit_cost")
+        return float(r.value)
+
+    def update_meshes_stats(self) -> dict:
+        """hr_scene_update_meshes_stats: launches of the per-level refit kernel, of the one-workgroup-per-mesh kernel, and stream waits so far"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().hr_scene_update_meshes_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "hr_scene_update_meshes_stats")
+        return dict(level_launches=int(a.value), top_launches=int(b.value), stream_waits=int(c.value))
+
+    def read_records(self) -> np.ndarray:
+        """hr_scene_read_instance_records: the shared scene's instance records, [n_instances][160] uint8, in the order of the top level's leaves"""
+        out = np.zeros((int(lib().hr_scene_instance_count(self.h)), 160), np.uint8)
+        _check(lib().hr_scene_read_instance_records(self.h, C.c_void_p(out.ctypes.data)), "hr_scene_read_instance_records")
+        return out
 
     def update(self, matrices, stream=None):
         """hr_scene_update_instances: matrices [n_instances][16] column-major (host); enqueued on ``stream`` (default: torch's current stream)"""

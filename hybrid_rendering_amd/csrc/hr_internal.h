@@ -4,6 +4,7 @@
 #include "../../include/hr_api.h"
 #include "bvh.h"
 #include <hip/hip_runtime.h>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -74,6 +75,12 @@ bool      finite_matrix(const float* m);
 bool      reject_shared_scene(const hr_scene* s, const char* pass);
 #define HR_REJECT_SHARED(scene, pass) do { if (::hr::reject_shared_scene(scene, pass)) return HR_ERR_UNSUPPORTED; } while (0)
 hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild);
+// instances_shared.hip: the second half of an update, over the standing matrices and mesh_bounds / shared_mesh_absmax — the instances' boxes, the
+// top level's refit (or re-build), the records, the two copies on `st` and geometry_epoch++ (hr_scene_update_instances and hr_scene_update_meshes)
+hr_status shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_rebuild);
+// instances_shared_deform.hip: what hr_scene_update_meshes needs, for a shared scene that holds the uploaded trees `blas` (flagged meshes built
+// without spatial splits): level lists, triangle -> reference map, node_box and the cost of every flagged tree as built.  Synchronous, like creation.
+hr_status shared_deform_adopt(hr_scene* s, const std::vector<BuiltBVH>& blas, const int32_t* mesh_n_tris, const uint8_t* flags);
 // api.hip: hr_scene_create (deformable = false) and hr_scene_create_deformable (the builder runs without spatial splits, then deformable_scene_adopt)
 hr_status scene_create_flat(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable);
 // deform.hip: what a refit needs, for a scene that holds the uploaded tree `b`; the exact bounds of the last hr_scene_update_vertices, read back on demand
@@ -129,6 +136,31 @@ struct DevBuf
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+};
+
+// What hr_scene_update_meshes keeps for a scene from hr_scene_create_instanced_shared_deformable (instances_shared_deform.hip).  Everything is
+// indexed by mesh; an unflagged mesh has no levels, no partials and -1 in tri_ref.
+struct SharedDeform
+{
+    std::vector<uint8_t>  flag;                   // per mesh: may be updated
+    std::vector<uint32_t> ref_base, tri_base;     // per mesh: its first reference in `tris` / first triangle in the mesh_* attribute arrays
+    std::vector<int32_t>  n_tris;
+    std::vector<int32_t>  n_levels, d_top;        // per mesh: levels of its tree / deepest level the one-workgroup launch takes (-1: unflagged)
+    std::vector<int32_t>  partial_base, n_partials;
+    std::vector<double>   cost_at_build;
+    std::vector<uint8_t>  cost_known;             // per mesh: cost_ratio is that of the last update
+    std::vector<double>   cost_ratio;
+    DevBuf   level_nodes;                         // the flagged meshes' level lists, GLOBAL node indices
+    std::vector<int32_t> levels_host;             // host copy of `levels`
+    DevBuf   levels;                              // per mesh two rows of kMaxTraversalDepth + 2 ints: offsets into level_nodes, first partial slot of the level
+    DevBuf   mesh;                                // per mesh: MeshDev (instances_shared_deform.hip)
+    DevBuf   tri_ref;                             // per mesh triangle (concatenated): global index of its one reference, -1: none
+    DevBuf   partials;                            // per refit workgroup: sum of its nodes' half areas (double)
+    DevBuf   root_box;                            // per mesh 8 floats: the refitted root box (lo xyz, 0, hi xyz, 0)
+    DevBuf   outside;                             // per mesh one word: the bounds given with the last update do not contain the refitted root box
+    float*   root_box_host = nullptr;             // pinned, per mesh 8 floats
+    int64_t  level_launches = 0, top_launches = 0, stream_waits = 0;   // what the updates so far enqueued (hr_scene_update_meshes_stats)
+    ~SharedDeform() { if (root_box_host) (void)hipHostFree(root_box_host); }
 };
 
 // Stage profiler: one event pair per named stage, recorded on the pass stream.
@@ -308,6 +340,8 @@ struct hr_scene
     std::vector<float>    shared_mesh_absmax;     // per mesh: max |p_k| over its bounds, per axis
     std::vector<uint32_t> shared_mesh_root;       // per mesh: node index of its root
     int           shared_mesh_depth = 0;          // deepest mesh tree (levels below its root)
+    std::vector<float>    shared_mesh_pad;        // per mesh: the leaf pad its builder used
+    std::unique_ptr<hr::SharedDeform> shared_deform;   // set by hr_scene_create_instanced_shared_deformable only
     // ---- deformable scenes (deform.hip): a flat scene built without spatial splits; hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`
     // and refits `nodes` through level_nodes / level_offsets / node_box (the arrays of the instanced scenes' refit)
     bool          deformable = false;

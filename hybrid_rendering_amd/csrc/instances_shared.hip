@@ -40,7 +40,8 @@ struct MeshTrees
     std::vector<int>      depth;    // per mesh: deepest node below the root (root = 0)
 };
 
-void build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want_cells)
+// flags (or null): meshes that may deform are built without spatial splits (hr_scene_create_instanced_shared_deformable)
+void build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want_cells, const uint8_t* flags = nullptr)
 {
     mt.blas.resize((size_t)d->n_meshes);
     mt.depth.assign((size_t)d->n_meshes, 0);
@@ -48,7 +49,7 @@ void build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want
     {
         BuiltBVH& b = mt.blas[(size_t)k];
         b.want_child_boxes = want_cells;
-        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, b);
+        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, b, !(flags && flags[k]));
         std::vector<int> dep(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
         for (size_t j = 0; j < b.nodes.size(); j++)
             for (int c = 0; c < (b.nodes[j].counts & 15); c++)
@@ -288,10 +289,11 @@ float world_pad(const hr_scene* s)
     return pad > 0.0f ? pad : 1e-6f;
 }
 
-hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out)
+// deformable_call: hr_scene_create_instanced_shared_deformable (flags may still be null: no mesh can be updated then)
+hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out, bool deformable_call = false, const uint8_t* flags = nullptr)
 {
     HR_CHECK_ARG(ctx && out);
-    hr_status st = validate_desc(d, "hr_scene_create_instanced_shared");
+    hr_status st = validate_desc(d, deformable_call ? "hr_scene_create_instanced_shared_deformable" : "hr_scene_create_instanced_shared");
     if (st != HR_OK) return st;
     HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
     const int M = d->n_meshes, I = d->n_instances;
@@ -314,7 +316,7 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     HR_HIP(hipSetDevice(ctx->device));
 
     MeshTrees mt;
-    build_mesh_trees(d, mt, false);
+    build_mesh_trees(d, mt, false, flags);
     std::unique_ptr<hr_scene> guard(new hr_scene());
     hr_scene* s = guard.get();
     s->ctx = ctx; s->shared = true;
@@ -331,12 +333,14 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     std::memset(nodes.data(), 0, n_nodes * sizeof(Node8));
     s->shared_mesh_root.resize((size_t)M);
     s->shared_mesh_absmax.assign((size_t)M * 3, 0.0f);
+    s->shared_mesh_pad.resize((size_t)M);
     s->shared_mesh_depth = 0;
     size_t node_at = (size_t)s->top_cap, ref_at = 0;
     for (int k = 0; k < M; k++)
     {
         const BuiltBVH& b = mt.blas[(size_t)k];
         s->shared_mesh_root[(size_t)k] = (uint32_t)node_at;
+        s->shared_mesh_pad[(size_t)k] = b.pad;
         s->shared_mesh_depth = std::max(s->shared_mesh_depth, mt.depth[(size_t)k]);
         if (d->meshes[k].n_tris > 0)
             for (int a = 0; a < 3; a++) s->shared_mesh_absmax[(size_t)k * 3 + a] = std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]));
@@ -423,6 +427,12 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     s->top_area_at_build = -1.0;   // the first update records it
     if ((st = shared_scene_update(s, mats.data(), nullptr, false)) != HR_OK) return st;
     HR_HIP(hipStreamSynchronize(nullptr));
+    if (deformable_call)
+    {
+        std::vector<int32_t> mesh_n_tris((size_t)M);
+        for (int k = 0; k < M; k++) mesh_n_tris[(size_t)k] = d->meshes[k].n_tris;
+        if ((st = shared_deform_adopt(s, mt.blas, mesh_n_tris.data(), flags)) != HR_OK) return st;
+    }
     s->geometry_epoch = 0;
     *out = guard.release();
     return HR_OK;
@@ -517,6 +527,14 @@ hr_status hr::shared_scene_update(hr_scene* s, const float* matrices, hipStream_
     }
     if (matrices)
         for (int i = 0; i < I; i++) std::memcpy(s->inst_host[(size_t)i].m, matrices + (size_t)i * 16, 64);
+    return shared_scene_host_tail(s, st, force_rebuild);
+}
+
+// the caller has waited for the previous call's uploads (instanced_scene_wait_uploads) and set the device
+hr_status hr::shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_rebuild)
+{
+    const int I = s->n_instances;
+    const bool first = s->top_area_at_build < 0.0;
     instanced_scene_boxes(s);
     s->info.box_pad = world_pad(s);
     for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a]; s->info.bounds_hi[a] = s->grid_hi[a]; }   // conservative: no vertex is ever transformed here
@@ -571,6 +589,24 @@ hr_status hr_scene_create_instanced_shared(hr_ctx* ctx, const hr_instanced_scene
     catch (const std::exception& e)
     {
         set_last_error(std::string("hr_scene_create_instanced_shared: ") + e.what());
+        return HR_ERR_UNSUPPORTED;
+    }
+}
+
+hr_status hr_scene_create_instanced_shared_deformable(hr_ctx* ctx, const hr_instanced_scene_desc* desc, const uint8_t* deformable, hr_scene** out)
+{
+    try
+    {
+        return create_shared_impl(ctx, desc, out, true, deformable);
+    }
+    catch (const std::bad_alloc&)
+    {
+        set_last_error("hr_scene_create_instanced_shared_deformable: host allocation failed");
+        return HR_ERR_OUT_OF_MEMORY;
+    }
+    catch (const std::exception& e)
+    {
+        set_last_error(std::string("hr_scene_create_instanced_shared_deformable: ") + e.what());
         return HR_ERR_UNSUPPORTED;
     }
 }

@@ -412,6 +412,16 @@ def deform(sd: SceneData, frame: int, kind: str) -> SceneData:
                      sd.uvs, sd.tangents, sd.material_textures, sd.textures)
 
 
+def deform_meshes(isd: InstancedSceneData, frame: int, kind: str, mesh_indices) -> InstancedSceneData:
+    """``isd`` with the meshes ``mesh_indices`` replaced by ``deform(mesh, frame, kind)`` (object space; ``kind`` may be a dict mesh index -> kind):
+    same instances, same triangle count and order under ``flatten()`` — what hr_scene_update_meshes and its tests are driven with."""
+    meshes = list(isd.meshes)
+    for k in mesh_indices:
+        meshes[k] = deform(isd.meshes[k], frame, kind[k] if isinstance(kind, dict) else kind)
+    return InstancedSceneData(meshes=meshes, instances=list(isd.instances), materials=isd.materials, name=f"{isd.name}:deformed{frame}",
+                              material_textures=isd.material_textures, textures=isd.textures)
+
+
 def heightfield(n: int = 64, size: float = 100.0, height: float = 12.0, seed: int = 11, strip: float = 0.0) -> SceneData:
     """n x n cells (2 n^2 triangles) of a smooth random terrain over [0, size]^2.  ``strip`` > 0 adds that many long thin triangles per side
     (fences across the whole field, 0.2 % of its width): input on which spatial splits pay, for tests that contrast the two builders."""

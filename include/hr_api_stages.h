@@ -1,5 +1,4 @@
 /* hr_api_stages.h — part of the C ABI of hybrid_rendering_amd (included by hr_api.h; do not include on its own).
- *
  * What hr_api.h leaves out because the reference's classes keep it PRIVATE: the stage-level entry points of the four passes (the
  * methods ray_trace / temporal_accumulation / a_trous_filter / upsample ... that render() calls), their intermediate images, profiling
  * and introspection — what a multi-GPU driver (halo exchange between stages: include/hr/tiled.hpp), the tests and the tools need — and
@@ -12,7 +11,6 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-
 /* ---- profiler ranges --------------------------------------------------------------------------------------------- */
 /* Profiler ranges under the reference's DW_SCOPED_SAMPLE names ("Ray Traced Shadows" > "Ray Trace", "Temporal Accumulation", "Iteration 0" ...;
  * "Ambient Occlusion", "Ray Traced Reflections", "DDGI" > "Probe Update" / "Sample Probe Grid", ...; stages fused into one launch carry the joined names) around every pass and
@@ -186,11 +184,7 @@ hr_status hr_hybrid_frame_destroy(hr_hybrid_frame* f);
  * sees them — per non-empty child slot the de-quantised box origin + q * 2^(e-127) (one fp32 fma per plane, the planes the walk's slab test is built on), the node's quantisation step per
  * axis, node index, slot, depth of the node (root = 0) and whether the slot is a leaf.  Writes min(*n_boxes, capacity) records to
  * `out` (may be NULL with capacity 0 to ask for the count).  For tests that aim rays at box faces, edges and corners. */
-typedef struct
-{
-    float   lo[3], hi[3], step[3];
-    int32_t node, slot, depth, is_leaf;
-} hr_child_box;
+typedef struct { float lo[3], hi[3], step[3]; int32_t node, slot, depth, is_leaf; } hr_child_box;
 hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes);
 
 /* ---- shared instanced scenes (added within revision 6, docs/API_HISTORY.md): every mesh's object-space BVH is stored ONCE and walked on two levels,
@@ -202,8 +196,7 @@ hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_bo
 hr_status hr_scene_create_instanced_shared(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out);
 int32_t   hr_scene_is_shared(const hr_scene* scene);   /* 1 for a scene from hr_scene_create_instanced_shared, else 0 */
 /* Host only, no device: n_tris, n_nodes, max_depth, node_bytes, tri_bytes, conservative bounds and box_pad of the scene either kind would build
- * for `desc` (shared != 0: the shared kind).  HR_ERR_UNSUPPORTED, with the sizes filled in, when that kind cannot hold it (private copies: >= 2^26
- * triangle references or >= 2^23 nodes); HR_ERR_INVALID_ARG as hr_scene_create_instanced. */
+ * for `desc` (shared != 0: the shared kind).  HR_ERR_UNSUPPORTED, with the sizes filled in, when that kind cannot hold it (private copies: >= 2^26 triangle references or >= 2^23 nodes); HR_ERR_INVALID_ARG as hr_scene_create_instanced. */
 hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info);
 /* ---- deformable scenes (added within revision 6): a flat scene, desc and errors as hr_scene_create, built without spatial splits.  update_vertices: `positions` / `normals` (NULL: keep) are DEVICE pointers, [n_tris][3][3] floats for the original triangles [first_tri, first_tri + n_tris); enqueued on `stream`, no host synchronisation; refits the BVH, answers equal a fresh scene's bit for bit.
  * Non-finite vertices are the caller's responsibility, as at creation (a triangle that was not finite when the tree was built is never hit).  HR_ERR_INVALID_ARG for a plain or instanced scene, a range outside the scene, NULL positions.  refit_cost: sum of the nodes' half areas after the last update / as built (synchronises when it lags).
@@ -213,6 +206,13 @@ hr_status hr_scene_update_vertices(hr_scene* scene, const float* positions, cons
 hr_status hr_scene_refit_cost(const hr_scene* scene, float* ratio);
 hr_status hr_scene_rebuild(hr_scene* scene, void* stream);
 hr_status hr_bvh_build_info_deformable(const float* positions, int32_t n_tris, hr_scene_info* info);   /* host only: the shape of that split-free tree */
+/* ---- deforming meshes in a shared instanced scene (added within revision 6): as hr_scene_create_instanced_shared; deformable[k] != 0: mesh k may be updated later and its tree is built without spatial splits (NULL: none).  update_meshes scatters the new vertices, refits the updated meshes' trees and the top level, all on `stream`; bounds == NULL: measured on the GPU, the call waits ONCE for them; given: no wait, and bounds that do not contain the mesh are reported by mesh_refit_cost (they can cost hits, never an out-of-range access).  Entries with n_tris == 0 do nothing; the last entry naming a mesh decides its bounds.
+ * HR_ERR_INVALID_ARG, before anything is enqueued: a scene of another kind, an unflagged mesh, mesh_idx >= n_meshes, a range outside the mesh, NULL positions, bounds not finite or lo > hi.  mesh_refit_cost: as hr_scene_refit_cost, per mesh.  update_meshes_stats (tests, tools): refit launches per level / per mesh root and stream waits so far; read_instance_records: n_instances x 160 bytes (csrc/bvh.h InstanceShared), any shared scene. */
+hr_status hr_scene_create_instanced_shared_deformable(hr_ctx* ctx, const hr_instanced_scene_desc* desc, const uint8_t* deformable /*[n_meshes]*/, hr_scene** out);
+typedef struct hr_mesh_update { uint32_t mesh_idx; int32_t first_tri, n_tris; /* mesh-local range of ORIGINAL triangles */ const float* positions; /* DEVICE, [n_tris][3][3], object space */ const float* normals; /* DEVICE or NULL: keep */ const float* bounds; /* HOST, lo xyz hi xyz, object space, conservative for the WHOLE mesh after this update; NULL: measured */ } hr_mesh_update;
+hr_status hr_scene_update_meshes(hr_scene* scene, const hr_mesh_update* updates, int32_t n_updates, void* stream);
+hr_status hr_scene_mesh_refit_cost(const hr_scene* scene, uint32_t mesh_idx, float* ratio);
+hr_status hr_scene_update_meshes_stats(const hr_scene* scene, int64_t* level_launches, int64_t* top_launches, int64_t* stream_waits); hr_status hr_scene_read_instance_records(const hr_scene* scene, void* records_out);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,10 @@ forced top-level re-build); after every update 20 k any-hit and closest-hit quer
 hr_scene_create over the flattened world vertices bit for bit, and every few configurations the shadows / AO masks + DDGI radiance + reflections trace
 image are compared with the oracle's instanced scene.   python tools/fuzz_instances.py [seed] [n_configs] [--shared]
 --shared: the scenes are created by hr_scene_create_instanced_shared (one BVH per mesh, two-level walk); of the passes only the G-buffer
-synthesiser and the shadows pass take such a scene, so only those are compared with the oracle, and the bounds only have to be conservative."""
+synthesiser and the shadows pass take such a scene, so only those are compared with the oracle, and the bounds only have to be conservative.
+--deform (implies --shared): hr_scene_create_instanced_shared_deformable with a random subset of the small meshes flagged; between the matrix
+updates and the forced top-level re-builds a random subset of the flagged meshes takes a synth.deform step through hr_scene_update_meshes (whole
+meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,8 +18,11 @@ from hybrid_rendering_amd import api as hr, api_gi, api_reflections, synth, synt
 from oracle import pyoracle as oracle, pyoracle_ddgi as od, pyoracle_reflections as orf
 import helpers
 
-SHARED = "--shared" in sys.argv
-if SHARED:
+DEFORM = "--deform" in sys.argv
+if DEFORM:
+    sys.argv.remove("--deform")
+SHARED = "--shared" in sys.argv or DEFORM
+if "--shared" in sys.argv:
     sys.argv.remove("--shared")
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -69,8 +75,10 @@ for trial in range(n):
     isd = synth.InstancedSceneData(meshes=meshes, instances=inst, materials=materials)
     msg = []
     try:
-        g = hr.InstancedScene(ctx, isd, shared=True) if SHARED else hr.InstancedScene(ctx, isd)
+        flags = [int(DEFORM and k > 0 and m.n_tris < 5000 and rng.rand() < 0.6) for k, m in enumerate(meshes)]
+        g = hr.InstancedScene(ctx, isd, shared=True, deformable=flags if DEFORM else None) if SHARED else hr.InstancedScene(ctx, isd)
         mats = isd.matrices().copy()
+        cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
         for step in range(int(rng.randint(3, 7))):
             if step:
                 move = rng.rand(I) < rng.choice([0.1, 0.5, 1.0])
@@ -83,6 +91,23 @@ for trial in range(n):
                 g.update(mats)
                 if rng.rand() < 0.15:
                     g.rebuild_top_level()
+                chosen = [k for k, f in enumerate(flags) if f and rng.rand() < 0.7]
+                if chosen:
+                    kinds = {k: str(rng.choice(["wave", "twist", "collapse"])) for k in chosen}
+                    isd = synth.InstancedSceneData(meshes=[synth.deform(meshes[k], step, kinds[k]) if k in kinds else m for k, m in enumerate(isd.meshes)], instances=inst, materials=materials)
+                    ups = []
+                    for k in chosen:
+                        m = isd.meshes[k]
+                        cut = int(rng.randint(0, m.n_tris + 1)) if rng.rand() < 0.5 else 0
+                        for first, cnt in ((cut, m.n_tris - cut), (0, cut)):
+                            u = dict(mesh_idx=k, first_tri=first, positions=cuda(m.verts[first:first + cnt]), normals=cuda(m.normals[first:first + cnt]))
+                            if rng.rand() < 0.5:
+                                u["bounds"] = m.bounds()
+                            ups.append(u)
+                    g.update_meshes(ups)
+                    if rng.rand() < 0.5:   # and the matrices once more, behind the mesh update
+                        mats[int(rng.randint(0, I)), 12:15] += rng.uniform(-2, 2, 3).astype(np.float32)
+                        g.update(mats)
             flat_sd = isd.flatten(mats)
             gf = hr.Scene(ctx, flat_sd)
             lo, hi = flat_sd.bounds()

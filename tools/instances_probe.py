@@ -3,7 +3,12 @@ Scene: the bench building (sponza_like(detail), identity instance) + `--movers` 
   * update: wall clock of N back-to-back updates (matrix upload + vertex transform + reference gather + per-level refit), per update;
   * quality: the shadows trace stage on the instanced scene after `--frames` updates of motion against hr_scene_create over the same world
     vertices (a fresh SAH build), same G-buffer — masks must be equal, the time ratio is the price of never rebuilding.
-    python tools/instances_probe.py [--detail 1.0 --movers 200 --frames 30 --width 1920 --height 1080]"""
+    python tools/instances_probe.py [--detail 1.0 --movers 200 --frames 30 --width 1920 --height 1080]
+--deform: what hr_scene_update_meshes costs.  Scene: the building + `--meshes` deforming heightfields (`--field` cells a side) placed `--copies`
+times each, created by hr_scene_create_instanced_shared_deformable.  Reported, per frame of a wave: all meshes in ONE call against one call each
+(bounds given, so nothing waits; and measured, with the wait); the same triangle count through hr_scene_update_vertices on a flat deformable
+scene; re-creating the shared scene (the only route before this call existed); the shadows trace stage on the refitted scene against one
+created fresh over the same deformed meshes (masks must be equal)."""
 import argparse, json, math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,7 +22,13 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--shared", action="store_true", help="hr_scene_create_instanced_shared: one BVH per mesh, two-level walk")
+    ap.add_argument("--deform", action="store_true", help="hr_scene_update_meshes on a shared scene with deforming meshes")
+    ap.add_argument("--meshes", type=int, default=16)
+    ap.add_argument("--copies", type=int, default=8)
+    ap.add_argument("--field", type=int, default=48)
     a = ap.parse_args()
+    if a.deform:
+        return deform_probe(a)
     import torch
     from hybrid_rendering_amd import api as hr, synth
     W, H = a.width, a.height
@@ -82,6 +93,93 @@ def main():
     res["masks_equal"] = True
     if a.shared:
         res["kind"] = "shared"
+    print(json.dumps(res))
+
+
+def deform_probe(a):
+    import torch
+    from hybrid_rendering_amd import api as hr, synth
+    W, H = a.width, a.height
+    building = synth.sponza_like(a.detail)
+    lo, hi = building.bounds()
+    rng = np.random.RandomState(2)
+    N = a.meshes
+    fields = [synth.heightfield(a.field, size=60.0, height=10.0, seed=11 + k) for k in range(N)]
+    fields = [synth.SceneData(f.verts, f.normals, f.tri_material, f.tri_mesh_id, building.materials, f.name) for f in fields]
+    inst = [(synth.model_matrix(), 0, 1)]
+    for k in range(N):
+        for c in range(a.copies):
+            at = rng.uniform(lo + 0.1 * (hi - lo), hi - 0.1 * (hi - lo))
+            inst.append((synth.model_matrix(at, (0, 1, 0), rng.uniform(0, 6.28), rng.uniform(0.5, 1.5, 3)), 1 + k, 2 + len(inst)))
+    isd = synth.InstancedSceneData(meshes=[building] + fields, instances=inst, materials=building.materials)
+    flags = [0] + [1] * N
+    ctx = hr.Context(0)
+    cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    t0 = time.perf_counter()
+    g = hr.InstancedScene(ctx, isd, shared=True, deformable=flags)
+    t_create = time.perf_counter() - t0
+    frames = [synth.deform_meshes(isd, f, "wave", range(1, N + 1)) for f in range(1, 4)]
+    dev = [[dict(mesh_idx=k, positions=cuda(d.meshes[k].verts), normals=cuda(d.meshes[k].normals), bounds=d.meshes[k].bounds()) for k in range(1, N + 1)] for d in frames]
+    measured = [[{k: v for k, v in u.items() if k != "bounds"} for u in ups] for ups in dev]
+
+    def timed(fn, reps=20):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(reps):
+            fn(i)
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) / reps * 1e3, 4)
+    res = dict(kind="shared, deforming meshes", meshes=N, copies=a.copies, tris_per_mesh=fields[0].n_tris, instances=len(inst), create_s=round(t_create, 2))
+    res["update_ms_one_call_bounds_given"] = timed(lambda i: g.update_meshes(dev[i % 3]))
+    res["update_ms_one_call_each_bounds_given"] = timed(lambda i: [g.update_meshes([u]) for u in dev[i % 3]])
+    res["update_ms_one_call_bounds_measured"] = timed(lambda i: g.update_meshes(measured[i % 3]))
+    res["update_ms_one_call_each_bounds_measured"] = timed(lambda i: [g.update_meshes([u]) for u in measured[i % 3]])
+    res["stats"] = g.update_meshes_stats()
+    res["refit_cost_mesh_1"] = round(g.mesh_refit_cost(1), 4)
+    # the same triangles as ONE flat deformable scene (object space, side by side: only the triangle count matters)
+    flat_sd = synth.InstancedSceneData(meshes=fields, instances=[(synth.model_matrix((70.0 * k, 0, 0)), k, k) for k in range(N)], materials=building.materials).flatten()
+    gd = hr.Scene(ctx, flat_sd, deformable=True)
+    pos = [cuda(synth.deform(flat_sd, f, "wave").verts) for f in range(1, 4)]
+    res["update_vertices_ms_flat_scene_same_triangles"] = timed(lambda i: gd.update_vertices(pos[i % 3]))
+    gd.close()
+
+    def recreate(i):
+        s = hr.InstancedScene(ctx, frames[i % 3], shared=True)
+        s.close()
+    res["recreate_shared_scene_ms"] = timed(recreate, reps=3)
+    # the trace on the refitted scene against a scene created fresh over the same meshes
+    g.update_meshes(dev[2])
+    fresh = hr.InstancedScene(ctx, frames[2], shared=True)
+    light = synth.sponza_light()
+    cams = [synth.sponza_camera(W / H, frame=f, dolly=0.5) for f in range(2)]
+    ubo = synth.make_ubo(cams[1], cams[0], light)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    gb = fresh.gbuffer(ubo, W, H)
+    fi = hr.frame_inputs(gb, gb, ubo, 0, 0, sob_d, sr_d)
+    out = {}
+    for tag, sc in (("refitted", g), ("fresh", fresh)):
+        p = hr.RayTracedShadows(ctx, W, H)
+        p.params.exact = 0
+        for k in range(6):
+            fi.num_frames = k
+            p.render(sc, fi)
+        p.set_profiling(True)
+        acc = {}
+        for k in range(6, 26):
+            fi.num_frames = k
+            p.render(sc, fi)
+            for n, t, b in p.stage_times():
+                acc[n] = acc.get(n, 0.0) + t / 20
+        torch.cuda.synchronize()
+        out[tag] = (p.image(p.IMG_MASK).cpu().numpy().copy(), acc)
+        p.close()
+    assert np.array_equal(out["refitted"][0], out["fresh"][0]), "masks differ between the refitted and the freshly created scene"
+    res["shadow_trace_ms_refitted"] = round(out["refitted"][1]["ray_trace"], 4)
+    res["shadow_trace_ms_fresh"] = round(out["fresh"][1]["ray_trace"], 4)
+    res["masks_equal"] = True
     print(json.dumps(res))
 
 
