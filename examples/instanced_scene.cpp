@@ -147,8 +147,9 @@ int main()
         for (uint32_t i = 0; i < 4; i++)
         {
             place((int)i, mats);
+            scene.motion_begin_frame(nullptr);                      // the instances as they stand are "previous frame" from here on
             scene.update_instances(mats, nullptr);                  // main.cpp:74 scene->build_tlas(cmd_buf)
-            hr::check(hr_gbuffer_raycast(scene.handle(), &u, W, H, gb1, gb2, gb3, (float*)depth, nullptr), "hr_gbuffer_raycast");
+            scene.gbuffer_raycast_motion(u, W, H, gb1, gb2, gb3, (float*)depth, nullptr);   // GB2.zw follows the moving cube
             frame.inputs.num_frames = i;
             frame.inputs.ping_pong  = i & 1;
             shadows.render(nullptr, frame);                         // main.cpp:80

@@ -100,6 +100,7 @@ ABI_SYMBOLS = [
     "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint",
     "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
     "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",
+    "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
 ]
 
 _lib = None
@@ -275,14 +276,28 @@ class Scene:
         _check(lib().hr_trace_closest_hit(self.h, C.c_int64(rays.shape[0]), _ptr(rays), _ptr(tuv), _ptr(prim), _stream_ptr(stream)), "hr_trace_closest_hit")
         return tuv, prim
 
-    def gbuffer(self, np_ubo, w, h, device="cuda", stream=None):
-        """GPU G-buffer synthesis (stands in for the raster GBuffer pass).  Returns dict of cuda tensors."""
+    def motion_begin_frame(self, stream=None):
+        """hr_scene_motion_begin_frame: remember the geometry as "previous frame" — once per frame, BEFORE that frame's update calls, on their
+        stream.  The first call allocates (not under stream capture); a plain hr_scene_create scene takes it as a no-op."""
+        L = lib()
+        L.hr_scene_motion_begin_frame.argtypes = [C.c_void_p, C.c_void_p]
+        _check(L.hr_scene_motion_begin_frame(self.h, _stream_ptr(stream)), "hr_scene_motion_begin_frame")
+
+    def gbuffer(self, np_ubo, w, h, device="cuda", stream=None, motion: bool = False):
+        """GPU G-buffer synthesis (stands in for the raster GBuffer pass).  Returns dict of cuda tensors.
+        ``motion=True``: hr_gbuffer_raycast_motion — GB2.zw follows the hit point's own motion since the last ``motion_begin_frame``."""
         import torch
         gb1 = torch.zeros((h, w, 4), dtype=torch.uint8, device=device)
         gb2 = torch.zeros((h, w, 4), dtype=torch.float16, device=device)
         gb3 = torch.zeros((h, w, 4), dtype=torch.float16, device=device)
         depth = torch.zeros((h, w), dtype=torch.float32, device=device)
         u = make_ubo(np_ubo)
+        if motion:
+            L = lib()
+            L.hr_gbuffer_raycast_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _check(L.hr_gbuffer_raycast_motion(self.h, C.byref(u), C.c_int32(w), C.c_int32(h), _ptr(gb1), _ptr(gb2), _ptr(gb3), _ptr(depth), _stream_ptr(stream)),
+                   "hr_gbuffer_raycast_motion")
+            return dict(gb1=gb1, gb2=gb2, gb3=gb3, depth=depth)
         _check(lib().hr_gbuffer_raycast(self.h, C.byref(u), C.c_int32(w), C.c_int32(h), _ptr(gb1), _ptr(gb2), _ptr(gb3), _ptr(depth), _stream_ptr(stream)),
                "hr_gbuffer_raycast")
         return dict(gb1=gb1, gb2=gb2, gb3=gb3, depth=depth)

@@ -215,7 +215,31 @@ HR_DEV bool gb_plane_bary(const GBufArgs& a, int prim, f3 o, f3 d, float& b0, fl
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a)
+// What the MOTION variants of the two synthesisers read AFTER the hit, one triangle per lane (hr_gbuffer_raycast_motion): the hit
+// triangle's previous world vertices are prev_verts[prim] (deformable scenes), or prev_mats[instance] * (p, 1) over the object-space positions
+// `mesh_positions` (instanced kinds; a shared deformable scene passes its previous object-space positions there) — mul_m4's operation order, the
+// bits k_instances_transform stores, so a matrix that stands gives the current vertices back and a delta of exactly 0.
+struct MotionArgs
+{
+    const float*       prev_verts;       // [n][3][3] by original triangle, or null
+    const float*       prev_mats;        // [n_instances][16] by instance, or null
+    const InstanceRec* inst;             // private-copy scenes: the records and the triangle -> instance map
+    const uint32_t*    tri_instance;
+    const float*       mesh_positions;   // object space, meshes concatenated (previous frame's where they deform)
+};
+
+// previous minus current position of the point (b0, b1, b2) of a triangle: both sums in the same expression, one rounding per operation
+HR_DEV f3 motion_delta(const float* vp, const float* vc, float b0, float b1, float b2)
+{
+    return mk3(((vp[0] * b0 + vp[3] * b1) + vp[6] * b2) - ((vc[0] * b0 + vc[3] * b1) + vc[6] * b2),
+               ((vp[1] * b0 + vp[4] * b1) + vp[7] * b2) - ((vc[1] * b0 + vc[4] * b1) + vc[7] * b2),
+               ((vp[2] * b0 + vp[5] * b1) + vp[8] * b2) - ((vc[2] * b0 + vc[5] * b1) + vc[8] * b2));
+}
+// P + delta; a delta of 0 gives P's own bits (also for a component that is -0)
+HR_DEV f3 motion_prev_point(f3 P, f3 dl) { return mk3(dl.x == 0.0f ? P.x : P.x + dl.x, dl.y == 0.0f ? P.y : P.y + dl.y, dl.z == 0.0f ? P.z : P.z + dl.z); }
+
+template <bool MOTION>
+__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs mo)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -239,8 +263,36 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a)
     }
     const f3 P     = add3(cam, scale3(d, hit.t));
     const f4 clip  = mul_m4(a.vp, P.x, P.y, P.z, 1.0f);
-    const f4 pclip = mul_m4(a.pvp, P.x, P.y, P.z, 1.0f);
     const float b0 = 1.0f - hit.u - hit.v;
+    f3 Pp = P;
+    if (MOTION)
+    {
+        const float* c = a.verts + (size_t)hit.prim * 9;
+        float vc[9], vp[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) vc[k] = c[k];
+        if (mo.prev_verts)
+        {
+            const float* p = mo.prev_verts + (size_t)hit.prim * 9;
+#pragma unroll
+            for (int k = 0; k < 9; k++) vp[k] = p[k];
+        }
+        else
+        {
+            const uint32_t     in = mo.tri_instance[hit.prim];
+            const InstanceRec& r  = mo.inst[in];
+            const float*       p  = mo.mesh_positions + ((size_t)r.mesh_tri_base + ((uint32_t)hit.prim - r.first_tri)) * 9;
+            const float*       m  = mo.prev_mats + (size_t)in * 16;
+#pragma unroll
+            for (int v = 0; v < 3; v++)
+            {
+                const f4 w = mul_m4(m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
+                vp[v * 3] = w.x; vp[v * 3 + 1] = w.y; vp[v * 3 + 2] = w.z;
+            }
+        }
+        Pp = motion_prev_point(P, motion_delta(vp, vc, b0, hit.u, hit.v));
+    }
+    const f4 pclip = mul_m4(a.pvp, Pp.x, Pp.y, Pp.z, 1.0f);
     const f3 nI    = gb_normal_at(a, hit.prim, b0, hit.u, hit.v);
     f3       n     = normalize3(nI);
     if (dot3(n, d) > 0.0f) n = neg3(n);
@@ -349,7 +401,8 @@ HR_DEV bool gb2_plane_bary(const float* wv, f3 o, f3 d, float& b0, float& b1, fl
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2)
+template <bool MOTION>
+__global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionArgs mo)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     const GBufArgs& a = a2.g;
@@ -398,8 +451,22 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2)
     const bool has_normals = a2.mesh_normals != nullptr;
     const f3 P     = add3(cam, scale3(d, hit.t));
     const f4 clip  = mul_m4(a.vp, P.x, P.y, P.z, 1.0f);
-    const f4 pclip = mul_m4(a.pvp, P.x, P.y, P.z, 1.0f);
     const float b0 = 1.0f - hit.u - hit.v;
+    f3 Pp = P;
+    if (MOTION)
+    {
+        const float* p = mo.mesh_positions + q * 9;
+        const float* m = mo.prev_mats + (size_t)rec.instance * 16;
+        float vp[9];
+#pragma unroll
+        for (int v = 0; v < 3; v++)
+        {
+            const f4 w = mul_m4(m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
+            vp[v * 3] = w.x; vp[v * 3 + 1] = w.y; vp[v * 3 + 2] = w.z;
+        }
+        Pp = motion_prev_point(P, motion_delta(vp, wv, b0, hit.u, hit.v));
+    }
+    const f4 pclip = mul_m4(a.pvp, Pp.x, Pp.y, Pp.z, 1.0f);
     const f3 nI    = gb2_normal_at(wn, wv, has_normals, b0, hit.u, hit.v);
     f3       n     = normalize3(nI);
     if (dot3(n, d) > 0.0f) n = neg3(n);
@@ -432,6 +499,21 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2)
     a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2((float)rec.mesh_id, clip.z));
     const float dd = __fdiv_rn(clip.z, clip.w);
     a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
+}
+
+// hr_scene_motion_begin_frame: the instances' matrices as the device records hold them, by instance index (a shared scene's records sit in the
+// order of the top level's leaves, which a re-build changes: `instance` names the row)
+__global__ __launch_bounds__(256) void k_motion_snapshot_private(const InstanceRec* inst, float* prev, int n_instances)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_instances * 16) prev[i] = inst[i >> 4].m[i & 15];
+}
+__global__ __launch_bounds__(256) void k_motion_snapshot_shared(const InstanceShared* recs, float* prev, int n_instances)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_instances * 16) return;
+    const uint32_t in = recs[i >> 4].instance;
+    if (in < (uint32_t)n_instances) prev[(size_t)in * 16 + (i & 15)] = recs[i >> 4].m[i & 15];
 }
 
 // the modes of hr_selftest_math / hr_selftest_math_sweep (include/hr_api_post.h); the tests' CPU mirror restates each
@@ -886,9 +968,22 @@ hr_status hr_trace_closest_hit(const hr_scene* scene, int64_t n, const float* ra
     return HR_OK;
 }
 
-hr_status hr_gbuffer_raycast(const hr_scene* scene, const hr_ubo* ubo, int32_t w, int32_t h, void* gb1, void* gb2, void* gb3, float* depth, void* stream)
+// motion: hr_gbuffer_raycast_motion on a scene that holds a previous state (a flat scene has none: nothing of it ever moves)
+static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, int32_t w, int32_t h, void* gb1, void* gb2, void* gb3, float* depth, void* stream, bool motion)
 {
     HR_CHECK_ARG(scene && ubo && w > 0 && h > 0 && gb1 && gb2 && gb3 && depth);
+    motion = motion && scene->motion && (scene->n_instances > 0 || scene->deformable);
+    MotionArgs mo = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (motion)
+    {
+        if (scene->n_instances > 0)
+        {
+            mo.prev_mats = (const float*)scene->prev_mats.p;
+            mo.inst = (const InstanceRec*)scene->inst_records.p; mo.tri_instance = (const uint32_t*)scene->tri_instance.p;
+            mo.mesh_positions = (const float*)(scene->shared_deform ? scene->prev_positions.p : scene->mesh_positions.p);
+        }
+        else mo.prev_verts = (const float*)scene->prev_positions.p;
+    }
     GBufArgs a;
     for (int i = 0; i < 16; i++) { a.vpi[i] = ubo->view_proj_inverse[i]; a.vp[i] = ubo->view_proj[i]; a.pvp[i] = ubo->prev_view_proj[i]; }
     for (int i = 0; i < 3; i++) a.cam[i] = ubo->cam_pos[i];
@@ -910,12 +1005,71 @@ hr_status hr_gbuffer_raycast(const hr_scene* scene, const hr_ubo* ubo, int32_t w
         a2.mesh_positions = (const float*)scene->mesh_positions.p;
         a2.mesh_normals = scene->has_normals ? (const float*)scene->mesh_normals.p : nullptr;
         a2.mesh_material = scene->has_material ? (const uint32_t*)scene->mesh_material.p : nullptr;
-        hipLaunchKernelGGL(k_gbuffer_raycast2, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2);
+        if (motion) hipLaunchKernelGGL(k_gbuffer_raycast2<true>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2, mo);
+        else hipLaunchKernelGGL(k_gbuffer_raycast2<false>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2, mo);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
-    hipLaunchKernelGGL(k_gbuffer_raycast, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+    if (motion) hipLaunchKernelGGL(k_gbuffer_raycast<true>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
+    else hipLaunchKernelGGL(k_gbuffer_raycast<false>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
     HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+hr_status hr_gbuffer_raycast(const hr_scene* scene, const hr_ubo* ubo, int32_t w, int32_t h, void* gb1, void* gb2, void* gb3, float* depth, void* stream)
+{
+    return gbuffer_raycast_impl(scene, ubo, w, h, gb1, gb2, gb3, depth, stream, false);
+}
+
+hr_status hr_gbuffer_raycast_motion(const hr_scene* scene, const hr_ubo* ubo, int32_t w, int32_t h, void* gb1, void* gb2, void* gb3, float* depth, void* stream)
+{
+    return gbuffer_raycast_impl(scene, ubo, w, h, gb1, gb2, gb3, depth, stream, true);
+}
+
+// The snapshot of a frame's geometry, on `stream`: the instances' matrices out of the DEVICE records (they hold what the updates enqueued so far
+// on that stream, whatever the host mirrors say by now), the vertices by device copies.  O(instances) for the instanced kinds, 36 B per triangle
+// for a deformable scene, 36 B per triangle of the flagged meshes more for a shared deformable one.
+hr_status hr_scene_motion_begin_frame(hr_scene* scene, void* stream)
+{
+    HR_CHECK_ARG(scene);
+    hr_scene* s = scene;
+    if (s->n_instances <= 0 && !s->deformable) return HR_OK;   // hr_scene_create: nothing of it ever moves
+    hipStream_t st = (hipStream_t)stream;
+    HR_HIP(hipSetDevice(s->ctx->device));
+    const bool first = !s->motion;
+    hr_status e;
+    if (s->n_instances > 0)
+    {
+        const int I = s->n_instances;
+        if (first && (e = s->prev_mats.alloc((size_t)I * 64)) != HR_OK) return e;
+        if (s->shared) hipLaunchKernelGGL(k_motion_snapshot_shared, dim3(cdiv(I * 16, 256)), dim3(256), 0, st, (const InstanceShared*)s->inst_shared.p, (float*)s->prev_mats.p, I);
+        else hipLaunchKernelGGL(k_motion_snapshot_private, dim3(cdiv(I * 16, 256)), dim3(256), 0, st, (const InstanceRec*)s->inst_records.p, (float*)s->prev_mats.p, I);
+        HR_HIP(hipGetLastError());
+        if (s->shared_deform)
+        {
+            const hr::SharedDeform& sd = *s->shared_deform;
+            if (first)
+            {
+                // the whole array once (the kernel indexes it like mesh_positions); afterwards only the meshes that can change
+                if ((e = s->prev_positions.alloc(s->mesh_positions.bytes)) != HR_OK) return e;
+                HR_HIP(hipMemcpyAsync(s->prev_positions.p, s->mesh_positions.p, s->mesh_positions.bytes, hipMemcpyDeviceToDevice, st));
+            }
+            else
+                for (size_t k = 0; k < sd.flag.size(); k++)
+                {
+                    const size_t off = (size_t)sd.tri_base[k] * 36, n = (size_t)sd.n_tris[k] * 36;
+                    if (!sd.flag[k] || n == 0 || off + n > s->prev_positions.bytes) continue;
+                    HR_HIP(hipMemcpyAsync((char*)s->prev_positions.p + off, (const char*)s->mesh_positions.p + off, n, hipMemcpyDeviceToDevice, st));
+                }
+        }
+    }
+    else
+    {
+        const size_t n = (size_t)s->info.n_tris * 36;
+        if (first && (e = s->prev_positions.alloc(n)) != HR_OK) return e;
+        if (n > 0) HR_HIP(hipMemcpyAsync(s->prev_positions.p, s->positions.p, n, hipMemcpyDeviceToDevice, st));
+    }
+    s->motion = true;
     return HR_OK;
 }
 

@@ -350,4 +350,9 @@ struct hr_scene
     double        cost_at_build = 0.0, cost_ratio = 1.0;   // the sum of the slots when the tree was built / last ratio read back
     bool          cost_stale = false;             // cost_ratio lags the last update until hr_scene_refit_cost reads the slots back
     mutable bool  bounds_stale = false;           // info.bounds_* lag the last update until hr_scene_get_info reads them back
+    // ---- motion vectors (api.hip hr_scene_motion_begin_frame / hr_gbuffer_raycast_motion): the geometry as of the last begin_frame, indexed by
+    // instance or by triangle, never by BVH reference — rebuilds, top-level re-builds and refits leave it alone
+    bool          motion = false;                 // begin_frame has been called: the buffers below stand
+    hr::DevBuf    prev_mats;                      // instanced kinds: [n_instances][16] model matrices, by instance index of the scene desc
+    hr::DevBuf    prev_positions;                 // deformable: [n_tris][3][3] world; shared deformable: the object-space mesh_positions
 };

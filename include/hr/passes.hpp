@@ -81,6 +81,10 @@ public:
     float    mesh_refit_cost(uint32_t mesh_idx) const { float r = 1.0f; check(hr_scene_mesh_refit_cost(m_scene, mesh_idx, &r), "hr_scene_mesh_refit_cost"); return r; }
     bool     is_shared() const { return hr_scene_is_shared(m_scene) != 0; }
     void     update_instances(const float* model_matrices, Stream cmd_buf) { check(hr_scene_update_instances(m_scene, model_matrices, cmd_buf), "hr_scene_update_instances"); }
+    // motion vectors that follow the geometry: motion_begin_frame() once per frame BEFORE that frame's update_*() calls, on their stream (the first
+    // call allocates: not under stream capture), then gbuffer_raycast_motion() in the place of hr_gbuffer_raycast (dynamic scenes)
+    void     motion_begin_frame(Stream cmd_buf) { check(hr_scene_motion_begin_frame(m_scene, cmd_buf), "hr_scene_motion_begin_frame"); }
+    void     gbuffer_raycast_motion(const hr_ubo& ubo, int32_t width, int32_t height, void* gb1, void* gb2, void* gb3, float* depth, Stream cmd_buf) const { check(hr_gbuffer_raycast_motion(m_scene, &ubo, width, height, gb1, gb2, gb3, depth, cmd_buf), "hr_gbuffer_raycast_motion"); }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }
     uint64_t id() const { return hr_scene_id(m_scene); }   // dw::Scene::id()
     ~Scene() { hr_scene_destroy(m_scene); }

@@ -95,6 +95,18 @@ hr_status hr_taa_destroy(hr_taa* p);
 hr_status hr_tone_map(hr_ctx* ctx, const hr_image_view* color, int32_t single_channel, float exposure, float* out_rgba32f, uint8_t* out_rgba8,
                       void* stream);
 
+/* ---- motion vectors that follow moving and deforming geometry ------------------------ */
+/* Remember the scene's geometry as "previous frame": call once per frame, BEFORE that frame's update calls, on the stream the updates use.
+ * Every scene kind takes it (hr_scene_create: a successful no-op).  The FIRST call on a scene allocates the previous-state storage (it
+ * synchronises like a creation call) and must not be made under stream capture; later calls only enqueue device copies on `stream`. */
+hr_status hr_scene_motion_begin_frame(hr_scene* scene, void* stream);
+/* hr_gbuffer_raycast, except that the previous clip position follows the hit point's own motion since the last hr_scene_motion_begin_frame:
+ * GB2.zw = uv(prev_view_proj * (P + (prev - cur))) - uv(view_proj * P), prev / cur = the hit triangle's previous / current world vertices
+ * interpolated at the hit.  Everything else, and every texel of geometry that did not move (or of a scene never marked), is
+ * hr_gbuffer_raycast's bit for bit. */
+hr_status hr_gbuffer_raycast_motion(const hr_scene* scene, const hr_ubo* ubo, int32_t width, int32_t height, void* gb1, void* gb2, void* gb3,
+                                    float* depth, void* stream);
+
 /* ---- self test ------------------------------------------------------------------------------------ */
 /* Evaluates the device-side arithmetic of the numerical contract on arrays so tests can
  * compare it bit for bit with a CPU replay.  which: 0 sincos(x)->(s,c)  1 exp(x)  2 log(x)  3 pow(x,y)

@@ -1,0 +1,350 @@
+"""G-buffer motion vectors that follow moving and deforming geometry (hr_scene_motion_begin_frame / hr_gbuffer_raycast_motion, csrc/api.hip;
+DESIGN.md §2).  Everything but GB2.zw is hr_gbuffer_raycast's bit for bit, and so is GB2.zw wherever the geometry stood; where it moved, GB2.zw is
+held against the float64 reference of tests/motion_cases.py (rigid and affine motion, no ray tracing) within fp16 rounding plus the reference's
+own uncertainty, and the kinds of scene are held against each other bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import helpers
+import motion_cases as mc
+import shared_deform_cases as sc
+from hybrid_rendering_amd import synth
+from test_gpu_instances import _mats
+
+pytestmark = pytest.mark.gpu
+W, H = 160, 120
+N_BOXES, SEED = 9, 5
+KEYS = ("gb1", "gb2", "gb3", "depth")
+
+
+def cuda(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+
+
+def bits(a):
+    return a.view(np.uint16) if a.dtype == np.float16 else a
+
+
+def images(g):
+    """cuda G-buffer dict -> numpy bit patterns (fp16 images as uint16, the form the oracle passes take)"""
+    return {k: np.ascontiguousarray(bits(g[k].cpu().numpy())) for k in KEYS}
+
+
+def assert_images_equal(a, b, what, keys=KEYS):
+    for k in keys:
+        assert np.array_equal(a[k], b[k]), f"{what}: {k} differs in {int((a[k] != b[k]).sum())} words"
+
+
+def ids_of(img):
+    return img["gb3"].view(np.float16)[..., 2].astype(np.int64)
+
+
+def ubo_for(f, moving_camera=True, w=W, h=H):
+    cams = helpers.cameras("cornell", w / h, 6, 1.0)
+    cur = cams[f] if moving_camera else cams[0]
+    prev = (cams[f - 1] if f else cams[0]) if moving_camera else cams[0]
+    return synth.make_ubo(cur, prev, helpers.light_for("cornell", "soft"))
+
+
+def entry(d, k):
+    m = d.meshes[k]
+    return dict(mesh_idx=k, positions=cuda(m.verts), normals=cuda(m.normals), first_tri=0)
+
+
+def five_kinds(hr, ctx):
+    isd = synth.instanced_cornell(N_BOXES, seed=SEED)
+    dsd = sc.scene()
+    return dict(flat=hr.Scene(ctx, isd.flatten()), deformable=hr.Scene(ctx, isd.flatten(), deformable=True), private=hr.InstancedScene(ctx, isd),
+                shared=hr.InstancedScene(ctx, isd, shared=True), shared_deformable=hr.InstancedScene(ctx, dsd, shared=True, deformable=sc.FLAGS))
+
+
+def test_a_scene_never_marked_gives_the_plain_gbuffer(hr, ctx):
+    """(a) one scene of each of the five kinds, no hr_scene_motion_begin_frame: the four images of gbuffer(motion=True) are gbuffer()'s"""
+    ubo = ubo_for(1)
+    for kind, g in five_kinds(hr, ctx).items():
+        plain, mot = images(g.gbuffer(ubo, W, H)), images(g.gbuffer(ubo, W, H, motion=True))
+        assert (plain["depth"] < 1.0).mean() > 0.5
+        assert_images_equal(mot, plain, f"{kind}, never marked")
+        g.close()
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_marked_and_partly_moved(hr, ctx, shared):
+    """(b) marked, nothing updated: the plain images.  Then instances 1-4 of 10 move: every texel of an instance that stands is the plain G-buffer's
+    in all four images, the texels of the moved ones differ from it in GB2.zw only — and some do"""
+    isd = synth.instanced_cornell(N_BOXES, seed=SEED)
+    g = hr.InstancedScene(ctx, isd, shared=shared)
+    ubo = ubo_for(1)
+    g.motion_begin_frame()
+    assert_images_equal(images(g.gbuffer(ubo, W, H, motion=True)), images(g.gbuffer(ubo, W, H)), "marked, nothing updated")
+    mats = isd.matrices().copy()
+    for i in range(1, 5):
+        mats[i, 12:15] += np.array([2.0, 1.0 + 0.5 * i, -1.5], np.float32)
+    g.motion_begin_frame()
+    g.update(mats)
+    plain, mot = images(g.gbuffer(ubo, W, H)), images(g.gbuffer(ubo, W, H, motion=True))
+    moved_ids = [isd.instances[i][2] for i in range(1, 5)]
+    moved = np.isin(ids_of(plain), moved_ids) & (plain["depth"] < 1.0)
+    assert moved.sum() > 200 and (~moved).sum() > 200
+    for k in KEYS:
+        assert np.array_equal(mot[k][~moved], plain[k][~moved]), f"{k}: a texel of an instance that stands differs from the plain G-buffer"
+    for k in ("gb1", "gb3", "depth"):
+        assert np.array_equal(mot[k][moved], plain[k][moved]), f"{k} of a moved instance"
+    assert np.array_equal(mot["gb2"][moved][:, :2], plain["gb2"][moved][:, :2]), "the normal of a moved instance"
+    differs = (mot["gb2"][moved][:, 2:] != plain["gb2"][moved][:, 2:]).any(axis=1)
+    assert differs.mean() > 0.9, f"only {differs.mean():.3f} of the moved instances' texels carry object motion"
+    g.close()
+
+
+def test_the_kinds_agree_bit_for_bit(hr, ctx):
+    """(c) four frames of test_gpu_instances._mats motion and one after a forced top-level re-build: the shared scene equals the private-copy scene in
+    all four images, both equal a deformable scene fed isd.flatten(mats) in GB2 and depth"""
+    isd = synth.instanced_cornell(N_BOXES, seed=SEED)
+    g, gp = hr.InstancedScene(ctx, isd, shared=True), hr.InstancedScene(ctx, isd)
+    gd = hr.Scene(ctx, isd.flatten(), deformable=True)
+    carried = 0
+    for f in range(5):
+        mats = _mats(isd, N_BOXES, SEED, f)
+        flat = isd.flatten(mats)
+        for s in (g, gp, gd):
+            s.motion_begin_frame()
+        g.update(mats); gp.update(mats)
+        gd.update_vertices(cuda(flat.verts), cuda(flat.normals))
+        if f == 4:
+            g.rebuild_top_level(); gp.rebuild_top_level()   # the shared scene's records change order, the private one's roots change slots
+        ubo = ubo_for(f)
+        a, b, c = (images(s.gbuffer(ubo, W, H, motion=True)) for s in (g, gp, gd))
+        assert_images_equal(a, b, f"frame {f}: shared against private copies")
+        assert_images_equal(a, c, f"frame {f}: instanced against the deformable scene over the flattened vertices", keys=("gb2", "depth"))
+        if f:
+            carried += int((a["gb2"][..., 2:] != images(g.gbuffer(ubo, W, H))["gb2"][..., 2:]).any())
+    assert carried == 4, "every frame after the first carries object motion"
+    assert g.top_level_rebuilds >= 1 and gp.top_level_rebuilds >= 1
+    for s in (g, gp, gd):
+        s.close()
+
+
+def test_a_shared_deformable_scene_agrees_with_the_flattened_and_the_private_copy_scene(hr, ctx):
+    """(c) meshes deforming (synth.deform through update_meshes) between matrix updates.  A private-copy scene cannot deform, so no single one holds
+    both frames' states: the motion is held against a deformable scene fed the deformed meshes flattened at BOTH states (GB2, depth), and everything
+    but GB2.zw against a private-copy scene created over the current deformed meshes"""
+    isd = sc.scene()
+    g = hr.InstancedScene(ctx, isd, shared=True, deformable=sc.FLAGS)
+    gd = hr.Scene(ctx, isd.flatten(), deformable=True)
+    for f, step in enumerate((0, 4, 8)):
+        d, mats, _ = sc.step_inputs(isd, step)
+        flat = d.flatten(mats)
+        g.motion_begin_frame(); gd.motion_begin_frame()
+        g.update_meshes([entry(d, sc.FIELD), entry(d, sc.BOX)]); g.update(mats)
+        gd.update_vertices(cuda(flat.verts), cuda(flat.normals))
+        ubo = ubo_for(f)
+        a, c = images(g.gbuffer(ubo, W, H, motion=True)), images(gd.gbuffer(ubo, W, H, motion=True))
+        assert_images_equal(a, c, f"frame {f}: shared deformable against the flattened deformable scene", keys=("gb2", "depth"))
+        fresh = hr.InstancedScene(ctx, d)
+        fresh.update(mats)
+        p = images(fresh.gbuffer(ubo, W, H))
+        assert_images_equal(a, p, f"frame {f}: against a private-copy scene over the deformed meshes", keys=("gb1", "gb3", "depth"))
+        assert np.array_equal(a["gb2"][..., :2], p["gb2"][..., :2]), f"frame {f}: normals"
+        deforming = np.isin(ids_of(a), [i for _, k, i in isd.instances if k >= sc.FIELD]) & (a["depth"] < 1.0)
+        assert deforming.sum() > 100
+        assert (a["gb2"][deforming][:, 2:] != p["gb2"][deforming][:, 2:]).any(), f"frame {f}: the deforming meshes carry motion of their own"
+        fresh.close()
+    g.close(); gd.close()
+
+
+def _moving_instances(frame):
+    """the placements of synth.instanced_cornell_instances(9, seed=5), every instance moving: the room drifts, the others turn 0.2 rad per frame
+    about their own axes, the odd ones drift, the even ones scale non-uniformly"""
+    rng = np.random.RandomState(SEED)
+    inst = [(synth.model_matrix(np.array([2.5, 1.5, 0.0]) * frame), 0, 1)]
+    for i in range(N_BOXES):
+        pos = np.array([rng.uniform(15, 85), rng.uniform(8, 40), rng.uniform(15, 85)])
+        axis, ang = rng.uniform(-1, 1, 3), rng.uniform(0, 2 * np.pi)
+        scale = rng.uniform(8, 28, 3)
+        if i % 2:
+            pos = pos + np.array([1.7, 0.9, -1.3]) * frame
+        else:
+            scale = scale * (1.0 + frame * np.array([0.06, -0.04, 0.03]))
+        inst.append((synth.model_matrix(pos, axis, ang + 0.2 * frame, scale), 1 + (i % 2), 2 + i))
+    return inst
+
+
+def _check_values(img, ubo, transforms, default, what, w=W):
+    ref, bound, surface, moved = mc.reference(img["depth"], img["gb3"], ubo, transforms, default)
+    got = img["gb2"].view(np.float16)[..., 2:].astype(np.float64)
+    err, tol = np.abs(got - ref)[surface], (2.0 ** -11 * np.abs(ref) + bound)[surface]
+    mag = np.linalg.norm(ref[moved], axis=1)
+    print(f"{what}: surface {surface.mean():.3f}, moved {moved.sum() / max(surface.sum(), 1):.3f} of it, median |motion| {np.median(mag) * w:.3f} texels, "
+          f"worst error / tolerance {float((err / tol).max()):.3f}, worst error {float(err.max()):.3e}")
+    assert moved.sum() >= 0.25 * surface.sum(), f"{what}: moved geometry covers {moved.sum()} of {surface.sum()} surface texels"
+    assert np.median(mag) > 1.0 / w, f"{what}: median |motion| {np.median(mag)}"
+    assert (err <= tol).all(), f"{what}: {int((err > tol).sum())} texels outside fp16 rounding + the reference's bound, worst {float((err / tol).max()):.2f} x"
+
+
+@pytest.mark.parametrize("moving_camera", [False, True])
+@pytest.mark.parametrize("shared", [False, True])
+def test_values_of_translating_rotating_and_scaling_instances(hr, ctx, shared, moving_camera):
+    """(d) every surface texel of two frames: |GB2.zw - reference| <= 2^-11 |reference| + the reference's bound, no exclusions"""
+    mesh = synth.instanced_cornell(N_BOXES, seed=SEED)
+    isd = synth.InstancedSceneData(mesh.meshes, _moving_instances(0), mesh.materials)
+    g = hr.InstancedScene(ctx, isd, shared=shared)
+    prev = isd.matrices()
+    for f in (1, 2):
+        mats = synth.InstancedSceneData(mesh.meshes, _moving_instances(f), mesh.materials).matrices()
+        g.motion_begin_frame()
+        g.update(mats)
+        ubo = ubo_for(f, moving_camera)
+        img = images(g.gbuffer(ubo, W, H, motion=True))
+        transforms = {int(mid): (mc.mat4(prev[i]), mc.mat4(mats[i])) for i, (_, _, mid) in enumerate(isd.instances)}
+        _check_values(img, ubo, transforms, None, f"{'shared' if shared else 'private'}, camera {'moving' if moving_camera else 'static'}, frame {f}")
+        prev = mats
+    g.close()
+
+
+def _affine(frame):
+    """about the room's centre: a turn of 0.2 rad per frame about a tilted axis, a non-uniform scale and a drift"""
+    c = np.array([50.0, 50.0, 50.0])
+    M = synth.model_matrix((0.0, 0.0, 0.0), (0.2, 1.0, 0.1), 0.2 * frame, 1.0 + frame * np.array([0.04, -0.03, 0.05]))
+    A = mc.mat4(M)
+    A[:3, 3] = c - A[:3, :3] @ c + np.array([2.0, -1.0, 1.5]) * frame
+    return A
+
+
+@pytest.mark.parametrize("moving_camera", [False, True])
+def test_values_of_a_deformable_scene_under_an_affine_map(hr, ctx, moving_camera):
+    """(d) the update is an affine map of the rest pose (vertices rounded to fp32 once: below the reference's floor at these distances)"""
+    rest = synth.instanced_cornell(N_BOXES, seed=SEED).flatten()
+    g = hr.Scene(ctx, rest, deformable=True)
+    pose = lambda A: cuda((rest.verts.reshape(-1, 3).astype(np.float64) @ A[:3, :3].T + A[:3, 3]).reshape(-1, 3, 3))
+    g.update_vertices(pose(_affine(1)))
+    for f in (2, 3):
+        g.motion_begin_frame()
+        g.update_vertices(pose(_affine(f)))
+        ubo = ubo_for(f, moving_camera)
+        img = images(g.gbuffer(ubo, W, H, motion=True))
+        _check_values(img, ubo, {}, (_affine(f - 1), _affine(f)), f"deformable, camera {'moving' if moving_camera else 'static'}, frame {f}")
+    g.close()
+
+
+def test_geometry_that_stops_moving(hr, ctx):
+    """(e) frame 1 moves a range of triangles / an instance, frame 2 does not, hr_scene_motion_begin_frame before each: at frame 2 the plain G-buffer"""
+    isd = synth.instanced_cornell(N_BOXES, seed=SEED)
+    rest = isd.flatten()
+    first, _, _, count = isd.layout()
+    lo, n = int(first[2]), int(count[2:7].sum())                         # instances 2 to 6: a range in the middle of the scene
+    gd, gs = hr.Scene(ctx, rest, deformable=True), hr.InstancedScene(ctx, isd, shared=True)
+    mats = _mats(isd, N_BOXES, SEED, 3)
+    ubo = ubo_for(1)
+    gd.motion_begin_frame(); gs.motion_begin_frame()
+    gd.update_vertices(cuda(rest.verts[lo:lo + n] + np.array([3.0, 2.0, 0.0], np.float32)), first_tri=lo)
+    gs.update(mats)
+    for what, g in (("deformable", gd), ("shared", gs)):
+        assert (images(g.gbuffer(ubo, W, H, motion=True))["gb2"] != images(g.gbuffer(ubo, W, H))["gb2"]).any(), f"{what}: frame 1 carries object motion"
+    gd.motion_begin_frame(); gs.motion_begin_frame()
+    gs.update(mats)                                                      # the same matrices: nothing moves
+    for what, g in (("deformable", gd), ("shared", gs)):
+        assert_images_equal(images(g.gbuffer(ubo, W, H, motion=True)), images(g.gbuffer(ubo, W, H)), f"{what}: frame 2, nothing moved")
+    gd.close(); gs.close()
+
+
+def test_a_rebuild_between_the_mark_and_the_draw(hr, ctx):
+    """(f) hr_scene_rebuild swaps the tree and the references; the previous state is indexed by triangle and does not notice"""
+    rest = synth.instanced_cornell(N_BOXES, seed=SEED).flatten()
+    a, b = hr.Scene(ctx, rest, deformable=True), hr.Scene(ctx, rest, deformable=True)
+    s1, s2 = synth.deform(rest, 1, "wave"), synth.deform(rest, 3, "twist")
+    ubo = ubo_for(2)
+    for g in (a, b):
+        g.update_vertices(cuda(s1.verts), cuda(s1.normals))
+        g.motion_begin_frame()
+        g.update_vertices(cuda(s2.verts), cuda(s2.normals))
+    b.rebuild()
+    ia, ib = images(a.gbuffer(ubo, W, H, motion=True)), images(b.gbuffer(ubo, W, H, motion=True))
+    assert_images_equal(ib, ia, "with a rebuild against without")
+    assert (ia["gb2"][..., 2:] != images(a.gbuffer(ubo, W, H))["gb2"][..., 2:]).any()
+    a.close(); b.close()
+
+
+def test_the_passes_consume_it(oracle, hr, ctx):
+    """(g) four frames of shadows and AO, exact mode, 96 x 64, private-copy scene, G-buffers from gbuffer(motion=True): every stage image equals the
+    oracle pass fed the same arrays"""
+    import torch
+    w, h = 96, 64
+    isd = synth.instanced_cornell(N_BOXES, seed=SEED)
+    g, osc = hr.InstancedScene(ctx, isd), oracle.InstancedScene(isd)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    zbp = synth.z_buffer_params()
+    gs, os_ = hr.RayTracedShadows(ctx, w, h), oracle.ShadowsPass(w, h)
+    ga, oa = hr.RayTracedAO(ctx, w, h, 0), oracle.AOPass(w, h, spp=2, zbp=zbp)
+    gs.params.exact = ga.params.exact = 1
+    ga.params.spp = 2
+    prev = None
+    for f in range(4):
+        mats = _mats(isd, N_BOXES, SEED, f)
+        g.motion_begin_frame()
+        g.update(mats); osc.update(mats)
+        ubo = ubo_for(f, True, w, h)
+        cur = images(g.gbuffer(ubo, w, h, motion=True))
+        if f:
+            assert (cur["gb2"][..., 2:] != images(g.gbuffer(ubo, w, h))["gb2"][..., 2:]).any(), f"frame {f}: the G-buffer carries object motion"
+        prv = prev if prev is not None else cur
+        ping = bool(f & 1)
+        fi = hr.frame_inputs(helpers.to_cuda(cur), helpers.to_cuda(prv), ubo, f, f & 1, sob_d, sr_d, z_buffer_params=zbp)
+        gs.render(g, fi)
+        os_.render(osc, ubo, cur, prv, sob, sr, f)
+        torch.cuda.synchronize()
+        st = os_.stages
+        assert np.array_equal(gs.image(gs.IMG_MASK).cpu().numpy().view(np.uint32), st["mask"]), f"frame {f}: shadow mask"
+        assert np.array_equal(gs.image(gs.IMG_TILES).cpu().numpy(), st["tiles"]), f"frame {f}: shadow tiles"
+        assert np.array_equal(helpers.bits16(gs.image(gs.IMG_TEMPORAL)), st["temporal"]), f"frame {f}: shadow temporal"
+        assert np.array_equal(helpers.bits16(gs.image(gs.IMG_MOMENTS1 if ping else gs.IMG_MOMENTS0)), st["moments"]), f"frame {f}: shadow moments"
+        assert np.array_equal(helpers.bits16(gs.image(gs.IMG_PREV)), os_.prev_image), f"frame {f}: shadow feedback image"
+        assert np.array_equal(helpers.bits16(gs.output(hr.OUTPUT_ATROUS)), st["output"]), f"frame {f}: denoised shadows"
+        ga.render(g, fi)
+        oa.render(osc, ubo, cur, prv, sob, sr, f)
+        torch.cuda.synchronize()
+        st = oa.stages
+        mh = (h + 3) // 4
+        assert np.array_equal(ga.image(ga.IMG_MASK).cpu().numpy().view(np.uint32)[:2 * mh].reshape(2, mh, -1), st["mask"]), f"frame {f}: AO masks"
+        assert np.array_equal(ga.image(ga.IMG_TILES).cpu().numpy(), st["tiles"]), f"frame {f}: AO tiles"
+        assert np.array_equal(helpers.bits16(ga.image(ga.IMG_AO1 if ping else ga.IMG_AO0)), st["temporal"]), f"frame {f}: temporal AO"
+        assert np.array_equal(helpers.bits16(ga.image(ga.IMG_LEN1 if ping else ga.IMG_LEN0)), st["length"]), f"frame {f}: AO history length"
+        assert np.array_equal(helpers.bits16(ga.image(ga.IMG_BLUR0)), st["blur0"]) and np.array_equal(helpers.bits16(ga.image(ga.IMG_BLUR1)), st["blur1"]), f"frame {f}: AO blur"
+        assert np.array_equal(helpers.bits16(ga.output(hr.OUTPUT_UPSAMPLE)), st["output"]), f"frame {f}: AO output"
+        prev = cur
+    for p in (gs, ga, g):
+        p.close()
+
+
+def test_errors_enqueue_nothing(hr, ctx):
+    """(h) NULL scene or images, non-positive sizes: HR_ERR_INVALID_ARG with a last-error string and untouched images; hr_scene_create scenes take
+    hr_scene_motion_begin_frame as a no-op"""
+    import torch
+    L = hr.lib()
+    L.hr_gbuffer_raycast_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hr_scene_motion_begin_frame.argtypes = [C.c_void_p, C.c_void_p]
+    isd = synth.instanced_cornell(3, seed=1)
+    flat, g = hr.Scene(ctx, isd.flatten()), hr.InstancedScene(ctx, isd)
+    u = hr.make_ubo(ubo_for(0))
+    w, h = 32, 16
+    gb1 = torch.full((h, w, 4), 7, dtype=torch.uint8, device="cuda")
+    gb2, gb3 = torch.full((h, w, 4), 3.0, dtype=torch.float16, device="cuda"), torch.full((h, w, 4), 3.0, dtype=torch.float16, device="cuda")
+    depth = torch.full((h, w), 0.25, dtype=torch.float32, device="cuda")
+    p = [C.c_void_p(t.data_ptr()) for t in (gb1, gb2, gb3, depth)]
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g.motion_begin_frame()
+    bad = [(None, C.byref(u), w, h, *p), (g.h, None, w, h, *p), (g.h, C.byref(u), 0, h, *p), (g.h, C.byref(u), w, -3, *p)]
+    bad += [(g.h, C.byref(u), w, h, *(p[:k] + [None] + p[k + 1:])) for k in range(4)]
+    for args in bad:
+        assert L.hr_gbuffer_raycast_motion(*args, st) == 1, "HR_ERR_INVALID_ARG"
+        assert L.hr_last_error().decode().startswith("invalid argument")
+    assert L.hr_scene_motion_begin_frame(None, st) == 1 and L.hr_last_error().decode().startswith("invalid argument")
+    torch.cuda.synchronize()
+    assert (gb1 == 7).all() and (gb2 == 3.0).all() and (gb3 == 3.0).all() and (depth == 0.25).all(), "a refused call wrote an image"
+    assert L.hr_scene_motion_begin_frame(flat.h, st) == 0
+    ubo = ubo_for(0)
+    assert_images_equal(images(flat.gbuffer(ubo, W, H, motion=True)), images(flat.gbuffer(ubo, W, H)), "a flat scene after begin_frame")
+    flat.close(); g.close()

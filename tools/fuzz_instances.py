@@ -8,7 +8,10 @@ image are compared with the oracle's instanced scene.   python tools/fuzz_instan
 synthesiser and the shadows pass take such a scene, so only those are compared with the oracle, and the bounds only have to be conservative.
 --deform (implies --shared): hr_scene_create_instanced_shared_deformable with a random subset of the small meshes flagged; between the matrix
 updates and the forced top-level re-builds a random subset of the flagged meshes takes a synth.deform step through hr_scene_update_meshes (whole
-meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes."""
+meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes.
+--motion (not with --deform): beside the scene under test, a shared scene, a private-copy scene and a deformable scene over the flattened vertices
+take hr_scene_motion_begin_frame and the same updates every step; the four images of hr_gbuffer_raycast_motion must be equal between the shared
+and the private-copy scene, and GB2 (normal + motion vector) and depth equal to the deformable scene's, bit for bit."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +24,11 @@ import helpers
 DEFORM = "--deform" in sys.argv
 if DEFORM:
     sys.argv.remove("--deform")
+MOTION = "--motion" in sys.argv
+if MOTION:
+    sys.argv.remove("--motion")
+    if DEFORM:
+        sys.exit("--motion compares with a private-copy scene, which cannot deform: not with --deform")
 SHARED = "--shared" in sys.argv or DEFORM
 if "--shared" in sys.argv:
     sys.argv.remove("--shared")
@@ -79,7 +87,9 @@ for trial in range(n):
         g = hr.InstancedScene(ctx, isd, shared=True, deformable=flags if DEFORM else None) if SHARED else hr.InstancedScene(ctx, isd)
         mats = isd.matrices().copy()
         cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+        mg = [hr.InstancedScene(ctx, isd, shared=True), hr.InstancedScene(ctx, isd), hr.Scene(ctx, isd.flatten(), deformable=True)] if MOTION else []
         for step in range(int(rng.randint(3, 7))):
+            forced = False
             if step:
                 move = rng.rand(I) < rng.choice([0.1, 0.5, 1.0])
                 move[0] = rng.rand() < 0.1
@@ -91,6 +101,7 @@ for trial in range(n):
                 g.update(mats)
                 if rng.rand() < 0.15:
                     g.rebuild_top_level()
+                    forced = True
                 chosen = [k for k, f in enumerate(flags) if f and rng.rand() < 0.7]
                 if chosen:
                     kinds = {k: str(rng.choice(["wave", "twist", "collapse"])) for k in chosen}
@@ -109,6 +120,19 @@ for trial in range(n):
                         mats[int(rng.randint(0, I)), 12:15] += rng.uniform(-2, 2, 3).astype(np.float32)
                         g.update(mats)
             flat_sd = isd.flatten(mats)
+            if MOTION:
+                for s_ in mg:
+                    s_.motion_begin_frame()
+                mg[0].update(mats); mg[1].update(mats)
+                mg[2].update_vertices(cuda(flat_sd.verts), cuda(flat_sd.normals))
+                if forced:
+                    mg[0].rebuild_top_level(); mg[1].rebuild_top_level()
+                cams = helpers.cameras("cornell", 96 / 72, 8, 1.0)
+                ubo = synth.make_ubo(cams[step + 1], cams[step], helpers.light_for("cornell", "soft"))
+                im = [{k: t.cpu().numpy().view(np.uint8) for k, t in s_.gbuffer(ubo, 96, 72, motion=True).items()} for s_ in mg]
+                for k in im[0]:
+                    if not np.array_equal(im[0][k], im[1][k]): msg.append(f"step {step}: motion G-buffer {k}: shared against private copies")
+                    if k in ("gb2", "depth") and not np.array_equal(im[0][k], im[2][k]): msg.append(f"step {step}: motion G-buffer {k}: against the flattened deformable scene")
             gf = hr.Scene(ctx, flat_sd)
             lo, hi = flat_sd.bounds()
             rays = np.zeros((20000, 8), np.float32)
@@ -167,6 +191,7 @@ for trial in range(n):
                 for p in (gs, gd, gr): p.close()
         rb = g.top_level_rebuilds
         g.close()
+        for s_ in mg: s_.close()
     except Exception as e:
         msg.append("ERROR " + repr(e)[:200]); rb = -1
     bad += 1 if msg else 0
