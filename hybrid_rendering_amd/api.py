@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "hr_shadows_atrous_iteration", "hr_shadows_upsample", "hr_shadows_image", "hr_shadows_history_apron_exceeded", "hr_shadows_set_profiling", "hr_shadows_get_stage_times",
     "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_bvh_child_boxes", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
     "hr_selftest_math_sweep", "hr_selftest_fast_math",
-    "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint",
+    "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint", "hr_scene_enable_two_level_passes", "hr_scene_two_level_passes",
     "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
     "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",
     "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
@@ -340,7 +340,8 @@ class InstancedScene(Scene):
     """dw::RayTracedScene as the reference holds it — meshes + instances — with the per-frame update of main.cpp:74 (build_tlas):
     hr_scene_create_instanced / hr_scene_update_instances.  ``isd``: synth.InstancedSceneData.  Every pass takes it like a Scene.
     ``shared=True``: hr_scene_create_instanced_shared — one BVH per mesh, walked on two levels; same answers, O(meshes + instances) memory;
-    queries, the G-buffer synthesiser and the shadows pass take it, the other passes raise HRError (HR_ERR_UNSUPPORTED).
+    queries, the G-buffer synthesiser and the shadows pass take it; AO, DDGI, reflections, the ground truth and the hybrid frame take it after
+    ``enable_two_level_passes()`` and raise HRError (HR_ERR_UNSUPPORTED) before it (the default, until the next API revision).
     ``deformable=[...]`` (with ``shared=True``): hr_scene_create_instanced_shared_deformable — one flag per mesh; a flagged mesh is built without
     spatial splits and ``update_meshes`` replaces its vertices on the GPU (``mesh_refit_cost`` for when its refitted tree has gone bad)."""
 
@@ -361,6 +362,16 @@ class InstancedScene(Scene):
             _check(lib().hr_scene_create_instanced(ctx.h, C.byref(d), C.byref(self.h)), "hr_scene_create_instanced")
         self.info = hr_scene_info()
         self.refresh_info()
+
+    def enable_two_level_passes(self, on: bool = True):
+        """hr_scene_enable_two_level_passes: let AO, DDGI, reflections, the ground truth and the hybrid frame walk this SHARED scene on two levels
+        (off by default: they refuse it).  Changes nothing about the scene's arrays or its answers; HRError (HR_ERR_INVALID_ARG) for another kind."""
+        _check(lib().hr_scene_enable_two_level_passes(self.h, C.c_int32(1 if on else 0)), "hr_scene_enable_two_level_passes")
+        return self
+
+    @property
+    def two_level_passes(self) -> bool:
+        return bool(lib().hr_scene_two_level_passes(self.h))
 
     def rebuild_top_level(self, stream=None):
         _check(lib().hr_scene_rebuild_top_level(self.h, _stream_ptr(stream)), "hr_scene_rebuild_top_level")

@@ -69,18 +69,31 @@ extern "C" int hr_debug_divergence_ddgi(uint64_t* out, int reset)
 #ifndef DDGI_COOP
 #define DDGI_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop); 0 = the per-lane loops
 #endif
+#ifndef DDGI_COOP2
+#define DDGI_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane: 0.400 -> 0.351 ms
+#endif                 // (16x8x16 probes, 256 rays, 201 instances; docs/EXPERIMENTS.md), images bit-identical
 #ifndef DDGI_TRACE_EU
 #define DDGI_TRACE_EU 6   // minimum waves per SIMD the register allocator must leave room for: 1 / 6 / 7 -> 325 / 318 / 338 us
 #endif
 // STATS: the instrumented build behind hr_ddgi_trace_stats — per-lane closest-hit walk (same hits as the cooperative one), every node
 // step and triangle test of the probe rays and of the hit shader's light / sky rays counted (the BVH term of the
 // algorithmic bytes).  The product launches <false>.
-template <bool STATS>
-__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a)
+// SHARED: the probe rays and the hit shader's visibility rays over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of
+// traverse2.h, one ray per lane, hit shading from the Hit2 (shading.h).  <STATS, false> is the kernel as it was.
+#ifndef DDGI_TRACE_SHARED_EU
+#define DDGI_TRACE_SHARED_EU 4   // SHARED: under the single-level kernel's bound of 6 the two-level walk spills (docs/EXPERIMENTS.md)
+#endif
+template <bool STATS, bool SHARED = false>
+__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a)
 {
+    static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(SHARED && DDGI_SEQ), "-DDDGI_SEQ walks one level: it cannot trace a shared instanced scene");
     __shared__ uint32_t s_stack[DDGI_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if DDGI_COOP
     __shared__ CoopWave s_coop[DDGI_TRACE_WAVES];
+#endif
+#if DDGI_COOP2
+    __shared__ CoopWave2 s_coop2[DDGI_TRACE_WAVES];   // SHARED only: the other instantiation never names it
 #endif
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int R = a.d.rays_per_probe;
@@ -99,21 +112,32 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_EU) void k_ddgi_t
         rays++;
     }
     uint32_t st_n = 0, st_t = 0;
-#if DDGI_COOP
-    HitRec h;
-    if (!STATS) h = trace_coop<false>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+    typename std::conditional<SHARED, Hit2, HitRec>::type h;
+    if constexpr (SHARED)
+    {
+#if DDGI_COOP2
+        h = trace_coop2<false>(valid, Scene2 { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+#else
+        h.prim = -1;
+        if (valid) h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+#endif
+    }
     else
     {
-        h.prim = -1;
-        if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
-    }
+#if DDGI_COOP
+        if (!STATS) h = trace_coop<false>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+        else
+        {
+            h.prim = -1;
+            if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+        }
 #else
-    HitRec h;
-    h.prim = -1;
-    DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
-    HR_DIV(dvp_ptr = &dvp;)
-    if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
+        h.prim = -1;
+        DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
+        HR_DIV(dvp_ptr = &dvp;)
+        if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
 #endif
+    }
     if (valid)
     {
         Rng   rng = rng_init((uint32_t)ray, (uint32_t)probe, a.num_frames);
@@ -131,8 +155,8 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_EU) void k_ddgi_t
             const f3 F0 = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
             const float r2x = next_float(rng), r2y = next_float(rng);
-            TraceCtx tc { a.nodes, a.tris, s_stack[wave], lane };
-            HR_DIV(tc.dv = &dvs;)
+            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
 #if DDGI_SEQ && !defined(HR_DEV_PATHS)
 #error "-DDDGI_SEQ=1 is an A/B path: build with -DHR_DEV_PATHS"
 #endif
@@ -606,6 +630,12 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
 {
     HR_CHECK_ARG(p && scene && in && env && prm && env->sky && env->sky_size > 0);
     HR_REJECT_SHARED(scene, "hr_ddgi_ray_trace");
+    // shared instanced scene (opted in): no statistics build and no wavefront form of the two-level kernel — refused before anything is enqueued
+    if (scene->shared && (p->want_stats || p->wavefront))
+    {
+        set_last_error("hr_ddgi_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
+        return HR_ERR_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong
@@ -661,7 +691,8 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
 #endif
     {
         const int tb = 64 * DDGI_TRACE_WAVES;
-        hipLaunchKernelGGL(k_ddgi_trace<false>, dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
+        if (scene->shared) hipLaunchKernelGGL((k_ddgi_trace<false, true>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
+        else hipLaunchKernelGGL((k_ddgi_trace<false, false>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
     }
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());

@@ -45,7 +45,8 @@ HR_DEV f3 sample_specular_ggx_lobe(f3 n, float alpha, float xi_x, float xi_y)
 }
 
 // INDIRECT = false is the reference as shipped (one invocation per pixel: no payload chain to keep)
-template <bool INDIRECT>
+// SHARED: every bounce and every visibility ray over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of traverse2.h
+template <bool INDIRECT, bool SHARED = false>
 __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
 {
     __shared__ uint32_t s_stack[HR_STACK_ENTRIES * 64];
@@ -77,7 +78,9 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
         {
             adds[depth] = mk3(0.0f, 0.0f, 0.0f);
             rays++;
-            const HitRec h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
+            typename std::conditional<SHARED, Hit2, HitRec>::type h;
+            if constexpr (SHARED) h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, o, d, t_min, 10000.0f, s_stack, lane);
+            else h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
             if (h.prim < 0)
             {
                 const f3 env = a.sky.fetch(d);
@@ -93,6 +96,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
             const float r1x = next_float(rng), r1y = next_float(rng), r2x = next_float(rng), r2y = next_float(rng);
             f3       Lo = mk3(0.0f, 0.0f, 0.0f);
             const f3 ray_origin = add3(s.P, scale3(s.N, 0.1f));
+            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack, lane);
             {
                 f3    Wi;
                 float t_max, attenuation;
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
                 if (attenuation > 0.0f)
                 {
                     rays++;
-                    attenuation = attenuation * (trace_any<false>(a.nodes, a.tris, ray_origin, Wi, 0.01f, t_max, s_stack, lane, nn, nt) ? 0.0f : 1.0f);
+                    attenuation = attenuation * (visibility_ray_occluded<false>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
                 }
                 const f3 brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
                 Lo = add3(Lo, mul3(scale3(mul3(T, brdf), attenuation), Li));
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
                 f3       Li = a.sky.fetch(Wi);
                 const f3 Wh = normalize3(add3(Wo, Wi));
                 rays++;
-                Li = scale3(Li, trace_any<false>(a.nodes, a.tris, ray_origin, Wi, 0.01f, 10000.0f, s_stack, lane, nn, nt) ? 0.0f : 1.0f);
+                Li = scale3(Li, visibility_ray_occluded<false>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
                 const f3 brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
                 Lo = add3(Lo, mul3(mul3(T, brdf), Li));
             }
@@ -249,8 +253,13 @@ hr_status hr_ground_truth_render(hr_ground_truth* p, const hr_scene* scene, cons
     const int tiles_y = cdiv(p->y1, 8) - a.tile_y0;
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
     int ev = p->prof.begin("path_trace", st, px * 16);
-    if (a.trace_indirect) hipLaunchKernelGGL(k_ground_truth<true>, dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_ground_truth<false>, dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
+    if (scene->shared)
+    {
+        if (a.trace_indirect) hipLaunchKernelGGL((k_ground_truth<true, true>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((k_ground_truth<false, true>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
+    }
+    else if (a.trace_indirect) hipLaunchKernelGGL((k_ground_truth<true, false>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_ground_truth<false, false>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     p->ping_pong = !p->ping_pong;

@@ -71,7 +71,8 @@ hr_status instanced_scene_wait_uploads(hr_scene* s);
 hr_status instanced_scene_mark_uploads(hr_scene* s, hipStream_t st);
 int       private_copy_top_depth(hr_scene* stub, const std::vector<int>& mesh_depth_of_instance);
 bool      finite_matrix(const float* m);
-// instances_shared.hip.  HR_REJECT_SHARED: first statement (after the argument checks) of every pass that cannot walk a shared scene yet
+// instances_shared.hip.  HR_REJECT_SHARED: first statement (after the argument checks) of every pass that walks a shared scene only after
+// hr_scene_enable_two_level_passes (the refusal is the published default of this API revision)
 bool      reject_shared_scene(const hr_scene* s, const char* pass);
 #define HR_REJECT_SHARED(scene, pass) do { if (::hr::reject_shared_scene(scene, pass)) return HR_ERR_UNSUPPORTED; } while (0)
 hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild);
@@ -331,6 +332,7 @@ struct hr_scene
     // ---- shared instanced scenes (instances_shared.hip): `nodes` = [ top level, top_cap slots | mesh 0's tree | mesh 1's ... ], `tris` = the meshes'
     // object-space references (prim = mesh-local triangle), inst_shared = one InstanceShared per top-level leaf
     bool          shared = false;
+    bool          two_level_passes = false;       // hr_scene_enable_two_level_passes: AO, DDGI, reflections and the ground truth take the scene (default: they refuse it)
     hr::DevBuf    inst_shared;
     std::vector<hr::InstanceShared> shared_host;  // upload staging, in leaf order
     std::vector<int32_t>  shared_leaf_of;         // per instance: its leaf (= record) index

@@ -502,7 +502,7 @@ hr_status footprint_impl(const hr_instanced_scene_desc* d, int32_t shared, hr_sc
 
 bool hr::reject_shared_scene(const hr_scene* s, const char* pass)
 {
-    if (!s || !s->shared) return false;
+    if (!s || !s->shared || s->two_level_passes) return false;
     set_last_error(std::string(pass) + ": a shared instanced scene (hr_scene_create_instanced_shared) is not supported by this pass yet; use hr_scene_create_instanced");
     return true;
 }
@@ -612,6 +612,16 @@ hr_status hr_scene_create_instanced_shared_deformable(hr_ctx* ctx, const hr_inst
 }
 
 int32_t hr_scene_is_shared(const hr_scene* scene) { return scene && scene->shared ? 1 : 0; }
+
+// a host-side flag only: no device array and no answer of the scene depends on it
+hr_status hr_scene_enable_two_level_passes(hr_scene* scene, int32_t enable)
+{
+    HR_CHECK_ARG(scene);
+    if (!scene->shared) { set_last_error("hr_scene_enable_two_level_passes: not a shared instanced scene (hr_scene_create_instanced_shared)"); return HR_ERR_INVALID_ARG; }
+    scene->two_level_passes = enable != 0;
+    return HR_OK;
+}
+int32_t hr_scene_two_level_passes(const hr_scene* scene) { return scene && scene->shared && scene->two_level_passes ? 1 : 0; }
 
 hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info)
 {

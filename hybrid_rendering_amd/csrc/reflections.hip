@@ -103,6 +103,9 @@ extern "C" int hr_debug_divergence_refl(uint64_t* out, int reset)
 #ifndef REFL_COOP
 #define REFL_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop); 0 = the per-lane loops
 #endif
+#ifndef REFL_COOP2
+#define REFL_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane: 0.239 -> 0.188 ms
+#endif                 // (half of 1080p, 201 instances; docs/EXPERIMENTS.md), trace image bit-identical
 #ifndef REFL_TRACE_EU
 #define REFL_TRACE_EU 1   // minimum waves per SIMD the register allocator must leave room for: 1 / 6 / 7 -> 216 / 226 / 235 us
 #endif
@@ -116,12 +119,18 @@ extern "C" int hr_debug_divergence_refl(uint64_t* out, int reset)
 // loop runs once per wave instead of once at each of two sites: 185 -> 172 us at 1080p, 488 -> 466 us at 4K; prepared denominators for the
 // atlas coordinates, shading.h IrrDiv: -> 165 / 454; the fast gather was 149 / 382).
 // The trace image is bit-exact in tolerance mode too.
-template <bool STATS>
+// SHARED: the reflection rays and the hit shader's light rays over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of
+// traverse2.h, one ray per lane, hit shading from the Hit2 (shading.h); both arithmetic modes launch it.  <STATS, false> is the kernel as it was.
+template <bool STATS, bool SHARED = false>
 __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace(ReflTraceArgs a)
 {
+    static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
     __shared__ uint32_t s_stack[REFL_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if REFL_COOP
     __shared__ CoopWave s_coop[REFL_TRACE_WAVES];
+#endif
+#if REFL_COOP2
+    __shared__ CoopWave2 s_coop2[REFL_TRACE_WAVES];   // SHARED only: the other instantiation never names it
 #endif
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * REFL_TRACE_WAVES + wave;
@@ -171,21 +180,32 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
     }
     if (trace) rays++;
     uint32_t st_n = 0, st_t = 0;
-#if REFL_COOP
-    HitRec hit;
-    if (!STATS) hit = trace_coop<false>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+    typename std::conditional<SHARED, Hit2, HitRec>::type hit;
+    if constexpr (SHARED)
+    {
+#if REFL_COOP2
+        hit = trace_coop2<false>(trace, Scene2 { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+#else
+        hit.prim = -1;
+        if (trace) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+#endif
+    }
     else
     {
-        hit.prim = -1;
-        if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
-    }
+#if REFL_COOP
+        if (!STATS) hit = trace_coop<false>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+        else
+        {
+            hit.prim = -1;
+            if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+        }
 #else
-    HitRec hit;
-    hit.prim = -1;
-    DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
-    HR_DIV(dvp_ptr = &dvp;)
-    if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
+        hit.prim = -1;
+        DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
+        HR_DIV(dvp_ptr = &dvp;)
+        if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
 #endif
+    }
     if (trace)
     {
         if (hit.prim < 0) { color = a.env.sky.fetch(dir); ray_length = -1.0f; }
@@ -195,8 +215,8 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
             const f3 hWo = neg3(dir);
             const f3 F0  = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
-            TraceCtx tc { a.nodes, a.tris, s_stack[wave], lane };
-            HR_DIV(tc.dv = &dvs;)
+            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
             CubeMap  none { nullptr, 0 };
             hLo = direct_lighting<STATS>(tc, a.light, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), false, 0.0f, 0.0f, none, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
@@ -560,6 +580,12 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     HR_REJECT_SHARED(scene, "hr_reflections_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
+    // shared instanced scene (opted in): no statistics build of the two-level kernel — refused before anything is enqueued or any state of the pass changes
+    if (scene->shared && p->want_stats)
+    {
+        set_last_error("hr_reflections_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
+        return HR_ERR_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int pp = in->ping_pong ? 1 : 0;
@@ -610,7 +636,8 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
         return HR_OK;
     }
     int ev = p->prof.begin("ray_trace", st, px * 28);
-    hipLaunchKernelGGL((k_refl_trace<false>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
+    if (scene->shared) hipLaunchKernelGGL((k_refl_trace<false, true>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
+    else hipLaunchKernelGGL((k_refl_trace<false, false>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     if (a.cost)

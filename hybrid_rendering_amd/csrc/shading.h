@@ -9,7 +9,8 @@
 // (ddgi.cpp:478,499) with fp32 weights mix(mix(t00,t10,fx), mix(t01,t11,fx), fy), clamp-to-edge.
 #pragma once
 #include "../../include/hr_api.h"
-#include "traverse.h"
+#include "traverse2.h"
+#include <type_traits>
 
 #ifdef HR_PROBE_FAST_HIT
 // developer probe (docs/EXPERIMENTS.md R5.6): an UPPER BOUND on what tolerance-mode hit shading could save — every correctly rounded
@@ -455,13 +456,17 @@ struct SceneShading
     // indexed by inst[tri_instance[prim]].mesh_tri_base + (prim - first_tri)
     const uint32_t*    tri_instance;
     const InstanceRec* inst;
+    // SHARED instanced scenes (null otherwise; tri_instance / inst are null then: no per-triangle array exists): the two-level walk's Hit2 names
+    // the record, the attributes are indexed by inst_shared[hit.inst].mesh_tri_base + hit.local
+    const InstanceShared* inst_shared;
 };
 // fills the members above from a scene (host)
 static inline void scene_shading_from(const hr_scene* scene, SceneShading& sh)
 {
     const bool inst = scene->n_instances > 0;
-    sh.tri_instance = inst ? (const uint32_t*)scene->tri_instance.p : nullptr;
-    sh.inst         = inst ? (const InstanceRec*)scene->inst_records.p : nullptr;
+    sh.tri_instance = inst && !scene->shared ? (const uint32_t*)scene->tri_instance.p : nullptr;
+    sh.inst         = inst && !scene->shared ? (const InstanceRec*)scene->inst_records.p : nullptr;
+    sh.inst_shared  = scene->shared ? (const InstanceShared*)scene->inst_shared.p : nullptr;
     sh.positions    = (const float*)(inst ? scene->mesh_positions.p : scene->positions.p);
     sh.normals      = scene->has_normals ? (const float*)(inst ? scene->mesh_normals.p : scene->tri_normals.p) : nullptr;
     sh.tri_material = scene->has_material ? (const uint32_t*)(inst ? scene->mesh_material.p : scene->tri_material.p) : nullptr;
@@ -512,17 +517,15 @@ HR_DEV f3 inst_point(const float* __restrict__ m, f3 p)
 {
     return mk3(((m[0] * p.x + m[4] * p.y) + m[8] * p.z) + m[12] * 1.0f, ((m[1] * p.x + m[5] * p.y) + m[9] * p.z) + m[13] * 1.0f, ((m[2] * p.x + m[6] * p.y) + m[10] * p.z) + m[14] * 1.0f);
 }
-HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
+// q: index into the attribute arrays; im: the instance's model matrix (column-major 16 floats), null for a flattened scene; hu, hv: the hit's barycentrics
+HR_DEV SurfaceHit surface_from(const SceneShading& s, const size_t q, const float* __restrict__ im, const float hu, const float hv)
 {
     SurfaceHit o;
-    // instanced scene: the attributes live per MESH in object space; interpolate there, then transform_vertex with the instance's matrix
-    const InstanceRec* ir = s.tri_instance ? s.inst + s.tri_instance[h.prim] : nullptr;
-    const size_t       q  = ir ? (size_t)ir->mesh_tri_base + ((uint32_t)h.prim - ir->first_tri) : (size_t)h.prim;
     const float* p = s.positions + q * 9;
     const f3 v0 = mk3(p[0], p[1], p[2]), v1 = mk3(p[3], p[4], p[5]), v2 = mk3(p[6], p[7], p[8]);
-    const float b0 = 1.0f - h.u - h.v, b1 = h.u, b2 = h.v;
+    const float b0 = 1.0f - hu - hv, b1 = hu, b2 = hv;
     o.P = add3(add3(scale3(v0, b0), scale3(v1, b1)), scale3(v2, b2));
-    if (ir) o.P = inst_point(ir->m, o.P);
+    if (im) o.P = inst_point(im, o.P);
     f3 n;
     if (s.normals)
     {
@@ -531,7 +534,7 @@ HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
     }
     else
         n = cross3(sub3(v1, v0), sub3(v2, v0));
-    o.N = ir ? normalize3(inst_mul3(ir->m, normalize3(n))) : normalize3(normalize3(n));
+    o.N = im ? normalize3(inst_mul3(im, normalize3(n))) : normalize3(normalize3(n));
     const uint32_t mat = s.tri_material ? s.tri_material[q] : 0u;
     if (s.materials)
     {
@@ -561,7 +564,7 @@ HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
                 const float* qt = s.tangents + q * 9;
                 tg = add3(add3(scale3(mk3(qt[0], qt[1], qt[2]), b0), scale3(mk3(qt[3], qt[4], qt[5]), b1)), scale3(mk3(qt[6], qt[7], qt[8]), b2));
             }
-            tg = ir ? normalize3(inst_mul3(ir->m, normalize3(tg))) : normalize3(normalize3(tg));   // interpolated_vertex, then transform_vertex
+            tg = im ? normalize3(inst_mul3(im, normalize3(tg))) : normalize3(normalize3(tg));   // interpolated_vertex, then transform_vertex
             const f3 T = normalize3(tg), Nn = normalize3(o.N);     // get_normal_from_map: TBN = (T, T, N)
             sample_texture(s, mt[1], tu, tv, c);
             const f3 tn = normalize3(sub3(scale3(mk3(c[0], c[1], c[2]), 2.0f), one3()));
@@ -569,6 +572,20 @@ HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
         }
     }
     return o;
+}
+HR_DEV SurfaceHit surface_at(const SceneShading& s, const HitRec& h)
+{
+    // instanced scene: the attributes live per MESH in object space; interpolate there, then transform_vertex with the instance's matrix
+    const InstanceRec* ir = s.tri_instance ? s.inst + s.tri_instance[h.prim] : nullptr;
+    const size_t       q  = ir ? (size_t)ir->mesh_tri_base + ((uint32_t)h.prim - ir->first_tri) : (size_t)h.prim;
+    return surface_from(s, q, ir ? ir->m : nullptr, h.u, h.v);
+}
+// shared instanced scene: the two-level walk has named the instance record and the mesh-local triangle; from there on surface_from's operations,
+// so the bits are the private-copy scene's (InstanceShared::m is InstanceRec::m)
+HR_DEV SurfaceHit surface_at(const SceneShading& s, const Hit2& h)
+{
+    const InstanceShared* ir = s.inst_shared + h.inst;
+    return surface_from(s, (size_t)ir->mesh_tri_base + h.local, ir->m, h.u, h.v);
 }
 
 // fetch_light_properties without SOFT_SHADOWS (lighting.glsl:6-111)
@@ -640,10 +657,36 @@ struct TraceCtx
     DivCounters*  dv = nullptr;   // developer instrumentation (traverse.h)
     uint32_t      nn = 0, nt = 0; // direct_lighting<true>: node steps / triangle tests of the light and sky rays (hr_*_trace_stats)
 };
+// the same over a shared instanced scene: the visibility rays take the two-level any-hit walk (no statistics build exists for it)
+struct TraceCtx2
+{
+    Scene2    sc;
+    uint32_t* wave_stack;
+    int       lane;
+    uint32_t  nn = 0, nt = 0;
+};
+template <bool STATS>
+HR_DEV bool visibility_ray_occluded(TraceCtx& tc, f3 o, f3 d, float t_min, float t_max, uint32_t& nn, uint32_t& nt)
+{
+    return trace_any<STATS>(tc.nodes, tc.tris, o, d, t_min, t_max, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv);
+}
+template <bool STATS>
+HR_DEV bool visibility_ray_occluded(TraceCtx2& tc, f3 o, f3 d, float t_min, float t_max, uint32_t&, uint32_t&)
+{
+    static_assert(!STATS, "no statistics build of the two-level walk");
+    return trace_any2(tc.sc, o, d, t_min, t_max, tc.wave_stack, tc.lane);
+}
 
-// direct_lighting (lighting.glsl:117-196)
-template <bool STATS = false>
-HR_DEV f3 direct_lighting(TraceCtx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 F0, f3 diffuse_color, float roughness, f3 T,
+template <bool SHARED>
+HR_DEV typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type make_trace_ctx(const Node8* nodes, const TriGPU* tris, const SceneShading& sh, uint32_t* wave_stack, int lane)
+{
+    if constexpr (SHARED) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared }, wave_stack, lane };
+    else return TraceCtx { nodes, tris, wave_stack, lane };
+}
+
+// direct_lighting (lighting.glsl:117-196); Ctx: TraceCtx or TraceCtx2
+template <bool STATS = false, class Ctx = TraceCtx>
+HR_DEV f3 direct_lighting(Ctx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 F0, f3 diffuse_color, float roughness, f3 T,
                           bool sample_sky, float r2x, float r2y, const CubeMap& sky, uint32_t& rays)
 {
     f3       Lo = mk3(0.0f, 0.0f, 0.0f);
@@ -657,7 +700,7 @@ HR_DEV f3 direct_lighting(TraceCtx& tc, const hr_light& light, f3 Wo, f3 N, f3 P
         if (attenuation > 0.0f)
         {
             rays++;
-            attenuation = attenuation * (trace_any<STATS>(tc.nodes, tc.tris, ray_origin, Wi, 0.01f, t_max, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv) ? 0.0f : 1.0f);
+            attenuation = attenuation * (visibility_ray_occluded<STATS>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
         }
 #endif
         const f3 brdf = evaluate_uber_brdf(diffuse_color, roughness, N, F0, Wo, Wh, Wi);
@@ -670,7 +713,7 @@ HR_DEV f3 direct_lighting(TraceCtx& tc, const hr_light& light, f3 Wo, f3 N, f3 P
         const f3 Wh = normalize3(add3(Wo, Wi));
 #ifndef HR_ABL_NO_SECONDARY
         rays++;
-        Li = scale3(Li, trace_any<STATS>(tc.nodes, tc.tris, ray_origin, Wi, 0.01f, 10000.0f, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv) ? 0.0f : 1.0f);
+        Li = scale3(Li, visibility_ray_occluded<STATS>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
 #endif
         const f3 brdf = evaluate_uber_brdf(diffuse_color, roughness, N, F0, Wo, Wh, Wi);
         Lo = add3(Lo, mul3(mul3(T, brdf), Li));

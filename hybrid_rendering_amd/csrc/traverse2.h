@@ -159,8 +159,12 @@ struct Hit2
 };
 
 // ANY: any-hit (a pure function of ray and triangle set).  Otherwise closest hit: smallest t, ties to the smallest global triangle index.
+// entry: the TOP-LEVEL node the walk starts from (0 = the root; HR_NO_ENTRY: nothing to walk, a miss).  entry_node_for_box (traverse.h) over a
+// shared scene's `nodes` yields one: it descends through internal children only and stops at the first node with a leaf — an instance — among
+// the overlapping children, so it never leaves the top level.  Any valid entry gives the root's answer.
 template <bool ANY, bool STATS = false>
-HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t* n_nodes = nullptr, uint32_t* n_tris = nullptr)
+HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t* n_nodes = nullptr, uint32_t* n_tris = nullptr,
+                   uint32_t entry = 0u)
 {
     constexpr int ORDER = ANY ? HR_ANY_ORDER : HR_ORDER_NEAR;
     const RayPre rw = ray_prepare(o, d);   // world space: the top level's boxes and every triangle test
@@ -169,13 +173,14 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
     uint32_t  spill_array[HR_SPILL_ENTRIES];
     LaneStack st;
     st.init(wave_stack, lane, spill_array);
-    uint32_t cur = 1u, ni;          // the top level's root is node 0
+    uint32_t cur = (entry << 9) | 1u, ni;   // the entry node (the top level's root is node 0) = "child 0 of child_base entry"
     uint32_t pend = 0u, pend_base = 0u, slot = 0u;   // instances the last top-level node hit and the walk has not entered yet
     int      sp_base = 0;           // stack height at which the level being walked is exhausted
     bool     inside = false;
     InstanceIn in;
     Hit2 best;
     best.t = t_max; best.u = 0.0f; best.v = 0.0f; best.prim = -1; best.inst = 0u; best.local = 0u;
+    if (entry == HR_NO_ENTRY) return best;
     for (;;)
     {
         if ((cur & 0xffu) == 0u && st.sp == sp_base)
@@ -233,7 +238,178 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
     return best;
 }
 
-HR_DEV bool   trace_any2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane) { return trace2<true>(sc, o, d, t_min, t_max, wave_stack, lane).prim == 0; }
+// ---- wave-cooperative triangle tests on two levels (traverse.h trace_coop) --------------------------------------------------------------------
+// A lane appends (owner lane, triangle reference, instance record) jobs to a ring in LDS and keeps walking; when the ring holds a job for every
+// lane, each lane takes one: it fetches the owner's WORLD ray by __shfl as coop_flush does, loads the twelve matrix floats and first_tri of
+// inst[slot], transforms the three vertices with instance_point and runs trace2's ray_tri on trace2's operands — the decisions are bit-identical.
+// Closest hit: 64-bit ds_min of ordered(t) << 32 | GLOBAL triangle (the reference's tie rule); the winner leaves u, v, the record and the
+// mesh-local triangle beside it.  The far limit a lane culls nodes with lags by at most one flush.  Inactive lanes serve as job lanes.
+struct CoopWave2
+{
+    uint2              jobs[HR_COOP_RING];   // x: triangle reference (< 2^31), y: owner lane << 26 | instance record (fewer than 2^23 of them)
+    unsigned long long key[64];              // closest: ordered(t) << 32 | global prim, ~0 = miss;  any-hit: 0 = occluded
+    float2             uv[64];
+    uint2              where[64];            // closest: record, mesh-local triangle of the winner
+};
+
+template <bool ANY>
+HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float t_min, float t_max, uint32_t rank, uint32_t head, uint32_t n, int lane)
+{
+    const bool  mine  = rank < n;
+    const uint2 job   = mine ? cw.jobs[(head + rank) & (HR_COOP_RING - 1)] : make_uint2(0u, (uint32_t)lane << 26);
+    const int   owner = (int)(job.y >> 26);
+    const uint32_t slot = job.y & ((1u << 26) - 1u);
+    RayPre q;
+    q.o.x = __shfl(r.o.x, owner); q.o.y = __shfl(r.o.y, owner); q.o.z = __shfl(r.o.z, owner);
+    q.Sx  = __shfl(r.Sx, owner);  q.Sy  = __shfl(r.Sy, owner);  q.Sz  = __shfl(r.Sz, owner);
+    const int kp = __shfl(r.kx | (r.ky << 2) | (r.kz << 4), owner);
+    q.kx = kp & 3; q.ky = (kp >> 2) & 3; q.kz = kp >> 4;
+    const float q_min = __shfl(t_min, owner), q_max = __shfl(t_max, owner);
+    bool     hit = false;
+    float    t = 0.0f, u = 0.0f, v = 0.0f;
+    uint32_t prim = 0u, local = 0u;
+    if (mine)
+    {
+        const uint4* p = reinterpret_cast<const uint4*>(sc.inst + slot);
+        const uint4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], i3 = p[7];
+        InstanceIn in;
+        in.m[0] = __uint_as_float(c0.x); in.m[1] = __uint_as_float(c0.y); in.m[2]  = __uint_as_float(c0.z);
+        in.m[3] = __uint_as_float(c1.x); in.m[4] = __uint_as_float(c1.y); in.m[5]  = __uint_as_float(c1.z);
+        in.m[6] = __uint_as_float(c2.x); in.m[7] = __uint_as_float(c2.y); in.m[8]  = __uint_as_float(c2.z);
+        in.m[9] = __uint_as_float(c3.x); in.m[10] = __uint_as_float(c3.y); in.m[11] = __uint_as_float(c3.z);
+        const TriRaw tr = load_tri_raw(sc.tris, job.x);
+        const f3 v0 = instance_point(in, __uint_as_float(tr.a.x), __uint_as_float(tr.a.y), __uint_as_float(tr.a.z));
+        const f3 v1 = instance_point(in, __uint_as_float(tr.b.x), __uint_as_float(tr.b.y), __uint_as_float(tr.b.z));
+        const f3 v2 = instance_point(in, __uint_as_float(tr.c.x), __uint_as_float(tr.c.y), __uint_as_float(tr.c.z));
+        hit   = ray_tri<!ANY>(q, v0, v1, v2, q_min, q_max, t, u, v);
+        local = tr.a.w;
+        prim  = i3.z + local;
+    }
+    if (ANY)
+    {
+        if (hit) cw.key[owner] = 0ull;
+    }
+    else
+    {
+        const unsigned long long k = ((unsigned long long)float_ordered(t) << 32) | prim;
+        if (hit) atomicMin(&cw.key[owner], k);
+        wave_fence();
+        if (hit && cw.key[owner] == k) { cw.uv[owner] = make_float2(u, v); cw.where[owner] = make_uint2(slot, local); }
+    }
+    wave_fence();
+}
+
+// trace2's answer bit for bit (ANY: Hit2.prim = 0 if occluded, -1 if not; t, u, v, inst, local unset).  The caller keeps the wave converged
+// around the call; lanes without a ray pass active = false.
+template <bool ANY>
+HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, CoopWave2& cw, int lane, uint32_t entry = 0u)
+{
+    constexpr int ORDER = ANY ? HR_ANY_ORDER : HR_ORDER_NEAR;
+    const unsigned long long exec  = __ballot(1);
+    const uint32_t           nproc = (uint32_t)__popcll(exec), rank = lanes_below(exec);
+    const RayPre rw = ray_prepare(o, d);
+    BoxRay   br;
+    boxray_world(br, rw);
+    uint32_t  spill_array[HR_SPILL_ENTRIES];
+    LaneStack st;
+    st.init(wave_stack, lane, spill_array);
+    bool     alive = active && entry != HR_NO_ENTRY, inside = false;
+    uint32_t cur   = alive ? ((entry << 9) | 1u) : 0u;
+    uint32_t ipend = 0u, ipend_base = 0u, slot = 0u;   // instances of the last top-level node still to enter
+    uint32_t tpend = 0u, tpend_base = 0u;              // leaf triangles of the last mesh node still to append
+    int      sp_base = 0;
+    uint32_t head = 0u, count = 0u;                    // wave-uniform
+    float    tfar = t_max;
+    InstanceIn in;
+    cw.key[lane] = ~0ull;
+    wave_fence();
+    for (;;)
+    {
+        if (alive && tpend == 0u)
+        {
+            bool step = true;
+            if ((cur & 0xffu) == 0u && st.sp == sp_base)
+            {
+                if (ipend)
+                {
+                    slot = ipend_base + (uint32_t)__builtin_ctz(ipend);
+                    ipend &= ipend - 1u;
+                    cur = (enter_instance(sc.inst, slot, o, d, in, br) << 9) | 1u;
+                    inside = true;
+                }
+                else if (inside)
+                {
+                    inside = false; sp_base = 0;
+                    boxray_world(br, rw);
+                    step = st.sp != 0;   // the parked top-level entries, if any
+                    alive = step;
+                }
+                else { alive = false; step = false; }
+            }
+            if (step)
+            {
+                uint32_t ni;
+                walk_next<ORDER != HR_ORDER_SLOTS>(cur, st, ni);
+                const NodeHits h = test_node2<ORDER>(load_node(sc.nodes, ni), br, t_min, tfar);
+                const uint32_t trimask = walk_expand(h, cur, st);
+                if (inside) { tpend = trimask; tpend_base = h.tri_base; }
+                else if (trimask)
+                {
+                    ipend = trimask; ipend_base = h.tri_base;
+                    if (cur & 0xffu) st.push(cur);
+                    cur = 0u; sp_base = st.sp;
+                }
+            }
+        }
+        uint32_t left = (uint32_t)__popc(tpend);
+        uint32_t pos  = head + count;
+#pragma unroll
+        for (int k = 0; k < HR_COOP_PUSH; k++)
+        {
+            const bool               has = left > (uint32_t)k;
+            const unsigned long long b   = __ballot(has);
+            if (has)
+            {
+                const uint32_t i = (uint32_t)__builtin_ctz(tpend);
+                tpend &= tpend - 1u;
+                cw.jobs[(pos + lanes_below(b)) & (HR_COOP_RING - 1)] = make_uint2(tpend_base + i, ((uint32_t)lane << 26) | slot);
+            }
+            pos += (uint32_t)__popcll(b);
+        }
+        count = pos - head;
+        const bool walking = __ballot(alive) != 0ull;
+        bool       flushed = false;
+        while (count >= nproc || (!walking && count > 0u))
+        {
+            const uint32_t n = count < nproc ? count : nproc;
+            wave_fence();
+            coop_flush2<ANY>(cw, sc, rw, t_min, t_max, rank, head, n, lane);
+            head += n; count -= n;
+            flushed = true;
+        }
+        if (flushed)
+        {
+            const unsigned long long k = cw.key[lane];
+            if (ANY) { if (k == 0ull) { alive = false; tpend = 0u; } }
+            else if (k != ~0ull) tfar = ordered_float((uint32_t)(k >> 32)) * 1.0000005f;
+        }
+        if (!walking && count == 0u) break;
+    }
+    Hit2 best;
+    best.t = t_max; best.u = 0.0f; best.v = 0.0f; best.prim = -1; best.inst = 0u; best.local = 0u;
+    const unsigned long long k = cw.key[lane];
+    if (ANY) { if (k == 0ull) best.prim = 0; }
+    else if (k != ~0ull)
+    {
+        const float2 uv = cw.uv[lane];
+        const uint2  w  = cw.where[lane];
+        best.t = ordered_float((uint32_t)(k >> 32)); best.u = uv.x; best.v = uv.y; best.prim = (int32_t)(uint32_t)k; best.inst = w.x; best.local = w.y;
+    }
+    wave_fence();   // the next call re-initialises key[]
+    return best;
+}
+
+HR_DEV bool   trace_any2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t entry = 0u) { return trace2<true>(sc, o, d, t_min, t_max, wave_stack, lane, nullptr, nullptr, entry).prim == 0; }
 HR_DEV Hit2   trace_closest2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane) { return trace2<false>(sc, o, d, t_min, t_max, wave_stack, lane); }
 
 } // namespace hr

@@ -80,6 +80,9 @@ public:
     void     update_meshes(const hr_mesh_update* updates, int32_t n_updates, Stream cmd_buf) { check(hr_scene_update_meshes(m_scene, updates, n_updates, cmd_buf), "hr_scene_update_meshes"); }
     float    mesh_refit_cost(uint32_t mesh_idx) const { float r = 1.0f; check(hr_scene_mesh_refit_cost(m_scene, mesh_idx, &r), "hr_scene_mesh_refit_cost"); return r; }
     bool     is_shared() const { return hr_scene_is_shared(m_scene) != 0; }
+    // a shared scene only: AO, DDGI, reflections, the ground truth and HybridFrame walk it on two levels once this is on (off: they refuse it)
+    void     enable_two_level_passes(bool enable = true) { check(hr_scene_enable_two_level_passes(m_scene, enable ? 1 : 0), "hr_scene_enable_two_level_passes"); }
+    bool     two_level_passes() const { return hr_scene_two_level_passes(m_scene) != 0; }
     void     update_instances(const float* model_matrices, Stream cmd_buf) { check(hr_scene_update_instances(m_scene, model_matrices, cmd_buf), "hr_scene_update_instances"); }
     // motion vectors that follow the geometry: motion_begin_frame() once per frame BEFORE that frame's update_*() calls, on their stream (the first
     // call allocates: not under stream capture), then gbuffer_raycast_motion() in the place of hr_gbuffer_raycast (dynamic scenes)

@@ -187,14 +187,14 @@ hr_status hr_hybrid_frame_destroy(hr_hybrid_frame* f);
 typedef struct { float lo[3], hi[3], step[3]; int32_t node, slot, depth, is_leaf; } hr_child_box;
 hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes);
 
-/* ---- shared instanced scenes (added within revision 6, docs/API_HISTORY.md): every mesh's object-space BVH is stored ONCE and walked on two levels,
- * a top level over the instances, then the mesh's tree.  Device memory is O(sum of meshes + instances): node_bytes =
- * 80 x (mesh nodes + max(1, n_instances)), tri_bytes = 48 x mesh references, plus one 160-byte record per instance.  Same desc, same answers, bit
- * for bit, as hr_scene_create_instanced; hr_scene_update_instances / hr_scene_rebuild_top_level work on it (host work over the instances only,
- * two copies); hr_scene_get_info reports conservative bounds.  hr_trace_any_hit / hr_trace_closest_hit / hr_gbuffer_raycast and the shadows pass
- * take it; AO, DDGI, reflections and the ground truth return HR_ERR_UNSUPPORTED for it before any launch. */
+/* ---- shared instanced scenes (added within revision 6, docs/API_HISTORY.md): every mesh's object-space BVH is stored ONCE and walked on two levels
+ * (DESIGN.md section 2).  Device memory: 80 x (mesh nodes + max(1, n_instances)) + 48 x mesh references + 160 per instance.  Same desc and answers, bit
+ * for bit, as hr_scene_create_instanced; update_instances / rebuild_top_level: host work over the instances + two copies; get_info: conservative bounds.
+ * Queries, hr_gbuffer_raycast and shadows take it; AO, DDGI, reflections, ground truth and hybrid frame only after the opt-in below. */
 hr_status hr_scene_create_instanced_shared(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out);
 int32_t   hr_scene_is_shared(const hr_scene* scene);   /* 1 for a scene from hr_scene_create_instanced_shared, else 0 */
+hr_status hr_scene_enable_two_level_passes(hr_scene* scene, int32_t enable);   /* host flag, off by default; HR_ERR_INVALID_ARG unless shared */
+int32_t   hr_scene_two_level_passes(const hr_scene* scene);
 /* Host only, no device: n_tris, n_nodes, max_depth, node_bytes, tri_bytes, conservative bounds and box_pad of the scene either kind would build
  * for `desc` (shared != 0: the shared kind).  HR_ERR_UNSUPPORTED, with the sizes filled in, when that kind cannot hold it (private copies: >= 2^26 triangle references or >= 2^23 nodes); HR_ERR_INVALID_ARG as hr_scene_create_instanced. */
 hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info);

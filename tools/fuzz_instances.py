@@ -4,8 +4,8 @@ random rotations, non-uniform / negative / zero scales and shears, 3-6 updates i
 forced top-level re-build); after every update 20 k any-hit and closest-hit queries (origins inside and around the scene, short and long rays) must equal
 hr_scene_create over the flattened world vertices bit for bit, and every few configurations the shadows / AO masks + DDGI radiance + reflections trace
 image are compared with the oracle's instanced scene.   python tools/fuzz_instances.py [seed] [n_configs] [--shared]
---shared: the scenes are created by hr_scene_create_instanced_shared (one BVH per mesh, two-level walk); of the passes only the G-buffer
-synthesiser and the shadows pass take such a scene, so only those are compared with the oracle, and the bounds only have to be conservative.
+--shared: the scenes are created by hr_scene_create_instanced_shared (one BVH per mesh, two-level walk) and opt in to the two-level passes
+(hr_scene_enable_two_level_passes) before AO, DDGI and reflections run on them; the bounds only have to be conservative.
 --deform (implies --shared): hr_scene_create_instanced_shared_deformable with a random subset of the small meshes flagged; between the matrix
 updates and the forced top-level re-builds a random subset of the flagged meshes takes a synth.deform step through hr_scene_update_meshes (whole
 meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes.
@@ -168,27 +168,34 @@ for trial in range(n):
             gs.render(g, fi); os_.render(osc, ubo, cur, cur, sob, sr, 0)
             torch.cuda.synchronize()
             if not np.array_equal(gs.image(gs.IMG_MASK).cpu().numpy().view(np.uint32), os_.stages["mask"]): msg.append("shadow mask differs from the oracle")
-            if SHARED:   # AO, DDGI and reflections do not take a shared scene yet
-                gs.close()
-            else:
-                flo, fhi = isd.flatten(mats).bounds()
-                ddgi = synth_env.ddgi_uniforms(np.maximum(flo, -50), np.minimum(fhi, 150), probe_counts=(3, 3, 3), rays_per_probe=32, normal_bias=1.0)
-                sky = synth_env.sky_cubemap(8)
-                pre, lut = synth_env.prefiltered_chain(sky, 4), synth_env.brdf_lut(8)
-                f16 = lambda a_: torch.from_numpy(a_).cuda().view(torch.float16)
-                env = api_gi.environment(f16(sky), f16(pre), 8, 4, f16(lut))
-                gd, odd = api_gi.DDGI(ctx, W, H, ddgi), od.DDGIPass(ddgi)
-                orient = synth_env.random_orientation(rng)
-                gd.render(g, fi, env, orient); odd.render(osc, ubo, cur, sky, orient, 0)
-                torch.cuda.synchronize()
-                if not np.array_equal(helpers.bits16(gd.image(gd.IMG_RADIANCE)), odd.stages["radiance"]): msg.append("DDGI radiance differs from the oracle")
-                irr, dep = odd.current_read()
-                gr, orr = api_reflections.RayTracedReflections(ctx, W, H, 0), orf.ReflectionsPass(W, H)
-                gr.render(g, fi, env, gd)
-                orr.render(osc, ubo, ddgi, cur, cur, sob, sr, 0, dict(sky=sky, prefiltered=pre, pre_size=8, pre_levels=4, lut=lut), irr, dep, ping_pong=False)
-                torch.cuda.synchronize()
-                if not np.array_equal(helpers.bits16(gr.image(gr.IMG_TRACE)), orr.stages["trace"]): msg.append("reflections trace image differs from the oracle")
-                for p in (gs, gd, gr): p.close()
+            if SHARED:
+                g.enable_two_level_passes()   # AO, DDGI and reflections take a shared scene once it has opted in
+            ga, oa = hr.RayTracedAO(ctx, W, H, 0), oracle.AOPass(W, H, spp=1, zbp=synth.z_buffer_params())
+            ga.render(g, fi); oa.render(osc, ubo, cur, cur, sob, sr, 0)
+            torch.cuda.synchronize()
+            mh = (H + 3) // 4
+            if not np.array_equal(ga.image(ga.IMG_MASK).cpu().numpy().view(np.uint32)[:mh].reshape(1, mh, -1), oa.stages["mask"].reshape(1, mh, -1)): msg.append("AO mask differs from the oracle")
+            ga.close()
+            flo, fhi = isd.flatten(mats).bounds()
+            ddgi = synth_env.ddgi_uniforms(np.maximum(flo, -50), np.minimum(fhi, 150), probe_counts=(3, 3, 3), rays_per_probe=32, normal_bias=1.0)
+            sky = synth_env.sky_cubemap(8)
+            pre, lut = synth_env.prefiltered_chain(sky, 4), synth_env.brdf_lut(8)
+            f16 = lambda a_: torch.from_numpy(a_).cuda().view(torch.float16)
+            env = api_gi.environment(f16(sky), f16(pre), 8, 4, f16(lut))
+            gd, odd = api_gi.DDGI(ctx, W, H, ddgi), od.DDGIPass(ddgi)
+            orient = synth_env.random_orientation(rng)
+            gd.render(g, fi, env, orient); odd.render(osc, ubo, cur, sky, orient, 0)
+            torch.cuda.synchronize()
+            if not np.array_equal(helpers.bits16(gd.image(gd.IMG_RADIANCE)), odd.stages["radiance"]): msg.append("DDGI radiance differs from the oracle")
+            irr, dep = odd.current_read()
+            girr, gdep = gd.current_read()
+            if not (np.array_equal(helpers.bits16(girr), irr) and np.array_equal(helpers.bits16(gdep), dep)): msg.append("DDGI atlases differ from the oracle")
+            gr, orr = api_reflections.RayTracedReflections(ctx, W, H, 0), orf.ReflectionsPass(W, H)
+            gr.render(g, fi, env, gd)
+            orr.render(osc, ubo, ddgi, cur, cur, sob, sr, 0, dict(sky=sky, prefiltered=pre, pre_size=8, pre_levels=4, lut=lut), irr, dep, ping_pong=False)
+            torch.cuda.synchronize()
+            if not np.array_equal(helpers.bits16(gr.image(gr.IMG_TRACE)), orr.stages["trace"]): msg.append("reflections trace image differs from the oracle")
+            for p in (gs, gd, gr): p.close()
         rb = g.top_level_rebuilds
         g.close()
         for s_ in mg: s_.close()

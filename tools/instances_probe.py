@@ -8,7 +8,11 @@ Scene: the bench building (sponza_like(detail), identity instance) + `--movers` 
 times each, created by hr_scene_create_instanced_shared_deformable.  Reported, per frame of a wave: all meshes in ONE call against one call each
 (bounds given, so nothing waits; and measured, with the wait); the same triangle count through hr_scene_update_vertices on a flat deformable
 scene; re-creating the shared scene (the only route before this call existed); the shadows trace stage on the refitted scene against one
-created fresh over the same deformed meshes (masks must be equal)."""
+created fresh over the same deformed meshes (masks must be equal).
+--shared --passes: the ray_trace stage of AO (4 spp), DDGI (16x8x16 probes, 256 rays) and reflections (half resolution) on the shared scene, opted
+in to the two-level passes, next to the PRIVATE-COPY scene of the same desc and matrices (the single-level kernels: the yardstick).  Both scenes
+see the same G-buffer; they are timed in alternating rounds of 10 profiled frames after a warm-up and the per-round averages are printed as
+mean [min, max]; masks, radiance and trace images must be equal."""
 import argparse, json, math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,12 +27,17 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--shared", action="store_true", help="hr_scene_create_instanced_shared: one BVH per mesh, two-level walk")
     ap.add_argument("--deform", action="store_true", help="hr_scene_update_meshes on a shared scene with deforming meshes")
+    ap.add_argument("--passes", action="store_true", help="with --shared: AO / DDGI / reflections trace stages, shared against private copies")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--meshes", type=int, default=16)
     ap.add_argument("--copies", type=int, default=8)
     ap.add_argument("--field", type=int, default=48)
     a = ap.parse_args()
     if a.deform:
         return deform_probe(a)
+    if a.passes:
+        assert a.shared, "--passes compares a shared scene with its private-copy twin: give --shared"
+        return passes_probe(a)
     import torch
     from hybrid_rendering_amd import api as hr, synth
     W, H = a.width, a.height
@@ -93,6 +102,76 @@ def main():
     res["masks_equal"] = True
     if a.shared:
         res["kind"] = "shared"
+    print(json.dumps(res))
+
+
+def passes_probe(a):
+    import torch
+    from hybrid_rendering_amd import api as hr, api_gi, api_reflections, synth, synth_env
+    W, H = a.width, a.height
+    building = synth.sponza_like(a.detail)
+    small = synth.instanced_cornell(2)
+    cube, pyr = small.meshes[1], small.meshes[2]
+    lo, hi = building.bounds()
+    rng = np.random.RandomState(1)
+    inst = [(synth.model_matrix(), 0, 1)]
+    for i in range(a.movers):   # the default scene of main() after `frames` frames of motion
+        p, ax, ang, sc, vel = rng.uniform(lo + 0.15 * (hi - lo), hi - 0.15 * (hi - lo)), rng.uniform(-1, 1, 3), rng.uniform(0, 6.28), rng.uniform(6, 30, 3), rng.uniform(-2, 2, 3)
+        inst.append((synth.model_matrix(p + vel * a.frames, ax, ang + 0.05 * a.frames, sc), 1 + (i & 1), 2 + i))
+    isd = synth.InstancedSceneData(meshes=[building, cube, pyr], instances=inst, materials=building.materials)
+    ctx = hr.Context(0)
+    scenes = dict(shared=hr.InstancedScene(ctx, isd, shared=True).enable_two_level_passes(), private=hr.InstancedScene(ctx, isd))
+    light = synth.sponza_light()
+    cams = [synth.sponza_camera(W / H, frame=f, dolly=0.5) for f in range(2)]
+    ubo = synth.make_ubo(cams[1], cams[0], light)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    gb = scenes["private"].gbuffer(ubo, W, H)
+    low = hr.gbuffer_mip(gb, 1)
+    fi = hr.frame_inputs(gb, gb, ubo, 0, 0, sob_d, sr_d, z_buffer_params=synth.z_buffer_params())
+    fl = hr.frame_inputs(low, low, ubo, 0, 0, sob_d, sr_d, cur_full=gb, z_buffer_params=synth.z_buffer_params())
+    ddgi_u = synth_env.ddgi_uniforms(lo, hi, probe_counts=(16, 8, 16), rays_per_probe=256, normal_bias=0.1)
+    sky = synth_env.sky_cubemap(32)
+    f16 = lambda x: torch.from_numpy(x).cuda().view(torch.float16)
+    env = api_gi.environment(f16(sky), f16(synth_env.prefiltered_chain(sky, 5)), 32, 5, f16(synth_env.brdf_lut(32)))
+    orient = synth_env.random_orientation(np.random.RandomState(1))
+    passes = {}
+    for tag in scenes:
+        ao, gi, rf = hr.RayTracedAO(ctx, W, H, 0), api_gi.DDGI(ctx, W, H, ddgi_u), api_reflections.RayTracedReflections(ctx, W, H, 1)
+        ao.params.spp = 4
+        for p in (ao, gi, rf):
+            p.params.exact = 0
+        passes[tag] = dict(ao=ao, ddgi=gi, reflections=rf)
+
+    def frame(tag, k):
+        sc, ps = scenes[tag], passes[tag]
+        fi.num_frames = fl.num_frames = k
+        ps["ao"].render(sc, fi); ps["ddgi"].render(sc, fi, env, orient); ps["reflections"].render(sc, fl, env, ps["ddgi"])
+    for tag in scenes:
+        for k in range(6):
+            frame(tag, k)
+    torch.cuda.synchronize()
+    rounds = {tag: {n: [] for n in ("ao", "ddgi", "reflections")} for tag in scenes}
+    for r in range(a.rounds):
+        for tag in scenes:   # alternating: both kinds see the same neighbours on the machine
+            for p in passes[tag].values():
+                p.set_profiling(True)
+                p.stage_times()
+            for k in range(6 + 10 * r, 16 + 10 * r):
+                frame(tag, k)
+            torch.cuda.synchronize()
+            for n, p in passes[tag].items():
+                rounds[tag][n].append(dict((s_, ms) for s_, ms, _ in p.stage_times())["ray_trace"])
+                p.set_profiling(False)
+    img = {tag: (ps["ao"].image(0).cpu().numpy().copy(), ps["ddgi"].image(0).cpu().numpy().copy(), ps["reflections"].image(0).cpu().numpy().copy()) for tag, ps in passes.items()}
+    for x, y, what in zip(img["shared"], img["private"], ("AO masks", "DDGI radiance", "reflections trace image")):
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), what + " differ between the shared and the private-copy scene"
+    res = dict(kind="shared against private copies, trace stages", width=W, height=H, instances=a.movers + 1, tris=scenes["private"].refresh_info().n_tris, rounds=a.rounds, images_equal=True)
+    for tag in scenes:
+        info = scenes[tag].refresh_info()
+        res[tag + "_scene_bytes"] = int(info.node_bytes) + int(info.tri_bytes)
+        for n, v in rounds[tag].items():
+            res[f"{n}_trace_ms_{tag}"] = [round(float(np.mean(v)), 4), round(min(v), 4), round(max(v), 4)]
     print(json.dumps(res))
 
 
