@@ -54,6 +54,7 @@ struct AOTraceArgs
     const uint32_t*    grid;
     float              grid_lo[3], grid_inv_c;
     int                grid_n[3];
+    const InstanceShared* inst;    // SHARED only: one record per top-level leaf (instances_shared.hip); last, so that no other member moves
 };
 
 // Entry-node table (round 5).  Every sample ray of a pixel stays within ray_length of its origin, so the traversals may start at the deepest
@@ -106,16 +107,38 @@ extern "C" int hr_debug_divergence_ao(uint64_t* out, int reset)
 #ifndef AO_COOP
 #define AO_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop) for the AO rays: 0.418 -> 0.399 ms at 1080p, 4 spp
 #endif
-template <bool STATS>
+#ifndef AO_COOP2
+#define AO_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane (trace2): 0.557 -> 0.546 ms at
+#endif               // 1080p, 4 spp, 201 instances (docs/EXPERIMENTS.md); masks bit-identical (tests/test_gpu_shared_passes.py)
 #ifndef AO_TRACE_EU
 #define AO_TRACE_EU 6   // minimum waves per SIMD the register allocator must leave room for.  Round 4 (new tree): 1 / 4 / 5 / 6 / 7 / 8 -> 372 / 373 / 372 / 361-368 / 374 / 372 us at 1080p, 1208 -> 1156 at 4K for 6;
                         // round 3: 1 / 6 / 8 -> 393 / 389 / 396
 #endif
-__global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_EU) void k_ao_trace(AOTraceArgs a)
+#ifndef AO_TRACE_SHARED_EU
+#define AO_TRACE_SHARED_EU 4   // SHARED: the two-level walk keeps the instance's matrix and both box-test rays live: under the bound of 6 it spills
+#endif
+// one sample's visibility bits of the tile -> the two 8x4 mask words of plane `m`
+HR_DEV void ao_store_mask_rows(const AOTraceArgs& a, uint32_t* m, int tx, int ty, unsigned long long bits)
 {
+    const int my = ty * 2;
+    if (my * 4 >= a.y0 && my * 4 < a.y1) m[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
+    if ((my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) m[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
+}
+// SHARED: over a shared instanced scene (instances_shared.hip) — the same pixel -> ray set-up, mask / ray_slots writes and tile ordering, the
+// two-level walk of traverse2.h.  The entry node is a TOP-LEVEL node there: entry_node_for_box stops at the first node with a leaf — an
+// instance — among the children that overlap the ball, and k_ao_entry_grid builds the pass's table with it, so both stay above the mesh trees.
+// <STATS, false> is the kernel as it was.
+template <bool STATS, bool SHARED = false>
+__global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : AO_TRACE_EU) void k_ao_trace(AOTraceArgs a)
+{
+    static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(SHARED && AO_SEQ), "-DAO_SEQ walks one level: it cannot trace a shared instanced scene");
     __shared__ uint32_t s_stack[AO_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if AO_COOP && !AO_SEQ
     __shared__ CoopWave s_coop[AO_TRACE_WAVES];
+#endif
+#if AO_COOP2
+    __shared__ CoopWave2 s_coop2[AO_TRACE_WAVES];   // SHARED only: the other instantiation never names it
 #endif
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * AO_TRACE_WAVES + wave;
@@ -191,13 +214,7 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_EU) void k_ao_trace(A
             for (int k = 0; k < n; k++)
             {
                 const unsigned long long bits = __ballot(active && !((occ >> k) & 1u));
-                if (lane == 0)
-                {
-                    const int my = ty * 2;
-                    uint32_t* m  = a.mask + (size_t)(s0 + k) * a.mh * a.mw;
-                    if (my * 4 >= a.y0 && my * 4 < a.y1) m[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
-                    if ((my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) m[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
-                }
+                if (lane == 0) ao_store_mask_rows(a, a.mask + (size_t)(s0 + k) * a.mh * a.mw, tx, ty, bits);
             }
         }
     }
@@ -206,6 +223,22 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_EU) void k_ao_trace(A
     for (int s = 0; s < a.spp; s++)
     {
         bool visible = false;
+        if constexpr (SHARED)
+        {
+            f3 dir = mk3(0.0f, 0.0f, 1.0f);
+            if (active)
+            {
+                const int   idx = (int)a.num_frames * a.spp + s;
+                const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
+                dir = sample_cosine_lobe(N, r0, r1);
+            }
+#if AO_COOP2
+            visible = trace_coop2<true>(active, { a.nodes, a.tris, a.inst }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry).prim != 0 && active;
+#else
+            if (active) visible = !trace_any2({ a.nodes, a.tris, a.inst }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry);
+#endif
+        }
+        else
 #if AO_COOP && !AO_SEQ
         if (!STATS)
         {
@@ -228,15 +261,9 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_EU) void k_ao_trace(A
             visible         = !trace_any<STATS, AO_ORDER>(a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, nn, nt, entry HR_DIV(, &dv));
         }
         const unsigned long long bits = __ballot(visible);
-        if (lane == 0)
-        {
-            const int my = ty * 2;
-            uint32_t* m  = a.mask + (size_t)s * a.mh * a.mw;
-            if (my * 4 >= a.y0 && my * 4 < a.y1) m[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
-            if ((my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) m[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
-        }
+        if (lane == 0) ao_store_mask_rows(a, a.mask + (size_t)s * a.mh * a.mw, tx, ty, bits);
     }
-    HR_DIV(div_flush(dv, g_div_ao);)
+    HR_DIV(if constexpr (!SHARED) div_flush(dv, g_div_ao);)   // the two-level walk counts nothing
     if (STATS)
         for (int o = 32; o > 0; o >>= 1) { nn += __shfl_down(nn, o); nt += __shfl_down(nt, o); }
     if (lane == 0)
@@ -251,98 +278,6 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_EU) void k_ao_trace(A
         {
             atomicAdd(a.stats + 0, (unsigned long long)nn);
             atomicAdd(a.stats + 1, (unsigned long long)nt);
-        }
-    }
-}
-
-// k_ao_trace over a SHARED instanced scene (instances_shared.hip): the same pixel -> ray set-up, mask / ray_slots writes and tile ordering, the
-// two-level walk of traverse2.h, one ray per lane.  The entry node is a TOP-LEVEL node: entry_node_for_box stops at the first node with a leaf —
-// an instance — among the children that overlap the ball, and k_ao_entry_grid builds the pass's table with it, so both stay above the mesh
-// trees.  A kernel of its own, so that k_ao_trace compiles to what it did before.
-#ifndef AO_COOP2
-#define AO_COOP2 1   // wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane (trace2): 0.557 -> 0.546 ms at
-#endif               // 1080p, 4 spp, 201 instances (docs/EXPERIMENTS.md); masks bit-identical (tests/test_gpu_shared_passes.py)
-#ifndef AO_TRACE_SHARED_EU
-#define AO_TRACE_SHARED_EU 4   // the two-level walk keeps the instance's matrix and both box-test rays live: under k_ao_trace's bound of 6 it spills
-#endif
-__global__ __launch_bounds__(64 * AO_TRACE_WAVES, AO_TRACE_SHARED_EU) void k_ao_trace_shared(AOTraceArgs a, Scene2 sc)
-{
-    __shared__ uint32_t s_stack[AO_TRACE_WAVES][HR_STACK_ENTRIES * 64];
-#if AO_COOP2
-    __shared__ CoopWave2 s_coop[AO_TRACE_WAVES];
-#endif
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int launch_slot = blockIdx.x * AO_TRACE_WAVES + wave;
-    if (launch_slot >= a.tiles_x * a.tiles_y) return;
-    const int tile = a.order ? (int)a.order[launch_slot] : launch_slot;
-    const unsigned long long t_begin = a.cost ? wall_clock64() : 0ull;
-    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x + a.tile_y0;
-    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-    bool  active = false;
-    f3    ro = mk3(0, 0, 0), N = mk3(0, 0, 1);
-    const int kind = trace_lane_kind(x, y, a.w, a.h, a.y0, a.y1);
-    if (kind)
-    {
-        const float d = kind == 1 ? a.depth[(size_t)y * a.w + x] : 0.0f;
-        if (d != 1.0f)
-        {
-            const float tu = __fdiv_rn((float)x + 0.5f, (float)a.w), tv = __fdiv_rn((float)y + 0.5f, (float)a.h);
-            const f3    P  = world_pos_from_depth(tu, tv, d, a.vpi);
-            const uint2 g2 = kind == 1 ? a.gb2[(size_t)y * a.w + x] : make_uint2(0u, 0u);
-            N      = oct_decode(h2f_lo(g2.x), h2f_hi(g2.x));
-            ro     = add3(P, scale3(N, a.bias));
-            active = true;
-        }
-    }
-    const unsigned long long fired = __ballot(active);
-    uint32_t entry = 0u;
-    if (active)
-    {
-        const float r = a.ray_length * 1.0001f + 1e-4f;
-        bool looked_up = false;
-        if (a.grid)   // wave-uniform
-        {
-            const float gx = (ro.x - a.grid_lo[0]) * a.grid_inv_c, gy = (ro.y - a.grid_lo[1]) * a.grid_inv_c, gz = (ro.z - a.grid_lo[2]) * a.grid_inv_c;
-            const int   ix = (int)floorf(gx), iy = (int)floorf(gy), iz = (int)floorf(gz);
-            if (ix >= 0 && iy >= 0 && iz >= 0 && ix < a.grid_n[0] && iy < a.grid_n[1] && iz < a.grid_n[2])
-            {
-                entry     = a.grid[((size_t)iz * a.grid_n[1] + iy) * a.grid_n[0] + ix];
-                looked_up = true;
-            }
-        }
-        if (!looked_up) entry = entry_node_for_box(sc.nodes, mk3(ro.x - r, ro.y - r, ro.z - r), mk3(ro.x + r, ro.y + r, ro.z + r));
-    }
-    for (int s = 0; s < a.spp; s++)
-    {
-        bool visible = false;
-        f3   dir = mk3(0.0f, 0.0f, 1.0f);
-        if (active)
-        {
-            const int   idx = (int)a.num_frames * a.spp + s;
-            const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
-            dir = sample_cosine_lobe(N, r0, r1);
-        }
-#if AO_COOP2
-        visible = trace_coop2<true>(active, sc, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry).prim != 0 && active;
-#else
-        if (active) visible = !trace_any2(sc, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry);
-#endif
-        const unsigned long long bits = __ballot(visible);
-        if (lane == 0)
-        {
-            const int my = ty * 2;
-            uint32_t* m  = a.mask + (size_t)s * a.mh * a.mw;
-            if (my * 4 >= a.y0 && my * 4 < a.y1) m[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
-            if ((my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) m[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
-        }
-    }
-    if (lane == 0)
-    {
-        a.ray_slots[(size_t)ty * a.tiles_x + tx] = (uint32_t)__popcll(fired) * (uint32_t)a.spp;
-        if (a.cost)
-        {
-            const unsigned long long ticks = wall_clock64() - t_begin;
-            a.cost[tile] = (uint16_t)(ticks > 65535ull ? 65535ull : ticks);
         }
     }
 }
@@ -630,12 +565,7 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     HR_CHECK_ARG(p && scene && in && prm && prm->spp >= 1 && prm->spp <= p->max_spp);
     HR_REJECT_SHARED(scene, "hr_ao_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
-    // shared instanced scene (opted in): no statistics build of the two-level kernel — refused before anything is enqueued or any state of the pass changes
-    if (scene->shared && p->want_stats)
-    {
-        set_last_error("hr_ao_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
-        return HR_ERR_UNSUPPORTED;
-    }
+    HR_REJECT_SHARED_DEV(scene, "hr_ao_ray_trace", p->want_stats);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     if (p->first_frame)
@@ -650,7 +580,7 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     for (int i = 0; i < 16; i++) a.vpi[i] = in->ubo.view_proj_inverse[i];
     a.depth = in->cur.depth; a.gb2 = (const uint2*)in->cur.gb2; a.sobol = in->sobol; a.sr = in->scrambling_ranking;
     a.mask = (uint32_t*)p->mask.p; a.ray_slots = (uint32_t*)p->ray_slots.p;
-    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p;
+    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p;
     a.stats = p->want_stats ? (unsigned long long*)((char*)p->counters.p + 16) : nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw; a.mh = p->mh;
     a.tile_y0 = p->y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(p->y1, 8) - a.tile_y0;
@@ -714,13 +644,8 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
         return HR_OK;
     }
     int ev = p->prof.begin("ray_trace", st, px * 12 + px * prm->spp / 8);
-    if (scene->shared)
-    {
-        const Scene2 sc = { a.nodes, a.tris, (const InstanceShared*)scene->inst_shared.p };
-        hipLaunchKernelGGL(k_ao_trace_shared, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a, sc);
-    }
-    else
-        hipLaunchKernelGGL(k_ao_trace<false>, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
+    if (scene->shared) hipLaunchKernelGGL((k_ao_trace<false, true>), dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
+    else hipLaunchKernelGGL(k_ao_trace<false>, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     if (a.cost)

@@ -940,8 +940,7 @@ hr_status hr_trace_any_hit(const hr_scene* scene, int64_t n, const float* rays, 
     if (n == 0) return HR_OK;
     if (scene->shared)
     {
-        const Scene2 sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
-        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sc, (long long)n, rays, out, (unsigned long long*)stats);
+        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene), (long long)n, rays, out, (unsigned long long*)stats);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -957,8 +956,7 @@ hr_status hr_trace_closest_hit(const hr_scene* scene, int64_t n, const float* ra
     if (n == 0) return HR_OK;
     if (scene->shared)
     {
-        const Scene2 sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
-        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sc, (long long)n, rays, out_tuv, out_prim);
+        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene), (long long)n, rays, out_tuv, out_prim);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -1001,7 +999,7 @@ static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, 
     {
         GBufArgs2 a2;
         a2.g = a;
-        a2.sc = { (const Node8*)scene->nodes.p, (const TriGPU*)scene->tris.p, (const InstanceShared*)scene->inst_shared.p };
+        a2.sc = scene2_of(scene);
         a2.mesh_positions = (const float*)scene->mesh_positions.p;
         a2.mesh_normals = scene->has_normals ? (const float*)scene->mesh_normals.p : nullptr;
         a2.mesh_material = scene->has_material ? (const uint32_t*)scene->mesh_material.p : nullptr;

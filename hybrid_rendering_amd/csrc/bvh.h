@@ -71,6 +71,13 @@ struct alignas(16) InstanceShared
     uint32_t pad[2];
 };
 static_assert(sizeof(InstanceShared) == 160, "InstanceShared must be 160 bytes");
+// what the two-level walk (traverse2.h) reads of a shared instanced scene
+struct Scene2
+{
+    const Node8*          nodes;
+    const TriGPU*         tris;
+    const InstanceShared* inst;
+};
 
 // deepest 8-wide tree the traversal's per-lane stack can walk (one entry per level, traverse.h LaneStack)
 constexpr int kMaxTraversalDepth = 64;

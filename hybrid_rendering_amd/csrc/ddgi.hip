@@ -112,14 +112,16 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
         rays++;
     }
     uint32_t st_n = 0, st_t = 0;
-    typename std::conditional<SHARED, Hit2, HitRec>::type h;
+    HitOf<SHARED> h;
     if constexpr (SHARED)
     {
+        // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
+        // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if DDGI_COOP2
-        h = trace_coop2<false>(valid, Scene2 { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        h = trace_coop2<false>(valid, { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
 #else
         h.prim = -1;
-        if (valid) h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (valid) h = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
 #endif
     }
     else
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
             const f3 F0 = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
             const float r2x = next_float(rng), r2y = next_float(rng);
-            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
 #if DDGI_SEQ && !defined(HR_DEV_PATHS)
 #error "-DDDGI_SEQ=1 is an A/B path: build with -DHR_DEV_PATHS"
@@ -630,12 +632,7 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
 {
     HR_CHECK_ARG(p && scene && in && env && prm && env->sky && env->sky_size > 0);
     HR_REJECT_SHARED(scene, "hr_ddgi_ray_trace");
-    // shared instanced scene (opted in): no statistics build and no wavefront form of the two-level kernel — refused before anything is enqueued
-    if (scene->shared && (p->want_stats || p->wavefront))
-    {
-        set_last_error("hr_ddgi_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
-        return HR_ERR_UNSUPPORTED;
-    }
+    HR_REJECT_SHARED_DEV(scene, "hr_ddgi_ray_trace", p->want_stats || p->wavefront);   // no wavefront form of the two-level kernel either
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong

@@ -74,12 +74,13 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
         f3       adds[INDIRECT ? GT_MAX_DEPTH : 1];
         int      depth = 0;
         uint32_t nn = 0, nt = 0;
+        TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack, lane);
         for (;; depth++)
         {
             adds[depth] = mk3(0.0f, 0.0f, 0.0f);
             rays++;
-            typename std::conditional<SHARED, Hit2, HitRec>::type h;
-            if constexpr (SHARED) h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, o, d, t_min, 10000.0f, s_stack, lane);
+            HitOf<SHARED> h;
+            if constexpr (SHARED) h = trace_closest2(tc.sc, o, d, t_min, 10000.0f, s_stack, lane);
             else h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
             if (h.prim < 0)
             {
@@ -96,7 +97,6 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
             const float r1x = next_float(rng), r1y = next_float(rng), r2x = next_float(rng), r2y = next_float(rng);
             f3       Lo = mk3(0.0f, 0.0f, 0.0f);
             const f3 ray_origin = add3(s.P, scale3(s.N, 0.1f));
-            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack, lane);
             {
                 f3    Wi;
                 float t_max, attenuation;

@@ -75,6 +75,10 @@ bool      finite_matrix(const float* m);
 // hr_scene_enable_two_level_passes (the refusal is the published default of this API revision)
 bool      reject_shared_scene(const hr_scene* s, const char* pass);
 #define HR_REJECT_SHARED(scene, pass) do { if (::hr::reject_shared_scene(scene, pass)) return HR_ERR_UNSUPPORTED; } while (0)
+// HR_REJECT_SHARED_DEV: the two-level walk has no instrumented or developer variants — a trace call that is asked for one (`wanted`) on a shared
+// scene refuses, before anything is enqueued or any state of the pass changes
+bool      reject_shared_dev_switches(const hr_scene* s, const char* call, bool wanted);
+#define HR_REJECT_SHARED_DEV(scene, call, wanted) do { if (::hr::reject_shared_dev_switches(scene, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
 hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild);
 // instances_shared.hip: the second half of an update, over the standing matrices and mesh_bounds / shared_mesh_absmax — the instances' boxes, the
 // top level's refit (or re-build), the records, the two copies on `st` and geometry_epoch++ (hr_scene_update_instances and hr_scene_update_meshes)
@@ -358,3 +362,7 @@ struct hr_scene
     hr::DevBuf    prev_mats;                      // instanced kinds: [n_instances][16] model matrices, by instance index of the scene desc
     hr::DevBuf    prev_positions;                 // deformable: [n_tris][3][3] world; shared deformable: the object-space mesh_positions
 };
+
+namespace hr {
+inline Scene2 scene2_of(const hr_scene* s) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p }; }
+} // namespace hr

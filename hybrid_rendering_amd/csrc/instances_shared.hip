@@ -507,6 +507,13 @@ bool hr::reject_shared_scene(const hr_scene* s, const char* pass)
     return true;
 }
 
+bool hr::reject_shared_dev_switches(const hr_scene* s, const char* call, bool wanted)
+{
+    if (!s->shared || !wanted) return false;
+    set_last_error(std::string(call) + ": trace statistics and developer switches are not available on a shared instanced scene");
+    return true;
+}
+
 // matrices == nullptr: the standing ones (force_rebuild: hr_scene_rebuild_top_level)
 hr_status hr::shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st, bool force_rebuild)
 {

@@ -180,14 +180,16 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
     }
     if (trace) rays++;
     uint32_t st_n = 0, st_t = 0;
-    typename std::conditional<SHARED, Hit2, HitRec>::type hit;
+    HitOf<SHARED> hit;
     if constexpr (SHARED)
     {
+        // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
+        // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if REFL_COOP2
-        hit = trace_coop2<false>(trace, Scene2 { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        hit = trace_coop2<false>(trace, { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
 #else
         hit.prim = -1;
-        if (trace) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (trace) hit = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
 #endif
     }
     else
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
             const f3 hWo = neg3(dir);
             const f3 F0  = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
-            typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
             CubeMap  none { nullptr, 0 };
             hLo = direct_lighting<STATS>(tc, a.light, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), false, 0.0f, 0.0f, none, rays);
@@ -580,12 +582,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     HR_REJECT_SHARED(scene, "hr_reflections_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
-    // shared instanced scene (opted in): no statistics build of the two-level kernel — refused before anything is enqueued or any state of the pass changes
-    if (scene->shared && p->want_stats)
-    {
-        set_last_error("hr_reflections_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
-        return HR_ERR_UNSUPPORTED;
-    }
+    HR_REJECT_SHARED_DEV(scene, "hr_reflections_ray_trace", p->want_stats);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int pp = in->ping_pong ? 1 : 0;

@@ -677,10 +677,13 @@ HR_DEV bool visibility_ray_occluded(TraceCtx2& tc, f3 o, f3 d, float t_min, floa
     return trace_any2(tc.sc, o, d, t_min, t_max, tc.wave_stack, tc.lane);
 }
 
-template <bool SHARED>
-HR_DEV typename std::conditional<SHARED, TraceCtx2, TraceCtx>::type make_trace_ctx(const Node8* nodes, const TriGPU* tris, const SceneShading& sh, uint32_t* wave_stack, int lane)
+// what a kernel templated on TWO_LEVEL (a shared instanced scene) walks with and gets back
+template <bool TWO_LEVEL> using TraceCtxOf = typename std::conditional<TWO_LEVEL, TraceCtx2, TraceCtx>::type;
+template <bool TWO_LEVEL> using HitOf      = typename std::conditional<TWO_LEVEL, Hit2, HitRec>::type;
+template <bool TWO_LEVEL>
+HR_DEV TraceCtxOf<TWO_LEVEL> make_trace_ctx(const Node8* nodes, const TriGPU* tris, const SceneShading& sh, uint32_t* wave_stack, int lane)
 {
-    if constexpr (SHARED) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared }, wave_stack, lane };
+    if constexpr (TWO_LEVEL) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared }, wave_stack, lane };
     else return TraceCtx { nodes, tris, wave_stack, lane };
 }
 

@@ -41,6 +41,7 @@ struct TraceArgs
     uint32_t        n_tri_refs;
     const uint32_t* order;     // nullable: launch slot -> tile, heaviest tiles of the last frame first (tile_order.h)
     uint16_t*       cost;      // nullable: per tile, how long its wave lived (100 MHz ticks)
+    const InstanceShared* inst; // SHARED only: one record per top-level leaf (instances_shared.hip); last, so that no other member moves
 };
 
 // One wave = one 8x8 pixel tile = two 8x4 mask words; lane l -> pixel (l & 7, l >> 3), so the
@@ -50,9 +51,13 @@ struct TraceArgs
 #ifndef SHADOWS_TRACE_EU
 #define SHADOWS_TRACE_EU 1   // minimum waves per SIMD the register allocator must leave room for (A/B: see docs/EXPERIMENTS.md R4.3)
 #endif
-template <bool STATS>
+// SHARED: over a shared instanced scene (instances_shared.hip) — the same pixel -> ray set-up, the two-level walk of traverse2.h.  The occluder
+// cache is off there (it stores an index into a world-space `tris`; the mask does not depend on it), and so are the developer switches and the
+// timeline, which the host refuses on such a scene.  <STATS, false> is the kernel as it was.
+template <bool STATS, bool SHARED = false>
 __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_trace(TraceArgs a)
 {
+    static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
     __shared__ uint32_t s_stack[TRACE_WAVES][HR_STACK_ENTRIES * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * TRACE_WAVES + wave;
@@ -60,9 +65,10 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
     // Tile order: row-major, or last frame's heaviest tiles first (tile_order.h).  Stride permutations lose BVH locality in L2.
     const int slot = a.order ? (int)a.order[launch_slot] : launch_slot;
     const int tx = slot % a.tiles_x, ty_local = slot / a.tiles_x, ty = ty_local + a.tile_y0;
-    if (a.debug_only_tx >= 0 && (tx != a.debug_only_tx || ty != a.debug_only_ty)) return;
+    if constexpr (!SHARED)
+        if (a.debug_only_tx >= 0 && (tx != a.debug_only_tx || ty != a.debug_only_ty)) return;
     unsigned long long t_begin = 0;
-    if (a.timeline || a.cost) t_begin = wall_clock64();
+    if ((!SHARED && a.timeline) || a.cost) t_begin = wall_clock64();
     const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
     bool      lit = false, fired = false;
     uint32_t  nn = 0, nt = 0, wave_max = 0;
@@ -73,7 +79,8 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
     const float    d_pre  = a.depth[pix];
     const uint2    g2_pre = a.gb2[pix];
     const uint32_t bn_pre = blue_noise_texel(x, y, a.sr);
-    const uint32_t occ_pre = a.occluder ? a.occluder[pix] : 0xffffffffu;
+    uint32_t occ_pre = 0xffffffffu;
+    if constexpr (!SHARED) occ_pre = a.occluder ? a.occluder[pix] : 0xffffffffu;
     if (kind)
     {
         const float d = kind == 1 ? d_pre : 0.0f;      // edge thread: out-of-image fetches read 0
@@ -92,34 +99,38 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             if (att > 0.0f)
             {
                 fired = true;
-                // Occluder cache: "is ANY triangle hit in (t_min, t_max)" is a pure function of the geometry, so testing one particular
-                // triangle FIRST and answering "occluded" when it is hit cannot change the mask — and the triangle that shadowed this
-                // pixel last frame (static light, camera moving a fraction of a pixel) shadows it again almost always.  66 % of the bench
-                // frame's shadow rays are occluded; a tile whose lanes are all answered by their cached triangle skips the walk, and in
-                // mixed tiles the occluded lanes (the ones that would otherwise walk until their first hit) drop out of the wave's
-                // longest-lane race.  A stale or foreign index is harmless: the CURRENT scene's triangle at that index is tested.
-                bool occluded = false;
-                uint32_t hit_tri = 0xffffffffu;
-                if (a.occluder && kind == 1 && !a.debug_skip_traversal)
+                if constexpr (SHARED) lit = !trace_any2({ a.nodes, a.tris, a.inst }, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
+                else
                 {
-                    const uint32_t c = occ_pre;
-                    if (c < a.n_tri_refs)
+                    // Occluder cache: "is ANY triangle hit in (t_min, t_max)" is a pure function of the geometry, so testing one particular
+                    // triangle FIRST and answering "occluded" when it is hit cannot change the mask — and the triangle that shadowed this
+                    // pixel last frame (static light, camera moving a fraction of a pixel) shadows it again almost always.  66 % of the bench
+                    // frame's shadow rays are occluded; a tile whose lanes are all answered by their cached triangle skips the walk, and in
+                    // mixed tiles the occluded lanes (the ones that would otherwise walk until their first hit) drop out of the wave's
+                    // longest-lane race.  A stale or foreign index is harmless: the CURRENT scene's triangle at that index is tested.
+                    bool occluded = false;
+                    uint32_t hit_tri = 0xffffffffu;
+                    if (a.occluder && kind == 1 && !a.debug_skip_traversal)
                     {
-                        const RayPre rp = ray_prepare(ro, Wi);
-                        float t, u, v;
-                        occluded = ray_tri_raw<false>(rp, load_tri_raw(a.tris, c), 0.01f, t_max, t, u, v);
-                        if (STATS) nt++;
-                        hit_tri = c;
+                        const uint32_t c = occ_pre;
+                        if (c < a.n_tri_refs)
+                        {
+                            const RayPre rp = ray_prepare(ro, Wi);
+                            float t, u, v;
+                            occluded = ray_tri_raw<false>(rp, load_tri_raw(a.tris, c), 0.01f, t_max, t, u, v);
+                            if (STATS) nt++;
+                            hit_tri = c;
+                        }
                     }
+                    if (a.debug_skip_traversal) lit = (ro.x + Wi.y > -1e30f);
+                    else if (!occluded)
+                    {
+                        hit_tri = 0xffffffffu;
+                        occluded = trace_any<STATS>(a.nodes, a.tris, ro, Wi, 0.01f, t_max, s_stack[wave], lane, nn, nt, 0u, nullptr, &hit_tri);
+                    }
+                    if (!a.debug_skip_traversal) lit = !occluded;
+                    if (a.occluder && kind == 1 && hit_tri != occ_pre) a.occluder[pix] = hit_tri;
                 }
-                if (a.debug_skip_traversal) lit = (ro.x + Wi.y > -1e30f);
-                else if (!occluded)
-                {
-                    hit_tri = 0xffffffffu;
-                    occluded = trace_any<STATS>(a.nodes, a.tris, ro, Wi, 0.01f, t_max, s_stack[wave], lane, nn, nt, 0u, nullptr, &hit_tri);
-                }
-                if (!a.debug_skip_traversal) lit = !occluded;
-                if (a.occluder && kind == 1 && hit_tri != occ_pre) a.occluder[pix] = hit_tri;
             }
         }
     }
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             const unsigned long long ticks = wall_clock64() - t_begin;
             a.cost[slot] = (uint16_t)(ticks > 65535ull ? 65535ull : ticks);
         }
-        if (a.timeline)
+        if (!SHARED && a.timeline)
         {
             const unsigned long long t_end = wall_clock64();
             uint32_t hw;
@@ -161,64 +172,6 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             atomicAdd(a.stats + 0, (unsigned long long)nn);
             atomicAdd(a.stats + 1, (unsigned long long)nt);
             atomicAdd(a.stats + 2, (unsigned long long)wave_max);
-        }
-    }
-}
-
-// k_shadows_trace over a SHARED instanced scene (instances_shared.hip): the same pixel -> ray set-up, the two-level walk of traverse2.h.  The
-// occluder cache is off here (it stores an index into a world-space `tris`); the mask does not depend on it.  A kernel of its own, so that
-// k_shadows_trace compiles to what it did before.
-__global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_trace_shared(TraceArgs a, Scene2 sc)
-{
-    __shared__ uint32_t s_stack[TRACE_WAVES][HR_STACK_ENTRIES * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int launch_slot = blockIdx.x * TRACE_WAVES + wave;
-    if (launch_slot >= a.tiles_x * a.tiles_y) return;
-    const int slot = a.order ? (int)a.order[launch_slot] : launch_slot;
-    const int tx = slot % a.tiles_x, ty_local = slot / a.tiles_x, ty = ty_local + a.tile_y0;
-    unsigned long long t_begin = 0;
-    if (a.cost) t_begin = wall_clock64();
-    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-    bool      lit = false, fired = false;
-    const int    kind = trace_lane_kind(x, y, a.w, a.h, a.y0, a.y1);
-    const size_t pix  = kind == 1 ? (size_t)y * a.w + x : (size_t)a.y0 * a.w;
-    const float    d_pre  = a.depth[pix];
-    const uint2    g2_pre = a.gb2[pix];
-    const uint32_t bn_pre = blue_noise_texel(x, y, a.sr);
-    if (kind)
-    {
-        const float d = kind == 1 ? d_pre : 0.0f;      // edge thread: out-of-image fetches read 0
-        if (d != 1.0f)
-        {
-            const float tu = __fdiv_rn((float)x + 0.5f, (float)a.w), tv = __fdiv_rn((float)y + 0.5f, (float)a.h);
-            const f3    P  = world_pos_from_depth(tu, tv, d, a.vpi);
-            const uint2 g2 = kind == 1 ? g2_pre : make_uint2(0u, 0u);
-            const f3    N  = oct_decode(h2f_lo(g2.x), h2f_hi(g2.x));
-            const f3    ro = add3(P, scale3(N, a.bias));
-            const float r0 = sample_blue_noise_t(bn_pre, (int)a.num_frames, 0, a.sobol);
-            const float r1 = sample_blue_noise_t(bn_pre, (int)a.num_frames, 1, a.sobol);
-            f3    Wi;
-            float t_max, att;
-            fetch_light_shadow(a.light, P, N, r0, r1, Wi, t_max, att);
-            if (att > 0.0f)
-            {
-                fired = true;
-                lit = !trace_any2(sc, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
-            }
-        }
-    }
-    const unsigned long long bits = __ballot(lit);
-    const unsigned long long fb   = __ballot(fired);
-    if (lane == 0)
-    {
-        const int my = ty * 2;
-        if (my * 4 >= a.y0 && my * 4 < a.y1) a.mask[(size_t)my * a.mw + tx] = (uint32_t)(bits & 0xffffffffull);
-        if ((my + 1) * 4 >= a.y0 && (my + 1) * 4 < a.y1 && (my + 1) * 4 < a.h) a.mask[(size_t)(my + 1) * a.mw + tx] = (uint32_t)(bits >> 32);
-        a.ray_slots[(size_t)ty * a.tiles_x + tx] = (uint16_t)__popcll(fb);
-        if (a.cost)
-        {
-            const unsigned long long ticks = wall_clock64() - t_begin;
-            a.cost[slot] = (uint16_t)(ticks > 65535ull ? 65535ull : ticks);
         }
     }
 }
@@ -804,13 +757,8 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     hr_status s = check_inputs(p, in, false);
     if (s != HR_OK) return s;
     HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
-    // the two-level walk has no instrumented or developer variants: statistics, timelines and the persistent-wave A/B kernel are refused for a
-    // shared instanced scene, before anything is enqueued or any state of the pass changes
-    if (scene->shared && (p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0))
-    {
-        set_last_error("hr_shadows_ray_trace: trace statistics and developer switches are not available on a shared instanced scene");
-        return HR_ERR_UNSUPPORTED;
-    }
+    // statistics, timelines, the persistent-wave A/B kernel and the debug switches
+    HR_REJECT_SHARED_DEV(scene, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     // clear_images() (ray_traced_shadows.cpp:938-968): first frame zeroes the feedback image and the
@@ -827,7 +775,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     a.depth = in->cur.depth; a.gb2 = (const uint2*)in->cur.gb2;
     a.sobol = in->sobol; a.sr = in->scrambling_ranking;
     a.mask = (uint32_t*)p->mask.p; a.ray_slots = (uint16_t*)p->ray_slots.p;
-    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p;
+    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p;
     a.stats = nullptr;
     a.timeline = nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw;
@@ -844,10 +792,8 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
     if (scene->shared)
     {
-        const Scene2 sc = { a.nodes, a.tris, (const InstanceShared*)scene->inst_shared.p };
-        a.occluder = nullptr;
         int ev = p->prof.begin("ray_trace", st, px * 12 + px / 8);
-        hipLaunchKernelGGL(k_shadows_trace_shared, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, sc);
+        hipLaunchKernelGGL((k_shadows_trace<false, true>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
         p->prof.end(ev, st);
         HR_HIP(hipGetLastError());
         if (a.cost && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;

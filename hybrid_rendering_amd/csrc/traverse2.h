@@ -25,13 +25,6 @@ namespace hr {
 #define HR_SHARED_SLACK 7.62939453125e-6f   // 2^-17 = 128 u.  Developer self-check: -DHR_SHARED_SLACK=0.0f must fail tests/test_gpu_instances_shared.py's edge test
 #endif
 
-struct Scene2
-{
-    const Node8*          nodes;
-    const TriGPU*         tris;
-    const InstanceShared* inst;
-};
-
 // the box-test side of a ray, in the space of the level being walked; w* = slack * |1 / d| widens every slab
 struct BoxRay
 {
@@ -118,16 +111,25 @@ struct InstanceIn
     uint32_t first_tri;
 };
 
-// loads record `slot`, moves the box-test ray into the instance's object space, returns the mesh root
-HR_DEV uint32_t enter_instance(const InstanceShared* __restrict__ inst, uint32_t slot, f3 o, f3 d, InstanceIn& in, BoxRay& b)
+// matrix and first_tri of record `slot` (quads 0..3 and 7 of the record); returns quad 7: extent, flags, first_tri
+HR_DEV uint4 load_instance_in(const InstanceShared* __restrict__ inst, uint32_t slot, InstanceIn& in)
 {
     const uint4* p = reinterpret_cast<const uint4*>(inst + slot);
-    const uint4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], i0 = p[4], i1 = p[5], i2 = p[6], i3 = p[7], i4 = p[8];
+    const uint4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], i3 = p[7];
     in.m[0] = __uint_as_float(c0.x); in.m[1] = __uint_as_float(c0.y); in.m[2]  = __uint_as_float(c0.z);
     in.m[3] = __uint_as_float(c1.x); in.m[4] = __uint_as_float(c1.y); in.m[5]  = __uint_as_float(c1.z);
     in.m[6] = __uint_as_float(c2.x); in.m[7] = __uint_as_float(c2.y); in.m[8]  = __uint_as_float(c2.z);
     in.m[9] = __uint_as_float(c3.x); in.m[10] = __uint_as_float(c3.y); in.m[11] = __uint_as_float(c3.z);
     in.first_tri = i3.z;
+    return i3;
+}
+
+// loads record `slot`, moves the box-test ray into the instance's object space, returns the mesh root
+HR_DEV uint32_t enter_instance(const InstanceShared* __restrict__ inst, uint32_t slot, f3 o, f3 d, InstanceIn& in, BoxRay& b)
+{
+    const uint4  i3 = load_instance_in(inst, slot, in);
+    const uint4* p  = reinterpret_cast<const uint4*>(inst + slot);
+    const uint4  i0 = p[4], i1 = p[5], i2 = p[6], i4 = p[8];
     const float v00 = __uint_as_float(i0.x), v10 = __uint_as_float(i0.y), v20 = __uint_as_float(i0.z);   // inv, column 0
     const float v01 = __uint_as_float(i0.w), v11 = __uint_as_float(i1.x), v21 = __uint_as_float(i1.y);   // column 1
     const float v02 = __uint_as_float(i1.z), v12 = __uint_as_float(i1.w), v22 = __uint_as_float(i2.x);   // column 2
@@ -150,12 +152,21 @@ HR_DEV f3 instance_point(const InstanceIn& in, float x, float y, float z)
                ((in.m[2] * x + in.m[5] * y) + in.m[8] * z) + in.m[11]);
 }
 
+// the world-space vertices of a leaf triangle of the instance
+HR_DEV void instance_tri(const InstanceIn& in, const TriRaw& q, f3& v0, f3& v1, f3& v2)
+{
+    v0 = instance_point(in, __uint_as_float(q.a.x), __uint_as_float(q.a.y), __uint_as_float(q.a.z));
+    v1 = instance_point(in, __uint_as_float(q.b.x), __uint_as_float(q.b.y), __uint_as_float(q.b.z));
+    v2 = instance_point(in, __uint_as_float(q.c.x), __uint_as_float(q.c.y), __uint_as_float(q.c.z));
+}
+
 struct Hit2
 {
     float    t, u, v;
     int32_t  prim;   // global triangle index (instance order, then mesh order); -1 = miss.  ANY: 0 = occluded
     uint32_t inst;   // record (= top-level leaf) of the hit instance
     uint32_t local;  // mesh-local triangle index
+    static HR_DEV Hit2 miss(float t_max) { return Hit2 { t_max, 0.0f, 0.0f, -1, 0u, 0u }; }
 };
 
 // ANY: any-hit (a pure function of ray and triangle set).  Otherwise closest hit: smallest t, ties to the smallest global triangle index.
@@ -178,8 +189,7 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
     int      sp_base = 0;           // stack height at which the level being walked is exhausted
     bool     inside = false;
     InstanceIn in;
-    Hit2 best;
-    best.t = t_max; best.u = 0.0f; best.v = 0.0f; best.prim = -1; best.inst = 0u; best.local = 0u;
+    Hit2 best = Hit2::miss(t_max);
     if (entry == HR_NO_ENTRY) return best;
     for (;;)
     {
@@ -223,9 +233,8 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
             trimask &= trimask - 1u;
             const TriRaw q = load_tri_raw(sc.tris, h.tri_base + i);
             if (STATS) (*n_tris)++;
-            const f3 v0 = instance_point(in, __uint_as_float(q.a.x), __uint_as_float(q.a.y), __uint_as_float(q.a.z));
-            const f3 v1 = instance_point(in, __uint_as_float(q.b.x), __uint_as_float(q.b.y), __uint_as_float(q.b.z));
-            const f3 v2 = instance_point(in, __uint_as_float(q.c.x), __uint_as_float(q.c.y), __uint_as_float(q.c.z));
+            f3 v0, v1, v2;
+            instance_tri(in, q, v0, v1, v2);
             float t, u, v;
             if (ray_tri<!ANY>(rw, v0, v1, v2, t_min, t_max, t, u, v))
             {
@@ -241,7 +250,7 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
 // ---- wave-cooperative triangle tests on two levels (traverse.h trace_coop) --------------------------------------------------------------------
 // A lane appends (owner lane, triangle reference, instance record) jobs to a ring in LDS and keeps walking; when the ring holds a job for every
 // lane, each lane takes one: it fetches the owner's WORLD ray by __shfl as coop_flush does, loads the twelve matrix floats and first_tri of
-// inst[slot], transforms the three vertices with instance_point and runs trace2's ray_tri on trace2's operands — the decisions are bit-identical.
+// inst[slot], transforms the three vertices with instance_tri and runs trace2's ray_tri on trace2's operands — the decisions are bit-identical.
 // Closest hit: 64-bit ds_min of ordered(t) << 32 | GLOBAL triangle (the reference's tie rule); the winner leaves u, v, the record and the
 // mesh-local triangle beside it.  The far limit a lane culls nodes with lags by at most one flush.  Inactive lanes serve as job lanes.
 struct CoopWave2
@@ -270,20 +279,14 @@ HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float 
     uint32_t prim = 0u, local = 0u;
     if (mine)
     {
-        const uint4* p = reinterpret_cast<const uint4*>(sc.inst + slot);
-        const uint4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], i3 = p[7];
         InstanceIn in;
-        in.m[0] = __uint_as_float(c0.x); in.m[1] = __uint_as_float(c0.y); in.m[2]  = __uint_as_float(c0.z);
-        in.m[3] = __uint_as_float(c1.x); in.m[4] = __uint_as_float(c1.y); in.m[5]  = __uint_as_float(c1.z);
-        in.m[6] = __uint_as_float(c2.x); in.m[7] = __uint_as_float(c2.y); in.m[8]  = __uint_as_float(c2.z);
-        in.m[9] = __uint_as_float(c3.x); in.m[10] = __uint_as_float(c3.y); in.m[11] = __uint_as_float(c3.z);
+        load_instance_in(sc.inst, slot, in);
         const TriRaw tr = load_tri_raw(sc.tris, job.x);
-        const f3 v0 = instance_point(in, __uint_as_float(tr.a.x), __uint_as_float(tr.a.y), __uint_as_float(tr.a.z));
-        const f3 v1 = instance_point(in, __uint_as_float(tr.b.x), __uint_as_float(tr.b.y), __uint_as_float(tr.b.z));
-        const f3 v2 = instance_point(in, __uint_as_float(tr.c.x), __uint_as_float(tr.c.y), __uint_as_float(tr.c.z));
+        f3 v0, v1, v2;
+        instance_tri(in, tr, v0, v1, v2);
         hit   = ray_tri<!ANY>(q, v0, v1, v2, q_min, q_max, t, u, v);
         local = tr.a.w;
-        prim  = i3.z + local;
+        prim  = in.first_tri + local;
     }
     if (ANY)
     {
@@ -395,8 +398,7 @@ HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, 
         }
         if (!walking && count == 0u) break;
     }
-    Hit2 best;
-    best.t = t_max; best.u = 0.0f; best.v = 0.0f; best.prim = -1; best.inst = 0u; best.local = 0u;
+    Hit2 best = Hit2::miss(t_max);
     const unsigned long long k = cw.key[lane];
     if (ANY) { if (k == 0ull) best.prim = 0; }
     else if (k != ~0ull)

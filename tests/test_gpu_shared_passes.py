@@ -328,6 +328,57 @@ def test_ragged_and_tiny_images(hr, ctx, W, H):
         p.close()
 
 
+def test_shadows_and_ao_on_ragged_and_banded_images(hr, ctx):
+    """65x33, the room and two instances, 2 frames (the second on the sorted launch list), shadows and AO (2 spp) as a whole frame and as the
+    row band [16, 33) + halo 8 (resident rows from y0 = 8, launched in image order: a band has no launch list): the trace stage's mask words,
+    per-tile ray slots and ray counts of the opted-in shared scene equal the private-copy scene's word for word.  The edge lanes of the ragged
+    tiles read depth 0 and start on the camera's near plane, which lies outside the scene's box: the AO entry table misses and the descent runs
+    (asserted from the geometry below, not observed in the kernel).  AO's per-tile ray slots have no accessor in the API: they are compared through
+    their sum, hr_ao_ray_count, which for a band adds the zeros the untouched tiles were allocated with."""
+    import torch
+    W, H = 65, 33
+    band = (16, 33, 8, 8)
+    y0 = band[0] - band[2]
+    isd = synth.instanced_cornell(2, seed=5)
+    g, gp = hr.InstancedScene(ctx, isd, shared=True).enable_two_level_passes(), hr.InstancedScene(ctx, isd)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    cams = helpers.cameras("cornell", W / H, 2, 1.0)
+    light = helpers.light_for("cornell", "soft")
+
+    def passes():
+        p = dict(sh=hr.RayTracedShadows(ctx, W, H), ao=hr.RayTracedAO(ctx, W, H, 0), sh_band=hr.RayTracedShadows(ctx, W, H, 0, band=band), ao_band=hr.RayTracedAO(ctx, W, H, 0, band=band))
+        p["ao"].params.spp = p["ao_band"].params.spp = 2
+        return p
+
+    ps, pp = passes(), passes()
+    mh = (H + 3) // 4
+    prev = None
+    for f in range(2):
+        assert cams[f].eye[2] - 2.0 * cams[f].near - ps["ao"].params.bias > max(g.info.bounds_hi[2], gp.info.bounds_hi[2]), "the near plane must lie outside the entry table's box"
+        ubo = synth.make_ubo(cams[f], cams[f - 1] if f else None, light)
+        cur = gp.gbuffer(ubo, W, H)
+        prev = prev if prev is not None else cur
+        fi = hr.frame_inputs(cur, prev, ubo, f, f & 1, sob_d, sr_d, z_buffer_params=synth.z_buffer_params())
+        snap = []
+        for scene, p in ((g, ps), (gp, pp)):
+            p["sh"].render(scene, fi); p["ao"].render(scene, fi)
+            p["sh_band"].ray_trace(scene, fi); p["ao_band"].ray_trace(scene, fi)
+            torch.cuda.synchronize()
+            words = lambda q, planes: q.image(q.IMG_MASK).cpu().numpy().view(np.uint32)[:planes * mh].reshape(planes, mh, -1)
+            snap.append(dict(shadow_mask=words(p["sh"], 1), shadow_slots=p["sh"].tile_ray_counts(), shadow_rays=p["sh"].ray_count(),
+                             ao_masks=words(p["ao"], 2), ao_rays=p["ao"].ray_count(),
+                             band_shadow_mask=words(p["sh_band"], 1)[:, y0 // 4:], band_shadow_slots=p["sh_band"].tile_ray_counts()[y0 // 8:],
+                             band_shadow_rays=p["sh_band"].ray_count(), band_ao_masks=words(p["ao_band"], 2)[:, y0 // 4:], band_ao_rays=p["ao_band"].ray_count()))
+        a, b = snap
+        assert a["shadow_rays"] > 0 and a["ao_rays"] > 0 and a["band_shadow_rays"] == a["band_shadow_slots"].sum() > 0 and 0 < a["band_ao_rays"] < a["ao_rays"]
+        assert_equal_snapshots(a, b, f"65x33, frame {f}")
+        assert np.array_equal(a["band_shadow_mask"], a["shadow_mask"][:, y0 // 4:]) and np.array_equal(a["band_ao_masks"], a["ao_masks"][:, y0 // 4:]), f"frame {f}: the band's rows of the whole frame"
+        prev = cur
+    for p in list(ps.values()) + list(pp.values()) + [g, gp]:
+        p.close()
+
+
 def test_hybrid_frame_modes(hr, ctx):
     """hr_hybrid_frame_render in serial, streams and graph mode on the opted-in shared scene, 96x64, 2 frames: every output equals the four
     serial render() calls on the same scene"""
