@@ -1,9 +1,10 @@
 // C++ host example: a scene as the reference holds it — meshes + instances { model_matrix, mesh_idx } (scene_descriptor_set.glsl:30-34) — with one
 // instance moving every frame: hr::Scene(ctx, hr_instanced_scene_desc) + scene.update_instances(matrices, cmd_buf) in the place of
 // dw::RayTracedScene::build_tlas(cmd_buf) (main.cpp:74), then RayTracedShadows::render(cmd_buf) as ever.  Every frame's visibility mask is
-// compared with the one a flattened hr_scene_create over the same world-space triangles gives: identical.
+// compared with the one a flattened hr_scene_create over the same world-space triangles gives: identical.  A fifth frame moves the cube through
+// matrices a kernel of this file writes on the GPU: shared_scene.update_instances_device(device_matrices, bounds, cmd_buf) — no copy to the host.
 //
-//   hipcc -std=c++17 -I include examples/instanced_scene.cpp -L hybrid_rendering_amd -lhybrid_rendering_amd \
+//   hipcc --offload-arch=gfx950 -std=c++17 -I include examples/instanced_scene.cpp -L hybrid_rendering_amd -lhybrid_rendering_amd \
 //         -Wl,-rpath,$PWD/hybrid_rendering_amd -o /tmp/instanced_scene && /tmp/instanced_scene
 #include <hr/passes.hpp>
 #include <hip/hip_runtime.h>
@@ -53,6 +54,13 @@ bool invert(const float* m, float* inv)
     for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) inv[c * 4 + r] = (float)a[r][4 + c];
     return true;
+}
+
+// what an animation or physics step would leave in device memory: the flying cube's matrix (translate * rotate_y * scale, column-major)
+__global__ void k_fly(float* m, float tx, float ty, float tz, float c, float s, float sx, float sy, float sz)
+{
+    const float r[16] = { c * sx, 0, -s * sx, 0, 0, sy, 0, 0, s * sz, 0, c * sz, 0, tx, ty, tz, 1 };
+    if (threadIdx.x < 16) m[threadIdx.x] = r[threadIdx.x];
 }
 
 #define HIP_OK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #e, hipGetErrorString(_e)); return 2; } } while (0)
@@ -187,10 +195,36 @@ int main()
             if (i == 0) lit_first = lit;
             lit_last = lit;
         }
+        // ---- a fifth frame from DEVICE matrices: the first three stay, a kernel writes the fourth -----------------------------------------------
+        float* dev_mats = nullptr;
+        HIP_OK(hipMalloc((void**)&dev_mats, sizeof(mats)));
+        HIP_OK(hipMemcpy(dev_mats, mats, sizeof(mats), hipMemcpyHostToDevice));
+        const float angle = 0.25f * 4, tx = 20.0f + 12.0f * 4;
+        hipLaunchKernelGGL(k_fly, dim3(1), dim3(64), 0, nullptr, dev_mats + 48, tx, 70.0f, 50.0f, std::cos(angle), std::sin(angle), 18.0f, 10.0f, 18.0f);
+        HIP_OK(hipGetLastError());
+        const float world[6] = { -1, -1, -1, S + 1, S + 1, S + 1 };     // the room holds everything: given, so nothing waits
+        shared_scene.update_instances_device(dev_mats, world, nullptr);
+        const hr::Scene::DeviceUpdateStatus dus = shared_scene.device_update_status();
+        place(4, mats);
+        scene.update_instances(mats, nullptr);
+        frame.inputs.num_frames = 4; frame.inputs.ping_pong = 0;
+        scene.gbuffer_raycast_motion(u, W, H, gb1, gb2, gb3, (float*)depth, nullptr);
+        shadows.render(nullptr, frame);
+        hr::Frame fs5 = frame;
+        fs5.scene = &shared_scene;
+        shadows_shared.render(nullptr, fs5);
+        HIP_OK(hipDeviceSynchronize());
+        hr::ImageView m5 = shadows.output_ds(), s5 = shadows_shared.output_ds();
+        std::vector<uint32_t> w5((size_t)m5.width * m5.height), x5(w5.size());
+        HIP_OK(hipMemcpy(w5.data(), m5.data, w5.size() * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(x5.data(), s5.data, x5.size() * 4, hipMemcpyDeviceToHost));
+        const bool device_ok = w5 == x5 && dus.rejected_instances == 0 && dus.bounds_violated == 0;
+        HIP_OK(hipFree(dev_mats));
         std::printf("instanced scene: %d instances of %d meshes, %dx%d, 4 frames with a moving instance: %d of 4 masks equal the flattened scene's; lit pixels %zu -> %zu\n",
                     I, 2, W, H, same, lit_first, lit_last);
         std::printf("shared instanced scene (one BVH per mesh, two-level walk): %d of 4 masks equal the private-copy scene's\n", same_shared);
-        return (same == 4 && same_shared == 4 && lit_first != lit_last && lit_last > 1000) ? 0 : 1;
+        std::printf("device-side update (matrices written by a kernel): mask %s the host-updated private-copy scene's, top-level cost ratio %.3f\n", device_ok ? "equals" : "DIFFERS from", dus.top_cost_ratio);
+        return (same == 4 && same_shared == 4 && device_ok && lit_first != lit_last && lit_last > 1000) ? 0 : 1;
     }
     catch (const hr::Error& e)
     {

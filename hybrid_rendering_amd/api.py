@@ -101,7 +101,15 @@ ABI_SYMBOLS = [
     "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
     "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",
     "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
+    "hr_scene_update_instances_device", "hr_scene_device_update_status", "hr_scene_device_update_stats",
 ]
+
+# argtypes of the device-side instance update's entry points (include/hr_api_stages.h)
+DEVICE_UPDATE_ARGTYPES = {
+    "hr_scene_update_instances_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hr_scene_device_update_status": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "hr_scene_device_update_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+}
 
 _lib = None
 
@@ -425,6 +433,43 @@ class InstancedScene(Scene):
         out = np.zeros((int(lib().hr_scene_instance_count(self.h)), 160), np.uint8)
         _check(lib().hr_scene_read_instance_records(self.h, C.c_void_p(out.ctypes.data)), "hr_scene_read_instance_records")
         return out
+
+    def update_device(self, matrices_cuda, bounds=None, stream=None):
+        """hr_scene_update_instances_device (shared scenes): ``matrices_cuda`` is a cuda float32 contiguous tensor [n_instances, 16], column-major,
+        read when the kernels RUN (a captured call picks up the buffer's contents at replay).  ``bounds``: host (lo xyz, hi xyz), conservative for
+        the whole scene after this update — then nothing but kernels is enqueued on ``stream`` (default: torch's current stream); None: measured on
+        the GPU, the call waits once (HRError while the stream is capturing).  The top level is refitted, never re-built: ``device_update_status``."""
+        import torch
+        n = int(lib().hr_scene_instance_count(self.h))
+        assert matrices_cuda.is_cuda and matrices_cuda.dtype == torch.float32 and matrices_cuda.is_contiguous() and tuple(matrices_cuda.shape) == (n, 16), \
+            "matrices: cuda float32 contiguous [n_instances, 16]"
+        b = None
+        if bounds is not None:
+            b = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in bounds]), np.float32)
+            assert b.shape == (6,), "bounds: (lo xyz, hi xyz)"
+        L = lib()
+        L.hr_scene_update_instances_device.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_update_instances_device"]
+        _check(L.hr_scene_update_instances_device(self.h, _ptr(matrices_cuda), C.c_void_p(b.ctypes.data) if b is not None else None, _stream_ptr(stream)),
+               "hr_scene_update_instances_device")
+
+    def device_update_status(self) -> dict:
+        """hr_scene_device_update_status (synchronises when it lags): top_cost_ratio — the top level's half-area sum after the last device update /
+        at its last build (the host path re-builds beyond 1.5; here the caller decides: ``rebuild_top_level``); rejected_instances — non-finite
+        matrices of the last update (those instances kept their record); bounds_violated — an instance box left the given bounds"""
+        r, a, b = C.c_float(1.0), C.c_int32(0), C.c_int32(0)
+        L = lib()
+        L.hr_scene_device_update_status.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_device_update_status"]
+        _check(L.hr_scene_device_update_status(self.h, C.byref(r), C.byref(a), C.byref(b)), "hr_scene_device_update_status")
+        return dict(top_cost_ratio=float(r.value), rejected_instances=int(a.value), bounds_violated=int(b.value))
+
+    def device_update_stats(self) -> dict:
+        """hr_scene_device_update_stats: kernel launches of the device updates so far, and stream waits (measured bounds; the read-back a host
+        call makes after a device update)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        L = lib()
+        L.hr_scene_device_update_stats.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_device_update_stats"]
+        _check(L.hr_scene_device_update_stats(self.h, C.byref(a), C.byref(b)), "hr_scene_device_update_stats")
+        return dict(launches=int(a.value), stream_waits=int(b.value))
 
     def update(self, matrices, stream=None):
         """hr_scene_update_instances: matrices [n_instances][16] column-major (host); enqueued on ``stream`` (default: torch's current stream)"""

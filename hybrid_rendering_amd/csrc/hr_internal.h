@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/hr_api.h"
 #include "bvh.h"
+#include "instance_math.h"
 #include <hip/hip_runtime.h>
 #include <memory>
 #include <string>
@@ -83,6 +84,13 @@ hr_status shared_scene_update(hr_scene* s, const float* matrices, hipStream_t st
 // instances_shared.hip: the second half of an update, over the standing matrices and mesh_bounds / shared_mesh_absmax — the instances' boxes, the
 // top level's refit (or re-build), the records, the two copies on `st` and geometry_epoch++ (hr_scene_update_instances and hr_scene_update_meshes)
 hr_status shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_rebuild);
+// instances_shared_update.hip.  shared_device_tables_upload: the device copies of the top level's topology (all = false) and, with all = true,
+// of inst_mesh and the per-mesh table too — asynchronous copies on `st` out of the scene's standing host vectors, allocating at the first call.
+// shared_device_mesh_table_upload: the per-mesh table alone (mesh_bounds / shared_mesh_absmax changed).  shared_mirrors_refresh: after a device
+// update, one wait and a read-back of the records' matrices into inst_host (the slow path of every host call that follows a device update).
+hr_status shared_device_tables_upload(hr_scene* s, hipStream_t st, bool all);
+hr_status shared_device_mesh_table_upload(hr_scene* s, hipStream_t st);
+hr_status shared_mirrors_refresh(hr_scene* s);
 // instances_shared_deform.hip: what hr_scene_update_meshes needs, for a shared scene that holds the uploaded trees `blas` (flagged meshes built
 // without spatial splits): level lists, triangle -> reference map, node_box and the cost of every flagged tree as built.  Synchronous, like creation.
 hr_status shared_deform_adopt(hr_scene* s, const std::vector<BuiltBVH>& blas, const int32_t* mesh_n_tris, const uint8_t* flags);
@@ -166,6 +174,23 @@ struct SharedDeform
     float*   root_box_host = nullptr;             // pinned, per mesh 8 floats
     int64_t  level_launches = 0, top_launches = 0, stream_waits = 0;   // what the updates so far enqueued (hr_scene_update_meshes_stats)
     ~SharedDeform() { if (root_box_host) (void)hipHostFree(root_box_host); }
+};
+
+// What hr_scene_update_instances_device keeps (instances_shared_update.hip); allocated by the first call, never after
+struct SharedDeviceUpdate
+{
+    DevBuf   inst_box;                            // per instance 6 floats: the world box of the last update
+    DevBuf   node_box;                            // per top-level slot 6 floats (the per-depth path; the one-launch path keeps them in LDS)
+    DevBuf   areas;                               // per top-level slot: its half area (double)
+    DevBuf   status;                              // DeviceUpdateStatus
+    void*    status_host = nullptr;               // pinned copy of `status`
+    bool     status_stale = false;                // status_host lags the last update
+    bool     given_bounds = false;                // the last update was given its bounds
+    bool     captured = false;                    // an update was enqueued on a capturing stream: replays run it unseen
+    hipStream_t last_stream = nullptr;            // of the last update enqueued
+    double   area_at_build = 0.0;                 // the scene's top_area_at_build when the last update was enqueued
+    int64_t  launches = 0, stream_waits = 0;
+    ~SharedDeviceUpdate() { if (status_host) (void)hipHostFree(status_host); }
 };
 
 // Stage profiler: one event pair per named stage, recorded on the pass stream.
@@ -340,7 +365,7 @@ struct hr_scene
     hr::DevBuf    inst_shared;
     std::vector<hr::InstanceShared> shared_host;  // upload staging, in leaf order
     std::vector<int32_t>  shared_leaf_of;         // per instance: its leaf (= record) index
-    struct SharedTopNode { int n_internal, n_leaves, child_base, leaf_base, axis, depth; };
+    using SharedTopNode = hr::SharedTopNode;     // instance_math.h
     std::vector<SharedTopNode> shared_top;        // per used top-level slot
     std::vector<int32_t>  shared_leaf_inst;       // per leaf: the instance
     std::vector<float>    shared_mesh_absmax;     // per mesh: max |p_k| over its bounds, per axis
@@ -348,6 +373,14 @@ struct hr_scene
     int           shared_mesh_depth = 0;          // deepest mesh tree (levels below its root)
     std::vector<float>    shared_mesh_pad;        // per mesh: the leaf pad its builder used
     std::unique_ptr<hr::SharedDeform> shared_deform;   // set by hr_scene_create_instanced_shared_deformable only
+    // hr_scene_update_instances_device (instances_shared_update.hip): device copies of the top level's topology and of what a record is made
+    // from, written at creation and wherever the host adopts a top level or new mesh bounds; `work` is allocated by the first device update
+    hr::DevBuf    dev_top, dev_leaf_inst, dev_leaf_of, dev_inst_mesh, dev_mesh_tab;
+    std::vector<int>      shared_depth_start;     // per top-level depth: its first slot (slots are breadth-first); one more entry: the slot count
+    std::vector<uint32_t> shared_mesh_tri_base;   // per mesh: first triangle in the concatenated attribute arrays
+    std::vector<float> mesh_tab_host;             // upload staging of dev_mesh_tab (per mesh 12 floats)
+    std::unique_ptr<hr::SharedDeviceUpdate> dev_update;
+    bool          mirrors_stale = false;          // a device update ran: inst_host / inst_box / top_nodes_host / shared_host lag the device
     // ---- deformable scenes (deform.hip): a flat scene built without spatial splits; hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`
     // and refits `nodes` through level_nodes / level_offsets / node_box (the arrays of the instanced scenes' refit)
     bool          deformable = false;

@@ -240,28 +240,10 @@ void instance_boxes(hr_scene* s)
     {
         const float* m  = s->inst_host[(size_t)i].m;
         const float* mb = &s->mesh_bounds[(size_t)s->inst_mesh[(size_t)i] * 6];
-        double l[3] = { 1e300, 1e300, 1e300 }, h[3] = { -1e300, -1e300, -1e300 };
+        float* box = &s->inst_box[(size_t)i * 6];
+        imath::world_box(m, mb, box);
         if (mb[0] <= mb[3])
-            for (int c = 0; c < 8; c++)
-            {
-                const double x = mb[(c & 1) ? 3 : 0], y = mb[(c & 2) ? 4 : 1], z = mb[(c & 4) ? 5 : 2];
-                for (int k = 0; k < 3; k++)
-                {
-                    const double v = (double)m[k] * x + (double)m[4 + k] * y + (double)m[8 + k] * z + (double)m[12 + k];
-                    const double e = 1e-6 * (std::fabs((double)m[k] * x) + std::fabs((double)m[4 + k] * y) + std::fabs((double)m[8 + k] * z) + std::fabs((double)m[12 + k]));
-                    l[k] = std::min(l[k], v - e); h[k] = std::max(h[k], v + e);
-                }
-            }
-        else
-            for (int k = 0; k < 3; k++) { l[k] = h[k] = (double)m[12 + k]; }   // empty mesh: a point at the instance's origin
-        for (int k = 0; k < 3; k++)
-        {
-            float lo = (float)l[k], hi = (float)h[k];
-            if ((double)lo > l[k]) lo = std::nextafter(lo, -INFINITY);
-            if ((double)hi < h[k]) hi = std::nextafter(hi, INFINITY);
-            s->inst_box[(size_t)i * 6 + k] = lo; s->inst_box[(size_t)i * 6 + 3 + k] = hi;
-            if (mb[0] <= mb[3]) { L[k] = std::min(L[k], (double)lo); H[k] = std::max(H[k], (double)hi); }
-        }
+            for (int k = 0; k < 3; k++) { L[k] = std::min(L[k], (double)box[k]); H[k] = std::max(H[k], (double)box[3 + k]); }
     }
     for (int k = 0; k < 3; k++)
     {

@@ -12,6 +12,7 @@
 // the private-copy kind), and two asynchronous copies — the top region of `nodes` and the records.  No vertex is transformed, no mesh node is
 // touched.  Answers are those of the private-copy kind and of a flattened scene bit for bit: see traverse2.h for what keeps them so.
 #include "hr_internal.h"
+#include "instance_math.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -95,11 +96,7 @@ struct SharedTop
     int                                  max_depth = 0;
 };
 
-inline double half_area3(const float* lo, const float* hi)
-{
-    const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
-    return x * y + y * z + z * x;
-}
+using imath::half_area3;
 
 void build_shared_top(const hr_scene* s, SharedTop& tl)
 {
@@ -156,22 +153,8 @@ void build_shared_top(const hr_scene* s, SharedTop& tl)
     }
 }
 
-uint8_t exponent_for_host(float extent)
-{
-    // smallest e with extent <= 255 * 2^(e - 127) (bvh_build.cpp exponent_for)
-    if (!(extent > 0.0f)) return 1;
-    int ex;
-    (void)std::frexp(extent / 255.0f, &ex);
-    int e = ex + 127;
-    if (e < 1) e = 1;
-    if (e > 254) e = 254;
-    while (e > 1 && std::ldexp(255.0, e - 1 - 127) >= (double)extent) e--;
-    while (e < 254 && std::ldexp(255.0, e - 127) < (double)extent) e++;
-    return (uint8_t)e;
-}
-
-// Boxes of a top level over the instances' current boxes, padded and quantised with the builder's rules (lo floored / hi ceiled).  Returns
-// the half-area sum of its nodes: what a re-build is judged by.
+// Boxes of a top level over the instances' current boxes, padded and quantised with the builder's rules (imath::top_node).  Returns the
+// half-area sum of its nodes: what a re-build is judged by.
 double refit_shared_top(const hr_scene* s, const SharedTop& tl, float pad, std::vector<Node8>& out)
 {
     const size_t n = tl.nodes.size();
@@ -183,9 +166,8 @@ double refit_shared_top(const hr_scene* s, const SharedTop& tl, float pad, std::
     {
         const hr_scene::SharedTopNode& t = tl.nodes[slot];
         const int nc = t.n_internal + t.n_leaves;
-        float clo[8][3], chi[8][3], lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+        float clo[8][3], chi[8][3], lo[3], hi[3];
         for (int c = 0; c < nc; c++)
-        {
             for (int k = 0; k < 3; k++)
             {
                 if (c < t.n_internal) { clo[c][k] = box[((size_t)t.child_base + c) * 6 + k]; chi[c][k] = box[((size_t)t.child_base + c) * 6 + 3 + k]; }
@@ -194,33 +176,9 @@ double refit_shared_top(const hr_scene* s, const SharedTop& tl, float pad, std::
                     const float* b = &s->inst_box[(size_t)tl.leaf_inst[(size_t)t.leaf_base + (c - t.n_internal)] * 6];
                     clo[c][k] = b[k] - pad; chi[c][k] = b[3 + k] + pad;
                 }
-                lo[k] = std::min(lo[k], clo[c][k]); hi[k] = std::max(hi[k], chi[c][k]);
             }
-        }
+        sum += imath::top_node(t, clo, chi, out[slot], lo, hi);
         for (int k = 0; k < 3; k++) { box[slot * 6 + k] = lo[k]; box[slot * 6 + 3 + k] = hi[k]; }
-        sum += half_area3(lo, hi);
-        Node8& nd = out[slot];
-        nd.ox = lo[0]; nd.oy = lo[1]; nd.oz = lo[2];
-        nd.ex = exponent_for_host(hi[0] - lo[0]); nd.ey = exponent_for_host(hi[1] - lo[1]); nd.ez = exponent_for_host(hi[2] - lo[2]);
-        nd.counts = (uint8_t)(t.n_internal | (nc << 4));
-        nd.child_base = (uint32_t)t.child_base;
-        nd.tri_base = (uint32_t)t.leaf_base;
-        const uint8_t eb[3] = { nd.ex, nd.ey, nd.ez };
-        for (int c = 0; c < nc; c++)
-        {
-            nd.meta[c] = c < t.n_internal ? (uint8_t)(0x10 | (c == 0 ? t.axis : 0)) : (uint8_t)((1 << 5) | (c - t.n_internal));
-            for (int k = 0; k < 3; k++)
-            {
-                const double sc = std::ldexp(1.0, (int)eb[k] - 127), o = (double)lo[k];
-                double l = std::floor(((double)clo[c][k] - o) / sc), h = std::ceil(((double)chi[c][k] - o) / sc);
-                if (!(l > 0.0)) l = 0.0;
-                if (l > 255.0) l = 255.0;
-                if (!(h < 255.0)) h = 255.0;
-                if (h < l) h = l;
-                nd.qlo[k][c] = (uint8_t)l; nd.qhi[k][c] = (uint8_t)h;
-            }
-        }
-        // a node without internal children keeps the sort axis out of slot 0's meta byte: a leaf's low bits are its offset
     }
     return sum;
 }
@@ -237,40 +195,7 @@ void fill_record(const hr_scene* s, int i, InstanceShared& r)
     std::memcpy(r.m, h.m, 64);
     r.first_tri = h.first_tri; r.mesh_tri_base = h.mesh_tri_base; r.mesh_id = h.mesh_id; r.n_tris = h.n_tris;
     r.mesh_root = s->shared_mesh_root[k]; r.instance = (uint32_t)i;
-    double A[3][3];   // A[row][column]
-    for (int c = 0; c < 3; c++) for (int q = 0; q < 3; q++) A[q][c] = (double)h.m[c * 4 + q];
-    double C[3][3];   // inverse = adjugate / det
-    C[0][0] = A[1][1] * A[2][2] - A[1][2] * A[2][1]; C[0][1] = A[0][2] * A[2][1] - A[0][1] * A[2][2]; C[0][2] = A[0][1] * A[1][2] - A[0][2] * A[1][1];
-    C[1][0] = A[1][2] * A[2][0] - A[1][0] * A[2][2]; C[1][1] = A[0][0] * A[2][2] - A[0][2] * A[2][0]; C[1][2] = A[0][2] * A[1][0] - A[0][0] * A[1][2];
-    C[2][0] = A[1][0] * A[2][1] - A[1][1] * A[2][0]; C[2][1] = A[0][1] * A[2][0] - A[0][0] * A[2][1]; C[2][2] = A[0][0] * A[1][1] - A[0][1] * A[1][0];
-    const double det = A[0][0] * C[0][0] + A[0][1] * C[1][0] + A[0][2] * C[2][0];
-    bool   ok = det != 0.0 && std::isfinite(det);
-    double norm_a = 0.0, norm_i = 0.0, extent = 0.0;
-    const float* am = &s->shared_mesh_absmax[(size_t)k * 3];
-    for (int q = 0; q < 3; q++)
-    {
-        double ra = 0.0, ri = 0.0;
-        for (int c = 0; c < 3; c++)
-        {
-            const double v = ok ? C[q][c] / det : 0.0;
-            r.inv[c * 3 + q] = (float)v;
-            ok = ok && std::isfinite(r.inv[c * 3 + q]);
-            ra += std::fabs(A[q][c]); ri += std::fabs(v);
-            extent += std::fabs(A[q][c]) * (double)am[c];
-        }
-        r.inv_abs_row[q] = (float)(ri * (1.0 + 1e-6));
-        extent += std::fabs((double)h.m[12 + q]);
-        norm_a = std::max(norm_a, ra); norm_i = std::max(norm_i, ri);
-    }
-    r.extent = (float)(extent * (1.0 + 1e-6));
-    // beyond a condition number of 1e7 the fp32 inverse says little about where the ray is: walk the mesh without culling (slow, rare, correct)
-    ok = ok && std::isfinite(r.extent) && std::isfinite(r.inv_abs_row[0]) && std::isfinite(r.inv_abs_row[1]) && std::isfinite(r.inv_abs_row[2]) && norm_a * norm_i <= 1e7;
-    if (!ok)
-    {
-        for (int q = 0; q < 9; q++) r.inv[q] = 0.0f;
-        r.inv_abs_row[0] = r.inv_abs_row[1] = r.inv_abs_row[2] = 0.0f; r.extent = 0.0f;
-        r.flags = 1u;
-    }
+    imath::record_terms(h.m, &s->shared_mesh_absmax[(size_t)k * 3], r.inv, r.inv_abs_row, &r.extent, &r.flags);
 }
 
 void adopt_shared_top(hr_scene* s, const SharedTop& tl)
@@ -282,12 +207,7 @@ void adopt_shared_top(hr_scene* s, const SharedTop& tl)
     s->info.max_depth = tl.max_depth + 1 + s->shared_mesh_depth;
 }
 
-float world_pad(const hr_scene* s)
-{
-    const double dx = (double)s->grid_hi[0] - s->grid_lo[0], dy = (double)s->grid_hi[1] - s->grid_lo[1], dz = (double)s->grid_hi[2] - s->grid_lo[2];
-    float pad = (float)(3e-5 * std::sqrt(dx * dx + dy * dy + dz * dz));   // bvh_build.cpp: well above the fp32 error of the triangle test
-    return pad > 0.0f ? pad : 1e-6f;
-}
+float world_pad(const hr_scene* s) { return imath::pad_of_bounds(s->grid_lo, s->grid_hi); }
 
 // deformable_call: hr_scene_create_instanced_shared_deformable (flags may still be null: no mesh can be updated then)
 hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out, bool deformable_call = false, const uint8_t* flags = nullptr)
@@ -425,6 +345,7 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     std::vector<float> mats((size_t)I * 16);
     for (int i = 0; i < I; i++) std::memcpy(&mats[(size_t)i * 16], d->instances[i].model_matrix, 64);
     s->top_area_at_build = -1.0;   // the first update records it
+    if ((st = shared_device_tables_upload(s, nullptr, true)) != HR_OK) return st;   // what hr_scene_update_instances_device reads
     if ((st = shared_scene_update(s, mats.data(), nullptr, false)) != HR_OK) return st;
     HR_HIP(hipStreamSynchronize(nullptr));
     if (deformable_call)
@@ -519,7 +440,7 @@ hr_status hr::shared_scene_update(hr_scene* s, const float* matrices, hipStream_
 {
     const int I = s->n_instances;
     const bool first = s->top_area_at_build < 0.0;
-    bool any = first || force_rebuild;
+    bool any = first || force_rebuild || s->mirrors_stale;   // after a device update every instance counts as changed
     if (matrices)
         for (int i = 0; i < I; i++)
         {
@@ -529,6 +450,8 @@ hr_status hr::shared_scene_update(hr_scene* s, const float* matrices, hipStream_
     if (!any) return HR_OK;
     HR_HIP(hipSetDevice(s->ctx->device));
     {
+        const hr_status ms = shared_mirrors_refresh(s);   // a device update ran since: the matrices come back from the records (one wait)
+        if (ms != HR_OK) return ms;
         const hr_status ws = instanced_scene_wait_uploads(s);   // the staging vectors below may still feed the previous call's copies
         if (ws != HR_OK) return ws;
     }
@@ -542,6 +465,7 @@ hr_status hr::shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_reb
 {
     const int I = s->n_instances;
     const bool first = s->top_area_at_build < 0.0;
+    bool adopted = false;
     instanced_scene_boxes(s);
     s->info.box_pad = world_pad(s);
     for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a]; s->info.bounds_hi[a] = s->grid_hi[a]; }   // conservative: no vertex is ever transformed here
@@ -563,6 +487,7 @@ hr_status hr::shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_reb
                 s->top_nodes_host.swap(fresh_nodes);
                 s->top_rebuilds++;
                 area = fresh_area;
+                adopted = true;
             }
         }
         s->top_area_at_build = area;   // adopted: the fresh one's; otherwise the spread is the new normal
@@ -570,6 +495,11 @@ hr_status hr::shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_reb
     if (first) s->top_area_at_build = area;
     s->shared_host.resize((size_t)I);
     for (int i = 0; i < I; i++) fill_record(s, i, s->shared_host[(size_t)s->shared_leaf_of[(size_t)i]]);
+    if (adopted)
+    {
+        const hr_status us = shared_device_tables_upload(s, st, false);   // the device update refits the topology the host adopted
+        if (us != HR_OK) return us;
+    }
     HR_HIP(hipMemcpyAsync(s->nodes.p, s->top_nodes_host.data(), (size_t)s->top_cap * sizeof(Node8), hipMemcpyHostToDevice, st));
     HR_HIP(hipMemcpyAsync(s->inst_shared.p, s->shared_host.data(), (size_t)I * sizeof(InstanceShared), hipMemcpyHostToDevice, st));
     {

@@ -270,6 +270,8 @@ hr_status update_impl(hr_scene* s, const hr_mesh_update* up, int32_t n_updates, 
     if (active.empty()) return HR_OK;
     HR_HIP(hipSetDevice(s->ctx->device));
     {
+        const hr_status mr = shared_mirrors_refresh(s);   // a device instance update ran since: the host tail below needs its matrices (one wait)
+        if (mr != HR_OK) return mr;
         const hr_status ws = instanced_scene_wait_uploads(s);   // the staging vectors of the host tail may still feed the previous call's copies
         if (ws != HR_OK) return ws;
     }
@@ -325,6 +327,10 @@ hr_status update_impl(hr_scene* s, const hr_mesh_update* up, int32_t n_updates, 
             s->mesh_bounds[m * 6 + k] = b[k]; s->mesh_bounds[m * 6 + 3 + k] = b[3 + k];
             s->shared_mesh_absmax[m * 3 + k] = std::max(std::fabs(b[k]), std::fabs(b[3 + k]));
         }
+    }
+    {
+        const hr_status mu = shared_device_mesh_table_upload(s, st);   // a device instance update after this one sees the new bounds
+        if (mu != HR_OK) return mu;
     }
     return shared_scene_host_tail(s, st, false);
 }

@@ -84,6 +84,15 @@ public:
     void     enable_two_level_passes(bool enable = true) { check(hr_scene_enable_two_level_passes(m_scene, enable ? 1 : 0), "hr_scene_enable_two_level_passes"); }
     bool     two_level_passes() const { return hr_scene_two_level_passes(m_scene) != 0; }
     void     update_instances(const float* model_matrices, Stream cmd_buf) { check(hr_scene_update_instances(m_scene, model_matrices, cmd_buf), "hr_scene_update_instances"); }
+    // a shared scene only: the same update from matrices in DEVICE memory ([n_instances][16]); world_bounds (host, lo xyz hi xyz) given: kernels
+    // only, no wait, legal under stream capture after one eager call; null: measured, one wait.  The top level is refitted, never re-built:
+    // device_update_status().top_cost_ratio beyond 1.5 is where the host path would call rebuild_top_level()
+    struct DeviceUpdateStatus { float top_cost_ratio; int32_t rejected_instances, bounds_violated; };
+    struct DeviceUpdateStats { int64_t launches, stream_waits; };
+    void     update_instances_device(const float* device_matrices, const float* world_bounds, Stream cmd_buf) { check(hr_scene_update_instances_device(m_scene, device_matrices, world_bounds, cmd_buf), "hr_scene_update_instances_device"); }
+    DeviceUpdateStatus device_update_status() const { DeviceUpdateStatus s { 1.0f, 0, 0 }; check(hr_scene_device_update_status(m_scene, &s.top_cost_ratio, &s.rejected_instances, &s.bounds_violated), "hr_scene_device_update_status"); return s; }
+    DeviceUpdateStats  device_update_stats() const { DeviceUpdateStats s { 0, 0 }; check(hr_scene_device_update_stats(m_scene, &s.launches, &s.stream_waits), "hr_scene_device_update_stats"); return s; }
+    void     rebuild_top_level(Stream cmd_buf) { check(hr_scene_rebuild_top_level(m_scene, cmd_buf), "hr_scene_rebuild_top_level"); }
     // motion vectors that follow the geometry: motion_begin_frame() once per frame BEFORE that frame's update_*() calls, on their stream (the first
     // call allocates: not under stream capture), then gbuffer_raycast_motion() in the place of hr_gbuffer_raycast (dynamic scenes)
     void     motion_begin_frame(Stream cmd_buf) { check(hr_scene_motion_begin_frame(m_scene, cmd_buf), "hr_scene_motion_begin_frame"); }

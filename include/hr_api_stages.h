@@ -213,7 +213,7 @@ typedef struct hr_mesh_update { uint32_t mesh_idx; int32_t first_tri, n_tris; /*
 hr_status hr_scene_update_meshes(hr_scene* scene, const hr_mesh_update* updates, int32_t n_updates, void* stream);
 hr_status hr_scene_mesh_refit_cost(const hr_scene* scene, uint32_t mesh_idx, float* ratio);
 hr_status hr_scene_update_meshes_stats(const hr_scene* scene, int64_t* level_launches, int64_t* top_launches, int64_t* stream_waits); hr_status hr_scene_read_instance_records(const hr_scene* scene, void* records_out);
-
+/* ---- device-side instance update of a shared scene (added within revision 6): update_instances_device refits the STANDING top level (never re-builds it) and rewrites the records from DEVICE matrices, kernels only on `stream`; world_bounds given: no host wait, no copy, no allocation after the first call, legal under stream capture (a replay reads the matrix buffer as it then stands); NULL: measured on the GPU, ONE wait, HR_ERR_INVALID_ARG while capturing.  HR_ERR_INVALID_ARG before anything is enqueued: not a shared scene, NULL matrices, bounds not finite or lo > hi.  A non-finite matrix keeps its instance's previous record and box (rejected_instances); bounds that were too small (bounds_violated) can cost hits, never an out-of-range access.  device_update_status synchronises when it lags; top_cost_ratio: top-level half-area sum now / at its last build (the host path re-builds beyond 1.5: hr_scene_rebuild_top_level).  The next host call on the scene (update_instances, rebuild_top_level, update_meshes) first reads the matrices back: one wait; once an update has been captured, every host call and every status call does (replays run unseen). */ hr_status hr_scene_update_instances_device(hr_scene* scene, const float* model_matrices /* DEVICE [n_instances][16], column-major */, const float* world_bounds /* HOST lo xyz hi xyz, conservative for the whole scene after this update, or NULL */, void* stream); hr_status hr_scene_device_update_status(const hr_scene* scene, float* top_cost_ratio, int32_t* rejected_instances, int32_t* bounds_violated); hr_status hr_scene_device_update_stats(const hr_scene* scene, int64_t* launches, int64_t* stream_waits);   /* tests, tools */
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,11 @@ updates and the forced top-level re-builds a random subset of the flagged meshes
 meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes.
 --motion (not with --deform): beside the scene under test, a shared scene, a private-copy scene and a deformable scene over the flattened vertices
 take hr_scene_motion_begin_frame and the same updates every step; the four images of hr_gbuffer_raycast_motion must be equal between the shared
-and the private-copy scene, and GB2 (normal + motion vector) and depth equal to the deformable scene's, bit for bit."""
+and the private-copy scene, and GB2 (normal + motion vector) and depth equal to the deformable scene's, bit for bit.
+--device (implies --shared; also with --deform): every matrix update of the scene under test goes through hr_scene_update_instances_device —
+the matrices uploaded first, the scene's bounds measured on the GPU or, every other time, given (the instances' transformed mesh bounds, widened) — so the forced
+top-level re-builds and the mesh updates that follow exercise the read-back of the host mirrors; after every step the status must report no
+rejected matrix and no violated bound."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +33,10 @@ if MOTION:
     sys.argv.remove("--motion")
     if DEFORM:
         sys.exit("--motion compares with a private-copy scene, which cannot deform: not with --deform")
-SHARED = "--shared" in sys.argv or DEFORM
+DEVICE = "--device" in sys.argv
+if DEVICE:
+    sys.argv.remove("--device")
+SHARED = "--shared" in sys.argv or DEFORM or DEVICE
 if "--shared" in sys.argv:
     sys.argv.remove("--shared")
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -61,6 +68,29 @@ def random_matrix(big):
         sh = np.eye(4, dtype=np.float32); sh[0, 1] = rng.uniform(-0.7, 0.7); sh[2, 0] = rng.uniform(-0.5, 0.5)
         m = (m @ sh).astype(np.float32)
     return np.ascontiguousarray(m.T.reshape(16), np.float32)
+
+
+def update(g, isd, mats):
+    """the scene under test takes new matrices: from host memory, or (--device) from device memory"""
+    if not DEVICE:
+        return g.update(mats)
+    bounds = None
+    if rng.rand() < 0.5:
+        # the instances' boxes are the eight corners of their mesh's bounds through the matrix (not the vertices'): bound those, with room to spare
+        lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+        for (_, k, _), m in zip(isd.instances, np.asarray(mats, np.float64).reshape(-1, 16)):
+            if isd.meshes[k].n_tris == 0:
+                continue
+            blo, bhi = [b.astype(np.float64) for b in isd.meshes[k].bounds()]
+            c = np.array([[(blo, bhi)[(j >> a) & 1][a] for a in range(3)] for j in range(8)])
+            w = c @ m.reshape(4, 4).T[:3, :3].T + m[12:15]
+            lo, hi = np.minimum(lo, w.min(0)), np.maximum(hi, w.max(0))
+        pad = 1e-3 * (hi - lo) + 1e-3 * np.maximum(np.abs(lo), np.abs(hi)) + 1e-3
+        bounds = ((lo - pad).astype(np.float32), (hi + pad).astype(np.float32))
+    g.update_device(torch.from_numpy(np.ascontiguousarray(mats, np.float32)).cuda(), bounds=bounds)
+    st = g.device_update_status()
+    if st["rejected_instances"] or st["bounds_violated"]:
+        raise RuntimeError(f"device update status {st}")
 
 
 bad = 0
@@ -98,7 +128,7 @@ for trial in range(n):
                         mats[i, 12:15] += rng.uniform(-4, 4, 3).astype(np.float32)
                     else:
                         mats[i] = random_matrix(big=rng.rand() < 0.2)
-                g.update(mats)
+                update(g, isd, mats)
                 if rng.rand() < 0.15:
                     g.rebuild_top_level()
                     forced = True
@@ -118,7 +148,7 @@ for trial in range(n):
                     g.update_meshes(ups)
                     if rng.rand() < 0.5:   # and the matrices once more, behind the mesh update
                         mats[int(rng.randint(0, I)), 12:15] += rng.uniform(-2, 2, 3).astype(np.float32)
-                        g.update(mats)
+                        update(g, isd, mats)
             flat_sd = isd.flatten(mats)
             if MOTION:
                 for s_ in mg:

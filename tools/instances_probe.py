@@ -12,7 +12,13 @@ created fresh over the same deformed meshes (masks must be equal).
 --shared --passes: the ray_trace stage of AO (4 spp), DDGI (16x8x16 probes, 256 rays) and reflections (half resolution) on the shared scene, opted
 in to the two-level passes, next to the PRIVATE-COPY scene of the same desc and matrices (the single-level kernels: the yardstick).  Both scenes
 see the same G-buffer; they are timed in alternating rounds of 10 profiled frames after a warm-up and the per-round averages are printed as
-mean [min, max]; masks, radiance and trace images must be equal."""
+mean [min, max]; masks, radiance and trace images must be equal.
+--shared --device: what hr_scene_update_instances_device costs next to hr_scene_update_instances on twin shared scenes over the same matrices
+(already resident on the GPU for the device path).  Every frame is timed on its own (update, then wait for the stream) and the MEDIAN over the
+frames is reported: the host path twice (`host_ms`, `host_ms_again`: their difference is the run-to-run spread), the device path with the bounds
+given and with the bounds measured; then the same frames back to back without waiting in between (what the calling thread pays per frame).
+Any-hit answers of 20 000 rays must agree after the last frame.  --host-only: the host path's numbers alone (a library built from a revision
+that does not have the device path, selected with HR_LIBRARY)."""
 import argparse, json, math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,6 +34,8 @@ def main():
     ap.add_argument("--shared", action="store_true", help="hr_scene_create_instanced_shared: one BVH per mesh, two-level walk")
     ap.add_argument("--deform", action="store_true", help="hr_scene_update_meshes on a shared scene with deforming meshes")
     ap.add_argument("--passes", action="store_true", help="with --shared: AO / DDGI / reflections trace stages, shared against private copies")
+    ap.add_argument("--device", action="store_true", help="with --shared: hr_scene_update_instances_device against the host update, per frame")
+    ap.add_argument("--host-only", action="store_true", help="with --shared --device: time the host path alone")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--meshes", type=int, default=16)
     ap.add_argument("--copies", type=int, default=8)
@@ -35,6 +43,9 @@ def main():
     a = ap.parse_args()
     if a.deform:
         return deform_probe(a)
+    if a.device:
+        assert a.shared, "--device times the device-side update of a shared scene: give --shared"
+        return device_probe(a)
     if a.passes:
         assert a.shared, "--passes compares a shared scene with its private-copy twin: give --shared"
         return passes_probe(a)
@@ -102,6 +113,67 @@ def main():
     res["masks_equal"] = True
     if a.shared:
         res["kind"] = "shared"
+    print(json.dumps(res))
+
+
+def device_probe(a):
+    import torch
+    from hybrid_rendering_amd import api as hr, synth
+    building = synth.sponza_like(a.detail)
+    small = synth.instanced_cornell(2)
+    cube, pyr = small.meshes[1], small.meshes[2]
+    lo, hi = building.bounds()
+    rng = np.random.RandomState(1)   # the scene and the motion of main()
+    base = [(rng.uniform(lo + 0.15 * (hi - lo), hi - 0.15 * (hi - lo)), rng.uniform(-1, 1, 3), rng.uniform(0, 6.28), rng.uniform(6, 30, 3), rng.uniform(-2, 2, 3)) for _ in range(a.movers)]
+
+    def instances(f):
+        return [(synth.model_matrix(), 0, 1)] + [(synth.model_matrix(p + vel * f, ax, ang + 0.05 * f, sc), 1 + (i & 1), 2 + i) for i, (p, ax, ang, sc, vel) in enumerate(base)]
+    isd = synth.InstancedSceneData(meshes=[building, cube, pyr], instances=instances(0), materials=building.materials)
+    ctx = hr.Context(0)
+    mats = [synth.InstancedSceneData(isd.meshes, instances(f), isd.materials).matrices() for f in range(a.frames + 1)]
+    g_host = hr.InstancedScene(ctx, isd, shared=True)
+
+    def per_frame(fn, frames):
+        """(median of the frames timed one by one, mean of the frames enqueued back to back), ms"""
+        for m in frames[:3]:
+            fn(m)
+        torch.cuda.synchronize()
+        one = []
+        for m in frames:
+            t0 = time.perf_counter()
+            fn(m)
+            torch.cuda.synchronize()
+            one.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        for m in frames:
+            fn(m)
+        torch.cuda.synchronize()
+        return round(float(np.median(one)), 4), round((time.perf_counter() - t0) / len(frames) * 1e3, 4)
+    res = dict(kind="shared, device-side instance update", instances=a.movers + 1, frames=len(mats))
+    res["host_ms"], res["host_ms_back_to_back"] = per_frame(g_host.update, mats)
+    if not a.host_only:
+        g_dev = hr.InstancedScene(ctx, isd, shared=True)
+        box = np.array([np.inf] * 3 + [-np.inf] * 3)
+        for m in mats:   # bounds that hold for every frame: the union of the host path's conservative ones
+            g_host.update(m)
+            i = g_host.refresh_info()
+            box = np.concatenate([np.minimum(box[:3], list(i.bounds_lo)), np.maximum(box[3:], list(i.bounds_hi))])
+        bounds = box.astype(np.float32).reshape(2, 3)
+        dev = [torch.from_numpy(m).cuda() for m in mats]
+        res["device_ms_bounds_given"], res["device_ms_bounds_given_back_to_back"] = per_frame(lambda m: g_dev.update_device(m, bounds=bounds), dev)
+        res["device_ms_bounds_measured"], res["device_ms_bounds_measured_back_to_back"] = per_frame(lambda m: g_dev.update_device(m), dev)
+        res["device_status"], res["device_stats"] = g_dev.device_update_status(), g_dev.device_update_stats()
+    res["host_ms_again"], res["host_ms_again_back_to_back"] = per_frame(g_host.update, mats)
+    res["host_spread_ms"] = round(abs(res["host_ms"] - res["host_ms_again"]), 4)
+    res["host_top_level_rebuilds"] = g_host.top_level_rebuilds
+    if not a.host_only:
+        r = np.zeros((20000, 8), np.float32)
+        r[:, :3] = rng.uniform(lo, hi, (20000, 3))
+        d = rng.normal(size=(20000, 3))
+        r[:, 4:7], r[:, 3], r[:, 7] = d / np.linalg.norm(d, axis=1, keepdims=True), 1e4, 0.01
+        rd = torch.from_numpy(r).cuda()
+        assert np.array_equal(g_host.any_hit(rd).cpu().numpy(), g_dev.any_hit(rd).cpu().numpy()), "any-hit answers differ between the host- and the device-updated scene"
+        res["answers_equal"] = True
     print(json.dumps(res))
 
 
