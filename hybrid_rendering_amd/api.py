@@ -102,6 +102,7 @@ ABI_SYMBOLS = [
     "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",
     "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
     "hr_scene_update_instances_device", "hr_scene_device_update_status", "hr_scene_device_update_stats",
+    "hr_scene_rebuild_top_level_device", "hr_scene_set_device_rebuild_threshold", "hr_scene_device_rebuild_status", "hr_shared_top_fixed_shape", "hr_shared_top_sort_keys",
 ]
 
 # argtypes of the device-side instance update's entry points (include/hr_api_stages.h)
@@ -109,6 +110,11 @@ DEVICE_UPDATE_ARGTYPES = {
     "hr_scene_update_instances_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "hr_scene_device_update_status": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "hr_scene_device_update_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "hr_scene_rebuild_top_level_device": [C.c_void_p, C.c_void_p],
+    "hr_scene_set_device_rebuild_threshold": [C.c_void_p, C.c_float, C.c_void_p],
+    "hr_scene_device_rebuild_status": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+    "hr_shared_top_fixed_shape": [C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "hr_shared_top_sort_keys": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
 }
 
 _lib = None
@@ -438,7 +444,8 @@ class InstancedScene(Scene):
         """hr_scene_update_instances_device (shared scenes): ``matrices_cuda`` is a cuda float32 contiguous tensor [n_instances, 16], column-major,
         read when the kernels RUN (a captured call picks up the buffer's contents at replay).  ``bounds``: host (lo xyz, hi xyz), conservative for
         the whole scene after this update — then nothing but kernels is enqueued on ``stream`` (default: torch's current stream); None: measured on
-        the GPU, the call waits once (HRError while the stream is capturing).  The top level is refitted, never re-built: ``device_update_status``."""
+        the GPU, the call waits once (HRError while the stream is capturing).  The top level is refitted, not re-built (``device_update_status``) —
+        unless ``set_device_rebuild_threshold`` is on: then the device re-builds it behind the refit when its cost ratio exceeds the threshold."""
         import torch
         n = int(lib().hr_scene_instance_count(self.h))
         assert matrices_cuda.is_cuda and matrices_cuda.dtype == torch.float32 and matrices_cuda.is_contiguous() and tuple(matrices_cuda.shape) == (n, 16), \
@@ -463,13 +470,37 @@ class InstancedScene(Scene):
         return dict(top_cost_ratio=float(r.value), rejected_instances=int(a.value), bounds_violated=int(b.value))
 
     def device_update_stats(self) -> dict:
-        """hr_scene_device_update_stats: kernel launches of the device updates so far, and stream waits (measured bounds; the read-back a host
+        """hr_scene_device_update_stats: kernel launches of the device updates and device re-builds so far, and stream waits (measured bounds; the read-back a host
         call makes after a device update)"""
         a, b = C.c_int64(0), C.c_int64(0)
         L = lib()
         L.hr_scene_device_update_stats.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_device_update_stats"]
         _check(L.hr_scene_device_update_stats(self.h, C.byref(a), C.byref(b)), "hr_scene_device_update_stats")
         return dict(launches=int(a.value), stream_waits=int(b.value))
+
+    def rebuild_top_level_device(self, stream=None):
+        """hr_scene_rebuild_top_level_device (shared scenes): the top level re-built by kernels on ``stream`` (default: torch's current stream) over
+        the boxes and bounds of the last update; nothing is read back.  The call that changes the shape (the first, or the first after
+        ``rebuild_top_level``) raises HRError while the stream is capturing; later ones may be captured."""
+        L = lib()
+        L.hr_scene_rebuild_top_level_device.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_rebuild_top_level_device"]
+        _check(L.hr_scene_rebuild_top_level_device(self.h, _stream_ptr(stream)), "hr_scene_rebuild_top_level_device")
+
+    def set_device_rebuild_threshold(self, ratio: float, stream=None):
+        """hr_scene_set_device_rebuild_threshold: 0 switches it off (the default); ``ratio`` > 1 brings the scene to the fixed shape at once and
+        makes every ``update_device`` enqueue the re-build behind its refit, run on the device only when top_cost_ratio exceeds ``ratio``."""
+        L = lib()
+        L.hr_scene_set_device_rebuild_threshold.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_set_device_rebuild_threshold"]
+        _check(L.hr_scene_set_device_rebuild_threshold(self.h, C.c_float(ratio), _stream_ptr(stream)), "hr_scene_set_device_rebuild_threshold")
+
+    def device_rebuild_status(self) -> dict:
+        """hr_scene_device_rebuild_status (synchronises when it lags): rebuilds_done — device re-builds that ran, counted on the device;
+        launches_enqueued — kernel launches enqueued for re-builds so far; fixed_shape — the top level has the shape of hr_shared_top_fixed_shape"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        L = lib()
+        L.hr_scene_device_rebuild_status.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_device_rebuild_status"]
+        _check(L.hr_scene_device_rebuild_status(self.h, C.byref(a), C.byref(b), C.byref(c)), "hr_scene_device_rebuild_status")
+        return dict(rebuilds_done=int(a.value), launches_enqueued=int(b.value), fixed_shape=int(c.value))
 
     def update(self, matrices, stream=None):
         """hr_scene_update_instances: matrices [n_instances][16] column-major (host); enqueued on ``stream`` (default: torch's current stream)"""
@@ -496,6 +527,32 @@ def bvh_selfcheck(verts, samples_per_triangle: int = 12) -> int:
     L.hr_bvh_selfcheck.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     _check(L.hr_bvh_selfcheck(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.c_int32(samples_per_triangle), C.byref(bad)), "hr_bvh_selfcheck")
     return int(bad.value)
+
+
+SHARED_TOP_NODE_DTYPE = np.dtype([(k, np.int32) for k in ("n_internal", "n_leaves", "child_base", "leaf_base", "axis", "depth")])
+
+
+def shared_top_fixed_shape(n_instances: int):
+    """Host-only: (nodes, n_depths) of the fixed 8-wide top level a device re-build gives a shared scene of ``n_instances`` instances — a
+    structured array (SHARED_TOP_NODE_DTYPE), slots breadth-first"""
+    L = lib()
+    L.hr_shared_top_fixed_shape.argtypes = DEVICE_UPDATE_ARGTYPES["hr_shared_top_fixed_shape"]
+    n, d = C.c_int32(0), C.c_int32(0)
+    _check(L.hr_shared_top_fixed_shape(C.c_int32(n_instances), None, C.c_int64(0), C.byref(n), C.byref(d)), "hr_shared_top_fixed_shape")
+    out = np.zeros(int(n.value), SHARED_TOP_NODE_DTYPE)
+    _check(L.hr_shared_top_fixed_shape(C.c_int32(n_instances), C.c_void_p(out.ctypes.data), C.c_int64(len(out)), C.byref(n), C.byref(d)), "hr_shared_top_fixed_shape")
+    return out, int(d.value)
+
+
+def shared_top_sort_keys(inst_boxes, bounds) -> np.ndarray:
+    """Host-only: the uint64 sort keys (30-bit Morton code << 32 | instance) of ``inst_boxes`` [n,6] (lo xyz, hi xyz) inside ``bounds`` (lo xyz, hi xyz)"""
+    b = np.ascontiguousarray(np.asarray(inst_boxes, np.float32).reshape(-1, 6))
+    w = np.ascontiguousarray(np.asarray(bounds, np.float32).reshape(6))
+    out = np.zeros(len(b), np.uint64)
+    L = lib()
+    L.hr_shared_top_sort_keys.argtypes = DEVICE_UPDATE_ARGTYPES["hr_shared_top_sort_keys"]
+    _check(L.hr_shared_top_sort_keys(C.c_void_p(b.ctypes.data), C.c_int32(len(b)), C.c_void_p(w.ctypes.data), C.c_void_p(out.ctypes.data)), "hr_shared_top_sort_keys")
+    return out
 
 
 CHILD_BOX_DTYPE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("step", np.float32, 3), ("node", np.int32), ("slot", np.int32), ("depth", np.int32), ("is_leaf", np.int32)])

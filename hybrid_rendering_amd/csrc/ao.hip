@@ -593,7 +593,9 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     if (p->grid_enabled && p->entry_grid.p && prm->ray_length > 0.0f)
     {
         bool enqueued = false;
-        if (p->grid_scene != scene->uid || p->grid_epoch != scene->geometry_epoch || p->grid_ray_length != prm->ray_length)
+        // order_replayed: a captured device re-build (instances_shared_rebuild.hip) moves instances between top-level nodes at every replay, which
+        // no epoch counts — a table of another order would start rays below nodes that no longer hold the nearby instances
+        if (p->grid_scene != scene->uid || p->grid_epoch != scene->geometry_epoch || p->grid_ray_length != prm->ray_length || scene->order_replayed)
         {
             // cells of half the ray length, no finer than 1/256 of the longest extent, coarsened until the table fits its fixed capacity
             const float* lo = scene->grid_lo; const float* hi = scene->grid_hi;   // no read-back: conservative bounds for an instanced scene

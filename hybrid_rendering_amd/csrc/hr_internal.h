@@ -190,6 +190,15 @@ struct SharedDeviceUpdate
     hipStream_t last_stream = nullptr;            // of the last update enqueued
     double   area_at_build = 0.0;                 // the scene's top_area_at_build when the last update was enqueued
     int64_t  launches = 0, stream_waits = 0;
+    // the device re-build of the top level (instances_shared_rebuild.hip); its buffers are allocated by the first re-build, never after
+    bool     boxes_current = false;               // inst_box and the status block's bounds are those of the standing records (a host update clears it)
+    bool     device_baseline = false;             // top_cost_ratio is relative to the status block's baseline (a host re-build clears it)
+    float    threshold = 0.0f;                    // hr_scene_set_device_rebuild_threshold; 0: off
+    bool     rebuild_ready = false;
+    DevBuf   rb_codes[2], rb_idx[2];              // per instance: Morton code / instance index, ping-pong of the radix sort; rb_idx[0]: the sorted order
+    DevBuf   rb_hist;                             // radix sort: per digit and workgroup, a count, then its exclusive prefix
+    DevBuf   rb_records;                          // the records gathered into the new leaf order, before they are copied back
+    int64_t  rebuild_launches = 0;
     ~SharedDeviceUpdate() { if (status_host) (void)hipHostFree(status_host); }
 };
 
@@ -380,6 +389,9 @@ struct hr_scene
     std::vector<uint32_t> shared_mesh_tri_base;   // per mesh: first triangle in the concatenated attribute arrays
     std::vector<float> mesh_tab_host;             // upload staging of dev_mesh_tab (per mesh 12 floats)
     std::unique_ptr<hr::SharedDeviceUpdate> dev_update;
+    bool          fixed_shape = false;            // the top level has the shape of imath::fixed_top_node (a device re-build made it; a host re-build ends it)
+    bool          order_replayed = false;         // a device re-build was CAPTURED: replays re-order the leaves where geometry_epoch cannot follow, so
+                                                  // caches of the passes that hold top-level node indices (AO's entry table) are rebuilt at every use
     bool          mirrors_stale = false;          // a device update ran: inst_host / inst_box / top_nodes_host / shared_host lag the device
     // ---- deformable scenes (deform.hip): a flat scene built without spatial splits; hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`
     // and refits `nodes` through level_nodes / level_offsets / node_box (the arrays of the instanced scenes' refit)

@@ -177,5 +177,67 @@ HR_HD double top_node(const SharedTopNode& t, const float (*clo)[3], const float
     return half_area3(lo, hi);
 }
 
+// ---- the device re-build of a shared scene's top level (instances_shared_rebuild.hip) ---------------------------------------------------------
+// The sort key of one instance: a 30-bit Morton code of the centre of its world box inside `bounds` (lo xyz, hi xyz), above the instance index.
+// Per axis, all in fp64 (every step one IEEE operation, no contraction):
+//     centre = (lo + hi) * 0.5          extent = bounds_hi - bounds_lo          q = ((centre - bounds_lo) / extent) * 1024
+//     cell   = floor(q) clamped to [0, 1023]; 0 when q is not finite (a zero extent, an infinite box, 0 / 0)
+// x takes bits 0, 3, 6, ..., y bits 1, 4, ..., z bits 2, 5, ...  The key is unique per instance, so the sorted order is a function of the boxes
+// and the bounds alone.  An instance of an empty mesh has a point box (world_box) and is sorted by it.
+HR_HD uint32_t morton_cell(float lo, float hi, float blo, float bhi)
+{
+    const double centre = ((double)lo + (double)hi) * 0.5, extent = (double)bhi - (double)blo;
+    const double q = ((centre - (double)blo) / extent) * 1024.0;
+    if (!finite_d(q)) return 0u;
+    const double f = __builtin_floor(q);
+    if (!(f > 0.0)) return 0u;
+    if (f > 1023.0) return 1023u;
+    return (uint32_t)f;
+}
+HR_HD uint32_t spread3(uint32_t v)   // bit i of a 10-bit value -> bit 3 i
+{
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+HR_HD uint32_t morton_code(const float* box /*[6]*/, const float* bounds /*[6]*/)
+{
+    return spread3(morton_cell(box[0], box[3], bounds[0], bounds[3])) | (spread3(morton_cell(box[1], box[4], bounds[1], bounds[4])) << 1)
+         | (spread3(morton_cell(box[2], box[5], bounds[2], bounds[5])) << 2);
+}
+HR_HD uint64_t sort_key(const float* box, const float* bounds, uint32_t instance) { return ((uint64_t)morton_code(box, bounds) << 32) | (uint64_t)instance; }
+
+// The fixed 8-wide top level over n instances: a shape that depends on n alone.  Leaves 0 .. n-1 are dealt in order to ceil(n / 8) bottom nodes,
+// node j of a level of c nodes over m items taking items [floor(j m / c), floor((j + 1) m / c)) — floor or ceil of m / c each, at least 4 when
+// m > 8 —; those nodes are grouped the same way until one root stands.  The depth count is the smallest any 8-wide tree over n leaves can have.
+// Slots are breadth-first (the root is slot 0, every depth a contiguous range), axis is 0 (the walk's ordering hint only), and a node without
+// leaves carries the first leaf below it as leaf_base.
+HR_HD int fixed_top_depths(int n) { int d = 1; for (long long c = 8; c < (long long)n; c *= 8) d++; return d; }
+HR_HD int fixed_top_level_count(int n, int level) { long long c = n; for (int l = 0; l <= level; l++) c = (c + 7) / 8; return (int)c; }   // level 0: the bottom nodes
+HR_HD int fixed_top_nodes(int n) { int s = 0; for (int l = 0; l < fixed_top_depths(n); l++) s += fixed_top_level_count(n, l); return s; }
+// first slot of depth d (d == n_depths: the slot count)
+HR_HD int fixed_top_depth_start(int n, int d) { const int D = fixed_top_depths(n); int s = 0; for (int k = 0; k < d; k++) s += fixed_top_level_count(n, D - 1 - k); return s; }
+// node j of depth d
+HR_HD SharedTopNode fixed_top_node(int n, int d, int j)
+{
+    const int D = fixed_top_depths(n), level = D - 1 - d;
+    const long long c = fixed_top_level_count(n, level), m = level == 0 ? n : fixed_top_level_count(n, level - 1);
+    const long long first = ((long long)j * m) / c, end = ((long long)(j + 1) * m) / c;
+    SharedTopNode t;
+    t.axis = 0; t.depth = d;
+    if (level == 0) { t.n_internal = 0; t.n_leaves = (int)(end - first); t.child_base = 0; t.leaf_base = (int)first; return t; }
+    t.n_internal = (int)(end - first); t.n_leaves = 0; t.child_base = fixed_top_depth_start(n, d + 1) + (int)first;
+    long long leaf = first;   // the first leaf below: follow the first child down
+    for (int l = level - 1; l >= 0; l--)
+    {
+        const long long cc = fixed_top_level_count(n, l), mm = l == 0 ? n : fixed_top_level_count(n, l - 1);
+        leaf = (leaf * mm) / cc;
+    }
+    t.leaf_base = (int)leaf;
+    return t;
+}
+
 } // namespace imath
 } // namespace hr

@@ -205,6 +205,8 @@ void adopt_shared_top(hr_scene* s, const SharedTop& tl)
     s->shared_leaf_of.assign((size_t)s->n_instances, 0);
     for (size_t l = 0; l < tl.leaf_inst.size(); l++) s->shared_leaf_of[(size_t)tl.leaf_inst[l]] = (int32_t)l;
     s->info.max_depth = tl.max_depth + 1 + s->shared_mesh_depth;
+    s->fixed_shape = false;   // a host-built shape; top_cost_ratio is relative to the host's sum again (instances_shared_rebuild.hip)
+    if (s->dev_update) s->dev_update->device_baseline = false;
 }
 
 float world_pad(const hr_scene* s) { return imath::pad_of_bounds(s->grid_lo, s->grid_hi); }
@@ -506,6 +508,7 @@ hr_status hr::shared_scene_host_tail(hr_scene* s, hipStream_t st, bool force_reb
         const hr_status ms = instanced_scene_mark_uploads(s, st);
         if (ms != HR_OK) return ms;
     }
+    if (s->dev_update) s->dev_update->boxes_current = false;   // the device's instance boxes are those of its own last update
     s->geometry_epoch++;
     return HR_OK;
 }

@@ -20,8 +20,12 @@
 // The pad of the leaf boxes is 3e-5 x the diagonal of the scene's bounds: a kernel argument when the caller gives the bounds, computed from the
 // accumulated bounds on the device when they are measured (then the call waits once, for the status block, so that the host's grid_lo / grid_hi and
 // info follow).  The accumulators are consumed and reset by (b)'s last workgroup, so no launch is spent on clearing them.
-#include "hr_internal.h"
-#include "instance_math.h"
+//
+// The refit (b) is also the tail of the device re-build of the top level (instances_shared_rebuild.hip, which sorts the leaves into a tree of
+// fixed shape): there it takes the last update's bounds and pad from the status block, makes its half-area sum the baseline top_cost_ratio is
+// relative to, and clears rebuild_flag — the flag an update's refit sets when a threshold is on and area / baseline exceeds it, and on which
+// the re-build's launches behind that update are predicated.
+#include "instances_shared_device.h"
 #include <cmath>
 #include <cstring>
 
@@ -31,21 +35,6 @@ namespace {
 
 constexpr int kOneLaunchNodes = 1024;
 constexpr int kLaunchesSmall  = 2;
-
-struct MeshTab { float bounds[6], absmax[3]; uint32_t root, tri_base, pad; };
-static_assert(sizeof(MeshTab) == 48, "MeshTab must be 48 bytes");
-
-// device block, mirrored into pinned host memory on demand
-struct DeviceUpdateStatus
-{
-    uint32_t acc_lo[3], acc_hi[3];   // ordered-uint min / max of the instance boxes, folded by (a), consumed and reset by (b)
-    uint32_t acc_rejected, acc_violated;
-    float    bounds[6];              // of the last update: measured, or as given
-    float    pad;
-    uint32_t rejected, violated, any_box;
-    double   area;                   // sum of the top-level nodes' half areas after the last update
-};
-static_assert(sizeof(DeviceUpdateStatus) == 80, "DeviceUpdateStatus layout");
 
 constexpr uint32_t kAccLoInit = 0xffffffffu, kAccHiInit = 0u;
 
@@ -132,11 +121,20 @@ struct TopArgs
     int                  given;
     float                pad;            // given bounds: the pad they make
     float                lo[3], hi[3];   // given bounds
+    int                  mode;           // kRefitUpdate, or the tail of a device re-build: bounds and pad are the status block's
+    int                  predicated;     // run only when the status block's rebuild_flag is set
+    float                ratio;          // kRefitUpdate: the re-build threshold (0: off)
 };
 
 // the pad of this update: the argument, or made from the bounds (a) accumulated
 __device__ inline float pad_of_update(const TopArgs& a, float* lo, float* hi, bool* any)
 {
+    if (a.mode != kRefitUpdate)
+    {
+        for (int k = 0; k < 3; k++) { lo[k] = a.status->bounds[k]; hi[k] = a.status->bounds[3 + k]; }
+        *any = a.status->any_box != 0u;
+        return a.status->pad;
+    }
     if (a.given)
     {
         for (int k = 0; k < 3; k++) { lo[k] = a.lo[k]; hi[k] = a.hi[k]; }
@@ -192,6 +190,13 @@ __device__ inline void finish_update(const TopArgs& a, double partial, double* r
     if (t == 0)
     {
         DeviceUpdateStatus* st = a.status;
+        if (a.mode != kRefitUpdate)   // a re-build's tail: the area is the new baseline; the last update's bounds and counts stand
+        {
+            st->area = red[0]; st->baseline = red[0]; st->rebuild_flag = 0u;
+            if (a.mode == kRefitRebuildCounted) st->rebuilds_done++;
+            return;
+        }
+        st->rebuild_flag = (a.ratio > 0.0f && st->baseline > 0.0 && red[0] / st->baseline > (double)a.ratio) ? 1u : 0u;   // threshold off: always clear
         for (int k = 0; k < 3; k++) { st->bounds[k] = lo[k]; st->bounds[3 + k] = hi[k]; }
         st->pad = pad; st->any_box = any ? 1u : 0u;
         st->rejected = st->acc_rejected; st->violated = st->acc_violated;
@@ -206,6 +211,7 @@ __global__ void __launch_bounds__(kOneLaunchNodes) k_shared_top_one(const TopArg
 {
     __shared__ float  box[kOneLaunchNodes * 6];
     __shared__ double red[kOneLaunchNodes];
+    if (a.predicated && a.status->rebuild_flag == 0u) return;   // the whole workgroup: the flag changes in this kernel's last statement only
     const int slot = (int)threadIdx.x;
     float lo[3], hi[3];
     bool  any;
@@ -224,6 +230,7 @@ __global__ void __launch_bounds__(256) k_shared_top_depth(const TopArgs a)
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= a.count) return;
+    if (a.predicated && a.status->rebuild_flag == 0u) return;   // cleared by the root's launch, behind every depth's
     float lo[3], hi[3];
     bool  any;
     const float pad = pad_of_update(a, lo, hi, &any);
@@ -234,6 +241,7 @@ __global__ void __launch_bounds__(256) k_shared_top_depth(const TopArgs a)
 __global__ void __launch_bounds__(kOneLaunchNodes) k_shared_top_root(const TopArgs a)
 {
     __shared__ double red[kOneLaunchNodes];
+    if (a.predicated && a.status->rebuild_flag == 0u) return;
     float lo[3], hi[3];
     bool  any;
     const float pad = pad_of_update(a, lo, hi, &any);
@@ -250,7 +258,17 @@ hr_status bad(const char* call, const std::string& what)
     return HR_ERR_INVALID_ARG;
 }
 
-hr_status ensure_work(hr_scene* s)
+} // namespace
+
+bool hr::stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(st, &cap);
+    if (ce != hipSuccess) (void)hipGetLastError();
+    return ce != hipSuccess || cap != hipStreamCaptureStatusNone;
+}
+
+hr_status hr::shared_device_work_ensure(hr_scene* s)
 {
     if (s->dev_update) return HR_OK;
     std::unique_ptr<SharedDeviceUpdate> du(new SharedDeviceUpdate());
@@ -270,6 +288,52 @@ hr_status ensure_work(hr_scene* s)
     return HR_OK;
 }
 
+// the top level's refit over the scene's standing topology: one workgroup up to kOneLaunchNodes nodes, else one launch per depth
+static hr_status refit_enqueue(hr_scene* s, hipStream_t st, const float* bounds, int mode, bool predicated)
+{
+    SharedDeviceUpdate& du = *s->dev_update;
+    const int n_nodes = (int)s->shared_top.size(), n_depths = (int)s->shared_depth_start.size() - 1;
+    TopArgs ta;
+    ta.top = (const SharedTopNode*)s->dev_top.p; ta.leaf_inst = (const int32_t*)s->dev_leaf_inst.p; ta.inst_box = (const float*)du.inst_box.p;
+    ta.nodes = (Node8*)s->nodes.p; ta.node_box = (float*)du.node_box.p; ta.areas = (double*)du.areas.p; ta.status = (DeviceUpdateStatus*)du.status.p;
+    ta.n_nodes = n_nodes; ta.first = 0; ta.count = n_nodes; ta.given = bounds ? 1 : 0;
+    ta.pad = bounds ? imath::pad_of_bounds(bounds, bounds + 3) : 0.0f;
+    for (int k = 0; k < 3; k++) { ta.lo[k] = bounds ? bounds[k] : 0.0f; ta.hi[k] = bounds ? bounds[3 + k] : 0.0f; }
+    ta.mode = mode; ta.predicated = predicated ? 1 : 0; ta.ratio = mode == kRefitUpdate ? du.threshold : 0.0f;
+    const int* start = s->shared_depth_start.data();   // slots are breadth-first: depth d is the slot range [start[d], start[d + 1])
+    ta.n_depths = n_depths;
+    int64_t launched = 0;
+    if (n_nodes <= kOneLaunchNodes)
+    {
+        int threads = 64;
+        while (threads < n_nodes) threads *= 2;
+        hipLaunchKernelGGL(k_shared_top_one, dim3(1), dim3(threads), 0, st, ta);
+        HR_HIP(hipGetLastError());
+        launched++;
+    }
+    else
+    {
+        for (int d = n_depths - 1; d >= 1; d--)
+        {
+            ta.first = start[d]; ta.count = start[d + 1] - start[d];
+            hipLaunchKernelGGL(k_shared_top_depth, dim3(cdiv(ta.count, 256)), dim3(256), 0, st, ta);
+            HR_HIP(hipGetLastError());
+            launched++;
+        }
+        ta.first = 0; ta.count = 1;
+        hipLaunchKernelGGL(k_shared_top_root, dim3(1), dim3(kOneLaunchNodes), 0, st, ta);
+        HR_HIP(hipGetLastError());
+        launched++;
+    }
+    du.launches += launched;
+    if (mode != kRefitUpdate) du.rebuild_launches += launched;
+    return HR_OK;
+}
+
+hr_status hr::shared_device_refit_enqueue(hr_scene* s, hipStream_t st, int mode, bool predicated) { return refit_enqueue(s, st, nullptr, mode, predicated); }
+
+namespace {
+
 hr_status update_device_impl(hr_scene* s, const float* mats, const float* bounds, hipStream_t st)
 {
     static const char* call = "hr_scene_update_instances_device";
@@ -282,23 +346,23 @@ hr_status update_device_impl(hr_scene* s, const float* mats, const float* bounds
         for (int k = 0; k < 3; k++) if (bounds[k] > bounds[3 + k]) return bad(call, "world_bounds have lo > hi");
     }
     HR_HIP(hipSetDevice(s->ctx->device));
-    bool capturing = false;
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        const hipError_t ce = hipStreamIsCapturing(st, &cap);
-        if (ce != hipSuccess) (void)hipGetLastError();
-        capturing = ce != hipSuccess || cap != hipStreamCaptureStatusNone;
-        if (capturing && !bounds)
-            return bad(call, "world_bounds == NULL measures the bounds and waits for them: not possible while the stream is capturing (give the bounds)");
-    }
+    const bool capturing = stream_is_capturing(st);
+    if (capturing && !bounds)
+        return bad(call, "world_bounds == NULL measures the bounds and waits for them: not possible while the stream is capturing (give the bounds)");
     const int n_depths = (int)s->shared_depth_start.size() - 1;   // shared_device_tables_upload: checked and laid out where the top level is adopted
     if (n_depths < 1 || s->shared_depth_start[(size_t)n_depths] != (int)s->shared_top.size()) return bad(call, "the scene has no device copy of its top level");
     {
-        const hr_status e = ensure_work(s);
+        const hr_status e = shared_device_work_ensure(s);
         if (e != HR_OK) return e;
     }
     SharedDeviceUpdate& du = *s->dev_update;
-    const int I = s->n_instances, n_nodes = (int)s->shared_top.size();
+    const bool thresholded = du.threshold > 0.0f;
+    if (thresholded && !s->fixed_shape)   // a host re-build took the scene off the fixed shape since the threshold was set: back onto it first
+    {
+        const hr_status e = shared_device_rebuild_enqueue(s, st, call, false, false);
+        if (e != HR_OK) return e;
+    }
+    const int I = s->n_instances;
 
     RecordArgs ra;
     ra.mats = mats; ra.records = (InstanceShared*)s->inst_shared.p; ra.leaf_of = (const int32_t*)s->dev_leaf_of.p;
@@ -309,36 +373,11 @@ hr_status update_device_impl(hr_scene* s, const float* mats, const float* bounds
     HR_HIP(hipGetLastError());
     du.launches++;
 
-    TopArgs ta;
-    ta.top = (const SharedTopNode*)s->dev_top.p; ta.leaf_inst = (const int32_t*)s->dev_leaf_inst.p; ta.inst_box = (const float*)du.inst_box.p;
-    ta.nodes = (Node8*)s->nodes.p; ta.node_box = (float*)du.node_box.p; ta.areas = (double*)du.areas.p; ta.status = (DeviceUpdateStatus*)du.status.p;
-    ta.n_nodes = n_nodes; ta.first = 0; ta.count = n_nodes; ta.given = bounds ? 1 : 0;
-    ta.pad = bounds ? imath::pad_of_bounds(bounds, bounds + 3) : 0.0f;
-    for (int k = 0; k < 3; k++) { ta.lo[k] = ra.lo[k]; ta.hi[k] = ra.hi[k]; }
-    const int* start = s->shared_depth_start.data();   // slots are breadth-first: depth d is the slot range [start[d], start[d + 1])
-    ta.n_depths = n_depths;
-    if (n_nodes <= kOneLaunchNodes)
     {
-        int threads = 64;
-        while (threads < n_nodes) threads *= 2;
-        hipLaunchKernelGGL(k_shared_top_one, dim3(1), dim3(threads), 0, st, ta);
-        HR_HIP(hipGetLastError());
-        du.launches++;
+        const hr_status e = refit_enqueue(s, st, bounds, kRefitUpdate, false);
+        if (e != HR_OK) return e;
     }
-    else
-    {
-        for (int d = n_depths - 1; d >= 1; d--)
-        {
-            ta.first = start[d]; ta.count = start[d + 1] - start[d];
-            hipLaunchKernelGGL(k_shared_top_depth, dim3(cdiv(ta.count, 256)), dim3(256), 0, st, ta);
-            HR_HIP(hipGetLastError());
-            du.launches++;
-        }
-        ta.first = 0; ta.count = 1;
-        hipLaunchKernelGGL(k_shared_top_root, dim3(1), dim3(kOneLaunchNodes), 0, st, ta);
-        HR_HIP(hipGetLastError());
-        du.launches++;
-    }
+    du.boxes_current = true;
     du.given_bounds = bounds != nullptr;
     du.area_at_build = s->top_area_at_build;
     du.status_stale = true;
@@ -363,6 +402,8 @@ hr_status update_device_impl(hr_scene* s, const float* mats, const float* bounds
     s->info.box_pad = imath::pad_of_bounds(s->grid_lo, s->grid_hi);
     for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a]; s->info.bounds_hi[a] = s->grid_hi[a]; }
     s->geometry_epoch++;
+    // the threshold mode: the re-build rides behind every update, its launches predicated on the flag the refit above has just written
+    if (thresholded) return shared_device_rebuild_enqueue(s, st, call, true, true);
     return HR_OK;
 }
 
@@ -438,6 +479,19 @@ hr_status wait_for_device_update(const hr_scene* s)
 }
 } // namespace
 
+hr_status hr::shared_device_status_refresh(const hr_scene* s)
+{
+    SharedDeviceUpdate& du = *s->dev_update;
+    if (du.status_stale || du.captured)
+    {
+        const hr_status w = wait_for_device_update(s);
+        if (w != HR_OK) return w;
+        HR_HIP(hipMemcpy(du.status_host, du.status.p, sizeof(DeviceUpdateStatus), hipMemcpyDeviceToHost));
+        du.status_stale = false;
+    }
+    return HR_OK;
+}
+
 hr_status hr::shared_mirrors_refresh(hr_scene* s)
 {
     if (!s->mirrors_stale) return HR_OK;
@@ -448,6 +502,11 @@ hr_status hr::shared_mirrors_refresh(hr_scene* s)
     }
     s->shared_host.resize(I);
     HR_HIP(hipMemcpy(s->shared_host.data(), s->inst_shared.p, I * sizeof(InstanceShared), hipMemcpyDeviceToHost));
+    if (s->fixed_shape)   // a device re-build decides the order of the leaves where the host cannot see it
+    {
+        HR_HIP(hipMemcpy(s->shared_leaf_inst.data(), s->dev_leaf_inst.p, I * 4, hipMemcpyDeviceToHost));
+        HR_HIP(hipMemcpy(s->shared_leaf_of.data(), s->dev_leaf_of.p, I * 4, hipMemcpyDeviceToHost));
+    }
     for (size_t i = 0; i < I; i++) std::memcpy(s->inst_host[i].m, s->shared_host[(size_t)s->shared_leaf_of[i]].m, 64);
     s->mirrors_stale = s->dev_update && s->dev_update->captured;   // sticky: a replay may rewrite the records at any time
     if (s->dev_update) s->dev_update->stream_waits++;
@@ -479,15 +538,12 @@ hr_status hr_scene_device_update_status(const hr_scene* scene, float* top_cost_r
     if (scene->dev_update)
     {
         SharedDeviceUpdate& du = *scene->dev_update;
-        if (du.status_stale || du.captured)
-        {
-            const hr_status w = wait_for_device_update(scene);
-            if (w != HR_OK) return w;
-            HR_HIP(hipMemcpy(du.status_host, du.status.p, sizeof(DeviceUpdateStatus), hipMemcpyDeviceToHost));
-            du.status_stale = false;
-        }
+        const hr_status w = shared_device_status_refresh(scene);
+        if (w != HR_OK) return w;
         const DeviceUpdateStatus* hs = (const DeviceUpdateStatus*)du.status_host;
-        if (du.area_at_build > 0.0) ratio = (float)(hs->area / du.area_at_build);
+        // after a device re-build the ratio is relative to the re-built top level's sum, not to the last host build's
+        const double base = du.device_baseline ? hs->baseline : du.area_at_build;
+        if (base > 0.0) ratio = (float)(hs->area / base);
         rej = (int32_t)hs->rejected; vio = du.given_bounds ? (int32_t)hs->violated : 0;
     }
     if (top_cost_ratio) *top_cost_ratio = ratio;

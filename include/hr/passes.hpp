@@ -93,6 +93,13 @@ public:
     DeviceUpdateStatus device_update_status() const { DeviceUpdateStatus s { 1.0f, 0, 0 }; check(hr_scene_device_update_status(m_scene, &s.top_cost_ratio, &s.rejected_instances, &s.bounds_violated), "hr_scene_device_update_status"); return s; }
     DeviceUpdateStats  device_update_stats() const { DeviceUpdateStats s { 0, 0 }; check(hr_scene_device_update_stats(m_scene, &s.launches, &s.stream_waits), "hr_scene_device_update_stats"); return s; }
     void     rebuild_top_level(Stream cmd_buf) { check(hr_scene_rebuild_top_level(m_scene, cmd_buf), "hr_scene_rebuild_top_level"); }
+    // a shared scene only: the top level re-built by kernels on cmd_buf, nothing read back (the call that changes the shape — the first, or the
+    // first after rebuild_top_level() — not under stream capture); a threshold > 1 makes every update_instances_device() re-build on the device
+    // when top_cost_ratio exceeds it (0: off).  device_rebuild_status() synchronises when it lags
+    struct DeviceRebuildStatus { int64_t rebuilds_done, launches_enqueued; int32_t fixed_shape; };
+    void     rebuild_top_level_device(Stream cmd_buf) { check(hr_scene_rebuild_top_level_device(m_scene, cmd_buf), "hr_scene_rebuild_top_level_device"); }
+    void     set_device_rebuild_threshold(float ratio, Stream cmd_buf) { check(hr_scene_set_device_rebuild_threshold(m_scene, ratio, cmd_buf), "hr_scene_set_device_rebuild_threshold"); }
+    DeviceRebuildStatus device_rebuild_status() const { DeviceRebuildStatus s { 0, 0, 0 }; check(hr_scene_device_rebuild_status(m_scene, &s.rebuilds_done, &s.launches_enqueued, &s.fixed_shape), "hr_scene_device_rebuild_status"); return s; }
     // motion vectors that follow the geometry: motion_begin_frame() once per frame BEFORE that frame's update_*() calls, on their stream (the first
     // call allocates: not under stream capture), then gbuffer_raycast_motion() in the place of hr_gbuffer_raycast (dynamic scenes)
     void     motion_begin_frame(Stream cmd_buf) { check(hr_scene_motion_begin_frame(m_scene, cmd_buf), "hr_scene_motion_begin_frame"); }

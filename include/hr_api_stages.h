@@ -24,7 +24,6 @@ int32_t   hr_markers_log(char* out, int32_t capacity);   /* returns the length o
 /* Introspection (tests, tools): copies the device BVH to the host after synchronising the device — hr_scene_info.node_bytes of 80-byte nodes
  * and .tri_bytes of 48-byte triangle references (layouts: csrc/bvh.h).  Either pointer may be NULL. */
 hr_status hr_scene_read_bvh(const hr_scene* scene, void* nodes_out, void* tris_out);
-
 /* ---- RayTracedShadows: stages + introspection (ray_traced_shadows.cpp:972-1255) ------------------------------------ */
 /* Stage-level entry points (the private methods ray_trace / temporal_accumulation / a_trous_filter /
  * upsample, ray_traced_shadows.cpp:972-1255) so a multi-GPU driver can exchange halos between them.
@@ -75,7 +74,6 @@ hr_status hr_shadows_trace_stats_timed(hr_shadows* p, const hr_scene* scene, con
 /* After hr_shadows_trace_stats: sum over waves of the slowest lane's (node + triangle) steps.  SIMD lane utilisation of
  * the traversal loop = (nodes + triangles) / (64 * wave_max_steps). */
 hr_status hr_shadows_trace_divergence(hr_shadows* p, uint64_t* wave_max_steps);
-
 /* ---- RayTracedAO: stages + introspection --------------------------------------------------------------------------- */
 /* stage-level entry points: ray_trace (:863-903), temporal_accumulation (:983-1028),
  * bilateral_blur pass 0 = direction (1,0), pass 1 = (0,1) (:1032-1137), upsample (:918-955) */
@@ -95,7 +93,6 @@ hr_status hr_ao_ray_count(hr_ao* p, uint64_t* rays);
 hr_status hr_ao_trace_stats(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_ao_params* params, uint64_t* out3, void* stream);
 /* as hr_shadows_launch_order */
 hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles);
-
 /* ---- DDGI: sharding, stages + introspection ------------------------------------------------------------------------ */
 /* Multi-GPU sharding (the reference is single-GPU): this instance traces and updates only the probes
  * of grid z-slabs [probe_z0, probe_z1) — their atlas rows [1 + z0*(side+2), 1 + z1*(side+2)) are contiguous
@@ -103,7 +100,6 @@ hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles);
  * slab rows of hr_ddgi_current_write() between hr_ddgi_probe_update and hr_ddgi_sample_probe_grid. */
 hr_status hr_ddgi_set_shard(hr_ddgi* p, int32_t probe_z0, int32_t probe_z1, int32_t row_y0, int32_t row_y1);
 hr_status hr_ddgi_current_write(hr_ddgi* p, hr_image_view* irradiance, hr_image_view* depth);
-
 /* ---- DDGI: stages -------------------------------------------------------------------------------------------------- */
 /* stage-level entry points (ddgi.cpp:767-986); probe range [probe0, probe1) lets a multi-GPU driver
  * split G1-G4 by z-slab and all-gather the atlas rows */
@@ -120,7 +116,6 @@ hr_status hr_ddgi_get_uniforms(hr_ddgi* p, hr_ddgi_uniforms* out);
 hr_status hr_ddgi_set_profiling(hr_ddgi* p, int32_t enable);
 hr_status hr_ddgi_get_stage_times(hr_ddgi* p, hr_stage_times* out);
 hr_status hr_ddgi_ray_count(hr_ddgi* p, uint64_t* rays);
-
 /* ---- RayTracedReflections: stages + introspection ------------------------------------------------------------------ */
 /* stage-level entry points: ray_trace (:997-1057), temporal_accumulation (:1087-1139), a_trous_filter iteration (:1143-1256), upsample (:1260-1296) */
 hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_environment* env, hr_ddgi* ddgi,
@@ -143,7 +138,6 @@ hr_status hr_reflections_history_apron_exceeded(hr_reflections* p, int32_t* exce
 hr_status hr_reflections_set_profiling(hr_reflections* p, int32_t enable);
 hr_status hr_reflections_get_stage_times(hr_reflections* p, hr_stage_times* out);
 hr_status hr_reflections_ray_count(hr_reflections* p, uint64_t* rays);
-
 /* ---- the frame (src/main.cpp:80-83) ------------------------------------------------------------------------------- */
 /* The reference records shadows, AO, DDGI and reflections into ONE command buffer with per-resource barriers, so the GPU overlaps the
  * independent chains.  hr_hybrid_frame gives a HIP host the same: the four render() calls of a frame enqueued as the dependency graph
@@ -186,7 +180,6 @@ hr_status hr_hybrid_frame_destroy(hr_hybrid_frame* f);
  * `out` (may be NULL with capacity 0 to ask for the count).  For tests that aim rays at box faces, edges and corners. */
 typedef struct { float lo[3], hi[3], step[3]; int32_t node, slot, depth, is_leaf; } hr_child_box;
 hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes);
-
 /* ---- shared instanced scenes (added within revision 6, docs/API_HISTORY.md): every mesh's object-space BVH is stored ONCE and walked on two levels
  * (DESIGN.md section 2).  Device memory: 80 x (mesh nodes + max(1, n_instances)) + 48 x mesh references + 160 per instance.  Same desc and answers, bit
  * for bit, as hr_scene_create_instanced; update_instances / rebuild_top_level: host work over the instances + two copies; get_info: conservative bounds.
@@ -214,6 +207,13 @@ hr_status hr_scene_update_meshes(hr_scene* scene, const hr_mesh_update* updates,
 hr_status hr_scene_mesh_refit_cost(const hr_scene* scene, uint32_t mesh_idx, float* ratio);
 hr_status hr_scene_update_meshes_stats(const hr_scene* scene, int64_t* level_launches, int64_t* top_launches, int64_t* stream_waits); hr_status hr_scene_read_instance_records(const hr_scene* scene, void* records_out);
 /* ---- device-side instance update of a shared scene (added within revision 6): update_instances_device refits the STANDING top level (never re-builds it) and rewrites the records from DEVICE matrices, kernels only on `stream`; world_bounds given: no host wait, no copy, no allocation after the first call, legal under stream capture (a replay reads the matrix buffer as it then stands); NULL: measured on the GPU, ONE wait, HR_ERR_INVALID_ARG while capturing.  HR_ERR_INVALID_ARG before anything is enqueued: not a shared scene, NULL matrices, bounds not finite or lo > hi.  A non-finite matrix keeps its instance's previous record and box (rejected_instances); bounds that were too small (bounds_violated) can cost hits, never an out-of-range access.  device_update_status synchronises when it lags; top_cost_ratio: top-level half-area sum now / at its last build (the host path re-builds beyond 1.5: hr_scene_rebuild_top_level).  The next host call on the scene (update_instances, rebuild_top_level, update_meshes) first reads the matrices back: one wait; once an update has been captured, every host call and every status call does (replays run unseen). */ hr_status hr_scene_update_instances_device(hr_scene* scene, const float* model_matrices /* DEVICE [n_instances][16], column-major */, const float* world_bounds /* HOST lo xyz hi xyz, conservative for the whole scene after this update, or NULL */, void* stream); hr_status hr_scene_device_update_status(const hr_scene* scene, float* top_cost_ratio, int32_t* rejected_instances, int32_t* bounds_violated); hr_status hr_scene_device_update_stats(const hr_scene* scene, int64_t* launches, int64_t* stream_waits);   /* tests, tools */
+/* ---- device re-build of a shared scene's top level (added within revision 6): kernels only on `stream`, nothing read back.  The shape becomes a function of the instance count (hr_shared_top_fixed_shape), the leaves are ordered by hr_shared_top_sort_keys over the boxes and bounds of the last update.  The call that CHANGES the shape (the first one, or the first after hr_scene_rebuild_top_level) uploads a table: HR_ERR_INVALID_ARG while capturing; from then on the call may be captured (the AO pass then rebuilds its entry table at every render of the scene).
+ * set_device_rebuild_threshold: 0 = off (default); ratio > 1: onto the fixed shape at once (same capture rule), then every update_instances_device enqueues the re-build behind its refit, predicated on a device flag set when top_cost_ratio > ratio (4 more launches per update up to 4096 instances, 16 above).  After a device re-build top_cost_ratio is relative to the re-built tree (1.0 until something moves); hr_scene_top_level_rebuilds counts host re-builds only.
+ * device_rebuild_status: re-builds that RAN (counted on the device; synchronises when it lags), launches enqueued for them, whether the scene has the fixed shape.  HR_ERR_INVALID_ARG: not a shared scene.  After HR_ERR_HIP from a re-build the top level is undefined until a re-build of either kind succeeds. */
+hr_status hr_scene_rebuild_top_level_device(hr_scene* scene, void* stream);
+hr_status hr_scene_set_device_rebuild_threshold(hr_scene* scene, float ratio, void* stream);
+hr_status hr_scene_device_rebuild_status(const hr_scene* scene, int64_t* rebuilds_done, int64_t* launches_enqueued, int32_t* fixed_shape);
+hr_status hr_shared_top_fixed_shape(int32_t n_instances, void* nodes_out, int64_t capacity, int32_t* n_nodes, int32_t* n_depths); hr_status hr_shared_top_sort_keys(const float* inst_boxes, int32_t n, const float bounds[6], uint64_t* keys_out);   /* host only (tests, tools): the fixed shape's 24-byte records { n_internal, n_leaves, child_base, leaf_base, axis, depth }, breadth-first (nodes_out NULL: the counts only); the 64-bit sort keys (30-bit Morton code << 32 | instance) of n boxes (lo xyz hi xyz) inside bounds */
 #ifdef __cplusplus
 }
 #endif

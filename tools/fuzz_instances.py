@@ -15,7 +15,10 @@ and the private-copy scene, and GB2 (normal + motion vector) and depth equal to 
 --device (implies --shared; also with --deform): every matrix update of the scene under test goes through hr_scene_update_instances_device —
 the matrices uploaded first, the scene's bounds measured on the GPU or, every other time, given (the instances' transformed mesh bounds, widened) — so the forced
 top-level re-builds and the mesh updates that follow exercise the read-back of the host mirrors; after every step the status must report no
-rejected matrix and no violated bound."""
+rejected matrix and no violated bound.
+--device-rebuild (implies --device): a device re-build of the top level (hr_scene_rebuild_top_level_device) after a random subset of the device
+updates, and a re-build threshold (hr_scene_set_device_rebuild_threshold, 1.2 to 2) on a random half of the scenes; the forced HOST re-builds
+stay in, so the scenes go back and forth between the SAH shape and the fixed one."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,8 +36,11 @@ if MOTION:
     sys.argv.remove("--motion")
     if DEFORM:
         sys.exit("--motion compares with a private-copy scene, which cannot deform: not with --deform")
-DEVICE = "--device" in sys.argv
-if DEVICE:
+DEVICE_REBUILD = "--device-rebuild" in sys.argv
+if DEVICE_REBUILD:
+    sys.argv.remove("--device-rebuild")
+DEVICE = "--device" in sys.argv or DEVICE_REBUILD
+if "--device" in sys.argv:
     sys.argv.remove("--device")
 SHARED = "--shared" in sys.argv or DEFORM or DEVICE
 if "--shared" in sys.argv:
@@ -91,6 +97,8 @@ def update(g, isd, mats):
     st = g.device_update_status()
     if st["rejected_instances"] or st["bounds_violated"]:
         raise RuntimeError(f"device update status {st}")
+    if DEVICE_REBUILD and rng.rand() < 0.4:
+        g.rebuild_top_level_device()
 
 
 bad = 0
@@ -115,6 +123,8 @@ for trial in range(n):
     try:
         flags = [int(DEFORM and k > 0 and m.n_tris < 5000 and rng.rand() < 0.6) for k, m in enumerate(meshes)]
         g = hr.InstancedScene(ctx, isd, shared=True, deformable=flags if DEFORM else None) if SHARED else hr.InstancedScene(ctx, isd)
+        if DEVICE_REBUILD and rng.rand() < 0.5:
+            g.set_device_rebuild_threshold(float(rng.uniform(1.2, 2.0)))
         mats = isd.matrices().copy()
         cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
         mg = [hr.InstancedScene(ctx, isd, shared=True), hr.InstancedScene(ctx, isd), hr.Scene(ctx, isd.flatten(), deformable=True)] if MOTION else []
@@ -226,7 +236,7 @@ for trial in range(n):
             torch.cuda.synchronize()
             if not np.array_equal(helpers.bits16(gr.image(gr.IMG_TRACE)), orr.stages["trace"]): msg.append("reflections trace image differs from the oracle")
             for p in (gs, gd, gr): p.close()
-        rb = g.top_level_rebuilds
+        rb = g.top_level_rebuilds if not DEVICE_REBUILD else f"{g.top_level_rebuilds} host + {g.device_rebuild_status()['rebuilds_done']} device"
         g.close()
         for s_ in mg: s_.close()
     except Exception as e:

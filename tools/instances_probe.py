@@ -18,7 +18,14 @@ mean [min, max]; masks, radiance and trace images must be equal.
 frames is reported: the host path twice (`host_ms`, `host_ms_again`: their difference is the run-to-run spread), the device path with the bounds
 given and with the bounds measured; then the same frames back to back without waiting in between (what the calling thread pays per frame).
 Any-hit answers of 20 000 rays must agree after the last frame.  --host-only: the host path's numbers alone (a library built from a revision
-that does not have the device path, selected with HR_LIBRARY)."""
+that does not have the device path, selected with HR_LIBRARY).
+--shared --device-rebuild: what hr_scene_rebuild_top_level_device costs.  Per size of synth.instanced_cornell (70, 600, 3300, 4096 boxes: the
+last one instance above the one-workgroup sort's limit), medians over `--reps` calls timed one by one (call, then wait for the stream) after a
+warm-up: the device re-build; hr_scene_rebuild_top_level on a twin that has just taken a device update (so its wall time includes the read-back
+it needs); a device update with the threshold off and with a threshold that never fires (what the predicated launches add to a frame on which
+nothing is re-built), one by one and back to back.  Then, on the scene of main() after `--frames` frames of motion through device updates: the
+shadows trace stage on the device-built top level against a fresh host SAH top level over the same matrices (masks must be equal), and the
+ratio of their half-area sums (numpy, over the nodes and records read back: top_area_np below)."""
 import argparse, json, math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,6 +42,8 @@ def main():
     ap.add_argument("--deform", action="store_true", help="hr_scene_update_meshes on a shared scene with deforming meshes")
     ap.add_argument("--passes", action="store_true", help="with --shared: AO / DDGI / reflections trace stages, shared against private copies")
     ap.add_argument("--device", action="store_true", help="with --shared: hr_scene_update_instances_device against the host update, per frame")
+    ap.add_argument("--device-rebuild", action="store_true", help="with --shared: hr_scene_rebuild_top_level_device against the host re-build, and the trace on either tree")
+    ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--host-only", action="store_true", help="with --shared --device: time the host path alone")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--meshes", type=int, default=16)
@@ -43,6 +52,9 @@ def main():
     a = ap.parse_args()
     if a.deform:
         return deform_probe(a)
+    if a.device_rebuild:
+        assert a.shared, "--device-rebuild times the device re-build of a shared scene's top level: give --shared"
+        return rebuild_probe(a)
     if a.device:
         assert a.shared, "--device times the device-side update of a shared scene: give --shared"
         return device_probe(a)
@@ -174,6 +186,157 @@ def device_probe(a):
         rd = torch.from_numpy(r).cuda()
         assert np.array_equal(g_host.any_hit(rd).cpu().numpy(), g_dev.any_hit(rd).cpu().numpy()), "any-hit answers differ between the host- and the device-updated scene"
         res["answers_equal"] = True
+    print(json.dumps(res))
+
+
+def instance_boxes_np(isd, mats):
+    """csrc/instance_math.h world_box: the eight corners of the mesh's bounds in fp64, widened by 1e-6 of their magnitude, rounded outward to fp32"""
+    out = np.zeros((len(mats), 6), np.float32)
+    for i, ((_, k, _), m) in enumerate(zip(isd.instances, np.asarray(mats, np.float32).reshape(-1, 16))):
+        m = m.astype(np.float64)
+        if isd.meshes[k].n_tris == 0:
+            l = h = m[12:15]
+        else:
+            lo, hi = [b.astype(np.float64) for b in isd.meshes[k].bounds()]
+            l, h = np.full(3, 1e300), np.full(3, -1e300)
+            for c in range(8):
+                p = [(hi if (c >> a) & 1 else lo)[a] for a in range(3)]
+                v = m[0:3] * p[0] + m[4:7] * p[1] + m[8:11] * p[2] + m[12:15]
+                e = 1e-6 * (np.abs(m[0:3] * p[0]) + np.abs(m[4:7] * p[1]) + np.abs(m[8:11] * p[2]) + np.abs(m[12:15]))
+                l, h = np.minimum(l, v - e), np.maximum(h, v + e)
+        lo32, hi32 = l.astype(np.float32), h.astype(np.float32)
+        out[i, :3] = np.where(lo32.astype(np.float64) > l, np.nextafter(lo32, np.float32(-np.inf)), lo32)
+        out[i, 3:] = np.where(hi32.astype(np.float64) < h, np.nextafter(hi32, np.float32(np.inf)), hi32)
+    return out
+
+
+def top_area_np(isd, mats, nodes, records, pad):
+    """sum over a shared scene's top-level nodes of the half area of the box of their children (leaves: instance box -+ pad in fp32); the
+    topology from the nodes (csrc/bvh.h Node8: counts, child_base, tri_base), the leaves' instances from the records (byte 140)"""
+    boxes, pad = instance_boxes_np(isd, mats), np.float32(pad)
+    inst_of_leaf = records[:, 140:144].copy().view(np.uint32)[:, 0]
+    kids, order, at = {}, [0], 0
+    while at < len(order):
+        n = nodes[order[at]]
+        n_int, nc = int(n[15]) & 15, int(n[15]) >> 4
+        child_base, leaf_base = int(n[16:20].copy().view(np.uint32)[0]), int(n[20:24].copy().view(np.uint32)[0])
+        kids[order[at]] = ([child_base + c for c in range(n_int)], [leaf_base + j for j in range(nc - n_int)])
+        order += kids[order[at]][0]
+        at += 1
+    box, total = {}, 0.0
+    for slot in reversed(order):
+        lo, hi = np.full(3, np.inf, np.float32), np.full(3, -np.inf, np.float32)
+        for c in kids[slot][0]:
+            lo, hi = np.minimum(lo, box[c][0]), np.maximum(hi, box[c][1])
+        for l in kids[slot][1]:
+            lo, hi = np.minimum(lo, boxes[inst_of_leaf[l]][:3] - pad), np.maximum(hi, boxes[inst_of_leaf[l]][3:] + pad)
+        box[slot] = (lo, hi)
+        d = hi.astype(np.float64) - lo.astype(np.float64)
+        total += d[0] * d[1] + d[1] * d[2] + d[2] * d[0]
+    return total, len(order)
+
+
+def rebuild_probe(a):
+    import torch
+    from hybrid_rendering_amd import api as hr, synth
+    _mats = lambda isd, n_boxes, seed, frame: synth.InstancedSceneData(isd.meshes, synth.instanced_cornell_instances(n_boxes, seed=seed, frame=frame), isd.materials).matrices()
+    ctx = hr.Context(0)
+    cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+
+    def one_by_one(fn, reps, before=None):
+        out = []
+        for k in range(reps + 5):   # 5 warm-up calls
+            if before:
+                before(k)
+                torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(k)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return round(float(np.median(out[5:])), 4)
+
+    def back_to_back(fn, reps):
+        for k in range(5):
+            fn(k)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(reps):
+            fn(k)
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) / reps * 1e3, 4)
+    res = dict(kind="shared, device re-build of the top level", reps=a.reps, sizes={})
+    bounds = np.array([-20, -20, -20, 130, 130, 130], np.float32).reshape(2, 3)
+    for n_boxes in (70, 600, 3300, 4096):
+        isd = synth.instanced_cornell(n_boxes, seed=4)
+        dev = [cuda(_mats(isd, n_boxes, 4, f)) for f in (88, 89, 90, 91)]
+        g, twin = hr.InstancedScene(ctx, isd, shared=True), hr.InstancedScene(ctx, isd, shared=True)
+        g.update_device(dev[0], bounds=bounds)
+        r = dict(top_level_nodes=len(hr.shared_top_fixed_shape(n_boxes + 1)[0]))
+        r["device_rebuild_ms"] = one_by_one(lambda k: g.rebuild_top_level_device(), a.reps, before=lambda k: g.update_device(dev[k & 3], bounds=bounds))
+        r["host_rebuild_after_device_update_ms"] = one_by_one(lambda k: twin.rebuild_top_level(), max(10, a.reps // 5), before=lambda k: twin.update_device(dev[k & 3], bounds=bounds))
+        g.set_device_rebuild_threshold(0.0)
+        r["update_ms_threshold_off"] = one_by_one(lambda k: g.update_device(dev[k & 3], bounds=bounds), a.reps)
+        r["update_ms_threshold_off_back_to_back"] = back_to_back(lambda k: g.update_device(dev[k & 3], bounds=bounds), a.reps)
+        launches = g.device_update_stats()["launches"]
+        g.set_device_rebuild_threshold(1e6)
+        before = g.device_rebuild_status()["rebuilds_done"]
+        r["update_ms_threshold_never_fires"] = one_by_one(lambda k: g.update_device(dev[k & 3], bounds=bounds), a.reps)
+        r["update_ms_threshold_never_fires_back_to_back"] = back_to_back(lambda k: g.update_device(dev[k & 3], bounds=bounds), a.reps)
+        assert g.device_rebuild_status()["rebuilds_done"] == before
+        r["update_ms_off_again"] = (g.set_device_rebuild_threshold(0.0), one_by_one(lambda k: g.update_device(dev[k & 3], bounds=bounds), a.reps))[1]
+        res["sizes"][n_boxes + 1] = r
+        g.close(); twin.close()
+    # the trace on either tree
+    W, H = a.width, a.height
+    building = synth.sponza_like(a.detail)
+    small = synth.instanced_cornell(2)
+    cube, pyr = small.meshes[1], small.meshes[2]
+    lo, hi = building.bounds()
+    rng = np.random.RandomState(1)   # the scene and the motion of main()
+    base = [(rng.uniform(lo + 0.15 * (hi - lo), hi - 0.15 * (hi - lo)), rng.uniform(-1, 1, 3), rng.uniform(0, 6.28), rng.uniform(6, 30, 3), rng.uniform(-2, 2, 3)) for _ in range(a.movers)]
+    inst = lambda f: [(synth.model_matrix(), 0, 1)] + [(synth.model_matrix(p + vel * f, ax, ang + 0.05 * f, sc), 1 + (i & 1), 2 + i) for i, (p, ax, ang, sc, vel) in enumerate(base)]
+    isd = synth.InstancedSceneData(meshes=[building, cube, pyr], instances=inst(0), materials=building.materials)
+    mats = synth.InstancedSceneData(isd.meshes, inst(a.frames), isd.materials).matrices()
+    scenes = dict(stale=hr.InstancedScene(ctx, isd, shared=True), device_built=hr.InstancedScene(ctx, isd, shared=True), host_sah=hr.InstancedScene(ctx, isd, shared=True))
+    for sc_ in scenes.values():
+        sc_.update_device(cuda(mats))
+    scenes["device_built"].rebuild_top_level_device()
+    scenes["host_sah"].rebuild_top_level()
+    top = a.movers + 1
+    area = {tag: top_area_np(isd, mats, sc_.read_bvh()[0][:top], sc_.read_records(), sc_.refresh_info().box_pad)[0] for tag, sc_ in scenes.items()}
+    light = synth.sponza_light()
+    cams = [synth.sponza_camera(W / H, frame=f, dolly=0.5) for f in range(2)]
+    ubo = synth.make_ubo(cams[1], cams[0], light)
+    sob, sr = synth.blue_noise_tables()
+    sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
+    gb = scenes["host_sah"].gbuffer(ubo, W, H)
+    fi = hr.frame_inputs(gb, gb, ubo, 0, 0, sob_d, sr_d)
+    passes = {tag: hr.RayTracedShadows(ctx, W, H) for tag in scenes}
+    for p in passes.values():
+        p.params.exact = 0
+    for tag, p in passes.items():
+        for k in range(6):
+            fi.num_frames = k
+            p.render(scenes[tag], fi)
+    torch.cuda.synchronize()
+    rounds = {tag: [] for tag in scenes}
+    for r_ in range(a.rounds):   # alternating rounds of 10 profiled frames: every tree sees the same neighbours on the machine
+        for tag, p in passes.items():
+            p.set_profiling(True)
+            p.stage_times()
+            for k in range(6 + 10 * r_, 16 + 10 * r_):
+                fi.num_frames = k
+                p.render(scenes[tag], fi)
+            torch.cuda.synchronize()
+            rounds[tag].append(dict((s_, ms) for s_, ms, _ in p.stage_times())["ray_trace"])
+            p.set_profiling(False)
+    masks = {tag: p.image(p.IMG_MASK).cpu().numpy().copy() for tag, p in passes.items()}
+    assert all(np.array_equal(m, masks["host_sah"]) for m in masks.values()), "masks differ between the top levels"
+    res["trace"] = dict(width=W, height=H, instances=top, frames_of_motion=a.frames, masks_equal=True, rounds=a.rounds,
+                        half_area_sum={k: round(v, 1) for k, v in area.items()},
+                        half_area_device_built_over_host_sah=round(area["device_built"] / area["host_sah"], 4), half_area_stale_over_host_sah=round(area["stale"] / area["host_sah"], 4))
+    for tag, v in rounds.items():
+        res["trace"][f"shadow_trace_ms_{tag}"] = [round(float(np.mean(v)), 4), round(min(v), 4), round(max(v), 4)]
     print(json.dumps(res))
 
 
