@@ -978,7 +978,7 @@ static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, 
         {
             mo.prev_mats = (const float*)scene->prev_mats.p;
             mo.inst = (const InstanceRec*)scene->inst_records.p; mo.tri_instance = (const uint32_t*)scene->tri_instance.p;
-            mo.mesh_positions = (const float*)(scene->shared_deform ? scene->prev_positions.p : scene->mesh_positions.p);
+            mo.mesh_positions = (const float*)(scene->deform ? scene->prev_positions.p : scene->mesh_positions.p);
         }
         else mo.prev_verts = (const float*)scene->prev_positions.p;
     }
@@ -1043,9 +1043,9 @@ hr_status hr_scene_motion_begin_frame(hr_scene* scene, void* stream)
         if (s->shared) hipLaunchKernelGGL(k_motion_snapshot_shared, dim3(cdiv(I * 16, 256)), dim3(256), 0, st, (const InstanceShared*)s->inst_shared.p, (float*)s->prev_mats.p, I);
         else hipLaunchKernelGGL(k_motion_snapshot_private, dim3(cdiv(I * 16, 256)), dim3(256), 0, st, (const InstanceRec*)s->inst_records.p, (float*)s->prev_mats.p, I);
         HR_HIP(hipGetLastError());
-        if (s->shared_deform)
+        if (s->deform)
         {
-            const hr::SharedDeform& sd = *s->shared_deform;
+            const hr::DeformRefit& sd = *s->deform;
             if (first)
             {
                 // the whole array once (the kernel indexes it like mesh_positions); afterwards only the meshes that can change

@@ -92,11 +92,11 @@ hr_status shared_device_tables_upload(hr_scene* s, hipStream_t st, bool all);
 hr_status shared_device_mesh_table_upload(hr_scene* s, hipStream_t st);
 hr_status shared_mirrors_refresh(hr_scene* s);
 // instances_shared_deform.hip: what hr_scene_update_meshes needs, for a shared scene that holds the uploaded trees `blas` (flagged meshes built
-// without spatial splits): level lists, triangle -> reference map, node_box and the cost of every flagged tree as built.  Synchronous, like creation.
+// without spatial splits): deform_refit.h deform_refit_adopt over all meshes.  Synchronous, like creation.
 hr_status shared_deform_adopt(hr_scene* s, const std::vector<BuiltBVH>& blas, const int32_t* mesh_n_tris, const uint8_t* flags);
 // api.hip: hr_scene_create (deformable = false) and hr_scene_create_deformable (the builder runs without spatial splits, then deformable_scene_adopt)
 hr_status scene_create_flat(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable);
-// deform.hip: what a refit needs, for a scene that holds the uploaded tree `b`; the exact bounds of the last hr_scene_update_vertices, read back on demand
+// deform.hip: what a refit needs, for a scene that holds the uploaded tree `b` (deform_refit.h deform_refit_adopt of one mesh); the exact bounds of the last hr_scene_update_vertices, read back on demand
 hr_status deformable_scene_adopt(hr_scene* s, const BuiltBVH& b);
 hr_status deformable_scene_refresh_bounds(const hr_scene* scene);
 
@@ -151,29 +151,30 @@ struct DevBuf
     DevBuf& operator=(const DevBuf&) = delete;
 };
 
-// What hr_scene_update_meshes keeps for a scene from hr_scene_create_instanced_shared_deformable (instances_shared_deform.hip).  Everything is
-// indexed by mesh; an unflagged mesh has no levels, no partials and -1 in tri_ref.
-struct SharedDeform
+// What the refit of split-free trees under new vertices keeps (deform_refit.hip) for a scene from hr_scene_create_deformable (one flagged mesh:
+// the scene) or hr_scene_create_instanced_shared_deformable.  Everything is indexed by mesh; an unflagged mesh has no levels, no partials and -1
+// in tri_ref.
+struct DeformRefit
 {
     std::vector<uint8_t>  flag;                   // per mesh: may be updated
-    std::vector<uint32_t> ref_base, tri_base;     // per mesh: its first reference in `tris` / first triangle in the mesh_* attribute arrays
+    std::vector<uint32_t> root, ref_base, tri_base;   // per mesh: its root in `nodes` / first reference in `tris` / first triangle in the attribute arrays
+    std::vector<float>    pad;                    // per mesh: the leaf pad its builder used
     std::vector<int32_t>  n_tris;
     std::vector<int32_t>  n_levels, d_top;        // per mesh: levels of its tree / deepest level the one-workgroup launch takes (-1: unflagged)
     std::vector<int32_t>  partial_base, n_partials;
     std::vector<double>   cost_at_build;
-    std::vector<uint8_t>  cost_known;             // per mesh: cost_ratio is that of the last update
+    std::vector<uint8_t>  cost_known;             // per mesh: cost_ratio is that of the last update (0: it lags until the slots are read back)
     std::vector<double>   cost_ratio;
     DevBuf   level_nodes;                         // the flagged meshes' level lists, GLOBAL node indices
-    std::vector<int32_t> levels_host;             // host copy of `levels`
-    DevBuf   levels;                              // per mesh two rows of kMaxTraversalDepth + 2 ints: offsets into level_nodes, first partial slot of the level
-    DevBuf   mesh;                                // per mesh: MeshDev (instances_shared_deform.hip)
-    DevBuf   tri_ref;                             // per mesh triangle (concatenated): global index of its one reference, -1: none
+    std::vector<int32_t> levels_host;             // per mesh two rows of kMaxTraversalDepth + 2 ints: offsets into level_nodes, first partial slot of the level
+                                                  // (they reach the kernels in their arguments)
+    DevBuf   tri_ref;                             // per mesh triangle (concatenated): global index of its one reference, -1: none (not finite when built)
     DevBuf   partials;                            // per refit workgroup: sum of its nodes' half areas (double)
     DevBuf   root_box;                            // per mesh 8 floats: the refitted root box (lo xyz, 0, hi xyz, 0)
     DevBuf   outside;                             // per mesh one word: the bounds given with the last update do not contain the refitted root box
     float*   root_box_host = nullptr;             // pinned, per mesh 8 floats
     int64_t  level_launches = 0, top_launches = 0, stream_waits = 0;   // what the updates so far enqueued (hr_scene_update_meshes_stats)
-    ~SharedDeform() { if (root_box_host) (void)hipHostFree(root_box_host); }
+    ~DeformRefit() { if (root_box_host) (void)hipHostFree(root_box_host); }
 };
 
 // What hr_scene_update_instances_device keeps (instances_shared_update.hip); allocated by the first call, never after
@@ -381,7 +382,6 @@ struct hr_scene
     std::vector<uint32_t> shared_mesh_root;       // per mesh: node index of its root
     int           shared_mesh_depth = 0;          // deepest mesh tree (levels below its root)
     std::vector<float>    shared_mesh_pad;        // per mesh: the leaf pad its builder used
-    std::unique_ptr<hr::SharedDeform> shared_deform;   // set by hr_scene_create_instanced_shared_deformable only
     // hr_scene_update_instances_device (instances_shared_update.hip): device copies of the top level's topology and of what a record is made
     // from, written at creation and wherever the host adopts a top level or new mesh bounds; `work` is allocated by the first device update
     hr::DevBuf    dev_top, dev_leaf_inst, dev_leaf_of, dev_inst_mesh, dev_mesh_tab;
@@ -393,13 +393,11 @@ struct hr_scene
     bool          order_replayed = false;         // a device re-build was CAPTURED: replays re-order the leaves where geometry_epoch cannot follow, so
                                                   // caches of the passes that hold top-level node indices (AO's entry table) are rebuilt at every use
     bool          mirrors_stale = false;          // a device update ran: inst_host / inst_box / top_nodes_host / shared_host lag the device
-    // ---- deformable scenes (deform.hip): a flat scene built without spatial splits; hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`
-    // and refits `nodes` through level_nodes / level_offsets / node_box (the arrays of the instanced scenes' refit)
+    // ---- deforming geometry (deform_refit.hip): trees built without spatial splits, refitted under new vertices through `deform` and node_box.
+    // deform.hip: a flat scene (`deformable`); hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`.  instances_shared_deform.hip: the
+    // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
+    std::unique_ptr<hr::DeformRefit> deform;      // set by hr_scene_create_deformable and hr_scene_create_instanced_shared_deformable only
     bool          deformable = false;
-    hr::DevBuf    tri_ref, cost_partials;         // per original triangle: index of its one reference (-1: none); per refit workgroup: sum of its nodes' half areas
-    int           n_cost_partials = 0;
-    double        cost_at_build = 0.0, cost_ratio = 1.0;   // the sum of the slots when the tree was built / last ratio read back
-    bool          cost_stale = false;             // cost_ratio lags the last update until hr_scene_refit_cost reads the slots back
     mutable bool  bounds_stale = false;           // info.bounds_* lag the last update until hr_scene_get_info reads them back
     // ---- motion vectors (api.hip hr_scene_motion_begin_frame / hr_gbuffer_raycast_motion): the geometry as of the last begin_frame, indexed by
     // instance or by triangle, never by BVH reference — rebuilds, top-level re-builds and refits leave it alone

@@ -1,5 +1,6 @@
 // The bottom-up refit of one 8-wide node, shared by the instanced scenes (instances.hip: subtrees under moving matrices, leaves cut to their
-// object-space cells) and the deformable scenes (deform.hip: new vertices, no instance, no cells, no dirty filter).  A thread recomputes the boxes
+// object-space cells) and the refit of split-free trees under new vertices (deform_refit.hip, for the flat deformable scenes of deform.hip and the
+// deforming meshes of instances_shared_deform.hip: no instance, no cells, no dirty filter).  A thread recomputes the boxes
 // of the node's eight children (internal children: the box their own thread stored one launch — or one barrier — earlier; leaves: the bounds of
 // their triangles plus the pad), the node's origin / scale exponents, and requantises: the encoding rules of bvh_build.cpp, in double like there.
 #pragma once

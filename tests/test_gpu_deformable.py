@@ -1,5 +1,5 @@
 """Deformable scenes on the GPU (hr_scene_create_deformable / hr_scene_update_vertices / hr_scene_refit_cost / hr_scene_rebuild: csrc/deform.hip,
-csrc/refit.h).  The contract needs no tolerance: any-hit is a function of the triangle set, closest hit is the smallest t with ties to the smallest
+csrc/deform_refit.hip, csrc/refit.h).  The contract needs no tolerance: any-hit is a function of the triangle set, closest hit is the smallest t with ties to the smallest
 triangle index, so a refitted tree answers bit for bit like hr_scene_create over the same vertices and like brute force; a refit with the creation
 vertices reproduces the builder's node bytes, which pins the refit's encoding to bvh_build.cpp's."""
 import numpy as np
@@ -198,6 +198,67 @@ def test_sub_range_updates(hr, ctx):
     (nb, tb) = b.read_bvh()
     assert np.array_equal(na, nb) and np.array_equal(ta, tb)
     assert list(a.refresh_info().bounds_lo) == list(b.refresh_info().bounds_lo)
+    a.close(); b.close()
+
+
+def level_widths(nodes):
+    """nodes per depth of a tree read back by read_bvh(): children follow their parent in the builder's breadth-first order"""
+    n_internal, child_base = nodes[:, 15] & 15, nodes[:, 16:20].copy().view(np.uint32)[:, 0]
+    depth = np.zeros(len(nodes), np.int64)
+    for j in range(len(nodes)):
+        depth[int(child_base[j]):int(child_base[j]) + int(n_internal[j])] = depth[j] + 1
+    return np.bincount(depth).tolist()
+
+
+def test_a_flat_scene_and_a_one_mesh_shared_scene_refit_alike(hr, ctx):
+    """One refit engine (csrc/deform_refit.hip) under two front ends: the same heightfield as a flat deformable scene (levels of up to 512 nodes in
+    the one-workgroup launch) and as the only, flagged mesh of a shared instanced scene under one identity instance (up to 32).  heightfield(86) is
+    the smallest whose split-free tree (levels of 1, 8, 64, 512, 515 and 2 nodes) has a level wider than 512 AND one of 33 to 512, so the per-level
+    kernel and the one-workgroup kernel both run in both scenes and split the levels differently.  After every step the flat scene's nodes equal
+    the mesh's subtree byte for byte (child_base of a node with internal children: less the subtree's root index), the references are equal, and
+    the two cost ratios — double sums of the same half areas in different workgroup partitions, which agree to about n_nodes * 2^-53 relative,
+    far below the 2^-24 of the rounding to float that follows the division — lie at most one float ulp apart; the creation vertices give exactly 1.0."""
+    sd0 = synth.heightfield(86)
+    isd = synth.InstancedSceneData(meshes=[sd0], instances=[(np.eye(4, dtype=F32).reshape(16), 0, 1)], materials=sd0.materials)
+    a, b = hr.Scene(ctx, sd0, deformable=True), hr.InstancedScene(ctx, isd, shared=True, deformable=[1])
+    widths = level_widths(a.read_bvh()[0])
+    print(f"{sd0.n_tris} triangles, nodes per level {widths}")
+    assert max(widths) > 512 and any(33 <= w <= 512 for w in widths), widths
+    root = len(b.read_bvh()[0]) - len(a.read_bvh()[0])
+    assert root >= 1
+
+    def both(sd, first=0, count=None):
+        count = sd.n_tris - first if count is None else count
+        update(a, sd, first=first, count=count)
+        b.update_meshes([dict(mesh_idx=0, positions=cuda(sd.verts[first:first + count]), normals=cuda(sd.normals[first:first + count]), first_tri=first)])
+
+    def compare(what):
+        (na, ta), (nb, tb) = a.read_bvh(), b.read_bvh()
+        nb = nb[root:].copy()
+        shifted = nb[:, 16:20].copy().view(np.uint32) - np.where(nb[:, 15:16] & 15, np.uint32(root), np.uint32(0)).astype(np.uint32)
+        nb[:, 16:20] = shifted.view(np.uint8)
+        diff = np.flatnonzero((na != nb).any(1))
+        assert len(diff) == 0, f"{what}: {len(diff)} of {len(na)} nodes differ between the two scenes, first {diff[:4]}"
+        assert np.array_equal(ta, tb), f"{what}: the references differ"
+        ca, cb = np.float32(a.refit_cost()), np.float32(b.mesh_refit_cost(0))
+        print(f"{what}: cost ratio flat {ca!r}, shared {cb!r}")
+        assert abs(int(ca.view(np.int32)) - int(cb.view(np.int32))) <= 1, (what, ca, cb)
+        return na, ca, cb
+
+    built, ca, cb = compare("as built")
+    assert ca == 1.0 and cb == 1.0
+    both(sd0)
+    nodes, ca, cb = compare("the creation vertices")
+    assert np.array_equal(nodes, built) and ca == 1.0 and cb == 1.0
+    for step, kind in ((1, "wave"), (2, "twist"), (3, "collapse")):
+        both(synth.deform(sd0, step, kind))
+        nodes, ca, cb = compare(f"{kind} {step}")
+        assert ca != 1.0 and not np.array_equal(nodes, built)
+    both(synth.deform(sd0, 2, "wave"), first=1000, count=3001)   # a sub-range that is no multiple of the scatter's 256 triangles per workgroup
+    compare("a sub-range of wave 2 over collapse 3")
+    both(sd0)
+    nodes, ca, cb = compare("the creation vertices again")
+    assert np.array_equal(nodes, built) and ca == 1.0 and cb == 1.0
     a.close(); b.close()
 
 
