@@ -1,11 +1,13 @@
-// C-ABI glue: context, scene (BVH build + upload), raw ray queries, G-buffer synthesis.
+// C-ABI glue: context, scene (BVH build + upload), raw ray queries, G-buffer synthesis (one kernel body for flat and shared instanced scenes).
 #include "hr_internal.h"
+#include "scene_create.h"
 #include <algorithm>
 #include <atomic>
 #include <memory>
 #include <new>
 #include "traverse.h"
 #include "traverse2.h"
+#include "shading.h"
 #include "selftest.h"
 #include <cstring>
 #include <cmath>
@@ -157,178 +159,7 @@ __global__ __launch_bounds__(256) void k_closest_hit_batch(const Node8* nodes, c
     out_prim[i]        = h.prim;
 }
 
-// ------------------------------------------------------------------------------------------------
-// G-buffer synthesis by primary rays.  Output conventions of g_buffer.frag:86-112 (see hr_api.h).
-struct GBufArgs
-{
-    float           vpi[16], vp[16], pvp[16];
-    float           cam[3];
-    const Node8*    nodes;
-    const TriGPU*   tris;
-    const float*    positions;     // unused (vertices come from TriGPU)
-    const float*    normals;       // [n][3][3] or null, indexed by original prim
-    const uint32_t* tri_material;  // or null
-    const uint32_t* tri_mesh_id;   // or null
-    const float*    materials;     // [m][8] or null
-    const float*    verts;         // [n][3][3] original positions by prim
-    int             w, h;
-    uint32_t*       gb1;
-    uint2*          gb2;
-    uint2*          gb3;
-    float*          depth;
-};
-
-HR_DEV f3 gb_pixel_dir(const GBufArgs& a, float px, float py)
-{
-    f3 far_p = world_pos_from_depth(__fdiv_rn(px, (float)a.w), __fdiv_rn(py, (float)a.h), 1.0f, a.vpi);
-    return normalize3(sub3(far_p, mk3(a.cam[0], a.cam[1], a.cam[2])));
-}
-
-HR_DEV f3 gb_normal_at(const GBufArgs& a, int prim, float b0, float b1, float b2)
-{
-    if (a.normals)
-    {
-        const float* n = a.normals + (size_t)prim * 9;
-        return mk3(n[0] * b0 + n[3] * b1 + n[6] * b2, n[1] * b0 + n[4] * b1 + n[7] * b2, n[2] * b0 + n[5] * b1 + n[8] * b2);
-    }
-    const float* p = a.verts + (size_t)prim * 9;
-    f3 v0 = mk3(p[0], p[1], p[2]), v1 = mk3(p[3], p[4], p[5]), v2 = mk3(p[6], p[7], p[8]);
-    return normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
-}
-
-HR_DEV bool gb_plane_bary(const GBufArgs& a, int prim, f3 o, f3 d, float& b0, float& b1, float& b2)
-{
-    const float* p = a.verts + (size_t)prim * 9;
-    f3 v0 = mk3(p[0], p[1], p[2]), v1 = mk3(p[3], p[4], p[5]), v2 = mk3(p[6], p[7], p[8]);
-    f3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
-    f3 n  = cross3(e1, e2);
-    float dn = dot3(n, d);
-    if (dn == 0.0f) return false;
-    float tt = __fdiv_rn(dot3(n, sub3(v0, o)), dn);
-    f3    pp = sub3(add3(o, scale3(d, tt)), v0);
-    float d11 = dot3(e1, e1), d12 = dot3(e1, e2), d22 = dot3(e2, e2), p1 = dot3(pp, e1), p2 = dot3(pp, e2);
-    float den = d11 * d22 - d12 * d12;
-    if (den == 0.0f) return false;
-    b1 = __fdiv_rn(d22 * p1 - d12 * p2, den);
-    b2 = __fdiv_rn(d11 * p2 - d12 * p1, den);
-    b0 = 1.0f - b1 - b2;
-    return true;
-}
-
-// What the MOTION variants of the two synthesisers read AFTER the hit, one triangle per lane (hr_gbuffer_raycast_motion): the hit
-// triangle's previous world vertices are prev_verts[prim] (deformable scenes), or prev_mats[instance] * (p, 1) over the object-space positions
-// `mesh_positions` (instanced kinds; a shared deformable scene passes its previous object-space positions there) — mul_m4's operation order, the
-// bits k_instances_transform stores, so a matrix that stands gives the current vertices back and a delta of exactly 0.
-struct MotionArgs
-{
-    const float*       prev_verts;       // [n][3][3] by original triangle, or null
-    const float*       prev_mats;        // [n_instances][16] by instance, or null
-    const InstanceRec* inst;             // private-copy scenes: the records and the triangle -> instance map
-    const uint32_t*    tri_instance;
-    const float*       mesh_positions;   // object space, meshes concatenated (previous frame's where they deform)
-};
-
-// previous minus current position of the point (b0, b1, b2) of a triangle: both sums in the same expression, one rounding per operation
-HR_DEV f3 motion_delta(const float* vp, const float* vc, float b0, float b1, float b2)
-{
-    return mk3(((vp[0] * b0 + vp[3] * b1) + vp[6] * b2) - ((vc[0] * b0 + vc[3] * b1) + vc[6] * b2),
-               ((vp[1] * b0 + vp[4] * b1) + vp[7] * b2) - ((vc[1] * b0 + vc[4] * b1) + vc[7] * b2),
-               ((vp[2] * b0 + vp[5] * b1) + vp[8] * b2) - ((vc[2] * b0 + vc[5] * b1) + vc[8] * b2));
-}
-// P + delta; a delta of 0 gives P's own bits (also for a component that is -0)
-HR_DEV f3 motion_prev_point(f3 P, f3 dl) { return mk3(dl.x == 0.0f ? P.x : P.x + dl.x, dl.y == 0.0f ? P.y : P.y + dl.y, dl.z == 0.0f ? P.z : P.z + dl.z); }
-
-template <bool MOTION>
-__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs mo)
-{
-    __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // one wave = one 8x8 tile for ray coherence
-    const int tiles_x = (a.w + 7) / 8, tiles_y = (a.h + 7) / 8;
-    const int tile = blockIdx.x * 4 + wave;
-    if (tile >= tiles_x * tiles_y) return;
-    const int x = (tile % tiles_x) * 8 + (lane & 7), y = (tile / tiles_x) * 8 + (lane >> 3);
-    if (x >= a.w || y >= a.h) return;
-    const size_t i   = (size_t)y * a.w + x;
-    const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
-    const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
-    HitRec       hit = trace_closest(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
-    if (hit.prim < 0)
-    {
-        a.gb1[i]   = 0u;
-        a.gb2[i]   = make_uint2(0u, 0u);
-        a.gb3[i]   = make_uint2(0u, pack_h2(0.0f, -1.0f));
-        a.depth[i] = 1.0f;
-        return;
-    }
-    const f3 P     = add3(cam, scale3(d, hit.t));
-    const f4 clip  = mul_m4(a.vp, P.x, P.y, P.z, 1.0f);
-    const float b0 = 1.0f - hit.u - hit.v;
-    f3 Pp = P;
-    if (MOTION)
-    {
-        const float* c = a.verts + (size_t)hit.prim * 9;
-        float vc[9], vp[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) vc[k] = c[k];
-        if (mo.prev_verts)
-        {
-            const float* p = mo.prev_verts + (size_t)hit.prim * 9;
-#pragma unroll
-            for (int k = 0; k < 9; k++) vp[k] = p[k];
-        }
-        else
-        {
-            const uint32_t     in = mo.tri_instance[hit.prim];
-            const InstanceRec& r  = mo.inst[in];
-            const float*       p  = mo.mesh_positions + ((size_t)r.mesh_tri_base + ((uint32_t)hit.prim - r.first_tri)) * 9;
-            const float*       m  = mo.prev_mats + (size_t)in * 16;
-#pragma unroll
-            for (int v = 0; v < 3; v++)
-            {
-                const f4 w = mul_m4(m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
-                vp[v * 3] = w.x; vp[v * 3 + 1] = w.y; vp[v * 3 + 2] = w.z;
-            }
-        }
-        Pp = motion_prev_point(P, motion_delta(vp, vc, b0, hit.u, hit.v));
-    }
-    const f4 pclip = mul_m4(a.pvp, Pp.x, Pp.y, Pp.z, 1.0f);
-    const f3 nI    = gb_normal_at(a, hit.prim, b0, hit.u, hit.v);
-    f3       n     = normalize3(nI);
-    if (dot3(n, d) > 0.0f) n = neg3(n);
-    float curvature = 0.0f;
-    if (a.normals)
-    {
-        float c0, c1, c2;
-        f3    dxv = mk3(0, 0, 0), dyv = mk3(0, 0, 0);
-        if (gb_plane_bary(a, hit.prim, cam, gb_pixel_dir(a, (float)x + 1.5f, (float)y + 0.5f), c0, c1, c2)) dxv = sub3(gb_normal_at(a, hit.prim, c0, c1, c2), nI);
-        if (gb_plane_bary(a, hit.prim, cam, gb_pixel_dir(a, (float)x + 0.5f, (float)y + 1.5f), c0, c1, c2)) dyv = sub3(gb_normal_at(a, hit.prim, c0, c1, c2), nI);
-        curvature = hr_sqrt(max2(dot3(dxv, dxv), dot3(dyv, dyv)));
-    }
-    float ox, oy;
-    oct_encode(n, ox, oy);
-    const float cx = __fdiv_rn(clip.x, clip.w) * 0.5f + 0.5f, cy = __fdiv_rn(clip.y, clip.w) * 0.5f + 0.5f;
-    const float px = __fdiv_rn(pclip.x, pclip.w) * 0.5f + 0.5f, py = __fdiv_rn(pclip.y, pclip.w) * 0.5f + 0.5f;
-    const uint32_t mat = a.tri_material ? a.tri_material[hit.prim] : 0u;
-    float albedo[3] = { 0.8f, 0.8f, 0.8f }, metallic = 0.0f, roughness = 0.5f;
-    if (a.materials)
-    {
-        const float* m = a.materials + (size_t)mat * 8;
-        albedo[0] = m[0]; albedo[1] = m[1]; albedo[2] = m[2]; metallic = m[3]; roughness = m[4];
-    }
-    uint32_t g1 = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) g1 |= (uint32_t)(clamp1(albedo[c], 0.0f, 1.0f) * 255.0f + 0.5f) << (8 * c);
-    g1 |= (uint32_t)(clamp1(metallic, 0.0f, 1.0f) * 255.0f + 0.5f) << 24;
-    a.gb1[i] = g1;
-    a.gb2[i] = make_uint2(pack_h2(ox, oy), pack_h2(px - cx, py - cy));
-    const float mesh_id = a.tri_mesh_id ? (float)a.tri_mesh_id[hit.prim] : 0.0f;
-    a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2(mesh_id, clip.z));
-    const float dd = __fdiv_rn(clip.z, clip.w);
-    a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
-}
-
-// ---- shared instanced scenes (instances_shared.hip): the same queries through the two-level walk (traverse2.h), kernels of their own ----------------
+// ---- shared instanced scenes: the queries through traverse2.h.  Kept apart from the two above: another walk (trace_coop's helper lanes there) is behaviour
 __global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, const float* rays, uint8_t* out, unsigned long long* stats)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
@@ -365,27 +196,49 @@ __global__ __launch_bounds__(256) void k_closest_hit_batch2(Scene2 sc, long long
     out_prim[i]        = h.prim;
 }
 
-// k_gbuffer_raycast over a shared scene: the hit triangle's world vertices and normals are what k_instances_transform would have stored
-// (model_matrix * (p, 1); mat3(model_matrix) * n), computed at the hit from the mesh's object-space arrays through the instance record
-struct GBufArgs2
+// ------------------------------------------------------------------------------------------------
+// G-buffer synthesis by primary rays.  Output conventions of g_buffer.frag:86-112 (see hr_api.h).  One kernel body for every kind of scene:
+// TWO_LEVEL (a shared instanced scene, instances_shared.hip) walks on two levels and makes the hit triangle's world vertices and normals at the
+// hit; every other kind reads them by `prim` from the arrays its creator or its updates stored.
+struct GBufArgs
 {
-    GBufArgs        g;               // nodes / tris / normals / verts / tri_material / tri_mesh_id unused
-    Scene2          sc;
-    const float*    mesh_positions;
-    const float*    mesh_normals;    // or null
-    const uint32_t* mesh_material;   // or null
+    float           vpi[16], vp[16], pvp[16];
+    float           cam[3];
+    // what the walk reads comes first, what only a hit lane reads last: of the orders tried, the one with the fewest scalar-register spills around
+    // the walk in all four instantiations (docs/EXPERIMENTS.md, "One G-buffer kernel body")
+    const Node8*    nodes;
+    const TriGPU*   tris;
+    const InstanceShared* inst;    // shared scenes only: the records of the top level's leaves
+    int             w, h;
+    uint32_t*       gb1;
+    uint2*          gb2;
+    uint2*          gb3;
+    float*          depth;
+    const float*    materials;     // [m][8] or null
+    // the hit triangle's attributes.  Shared scenes: the meshes' arrays, object space, by mesh triangle; every other kind: world space, by original prim
+    const float*    verts;         // [n][3][3]
+    const float*    normals;       // [n][3][3] or null
+    const uint32_t* tri_material;  // [n] or null
+    const uint32_t* tri_mesh_id;   // [n] or null; not read for a shared scene (its mesh id is the record's)
 };
 
-HR_DEV f3 gb2_normal_at(const float* wn, const float* wv, bool has_normals, float b0, float b1, float b2)
+HR_DEV f3 gb_pixel_dir(const GBufArgs& a, float px, float py)
 {
-    if (has_normals) return mk3(wn[0] * b0 + wn[3] * b1 + wn[6] * b2, wn[1] * b0 + wn[4] * b1 + wn[7] * b2, wn[2] * b0 + wn[5] * b1 + wn[8] * b2);
-    f3 v0 = mk3(wv[0], wv[1], wv[2]), v1 = mk3(wv[3], wv[4], wv[5]), v2 = mk3(wv[6], wv[7], wv[8]);
+    f3 far_p = world_pos_from_depth(__fdiv_rn(px, (float)a.w), __fdiv_rn(py, (float)a.h), 1.0f, a.vpi);
+    return normalize3(sub3(far_p, mk3(a.cam[0], a.cam[1], a.cam[2])));
+}
+
+// n, v: the hit triangle's nine world vertex-normal floats (read only where has_normals) and nine world vertex floats
+HR_DEV f3 gb_normal_at(const float* n, const float* v, bool has_normals, float b0, float b1, float b2)
+{
+    if (has_normals) return mk3(n[0] * b0 + n[3] * b1 + n[6] * b2, n[1] * b0 + n[4] * b1 + n[7] * b2, n[2] * b0 + n[5] * b1 + n[8] * b2);
+    f3 v0 = mk3(v[0], v[1], v[2]), v1 = mk3(v[3], v[4], v[5]), v2 = mk3(v[6], v[7], v[8]);
     return normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
 }
 
-HR_DEV bool gb2_plane_bary(const float* wv, f3 o, f3 d, float& b0, float& b1, float& b2)
+HR_DEV bool gb_plane_bary(const float* v, f3 o, f3 d, float& b0, float& b1, float& b2)
 {
-    f3 v0 = mk3(wv[0], wv[1], wv[2]), v1 = mk3(wv[3], wv[4], wv[5]), v2 = mk3(wv[6], wv[7], wv[8]);
+    f3 v0 = mk3(v[0], v[1], v[2]), v1 = mk3(v[3], v[4], v[5]), v2 = mk3(v[6], v[7], v[8]);
     f3 e1 = sub3(v1, v0), e2 = sub3(v2, v0);
     f3 n  = cross3(e1, e2);
     float dn = dot3(n, d);
@@ -401,12 +254,46 @@ HR_DEV bool gb2_plane_bary(const float* wv, f3 o, f3 d, float& b0, float& b1, fl
     return true;
 }
 
-template <bool MOTION>
-__global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionArgs mo)
+// What the MOTION instantiations read AFTER the hit, one triangle per lane (hr_gbuffer_raycast_motion): the hit triangle's previous
+// world vertices are prev_verts[prim] (deformable scenes), or prev_mats[instance] * (p, 1) over the object-space positions `mesh_positions`
+// (instanced kinds; a shared deformable scene passes its previous object-space positions there) — mul_m4's operation order, the bits
+// k_instances_transform stores, so a matrix that stands gives the current vertices back and a delta of exactly 0.
+struct MotionArgs
+{
+    const float*       prev_verts;       // [n][3][3] by original triangle, or null
+    const float*       prev_mats;        // [n_instances][16] by instance, or null
+    const InstanceRec* inst;             // private-copy scenes: the records and the triangle -> instance map
+    const uint32_t*    tri_instance;
+    const float*       mesh_positions;   // object space, meshes concatenated (previous frame's where they deform)
+};
+
+// previous minus current position of the point (b0, b1, b2) of a triangle: both sums in the same expression, one rounding per operation
+HR_DEV f3 motion_delta(const float* vp, const float* vc, float b0, float b1, float b2)
+{
+    return mk3(((vp[0] * b0 + vp[3] * b1) + vp[6] * b2) - ((vc[0] * b0 + vc[3] * b1) + vc[6] * b2),
+               ((vp[1] * b0 + vp[4] * b1) + vp[7] * b2) - ((vc[1] * b0 + vc[4] * b1) + vc[7] * b2),
+               ((vp[2] * b0 + vp[5] * b1) + vp[8] * b2) - ((vc[2] * b0 + vc[5] * b1) + vc[8] * b2));
+}
+// P + delta; a delta of 0 gives P's own bits (also for a component that is -0)
+HR_DEV f3 motion_prev_point(f3 P, f3 dl) { return mk3(dl.x == 0.0f ? P.x : P.x + dl.x, dl.y == 0.0f ? P.y : P.y + dl.y, dl.z == 0.0f ? P.z : P.z + dl.z); }
+
+// m * (p, 1) for the three vertices at p: what k_instances_transform stores
+HR_DEV void gb_transform_triangle(const float* m, const float* p, float* out)
+{
+#pragma unroll
+    for (int v = 0; v < 3; v++)
+    {
+        const f4 w = mul_m4(m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
+        out[v * 3] = w.x; out[v * 3 + 1] = w.y; out[v * 3 + 2] = w.z;
+    }
+}
+
+template <bool MOTION, bool TWO_LEVEL>
+__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs mo)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
-    const GBufArgs& a = a2.g;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // one wave = one 8x8 tile for ray coherence
     const int tiles_x = (a.w + 7) / 8, tiles_y = (a.h + 7) / 8;
     const int tile = blockIdx.x * 4 + wave;
     if (tile >= tiles_x * tiles_y) return;
@@ -415,7 +302,9 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionAr
     const size_t i   = (size_t)y * a.w + x;
     const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
     const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
-    const Hit2   hit = trace_closest2(a2.sc, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
+    HitOf<TWO_LEVEL> hit;
+    if constexpr (TWO_LEVEL) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.inst }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
+    else hit = trace_closest(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
     if (hit.prim < 0)
     {
         a.gb1[i]   = 0u;
@@ -424,50 +313,65 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionAr
         a.depth[i] = 1.0f;
         return;
     }
-    const InstanceShared& rec = a2.sc.inst[hit.inst];
-    const size_t q = (size_t)rec.mesh_tri_base + hit.local;
-    float wv[9], wn[9];
+    // ---- the hit triangle, the one step the kinds differ in: q, its index in verts / normals / tri_material; v and vn, its nine world vertex and
+    // nine world vertex-normal floats.  A shared scene computes what k_instances_transform would have stored (model_matrix * (p, 1);
+    // mat3(model_matrix) * n) into registers, through the instance record; the other kinds name the global arrays
+    const bool has_normals = a.normals != nullptr;
+    const InstanceShared* rec = nullptr;
+    size_t       q;
+    const float *v, *vn;
+    float        wv[9], wn[9];
+    if constexpr (TWO_LEVEL)
     {
-        const float* p = a2.mesh_positions + q * 9;
-#pragma unroll
-        for (int v = 0; v < 3; v++)
+        rec = &a.inst[hit.inst];
+        q   = (size_t)rec->mesh_tri_base + hit.local;
+        gb_transform_triangle(rec->m, a.verts + q * 9, wv);
+        if (has_normals)
         {
-            const f4 w = mul_m4(rec.m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
-            wv[v * 3] = w.x; wv[v * 3 + 1] = w.y; wv[v * 3 + 2] = w.z;
-        }
-        if (a2.mesh_normals)
-        {
-            const float* n = a2.mesh_normals + q * 9;
+            const float* n = a.normals + q * 9;
 #pragma unroll
-            for (int v = 0; v < 3; v++)
+            for (int k = 0; k < 3; k++)
             {
-                const float nx = n[v * 3], ny = n[v * 3 + 1], nz = n[v * 3 + 2];
-                wn[v * 3]     = (rec.m[0] * nx + rec.m[4] * ny) + rec.m[8] * nz;
-                wn[v * 3 + 1] = (rec.m[1] * nx + rec.m[5] * ny) + rec.m[9] * nz;
-                wn[v * 3 + 2] = (rec.m[2] * nx + rec.m[6] * ny) + rec.m[10] * nz;
+                const float nx = n[k * 3], ny = n[k * 3 + 1], nz = n[k * 3 + 2];
+                wn[k * 3]     = (rec->m[0] * nx + rec->m[4] * ny) + rec->m[8] * nz;
+                wn[k * 3 + 1] = (rec->m[1] * nx + rec->m[5] * ny) + rec->m[9] * nz;
+                wn[k * 3 + 2] = (rec->m[2] * nx + rec->m[6] * ny) + rec->m[10] * nz;
             }
         }
+        v = wv; vn = wn;
     }
-    const bool has_normals = a2.mesh_normals != nullptr;
+    else
+    {
+        q  = (size_t)hit.prim;
+        v  = a.verts + q * 9;
+        vn = has_normals ? a.normals + q * 9 : nullptr;
+    }
     const f3 P     = add3(cam, scale3(d, hit.t));
     const f4 clip  = mul_m4(a.vp, P.x, P.y, P.z, 1.0f);
     const float b0 = 1.0f - hit.u - hit.v;
     f3 Pp = P;
     if (MOTION)
     {
-        const float* p = mo.mesh_positions + q * 9;
-        const float* m = mo.prev_mats + (size_t)rec.instance * 16;
-        float vp[9];
+        float vp[9], vc[9];   // the current vertices are read before the previous state, not where motion_delta uses them
 #pragma unroll
-        for (int v = 0; v < 3; v++)
+        for (int k = 0; k < 9; k++) vc[k] = v[k];
+        if constexpr (TWO_LEVEL) gb_transform_triangle(mo.prev_mats + (size_t)rec->instance * 16, mo.mesh_positions + q * 9, vp);
+        else if (mo.prev_verts)
         {
-            const f4 w = mul_m4(m, p[v * 3], p[v * 3 + 1], p[v * 3 + 2], 1.0f);
-            vp[v * 3] = w.x; vp[v * 3 + 1] = w.y; vp[v * 3 + 2] = w.z;
+            const float* p = mo.prev_verts + q * 9;
+#pragma unroll
+            for (int k = 0; k < 9; k++) vp[k] = p[k];
         }
-        Pp = motion_prev_point(P, motion_delta(vp, wv, b0, hit.u, hit.v));
+        else
+        {
+            const uint32_t     in = mo.tri_instance[q];
+            const InstanceRec& r  = mo.inst[in];
+            gb_transform_triangle(mo.prev_mats + (size_t)in * 16, mo.mesh_positions + ((size_t)r.mesh_tri_base + ((uint32_t)q - r.first_tri)) * 9, vp);
+        }
+        Pp = motion_prev_point(P, motion_delta(vp, vc, b0, hit.u, hit.v));
     }
     const f4 pclip = mul_m4(a.pvp, Pp.x, Pp.y, Pp.z, 1.0f);
-    const f3 nI    = gb2_normal_at(wn, wv, has_normals, b0, hit.u, hit.v);
+    const f3 nI    = gb_normal_at(vn, v, has_normals, b0, hit.u, hit.v);
     f3       n     = normalize3(nI);
     if (dot3(n, d) > 0.0f) n = neg3(n);
     float curvature = 0.0f;
@@ -475,15 +379,15 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionAr
     {
         float c0, c1, c2;
         f3    dxv = mk3(0, 0, 0), dyv = mk3(0, 0, 0);
-        if (gb2_plane_bary(wv, cam, gb_pixel_dir(a, (float)x + 1.5f, (float)y + 0.5f), c0, c1, c2)) dxv = sub3(gb2_normal_at(wn, wv, true, c0, c1, c2), nI);
-        if (gb2_plane_bary(wv, cam, gb_pixel_dir(a, (float)x + 0.5f, (float)y + 1.5f), c0, c1, c2)) dyv = sub3(gb2_normal_at(wn, wv, true, c0, c1, c2), nI);
+        if (gb_plane_bary(v, cam, gb_pixel_dir(a, (float)x + 1.5f, (float)y + 0.5f), c0, c1, c2)) dxv = sub3(gb_normal_at(vn, v, true, c0, c1, c2), nI);
+        if (gb_plane_bary(v, cam, gb_pixel_dir(a, (float)x + 0.5f, (float)y + 1.5f), c0, c1, c2)) dyv = sub3(gb_normal_at(vn, v, true, c0, c1, c2), nI);
         curvature = hr_sqrt(max2(dot3(dxv, dxv), dot3(dyv, dyv)));
     }
     float ox, oy;
     oct_encode(n, ox, oy);
     const float cx = __fdiv_rn(clip.x, clip.w) * 0.5f + 0.5f, cy = __fdiv_rn(clip.y, clip.w) * 0.5f + 0.5f;
     const float px = __fdiv_rn(pclip.x, pclip.w) * 0.5f + 0.5f, py = __fdiv_rn(pclip.y, pclip.w) * 0.5f + 0.5f;
-    const uint32_t mat = a2.mesh_material ? a2.mesh_material[q] : 0u;
+    const uint32_t mat = a.tri_material ? a.tri_material[q] : 0u;
     float albedo[3] = { 0.8f, 0.8f, 0.8f }, metallic = 0.0f, roughness = 0.5f;
     if (a.materials)
     {
@@ -496,7 +400,10 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast2(GBufArgs2 a2, MotionAr
     g1 |= (uint32_t)(clamp1(metallic, 0.0f, 1.0f) * 255.0f + 0.5f) << 24;
     a.gb1[i] = g1;
     a.gb2[i] = make_uint2(pack_h2(ox, oy), pack_h2(px - cx, py - cy));
-    a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2((float)rec.mesh_id, clip.z));
+    float mesh_id;
+    if constexpr (TWO_LEVEL) mesh_id = (float)rec->mesh_id;
+    else mesh_id = a.tri_mesh_id ? (float)a.tri_mesh_id[q] : 0.0f;
+    a.gb3[i] = make_uint2(pack_h2(max2(roughness, 0.1f), curvature), pack_h2(mesh_id, clip.z));
     const float dd = __fdiv_rn(clip.z, clip.w);
     a.depth[i] = dd >= 1.0f ? 0.99999994f : dd;
 }
@@ -662,8 +569,7 @@ static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene
 static hr_status build_info_impl(const float* positions, int32_t n_tris, hr_scene_info* info, bool spatial, const char* call)
 {
     HR_CHECK_ARG(info && n_tris >= 0 && (positions || n_tris == 0));
-    try
-    {
+    return guarded(call, [&]() -> hr_status {
         BuiltBVH b;
         build_bvh8(positions, n_tris, b, spatial);
         std::memset(info, 0, sizeof(*info));
@@ -675,17 +581,7 @@ static hr_status build_info_impl(const float* positions, int32_t n_tris, hr_scen
         info->box_pad    = b.pad;
         for (int a = 0; a < 3; a++) { info->bounds_lo[a] = b.lo[a]; info->bounds_hi[a] = b.hi[a]; }
         return (b.nodes.size() >= (1u << 23) || b.max_depth >= kMaxTraversalDepth) ? HR_ERR_UNSUPPORTED : HR_OK;
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error(std::string(call) + ": host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)   // nothing else is expected; no exception may cross the C ABI
-    {
-        set_last_error(std::string(call) + ": " + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    });
 }
 
 hr_status hr_bvh_build_info(const float* positions, int32_t n_tris, hr_scene_info* info) { return build_info_impl(positions, n_tris, info, true, "hr_bvh_build_info"); }
@@ -697,31 +593,19 @@ hr_status hr_bvh_build_info_deformable(const float* positions, int32_t n_tris, h
 hr_status hr_bvh_selfcheck(const float* positions, int32_t n_tris, int32_t samples_per_triangle, int64_t* uncovered)
 {
     HR_CHECK_ARG(uncovered && n_tris >= 0 && samples_per_triangle > 0 && (positions || n_tris == 0));
-    try
-    {
+    return guarded("hr_bvh_selfcheck", [&]() -> hr_status {
         BuiltBVH b;
         build_bvh8(positions, n_tris, b);
         *uncovered = check_bvh8_coverage(positions, n_tris, b, samples_per_triangle);
         return HR_OK;
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_bvh_selfcheck: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_bvh_selfcheck: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    });
 }
 
 // Host-only: the child boxes of the same BVH, de-quantised the way the traversal does it (origin + q * 2^(e-127), one fma per plane).
 hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_box* out, int64_t capacity, int64_t* n_boxes)
 {
     HR_CHECK_ARG(n_boxes && n_tris >= 0 && capacity >= 0 && (out || capacity == 0) && (positions || n_tris == 0));
-    try
-    {
+    return guarded("hr_bvh_child_boxes", [&]() -> hr_status {
         BuiltBVH b;
         build_bvh8(positions, n_tris, b);
         std::vector<int> depth(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
@@ -751,52 +635,27 @@ hr_status hr_bvh_child_boxes(const float* positions, int32_t n_tris, hr_child_bo
         }
         *n_boxes = n;
         return HR_OK;
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_bvh_child_boxes: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_bvh_child_boxes: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    });
 }
 
-// No exception crosses the C ABI: the builder's and the staging vectors' allocation failures become HR_ERR_OUT_OF_MEMORY.
 hr_status hr_scene_create(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out)
 {
-    try
-    {
-        return scene_create_impl(ctx, d, out, false);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_scene_create: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_scene_create: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_scene_create", [&] { return scene_create_impl(ctx, d, out, false); });
 }
 
 static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out, bool deformable)
 {
     HR_CHECK_ARG(ctx && d && out && d->n_tris >= 0 && (d->positions || d->n_tris == 0));
     HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
-    // every triangle's material index is dereferenced by the hit shading (shading.h surface_at: materials[m * 8], mat_tex[m * 6])
     if (d->tri_material)
     {
         if (!d->materials) { set_last_error("hr_scene_create: tri_material given without materials"); return HR_ERR_INVALID_ARG; }
-        for (int i = 0; i < d->n_tris; i++)
-            if (d->tri_material[i] >= (uint32_t)d->n_materials)
-            {
-                set_last_error("hr_scene_create: tri_material[" + std::to_string(i) + "] = " + std::to_string(d->tri_material[i]) + " >= n_materials");
-                return HR_ERR_INVALID_ARG;
-            }
+        const int i = first_bad_material(d->tri_material, d->n_tris, d->n_materials);
+        if (i >= 0)
+        {
+            set_last_error("hr_scene_create: tri_material[" + std::to_string(i) + "] = " + std::to_string(d->tri_material[i]) + " >= n_materials");
+            return HR_ERR_INVALID_ARG;
+        }
     }
     HR_HIP(hipSetDevice(ctx->device));
     BuiltBVH b;
@@ -819,46 +678,19 @@ static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene
     std::unique_ptr<hr_scene> guard(new hr_scene());
     hr_scene* s = guard.get();
     s->ctx      = ctx;
-    hr_status st;
-#define UP(buf, src, nbytes)                                                                     \
-    if ((st = s->buf.alloc(nbytes)) != HR_OK) return st;                                         \
-    if ((nbytes) > 0) { hipError_t e_ = hipMemcpy(s->buf.p, src, nbytes, hipMemcpyHostToDevice); \
-        if (e_ != hipSuccess) { set_last_error(std::string("hipMemcpy H2D failed: ") + hipGetErrorString(e_)); return HR_ERR_HIP; } }
-    UP(nodes, b.nodes.data(), b.nodes.size() * sizeof(Node8))
-    UP(tris, b.tris.data(), b.tris.size() * sizeof(TriGPU))
+    HR_TRY(upload(s->nodes, b.nodes.data(), b.nodes.size() * sizeof(Node8)));
+    HR_TRY(upload(s->tris, b.tris.data(), b.tris.size() * sizeof(TriGPU)));
     const size_t n = (size_t)d->n_tris;
-    // original-order vertex positions are kept for shading-time interpolation
-    UP(materials, d->materials, d->materials ? (size_t)d->n_materials * 32 : 0)
-    if (d->normals) { UP(tri_normals, d->normals, n * 36) s->has_normals = true; }
-    if (d->tri_material) { UP(tri_material, d->tri_material, n * 4) s->has_material = true; }
-    if (d->tri_mesh_id) { UP(tri_mesh_id, d->tri_mesh_id, n * 4) s->has_mesh_id = true; }
-    UP(positions, d->positions, n * 36)
-    if (d->material_textures && d->materials && d->n_textures > 0 && d->textures)
+    if (d->normals) { HR_TRY(upload(s->tri_normals, d->normals, n * 36)); s->has_normals = true; }
+    if (d->tri_material) { HR_TRY(upload(s->tri_material, d->tri_material, n * 4)); s->has_material = true; }
+    if (d->tri_mesh_id) { HR_TRY(upload(s->tri_mesh_id, d->tri_mesh_id, n * 4)); s->has_mesh_id = true; }
+    HR_TRY(upload(s->positions, d->positions, n * 36));   // original-order vertex positions are kept for shading-time interpolation
+    HR_TRY(stage_materials(s, d, "hr_scene_create"));
+    if (s->has_textures)
     {
-        // one buffer of texels + a table {texel offset, width, height, 0} per texture
-        std::vector<uint32_t> table;
-        std::vector<uint8_t>  texels;
-        for (int i = 0; i < d->n_textures; i++)
-        {
-            const hr_texture& t = d->textures[i];
-            if (!t.rgba8 || t.width <= 0 || t.height <= 0) { set_last_error("hr_scene_create: empty texture"); return HR_ERR_INVALID_ARG; }
-            table.insert(table.end(), { (uint32_t)(texels.size() / 4), (uint32_t)t.width, (uint32_t)t.height, 0u });
-            texels.insert(texels.end(), t.rgba8, t.rgba8 + (size_t)t.width * t.height * 4);
-        }
-        for (int i = 0; i < d->n_materials * 4; i++)
-        {
-            const int32_t ti = d->material_textures[(i / 4) * 6 + (i % 4)];
-            if (ti >= d->n_textures) { set_last_error("hr_scene_create: material texture index out of range"); return HR_ERR_INVALID_ARG; }
-        }
-        UP(mat_tex, d->material_textures, (size_t)d->n_materials * 24)
-        UP(tex_table, table.data(), table.size() * 4)
-        UP(tex_data, texels.data(), texels.size())
-        if (d->uvs) { UP(tri_uvs, d->uvs, n * 24) s->has_uvs = true; }
-        if (d->tangents) { UP(tri_tangents, d->tangents, n * 36) s->has_tangents = true; }
-        s->has_textures = true;
+        if (d->uvs) { HR_TRY(upload(s->tri_uvs, d->uvs, n * 24)); s->has_uvs = true; }
+        if (d->tangents) { HR_TRY(upload(s->tri_tangents, d->tangents, n * 36)); s->has_tangents = true; }
     }
-#undef UP
-    s->n_materials      = d->materials ? d->n_materials : 0;
     { static std::atomic<uint64_t> next_uid { 1 }; s->uid = next_uid.fetch_add(1); }
     s->info.n_tris      = d->n_tris;
     s->info.n_nodes     = (int32_t)b.nodes.size();
@@ -867,7 +699,7 @@ static hr_status scene_create_impl(hr_ctx* ctx, const hr_scene_desc* d, hr_scene
     s->info.tri_bytes   = b.tris.size() * sizeof(TriGPU);
     s->info.box_pad     = b.pad;
     for (int a = 0; a < 3; a++) { s->info.bounds_lo[a] = s->grid_lo[a] = b.lo[a]; s->info.bounds_hi[a] = s->grid_hi[a] = b.hi[a]; }
-    if (deformable && (st = deformable_scene_adopt(s, b)) != HR_OK) return st;
+    if (deformable) HR_TRY(deformable_scene_adopt(s, b));
     *out = guard.release();
     return HR_OK;
 }
@@ -982,34 +814,23 @@ static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, 
         }
         else mo.prev_verts = (const float*)scene->prev_positions.p;
     }
+    // a shared scene's attribute arrays are its meshes' (object space); the hit makes world vertices and normals of them
+    const bool sh = scene->shared;
     GBufArgs a;
     for (int i = 0; i < 16; i++) { a.vpi[i] = ubo->view_proj_inverse[i]; a.vp[i] = ubo->view_proj[i]; a.pvp[i] = ubo->prev_view_proj[i]; }
     for (int i = 0; i < 3; i++) a.cam[i] = ubo->cam_pos[i];
     a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p;
-    a.positions = nullptr;
-    a.normals = scene->has_normals ? (const float*)scene->tri_normals.p : nullptr;
-    a.tri_material = scene->has_material ? (const uint32_t*)scene->tri_material.p : nullptr;
-    a.tri_mesh_id = scene->has_mesh_id ? (const uint32_t*)scene->tri_mesh_id.p : nullptr;
+    a.inst = sh ? (const InstanceShared*)scene->inst_shared.p : nullptr;
+    a.normals = scene->has_normals ? (const float*)(sh ? scene->mesh_normals.p : scene->tri_normals.p) : nullptr;
+    a.tri_material = scene->has_material ? (const uint32_t*)(sh ? scene->mesh_material.p : scene->tri_material.p) : nullptr;
+    a.tri_mesh_id = scene->has_mesh_id && !sh ? (const uint32_t*)scene->tri_mesh_id.p : nullptr;
     a.materials = scene->n_materials ? (const float*)scene->materials.p : nullptr;
-    a.verts = (const float*)scene->positions.p;
+    a.verts = (const float*)(sh ? scene->mesh_positions.p : scene->positions.p);
     a.w = w; a.h = h;
     a.gb1 = (uint32_t*)gb1; a.gb2 = (uint2*)gb2; a.gb3 = (uint2*)gb3; a.depth = depth;
     const int tiles = ((w + 7) / 8) * ((h + 7) / 8);
-    if (scene->shared)
-    {
-        GBufArgs2 a2;
-        a2.g = a;
-        a2.sc = scene2_of(scene);
-        a2.mesh_positions = (const float*)scene->mesh_positions.p;
-        a2.mesh_normals = scene->has_normals ? (const float*)scene->mesh_normals.p : nullptr;
-        a2.mesh_material = scene->has_material ? (const uint32_t*)scene->mesh_material.p : nullptr;
-        if (motion) hipLaunchKernelGGL(k_gbuffer_raycast2<true>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2, mo);
-        else hipLaunchKernelGGL(k_gbuffer_raycast2<false>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a2, mo);
-        HR_HIP(hipGetLastError());
-        return HR_OK;
-    }
-    if (motion) hipLaunchKernelGGL(k_gbuffer_raycast<true>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
-    else hipLaunchKernelGGL(k_gbuffer_raycast<false>, dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
+    void (*const kernel[2][2])(GBufArgs, MotionArgs) = { { k_gbuffer_raycast<false, false>, k_gbuffer_raycast<false, true> }, { k_gbuffer_raycast<true, false>, k_gbuffer_raycast<true, true> } };
+    hipLaunchKernelGGL(kernel[motion][sh], dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }

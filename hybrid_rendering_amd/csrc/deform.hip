@@ -10,6 +10,7 @@
 // function of the triangle set, closest hit is the smallest t with ties to the smallest triangle index); only the boxes' quality decays.
 // hr_scene_rebuild is the slow way back: vertices read back, host build, upload.  Nothing calls it automatically.
 #include "deform_refit.h"
+#include "scene_create.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -149,20 +150,7 @@ extern "C" {
 
 hr_status hr_scene_create_deformable(hr_ctx* ctx, const hr_scene_desc* desc, hr_scene** out)
 {
-    try
-    {
-        return scene_create_flat(ctx, desc, out, true);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_scene_create_deformable: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_scene_create_deformable: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_scene_create_deformable", [&] { return scene_create_flat(ctx, desc, out, true); });
 }
 
 hr_status hr_scene_update_vertices(hr_scene* scene, const float* positions, const float* normals, int32_t first_tri, int32_t n_tris, void* stream)

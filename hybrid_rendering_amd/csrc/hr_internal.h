@@ -345,7 +345,6 @@ struct hr_scene
     std::vector<float>    inst_root_cells;        // per instance: the 48 leaf-cell floats of that root
     std::vector<int32_t>  node_inst_host, node_rel_depth;   // per node: owning instance (-1 top level) / depth below the instance root
     std::vector<float>    inst_box;               // per instance: conservative world box (lo xyz, hi xyz) of the last update, host side
-    std::vector<int32_t>  top_parent, top_first_child;      // host mirror of the top level (slot -> parent slot / first child slot) for its quality check
     std::vector<hr::Node8> top_nodes_host;        // upload staging, kept alive for the asynchronous copies
     std::vector<uint32_t> level_nodes_host;
     std::vector<int32_t>  inst_root_slot;

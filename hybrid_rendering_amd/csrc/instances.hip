@@ -28,7 +28,10 @@
 // The topology (which triangles share a leaf, which nodes share a parent) never changes, so a query's ANSWER is the one a fresh build over
 // the same world-space vertices would give — any-hit is a function of the geometry, closest hit is the smallest t with ties to the
 // smallest triangle index — while the boxes stay as tight as the moved geometry allows: a rigidly moving instance keeps its own subtree.
+// Creation shares its staging with the other kinds (scene_create.h); what of it is about instanced descs — validation, the meshes' attributes and
+// trees, the per-instance host fields, the collapse of the binary top-level tree to eight-wide nodes — is defined at the end of this file.
 #include "hr_internal.h"
+#include "scene_create.h"
 #include "device_math.h"
 #include "refit.h"
 #include <atomic>
@@ -183,11 +186,7 @@ struct TopLevel
     int                  used = 0, max_depth = 0;
 };
 
-inline double half_area(const float* lo, const float* hi)
-{
-    const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
-    return x * y + y * z + z * x;
-}
+using imath::half_area3;
 
 int build_binary(std::vector<BinNode>& t, std::vector<int>& items, int begin, int end, const float* boxes, int depth)
 {
@@ -213,13 +212,13 @@ int build_binary(std::vector<BinNode>& t, std::vector<int>& items, int begin, in
             for (int k = cnt - 1; k > 0; k--)
             {
                 for (int b = 0; b < 3; b++) { lo[b] = std::min(lo[b], boxes[(size_t)sorted[(size_t)k] * 6 + b]); hi[b] = std::max(hi[b], boxes[(size_t)sorted[(size_t)k] * 6 + 3 + b]); }
-                right_area[(size_t)k] = half_area(lo, hi);
+                right_area[(size_t)k] = half_area3(lo, hi);
             }
             for (int b = 0; b < 3; b++) { lo[b] = INFINITY; hi[b] = -INFINITY; }
             for (int k = 1; k < cnt; k++)
             {
                 for (int b = 0; b < 3; b++) { lo[b] = std::min(lo[b], boxes[(size_t)sorted[(size_t)k - 1] * 6 + b]); hi[b] = std::max(hi[b], boxes[(size_t)sorted[(size_t)k - 1] * 6 + 3 + b]); }
-                const double c = half_area(lo, hi) * k + right_area[(size_t)k] * (cnt - k);
+                const double c = half_area3(lo, hi) * k + right_area[(size_t)k] * (cnt - k);
                 if (c < best_cost) { best_cost = c; best_axis = a; best_split = begin + k; best_sorted = sorted; }
             }
         }
@@ -272,29 +271,10 @@ void build_top_level(const hr_scene* s, TopLevel& tl)
     for (size_t qi = 0; qi < queue.size(); qi++)
     {
         const Q q = queue[qi];
-        // open the child of largest area until eight children stand (instance leaves cannot be opened)
-        int kids[8], nk = 2;
-        kids[0] = bin[(size_t)q.bin].left; kids[1] = bin[(size_t)q.bin].right;
-        while (nk < 8)
-        {
-            int    best = -1;
-            double ba = -1.0;
-            for (int c = 0; c < nk; c++)
-                if (bin[(size_t)kids[c]].inst < 0)
-                {
-                    const double ar = half_area(bin[(size_t)kids[c]].lo, bin[(size_t)kids[c]].hi);
-                    if (ar > ba) { ba = ar; best = c; }
-                }
-            if (best < 0) break;
-            const int k = kids[best];
-            kids[best] = bin[(size_t)k].left; kids[nk++] = bin[(size_t)k].right;
-        }
-        // sorted along the longest axis of the node's box: the traversal walks them near to far / far to near by the ray's sign (bvh.h)
-        const BinNode& me = bin[(size_t)q.bin];
-        int ax = 0;
-        if (me.hi[1] - me.lo[1] > me.hi[ax] - me.lo[ax]) ax = 1;
-        if (me.hi[2] - me.lo[2] > me.hi[ax] - me.lo[ax]) ax = 2;
-        std::stable_sort(kids, kids + nk, [&](int x, int y) { return (double)bin[(size_t)x].lo[ax] + bin[(size_t)x].hi[ax] < (double)bin[(size_t)y].lo[ax] + bin[(size_t)y].hi[ax]; });
+        // all children sorted along the node's longest axis: the traversal walks them near to far / far to near by the ray's sign (bvh.h)
+        int kids[8], ax;
+        const int nk = top_level_children(bin, q.bin, kids, ax);
+        std::stable_sort(kids, kids + nk, [&](int x, int y) { return bin_before(bin, ax, x, y); });
         Node8& n = tl.nodes[(size_t)q.slot];
         n.ex = n.ey = n.ez = 1;
         n.counts = (uint8_t)(nk | (nk << 4));
@@ -330,7 +310,7 @@ double top_level_area(const hr_scene* s, const TopLevel* fresh = nullptr)
         for (int a = 0; a < 3; a++) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
         for (int c = 0; c < (n.counts >> 4); c++)
             for (int a = 0; a < 3; a++) { b[a] = std::min(b[a], box[((size_t)n.child_base + c) * 6 + a]); b[3 + a] = std::max(b[3 + a], box[((size_t)n.child_base + c) * 6 + 3 + a]); }
-        sum += half_area(b, b + 3);
+        sum += half_area3(b, b + 3);
     }
     return sum;
 }
@@ -506,69 +486,29 @@ hr_status update_impl(hr_scene* s, const float* matrices, hipStream_t st, bool a
 
 hr_status create_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out)
 {
+    const char* who = "hr_scene_create_instanced";
     HR_CHECK_ARG(ctx && d && out && d->n_meshes > 0 && d->meshes && d->n_instances > 0 && d->instances);
     HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
-    const int M = d->n_meshes, I = d->n_instances;
-    bool all_normals = true, any_normals = false, all_mat = true, any_mat = false, all_uv = true, all_tan = true;
-    for (int k = 0; k < M; k++)
-    {
-        const hr_mesh_desc& me = d->meshes[k];
-        HR_CHECK_ARG(me.n_tris >= 0 && (me.positions || me.n_tris == 0));
-        all_normals = all_normals && me.normals; any_normals = any_normals || me.normals;
-        all_mat = all_mat && me.tri_material; any_mat = any_mat || me.tri_material;
-        all_uv = all_uv && me.uvs; all_tan = all_tan && me.tangents;
-        if (me.tri_material)
-        {
-            if (!d->materials) { set_last_error("hr_scene_create_instanced: tri_material given without materials"); return HR_ERR_INVALID_ARG; }
-            for (int i = 0; i < me.n_tris; i++)
-                if (me.tri_material[i] >= (uint32_t)d->n_materials) { set_last_error("hr_scene_create_instanced: a tri_material entry >= n_materials"); return HR_ERR_INVALID_ARG; }
-        }
-    }
-    if (any_normals && !all_normals) { set_last_error("hr_scene_create_instanced: vertex normals on some meshes only"); return HR_ERR_INVALID_ARG; }
-    if (any_mat && !all_mat) { set_last_error("hr_scene_create_instanced: tri_material on some meshes only"); return HR_ERR_INVALID_ARG; }
-    for (int i = 0; i < I; i++)
-    {
-        if (d->instances[i].mesh_idx >= (uint32_t)M) { set_last_error("hr_scene_create_instanced: instances[" + std::to_string(i) + "].mesh_idx >= n_meshes"); return HR_ERR_INVALID_ARG; }
-        if (!finite16(d->instances[i].model_matrix)) { set_last_error("hr_scene_create_instanced: instances[" + std::to_string(i) + "].model_matrix is not finite"); return HR_ERR_INVALID_ARG; }
-    }
+    const int I = d->n_instances;
+    MeshAttributes ma;
+    HR_TRY(mesh_attributes(d, who, ma));
+    HR_TRY(validate_instances(d, who));
     HR_HIP(hipSetDevice(ctx->device));
 
     // ---- per-mesh topologies (object space) ------------------------------------------------------------------------------------------
-    std::vector<BuiltBVH> blas((size_t)M);
-    std::vector<std::vector<int>> blas_depth((size_t)M);
-    std::vector<uint32_t> mesh_tri_base((size_t)M + 1, 0u);
+    MeshTrees mt;
+    build_mesh_trees(d, mt, true);
+    const std::vector<BuiltBVH>& blas = mt.blas;
     std::unique_ptr<hr_scene> guard(new hr_scene());
     hr_scene* s = guard.get();
     s->ctx = ctx;
-    s->mesh_bounds.assign((size_t)M * 6, 0.0f);
-    for (int k = 0; k < M; k++)
-    {
-        blas[(size_t)k].want_child_boxes = true;
-        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, blas[(size_t)k]);
-        blas[(size_t)k].child_boxes.resize(blas[(size_t)k].nodes.size() * 48, 0.0f);
-        const BuiltBVH& b = blas[(size_t)k];
-        mesh_tri_base[(size_t)k + 1] = mesh_tri_base[(size_t)k] + (uint32_t)d->meshes[k].n_tris;
-        for (int a = 0; a < 3; a++) { s->mesh_bounds[(size_t)k * 6 + a] = b.lo[a]; s->mesh_bounds[(size_t)k * 6 + 3 + a] = b.hi[a]; }
-        if (d->meshes[k].n_tris == 0) { s->mesh_bounds[(size_t)k * 6] = 1.0f; s->mesh_bounds[(size_t)k * 6 + 3] = 0.0f; }   // empty: lo > hi
-        // depth of every node (children follow their parent in the builder's breadth-first order)
-        std::vector<int>& dep = blas_depth[(size_t)k];
-        dep.assign(b.nodes.size(), 0);
-        for (size_t j = 0; j < b.nodes.size(); j++)
-            for (int c = 0; c < (b.nodes[j].counts & 15); c++) dep[(size_t)b.nodes[j].child_base + c] = dep[j] + 1;
-    }
+    fill_instances(s, d, mt);
 
     // ---- layout: [ top region: top-level nodes + instance roots, top_cap slots | instance 0's other nodes | instance 1's ... ] ------------------
-    s->n_instances = I;
-    s->inst_mesh.resize((size_t)I);
-    s->inst_host.resize((size_t)I);
     uint64_t total_tris = 0, total_refs = 0, total_sub_nodes = 0;
     for (int i = 0; i < I; i++)
     {
-        const uint32_t k = d->instances[i].mesh_idx;
-        s->inst_mesh[(size_t)i] = k;
-        InstanceRec& r = s->inst_host[(size_t)i];
-        std::memcpy(r.m, d->instances[i].model_matrix, 64);
-        r.first_tri = (uint32_t)total_tris; r.mesh_tri_base = mesh_tri_base[k]; r.mesh_id = d->instances[i].mesh_id; r.n_tris = (uint32_t)d->meshes[k].n_tris;
+        const uint32_t k = s->inst_mesh[(size_t)i];
         total_tris += (uint64_t)d->meshes[k].n_tris; total_refs += blas[k].tris.size(); total_sub_nodes += blas[k].nodes.size() - 1;
     }
     if (total_tris >= (1ull << 31) || total_refs >= (1ull << 26)) { set_last_error("hr_scene_create_instanced: more than 2^26 triangle references"); return HR_ERR_UNSUPPORTED; }
@@ -606,9 +546,9 @@ hr_status create_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** 
             const size_t at = base + j - 1;
             nodes[at] = n;
             s->node_inst_host[at] = i;
-            s->node_rel_depth[at] = blas_depth[k][j];
+            s->node_rel_depth[at] = mt.node_depth[k][j];
             std::memcpy(&cells[at * 48], &b.child_boxes[j * 48], 48 * sizeof(float));
-            max_rel = std::max(max_rel, blas_depth[k][j]);
+            max_rel = std::max(max_rel, mt.node_depth[k][j]);
         }
         const InstanceRec& r = s->inst_host[(size_t)i];
         for (size_t t = 0; t < b.tris.size(); t++)
@@ -633,91 +573,55 @@ hr_status create_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** 
     std::memcpy(cells.data(), s->top_cells_host.data(), (size_t)s->top_cap * 48 * sizeof(float));
     const std::vector<int32_t>&  node_inst = s->node_inst_host;
     const std::vector<uint32_t>& level_nodes = s->level_nodes_host;
-    const int max_depth = s->info.max_depth;
 
-    // ---- attributes --------------------------------------------------------------------------------------------------------------------
-    const size_t MT = mesh_tri_base[(size_t)M], N = (size_t)total_tris;
-    std::vector<float> mpos(MT * 9), mnor(all_normals ? MT * 9 : 0), muv(all_uv ? MT * 6 : 0), mtan(all_tan ? MT * 9 : 0);
-    std::vector<uint32_t> mmat(all_mat ? MT : 0), gmat(all_mat ? N : 0), gid(N);
-    for (int k = 0; k < M; k++)
-    {
-        const hr_mesh_desc& me = d->meshes[k];
-        const size_t o = mesh_tri_base[(size_t)k], n = (size_t)me.n_tris;
-        if (n == 0) continue;
-        std::memcpy(&mpos[o * 9], me.positions, n * 36);
-        if (all_normals) std::memcpy(&mnor[o * 9], me.normals, n * 36);
-        if (all_uv) std::memcpy(&muv[o * 6], me.uvs, n * 24);
-        if (all_tan) std::memcpy(&mtan[o * 9], me.tangents, n * 36);
-        if (all_mat) std::memcpy(&mmat[o], me.tri_material, n * 4);
-    }
+    // ---- attributes: the meshes' (object space) as they come, material and mesh id also per global triangle ----------------------------------------
+    const size_t MT = ma.n_tris, N = (size_t)total_tris;
+    std::vector<uint32_t> gmat(ma.material ? N : 0), gid(N);
     for (int i = 0; i < I; i++)
     {
         const InstanceRec& r = s->inst_host[(size_t)i];
         for (uint32_t t = 0; t < r.n_tris; t++)
         {
             gid[(size_t)r.first_tri + t] = r.mesh_id;
-            if (all_mat) gmat[(size_t)r.first_tri + t] = mmat[(size_t)r.mesh_tri_base + t];
+            if (ma.material) gmat[(size_t)r.first_tri + t] = ma.mat[(size_t)r.mesh_tri_base + t];
         }
     }
-    hr_status st;
-#define UP(buf, src, nbytes)                                                                     \
-    if ((st = s->buf.alloc(nbytes)) != HR_OK) return st;                                         \
-    if ((nbytes) > 0) { hipError_t e_ = hipMemcpy(s->buf.p, src, nbytes, hipMemcpyHostToDevice); \
-        if (e_ != hipSuccess) { set_last_error(std::string("hipMemcpy H2D failed: ") + hipGetErrorString(e_)); return HR_ERR_HIP; } }
-    UP(nodes, nodes.data(), n_nodes * sizeof(Node8))
-    UP(tris, tris.data(), tris.size() * sizeof(TriGPU))
-    UP(level_nodes, level_nodes.data(), n_nodes * 4)
-    UP(leaf_cells, cells.data(), cells.size() * 4)
-    UP(node_inst, node_inst.data(), n_nodes * 4)
-    UP(tri_instance, tri_instance.data(), N * 4)
-    UP(mesh_positions, mpos.data(), MT * 36)
-    UP(materials, d->materials, d->materials ? (size_t)d->n_materials * 32 : 0)
-    if (all_normals) { UP(mesh_normals, mnor.data(), MT * 36) s->has_normals = true; if ((st = s->tri_normals.alloc(N * 36)) != HR_OK) return st; }
-    if (all_mat) { UP(mesh_material, mmat.data(), MT * 4) UP(tri_material, gmat.data(), N * 4) s->has_material = true; }
-    UP(tri_mesh_id, gid.data(), N * 4)
+    HR_TRY(upload(s->nodes, nodes.data(), n_nodes * sizeof(Node8)));
+    HR_TRY(upload(s->tris, tris.data(), tris.size() * sizeof(TriGPU)));
+    HR_TRY(upload(s->level_nodes, level_nodes.data(), n_nodes * 4));
+    HR_TRY(upload(s->leaf_cells, cells.data(), cells.size() * 4));
+    HR_TRY(upload(s->node_inst, node_inst.data(), n_nodes * 4));
+    HR_TRY(upload(s->tri_instance, tri_instance.data(), N * 4));
+    HR_TRY(upload(s->mesh_positions, ma.pos.data(), MT * 36));
+    if (ma.normals) { HR_TRY(upload(s->mesh_normals, ma.nor.data(), MT * 36)); s->has_normals = true; HR_TRY(s->tri_normals.alloc(N * 36)); }
+    if (ma.material) { HR_TRY(upload(s->mesh_material, ma.mat.data(), MT * 4)); HR_TRY(upload(s->tri_material, gmat.data(), N * 4)); s->has_material = true; }
+    HR_TRY(upload(s->tri_mesh_id, gid.data(), N * 4));
     s->has_mesh_id = true;
-    if ((st = s->positions.alloc(N * 36)) != HR_OK) return st;
-    if ((st = s->node_box.alloc(n_nodes * 32)) != HR_OK) return st;
-    if ((st = s->bounds_bits.alloc((size_t)I * 24)) != HR_OK) return st;
-    if ((st = s->inst_dirty_dev.alloc((size_t)I * 4)) != HR_OK) return st;
-    if ((st = s->inst_records.alloc((size_t)I * sizeof(InstanceRec))) != HR_OK) return st;
-    if (d->material_textures && d->materials && d->n_textures > 0 && d->textures)
+    HR_TRY(s->positions.alloc(N * 36));
+    HR_TRY(s->node_box.alloc(n_nodes * 32));
+    HR_TRY(s->bounds_bits.alloc((size_t)I * 24));
+    HR_TRY(s->inst_dirty_dev.alloc((size_t)I * 4));
+    HR_TRY(s->inst_records.alloc((size_t)I * sizeof(InstanceRec)));
+    HR_TRY(stage_materials(s, d, who));
+    if (s->has_textures)
     {
-        std::vector<uint32_t> table;
-        std::vector<uint8_t>  texels;
-        for (int i = 0; i < d->n_textures; i++)
-        {
-            const hr_texture& t = d->textures[i];
-            if (!t.rgba8 || t.width <= 0 || t.height <= 0) { set_last_error("hr_scene_create_instanced: empty texture"); return HR_ERR_INVALID_ARG; }
-            table.insert(table.end(), { (uint32_t)(texels.size() / 4), (uint32_t)t.width, (uint32_t)t.height, 0u });
-            texels.insert(texels.end(), t.rgba8, t.rgba8 + (size_t)t.width * t.height * 4);
-        }
-        for (int i = 0; i < d->n_materials * 4; i++)
-            if (d->material_textures[(i / 4) * 6 + (i % 4)] >= d->n_textures) { set_last_error("hr_scene_create_instanced: material texture index out of range"); return HR_ERR_INVALID_ARG; }
-        UP(mat_tex, d->material_textures, (size_t)d->n_materials * 24)
-        UP(tex_table, table.data(), table.size() * 4)
-        UP(tex_data, texels.data(), texels.size())
-        if (all_uv) { UP(mesh_uvs, muv.data(), MT * 24) s->has_uvs = true; }
-        if (all_tan) { UP(mesh_tangents, mtan.data(), MT * 36) s->has_tangents = true; }
-        s->has_textures = true;
+        if (ma.uvs) { HR_TRY(upload(s->mesh_uvs, ma.uv.data(), MT * 24)); s->has_uvs = true; }
+        if (ma.tangents) { HR_TRY(upload(s->mesh_tangents, ma.tan.data(), MT * 36)); s->has_tangents = true; }
     }
-#undef UP
-    s->n_materials = d->materials ? d->n_materials : 0;
     { static std::atomic<uint64_t> next_uid { 1ull << 40 }; s->uid = next_uid.fetch_add(1); }   // disjoint from hr_scene_create's counter
     if (const char* e = getenv("HR_TOP_LEVEL_REBUILD")) s->auto_rebuild = atoi(e) != 0;
     s->info.n_tris     = (int32_t)N;
     s->info.n_nodes    = (int32_t)n_nodes;
-    (void)max_depth;   // set by adopt_top_level
     s->info.node_bytes = n_nodes * sizeof(Node8);
     s->info.tri_bytes  = tris.size() * sizeof(TriGPU);
     // first update: the instances' own matrices, then wait (creation is synchronous like hr_scene_create)
     std::vector<float> mats((size_t)I * 16);
     for (int i = 0; i < I; i++) std::memcpy(&mats[(size_t)i * 16], d->instances[i].model_matrix, 64);
-    if ((st = update_impl(s, mats.data(), nullptr, true)) != HR_OK) return st;
+    HR_TRY(update_impl(s, mats.data(), nullptr, true));
     HR_HIP(hipStreamSynchronize(nullptr));
     s->geometry_epoch = 0;
     hr_scene_info tmp;
-    if ((st = hr_scene_get_info(s, &tmp)) != HR_OK) return st;
+    HR_TRY(hr_scene_get_info(s, &tmp));
     *out = guard.release();
     return HR_OK;
 }
@@ -738,6 +642,134 @@ int       hr::private_copy_top_depth(hr_scene* stub, const std::vector<int>& mes
     int d = 0;
     for (int i = 0; i < stub->n_instances; i++) d = std::max(d, tl.depth[(size_t)tl.root_slot[(size_t)i]] + mesh_depth_of_instance[(size_t)i]);
     return d;
+}
+
+// ---- scene_create.h: what the two instanced creators and hr_instanced_scene_footprint share ------------------------------------------------------
+hr_status hr::validate_instances(const hr_instanced_scene_desc* d, const char* who)
+{
+    for (int i = 0; i < d->n_instances; i++)
+    {
+        if (d->instances[i].mesh_idx >= (uint32_t)d->n_meshes) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].mesh_idx >= n_meshes"); return HR_ERR_INVALID_ARG; }
+        if (!finite16(d->instances[i].model_matrix)) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].model_matrix is not finite"); return HR_ERR_INVALID_ARG; }
+    }
+    return HR_OK;
+}
+
+hr_status hr::validate_desc(const hr_instanced_scene_desc* d, const char* who)
+{
+    HR_CHECK_ARG(d && d->n_meshes > 0 && d->meshes && d->n_instances > 0 && d->instances);
+    for (int k = 0; k < d->n_meshes; k++) HR_CHECK_ARG(d->meshes[k].n_tris >= 0 && (d->meshes[k].positions || d->meshes[k].n_tris == 0));
+    return validate_instances(d, who);
+}
+
+hr_status hr::mesh_attributes(const hr_instanced_scene_desc* d, const char* who, MeshAttributes& ma)
+{
+    bool any_normals = false, any_mat = false;
+    for (int k = 0; k < d->n_meshes; k++)
+    {
+        const hr_mesh_desc& me = d->meshes[k];
+        HR_CHECK_ARG(me.n_tris >= 0 && (me.positions || me.n_tris == 0));
+        ma.normals = ma.normals && me.normals; any_normals = any_normals || me.normals;
+        ma.material = ma.material && me.tri_material; any_mat = any_mat || me.tri_material;
+        ma.uvs = ma.uvs && me.uvs; ma.tangents = ma.tangents && me.tangents;
+        ma.n_tris += (size_t)me.n_tris;
+        if (me.tri_material)
+        {
+            if (!d->materials) { set_last_error(std::string(who) + ": tri_material given without materials"); return HR_ERR_INVALID_ARG; }
+            if (first_bad_material(me.tri_material, me.n_tris, d->n_materials) >= 0) { set_last_error(std::string(who) + ": a tri_material entry >= n_materials"); return HR_ERR_INVALID_ARG; }
+        }
+    }
+    if (any_normals && !ma.normals) { set_last_error(std::string(who) + ": vertex normals on some meshes only"); return HR_ERR_INVALID_ARG; }
+    if (any_mat && !ma.material) { set_last_error(std::string(who) + ": tri_material on some meshes only"); return HR_ERR_INVALID_ARG; }
+    const size_t T = ma.n_tris;
+    ma.pos.resize(T * 9); ma.nor.resize(ma.normals ? T * 9 : 0); ma.uv.resize(ma.uvs ? T * 6 : 0); ma.tan.resize(ma.tangents ? T * 9 : 0); ma.mat.resize(ma.material ? T : 0);
+    size_t o = 0;
+    for (int k = 0; k < d->n_meshes; k++)
+    {
+        const hr_mesh_desc& me = d->meshes[k];
+        const size_t n = (size_t)me.n_tris;
+        if (n == 0) continue;
+        std::memcpy(&ma.pos[o * 9], me.positions, n * 36);
+        if (ma.normals) std::memcpy(&ma.nor[o * 9], me.normals, n * 36);
+        if (ma.uvs) std::memcpy(&ma.uv[o * 6], me.uvs, n * 24);
+        if (ma.tangents) std::memcpy(&ma.tan[o * 9], me.tangents, n * 36);
+        if (ma.material) std::memcpy(&ma.mat[o], me.tri_material, n * 4);
+        o += n;
+    }
+    return HR_OK;
+}
+
+void hr::build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want_cells, const uint8_t* flags)
+{
+    mt.blas.resize((size_t)d->n_meshes);
+    mt.depth.assign((size_t)d->n_meshes, 0);
+    mt.node_depth.resize((size_t)d->n_meshes);
+    for (int k = 0; k < d->n_meshes; k++)
+    {
+        BuiltBVH& b = mt.blas[(size_t)k];
+        b.want_child_boxes = want_cells;
+        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, b, !(flags && flags[k]));
+        if (want_cells) b.child_boxes.resize(b.nodes.size() * 48, 0.0f);
+        std::vector<int>& dep = mt.node_depth[(size_t)k];
+        dep.assign(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
+        for (size_t j = 0; j < b.nodes.size(); j++)
+            for (int c = 0; c < (b.nodes[j].counts & 15); c++)
+            {
+                dep[(size_t)b.nodes[j].child_base + c] = dep[j] + 1;
+                mt.depth[(size_t)k] = std::max(mt.depth[(size_t)k], dep[j] + 1);
+            }
+    }
+}
+
+void hr::fill_instances(hr_scene* s, const hr_instanced_scene_desc* d, const MeshTrees& mt)
+{
+    const int M = d->n_meshes, I = d->n_instances;
+    std::vector<uint32_t> mesh_tri_base((size_t)M + 1, 0u);
+    s->mesh_bounds.assign((size_t)M * 6, 0.0f);
+    for (int k = 0; k < M; k++)
+    {
+        mesh_tri_base[(size_t)k + 1] = mesh_tri_base[(size_t)k] + (uint32_t)d->meshes[k].n_tris;
+        for (int a = 0; a < 3; a++) { s->mesh_bounds[(size_t)k * 6 + a] = mt.blas[(size_t)k].lo[a]; s->mesh_bounds[(size_t)k * 6 + 3 + a] = mt.blas[(size_t)k].hi[a]; }
+        if (d->meshes[k].n_tris == 0) { s->mesh_bounds[(size_t)k * 6] = 1.0f; s->mesh_bounds[(size_t)k * 6 + 3] = 0.0f; }   // empty: lo > hi
+    }
+    s->n_instances = I;
+    s->inst_mesh.resize((size_t)I);
+    s->inst_host.resize((size_t)I);
+    uint64_t total = 0;
+    for (int i = 0; i < I; i++)
+    {
+        const uint32_t k = d->instances[i].mesh_idx;
+        s->inst_mesh[(size_t)i] = k;
+        InstanceRec& r = s->inst_host[(size_t)i];
+        std::memcpy(r.m, d->instances[i].model_matrix, 64);
+        r.first_tri = (uint32_t)total; r.mesh_tri_base = mesh_tri_base[k]; r.mesh_id = d->instances[i].mesh_id; r.n_tris = (uint32_t)d->meshes[k].n_tris;
+        total += (uint64_t)d->meshes[k].n_tris;
+    }
+}
+
+int hr::top_level_children(const std::vector<BinNode>& bin, int node, int kids[8], int& axis)
+{
+    int nk = 2;
+    kids[0] = bin[(size_t)node].left; kids[1] = bin[(size_t)node].right;
+    while (nk < 8)
+    {
+        int    best = -1;
+        double ba = -1.0;
+        for (int c = 0; c < nk; c++)
+            if (bin[(size_t)kids[c]].inst < 0)
+            {
+                const double ar = imath::half_area3(bin[(size_t)kids[c]].lo, bin[(size_t)kids[c]].hi);
+                if (ar > ba) { ba = ar; best = c; }
+            }
+        if (best < 0) break;
+        const int k = kids[best];
+        kids[best] = bin[(size_t)k].left; kids[nk++] = bin[(size_t)k].right;
+    }
+    const BinNode& me = bin[(size_t)node];
+    axis = 0;
+    if (me.hi[1] - me.lo[1] > me.hi[axis] - me.lo[axis]) axis = 1;
+    if (me.hi[2] - me.lo[2] > me.hi[axis] - me.lo[axis]) axis = 2;
+    return nk;
 }
 
 // hr_scene_get_info of an instanced scene: the exact bounds of the last update, read back on demand (synchronises the device)
@@ -766,20 +798,7 @@ extern "C" {
 
 hr_status hr_scene_create_instanced(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out)
 {
-    try
-    {
-        return create_impl(ctx, desc, out);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_scene_create_instanced: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_scene_create_instanced: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_scene_create_instanced", [&] { return create_impl(ctx, desc, out); });
 }
 
 hr_status hr_scene_update_instances(hr_scene* scene, const float* model_matrices, void* stream)

@@ -11,7 +11,10 @@
 // conservative world boxes, a refit of the top level's boxes (or a fresh SAH top level when the standing one has degraded: the same trigger as
 // the private-copy kind), and two asynchronous copies — the top region of `nodes` and the records.  No vertex is transformed, no mesh node is
 // touched.  Answers are those of the private-copy kind and of a flattened scene bit for bit: see traverse2.h for what keeps them so.
+// Creation validates, builds the meshes' trees, fills the per-instance host fields and stages attributes, materials and textures through the
+// functions the private-copy kind uses (scene_create.h, defined in instances.hip); the top level is collapsed by the same top_level_children.
 #include "hr_internal.h"
+#include "scene_create.h"
 #include "instance_math.h"
 #include <algorithm>
 #include <atomic>
@@ -23,71 +26,6 @@ using namespace hr;
 
 namespace {
 
-hr_status validate_desc(const hr_instanced_scene_desc* d, const char* who)
-{
-    HR_CHECK_ARG(d && d->n_meshes > 0 && d->meshes && d->n_instances > 0 && d->instances);
-    for (int k = 0; k < d->n_meshes; k++) HR_CHECK_ARG(d->meshes[k].n_tris >= 0 && (d->meshes[k].positions || d->meshes[k].n_tris == 0));
-    for (int i = 0; i < d->n_instances; i++)
-    {
-        if (d->instances[i].mesh_idx >= (uint32_t)d->n_meshes) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].mesh_idx >= n_meshes"); return HR_ERR_INVALID_ARG; }
-        if (!finite_matrix(d->instances[i].model_matrix)) { set_last_error(std::string(who) + ": instances[" + std::to_string(i) + "].model_matrix is not finite"); return HR_ERR_INVALID_ARG; }
-    }
-    return HR_OK;
-}
-
-struct MeshTrees
-{
-    std::vector<BuiltBVH> blas;
-    std::vector<int>      depth;    // per mesh: deepest node below the root (root = 0)
-};
-
-// flags (or null): meshes that may deform are built without spatial splits (hr_scene_create_instanced_shared_deformable)
-void build_mesh_trees(const hr_instanced_scene_desc* d, MeshTrees& mt, bool want_cells, const uint8_t* flags = nullptr)
-{
-    mt.blas.resize((size_t)d->n_meshes);
-    mt.depth.assign((size_t)d->n_meshes, 0);
-    for (int k = 0; k < d->n_meshes; k++)
-    {
-        BuiltBVH& b = mt.blas[(size_t)k];
-        b.want_child_boxes = want_cells;
-        build_bvh8(d->meshes[k].positions, d->meshes[k].n_tris, b, !(flags && flags[k]));
-        std::vector<int> dep(b.nodes.size(), 0);   // children follow their parent in the builder's breadth-first order
-        for (size_t j = 0; j < b.nodes.size(); j++)
-            for (int c = 0; c < (b.nodes[j].counts & 15); c++)
-            {
-                dep[(size_t)b.nodes[j].child_base + c] = dep[j] + 1;
-                mt.depth[(size_t)k] = std::max(mt.depth[(size_t)k], dep[j] + 1);
-            }
-    }
-}
-
-// the host-side fields both kinds of instanced scene keep per instance and per mesh (what hr::instanced_scene_boxes reads)
-void fill_instances(hr_scene* s, const hr_instanced_scene_desc* d, const MeshTrees& mt)
-{
-    const int M = d->n_meshes, I = d->n_instances;
-    std::vector<uint32_t> mesh_tri_base((size_t)M + 1, 0u);
-    s->mesh_bounds.assign((size_t)M * 6, 0.0f);
-    for (int k = 0; k < M; k++)
-    {
-        mesh_tri_base[(size_t)k + 1] = mesh_tri_base[(size_t)k] + (uint32_t)d->meshes[k].n_tris;
-        for (int a = 0; a < 3; a++) { s->mesh_bounds[(size_t)k * 6 + a] = mt.blas[(size_t)k].lo[a]; s->mesh_bounds[(size_t)k * 6 + 3 + a] = mt.blas[(size_t)k].hi[a]; }
-        if (d->meshes[k].n_tris == 0) { s->mesh_bounds[(size_t)k * 6] = 1.0f; s->mesh_bounds[(size_t)k * 6 + 3] = 0.0f; }   // empty: lo > hi
-    }
-    s->n_instances = I;
-    s->inst_mesh.resize((size_t)I);
-    s->inst_host.resize((size_t)I);
-    uint64_t total = 0;
-    for (int i = 0; i < I; i++)
-    {
-        const uint32_t k = d->instances[i].mesh_idx;
-        s->inst_mesh[(size_t)i] = k;
-        InstanceRec& r = s->inst_host[(size_t)i];
-        std::memcpy(r.m, d->instances[i].model_matrix, 64);
-        r.first_tri = (uint32_t)total; r.mesh_tri_base = mesh_tri_base[k]; r.mesh_id = d->instances[i].mesh_id; r.n_tris = (uint32_t)d->meshes[k].n_tris;
-        total += (uint64_t)d->meshes[k].n_tris;
-    }
-}
-
 // ---- the top level: the binary SAH tree of instances.hip collapsed to 8-wide nodes whose leaves are instances --------------------------------------
 struct SharedTop
 {
@@ -95,8 +33,6 @@ struct SharedTop
     std::vector<int32_t>                 leaf_inst;
     int                                  max_depth = 0;
 };
-
-using imath::half_area3;
 
 void build_shared_top(const hr_scene* s, SharedTop& tl)
 {
@@ -118,34 +54,15 @@ void build_shared_top(const hr_scene* s, SharedTop& tl)
     for (size_t qi = 0; qi < queue.size(); qi++)
     {
         const Q q = queue[qi];
-        // open the child of largest area until eight children stand (instance leaves cannot be opened)
-        int kids[8], nk = 2;
-        kids[0] = bin[(size_t)q.bin].left; kids[1] = bin[(size_t)q.bin].right;
-        while (nk < 8)
-        {
-            int    best = -1;
-            double ba = -1.0;
-            for (int c = 0; c < nk; c++)
-                if (bin[(size_t)kids[c]].inst < 0)
-                {
-                    const double ar = half_area3(bin[(size_t)kids[c]].lo, bin[(size_t)kids[c]].hi);
-                    if (ar > ba) { ba = ar; best = c; }
-                }
-            if (best < 0) break;
-            const int k = kids[best];
-            kids[best] = bin[(size_t)k].left; kids[nk++] = bin[(size_t)k].right;
-        }
-        const BinNode& me = bin[(size_t)q.bin];
-        int ax = 0;
-        if (me.hi[1] - me.lo[1] > me.hi[ax] - me.lo[ax]) ax = 1;
-        if (me.hi[2] - me.lo[2] > me.hi[ax] - me.lo[ax]) ax = 2;
+        int kids[8], ax;
+        const int nk = top_level_children(bin, q.bin, kids, ax);
         int internal[8], ni = 0;
         hr_scene::SharedTopNode n { 0, 0, (int)queue.size(), (int)tl.leaf_inst.size(), ax, q.depth };
         for (int c = 0; c < nk; c++)
             if (bin[(size_t)kids[c]].inst < 0) internal[ni++] = kids[c];
             else { tl.leaf_inst.push_back(bin[(size_t)kids[c]].inst); n.n_leaves++; }
         // internal children sorted along the node's longest axis: the walk's near-to-far / far-to-near hint (bvh.h)
-        std::stable_sort(internal, internal + ni, [&](int x, int y) { return (double)bin[(size_t)x].lo[ax] + bin[(size_t)x].hi[ax] < (double)bin[(size_t)y].lo[ax] + bin[(size_t)y].hi[ax]; });
+        std::stable_sort(internal, internal + ni, [&](int x, int y) { return bin_before(bin, ax, x, y); });
         n.n_internal = ni;
         for (int c = 0; c < ni; c++) queue.push_back({ internal[c], q.depth + 1 });
         if (ni) tl.max_depth = std::max(tl.max_depth, q.depth + 1);
@@ -215,26 +132,12 @@ float world_pad(const hr_scene* s) { return imath::pad_of_bounds(s->grid_lo, s->
 hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_scene** out, bool deformable_call = false, const uint8_t* flags = nullptr)
 {
     HR_CHECK_ARG(ctx && out);
-    hr_status st = validate_desc(d, deformable_call ? "hr_scene_create_instanced_shared_deformable" : "hr_scene_create_instanced_shared");
-    if (st != HR_OK) return st;
+    HR_TRY(validate_desc(d, deformable_call ? "hr_scene_create_instanced_shared_deformable" : "hr_scene_create_instanced_shared"));
     HR_CHECK_ARG(d->n_materials >= 0 && (d->materials || d->n_materials == 0));
     const int M = d->n_meshes, I = d->n_instances;
-    bool all_normals = true, any_normals = false, all_mat = true, any_mat = false, all_uv = true, all_tan = true;
-    for (int k = 0; k < M; k++)
-    {
-        const hr_mesh_desc& me = d->meshes[k];
-        all_normals = all_normals && me.normals; any_normals = any_normals || me.normals;
-        all_mat = all_mat && me.tri_material; any_mat = any_mat || me.tri_material;
-        all_uv = all_uv && me.uvs; all_tan = all_tan && me.tangents;
-        if (me.tri_material)
-        {
-            if (!d->materials) { set_last_error("hr_scene_create_instanced_shared: tri_material given without materials"); return HR_ERR_INVALID_ARG; }
-            for (int i = 0; i < me.n_tris; i++)
-                if (me.tri_material[i] >= (uint32_t)d->n_materials) { set_last_error("hr_scene_create_instanced_shared: a tri_material entry >= n_materials"); return HR_ERR_INVALID_ARG; }
-        }
-    }
-    if (any_normals && !all_normals) { set_last_error("hr_scene_create_instanced_shared: vertex normals on some meshes only"); return HR_ERR_INVALID_ARG; }
-    if (any_mat && !all_mat) { set_last_error("hr_scene_create_instanced_shared: tri_material on some meshes only"); return HR_ERR_INVALID_ARG; }
+    const char* who = "hr_scene_create_instanced_shared";   // also what the deformable call's messages say from here on
+    MeshAttributes ma;
+    HR_TRY(mesh_attributes(d, who, ma));
     HR_HIP(hipSetDevice(ctx->device));
 
     MeshTrees mt;
@@ -282,61 +185,20 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     if (!shared_top_fits(s, tl)) { set_last_error("hr_scene_create_instanced_shared: top level + deepest mesh tree exceed the traversal stack"); return HR_ERR_UNSUPPORTED; }
     adopt_shared_top(s, tl);
 
-    size_t mesh_tris = 0;
-    for (int k = 0; k < M; k++) mesh_tris += (size_t)d->meshes[k].n_tris;
-    std::vector<float>    mpos(mesh_tris * 9), mnor(all_normals ? mesh_tris * 9 : 0), muv(all_uv ? mesh_tris * 6 : 0), mtan(all_tan ? mesh_tris * 9 : 0);
-    std::vector<uint32_t> mmat(all_mat ? mesh_tris : 0);
+    HR_TRY(upload(s->nodes, nodes.data(), n_nodes * sizeof(Node8)));
+    HR_TRY(upload(s->tris, tris.data(), tris.size() * sizeof(TriGPU)));
+    HR_TRY(upload(s->mesh_positions, ma.pos.data(), ma.n_tris * 36));
+    if (ma.normals) { HR_TRY(upload(s->mesh_normals, ma.nor.data(), ma.n_tris * 36)); s->has_normals = true; }
+    if (ma.material) { HR_TRY(upload(s->mesh_material, ma.mat.data(), ma.n_tris * 4)); s->has_material = true; }
+    // textured materials, per mesh like the other attributes (same checks and layout as hr_scene_create_instanced)
+    HR_TRY(stage_materials(s, d, who));
+    if (s->has_textures)
     {
-        size_t o = 0;
-        for (int k = 0; k < M; k++)
-        {
-            const hr_mesh_desc& me = d->meshes[k];
-            const size_t n = (size_t)me.n_tris;
-            if (n == 0) continue;
-            std::memcpy(&mpos[o * 9], me.positions, n * 36);
-            if (all_normals) std::memcpy(&mnor[o * 9], me.normals, n * 36);
-            if (all_mat) std::memcpy(&mmat[o], me.tri_material, n * 4);
-            if (all_uv) std::memcpy(&muv[o * 6], me.uvs, n * 24);
-            if (all_tan) std::memcpy(&mtan[o * 9], me.tangents, n * 36);
-            o += n;
-        }
+        if (ma.uvs) { HR_TRY(upload(s->mesh_uvs, ma.uv.data(), ma.n_tris * 24)); s->has_uvs = true; }
+        if (ma.tangents) { HR_TRY(upload(s->mesh_tangents, ma.tan.data(), ma.n_tris * 36)); s->has_tangents = true; }
     }
-#define UP(buf, src, nbytes)                                                                     \
-    if ((st = s->buf.alloc(nbytes)) != HR_OK) return st;                                         \
-    if ((nbytes) > 0) { hipError_t e_ = hipMemcpy(s->buf.p, src, nbytes, hipMemcpyHostToDevice); \
-        if (e_ != hipSuccess) { set_last_error(std::string("hipMemcpy H2D failed: ") + hipGetErrorString(e_)); return HR_ERR_HIP; } }
-    UP(nodes, nodes.data(), n_nodes * sizeof(Node8))
-    UP(tris, tris.data(), tris.size() * sizeof(TriGPU))
-    UP(mesh_positions, mpos.data(), mesh_tris * 36)
-    UP(materials, d->materials, d->materials ? (size_t)d->n_materials * 32 : 0)
-    if (all_normals) { UP(mesh_normals, mnor.data(), mesh_tris * 36) s->has_normals = true; }
-    if (all_mat) { UP(mesh_material, mmat.data(), mesh_tris * 4) s->has_material = true; }
-    // textured materials: nothing that takes a shared scene today reads them (queries, G-buffer synthesiser, shadows); they are kept, per mesh
-    // like the other attributes, for the hit shading of the passes that follow (same checks and layout as hr_scene_create_instanced)
-    if (d->material_textures && d->materials && d->n_textures > 0 && d->textures)
-    {
-        std::vector<uint32_t> table;
-        std::vector<uint8_t>  texels;
-        for (int i = 0; i < d->n_textures; i++)
-        {
-            const hr_texture& t = d->textures[i];
-            if (!t.rgba8 || t.width <= 0 || t.height <= 0) { set_last_error("hr_scene_create_instanced_shared: empty texture"); return HR_ERR_INVALID_ARG; }
-            table.insert(table.end(), { (uint32_t)(texels.size() / 4), (uint32_t)t.width, (uint32_t)t.height, 0u });
-            texels.insert(texels.end(), t.rgba8, t.rgba8 + (size_t)t.width * t.height * 4);
-        }
-        for (int i = 0; i < d->n_materials * 4; i++)
-            if (d->material_textures[(i / 4) * 6 + (i % 4)] >= d->n_textures) { set_last_error("hr_scene_create_instanced_shared: material texture index out of range"); return HR_ERR_INVALID_ARG; }
-        UP(mat_tex, d->material_textures, (size_t)d->n_materials * 24)
-        UP(tex_table, table.data(), table.size() * 4)
-        UP(tex_data, texels.data(), texels.size())
-        if (all_uv) { UP(mesh_uvs, muv.data(), mesh_tris * 24) s->has_uvs = true; }
-        if (all_tan) { UP(mesh_tangents, mtan.data(), mesh_tris * 36) s->has_tangents = true; }
-        s->has_textures = true;
-    }
-#undef UP
     s->has_mesh_id = true;
-    if ((st = s->inst_shared.alloc((size_t)I * sizeof(InstanceShared))) != HR_OK) return st;
-    s->n_materials = d->materials ? d->n_materials : 0;
+    HR_TRY(s->inst_shared.alloc((size_t)I * sizeof(InstanceShared)));
     { static std::atomic<uint64_t> next_uid { 1ull << 41 }; s->uid = next_uid.fetch_add(1); }   // disjoint from the other kinds' counters
     if (const char* e = getenv("HR_TOP_LEVEL_REBUILD")) s->auto_rebuild = atoi(e) != 0;
     s->info.n_tris     = (int32_t)n_tris64;
@@ -347,14 +209,14 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     std::vector<float> mats((size_t)I * 16);
     for (int i = 0; i < I; i++) std::memcpy(&mats[(size_t)i * 16], d->instances[i].model_matrix, 64);
     s->top_area_at_build = -1.0;   // the first update records it
-    if ((st = shared_device_tables_upload(s, nullptr, true)) != HR_OK) return st;   // what hr_scene_update_instances_device reads
-    if ((st = shared_scene_update(s, mats.data(), nullptr, false)) != HR_OK) return st;
+    HR_TRY(shared_device_tables_upload(s, nullptr, true));   // what hr_scene_update_instances_device reads
+    HR_TRY(shared_scene_update(s, mats.data(), nullptr, false));
     HR_HIP(hipStreamSynchronize(nullptr));
     if (deformable_call)
     {
         std::vector<int32_t> mesh_n_tris((size_t)M);
         for (int k = 0; k < M; k++) mesh_n_tris[(size_t)k] = d->meshes[k].n_tris;
-        if ((st = shared_deform_adopt(s, mt.blas, mesh_n_tris.data(), flags)) != HR_OK) return st;
+        HR_TRY(shared_deform_adopt(s, mt.blas, mesh_n_tris.data(), flags));
     }
     s->geometry_epoch = 0;
     *out = guard.release();
@@ -364,8 +226,7 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
 hr_status footprint_impl(const hr_instanced_scene_desc* d, int32_t shared, hr_scene_info* info)
 {
     HR_CHECK_ARG(info);
-    hr_status st = validate_desc(d, "hr_instanced_scene_footprint");
-    if (st != HR_OK) return st;
+    HR_TRY(validate_desc(d, "hr_instanced_scene_footprint"));
     std::memset(info, 0, sizeof(*info));
     MeshTrees mt;
     build_mesh_trees(d, mt, false);
@@ -517,38 +378,12 @@ extern "C" {
 
 hr_status hr_scene_create_instanced_shared(hr_ctx* ctx, const hr_instanced_scene_desc* desc, hr_scene** out)
 {
-    try
-    {
-        return create_shared_impl(ctx, desc, out);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_scene_create_instanced_shared: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_scene_create_instanced_shared: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_scene_create_instanced_shared", [&] { return create_shared_impl(ctx, desc, out); });
 }
 
 hr_status hr_scene_create_instanced_shared_deformable(hr_ctx* ctx, const hr_instanced_scene_desc* desc, const uint8_t* deformable, hr_scene** out)
 {
-    try
-    {
-        return create_shared_impl(ctx, desc, out, true, deformable);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_scene_create_instanced_shared_deformable: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_scene_create_instanced_shared_deformable: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_scene_create_instanced_shared_deformable", [&] { return create_shared_impl(ctx, desc, out, true, deformable); });
 }
 
 int32_t hr_scene_is_shared(const hr_scene* scene) { return scene && scene->shared ? 1 : 0; }
@@ -565,20 +400,7 @@ int32_t hr_scene_two_level_passes(const hr_scene* scene) { return scene && scene
 
 hr_status hr_instanced_scene_footprint(const hr_instanced_scene_desc* desc, int32_t shared, hr_scene_info* info)
 {
-    try
-    {
-        return footprint_impl(desc, shared, info);
-    }
-    catch (const std::bad_alloc&)
-    {
-        set_last_error("hr_instanced_scene_footprint: host allocation failed");
-        return HR_ERR_OUT_OF_MEMORY;
-    }
-    catch (const std::exception& e)
-    {
-        set_last_error(std::string("hr_instanced_scene_footprint: ") + e.what());
-        return HR_ERR_UNSUPPORTED;
-    }
+    return guarded("hr_instanced_scene_footprint", [&] { return footprint_impl(desc, shared, info); });
 }
 
 } // extern "C"

@@ -278,3 +278,124 @@ def test_textured_instances(oracle, hr, ctx):
         prev = cur
     for p in (gd, gr, gt, g):
         p.close()
+
+
+# ---- one refusal table for the creators: (kind, defect) -> (status, hr_last_error()) ---------------------------------------------------------------
+KINDS = ("flat", "flat_deformable", "private", "shared", "shared_deformable")
+REFUSALS = {
+    ("flat", "material_range"): (1, "hr_scene_create: tri_material[14] = 5 >= n_materials"),
+    ("flat", "no_materials"): (1, "hr_scene_create: tri_material given without materials"),
+    ("flat", "texture_range"): (1, "hr_scene_create: material texture index out of range"),
+    ("flat", "texture_of_zero_width"): (1, "hr_scene_create: empty texture"),
+    ("flat_deformable", "material_range"): (1, "hr_scene_create: tri_material[14] = 5 >= n_materials"),
+    ("flat_deformable", "no_materials"): (1, "hr_scene_create: tri_material given without materials"),
+    ("flat_deformable", "texture_range"): (1, "hr_scene_create: material texture index out of range"),
+    ("flat_deformable", "texture_of_zero_width"): (1, "hr_scene_create: empty texture"),
+    ("private", "material_range"): (1, "hr_scene_create_instanced: a tri_material entry >= n_materials"),
+    ("private", "no_materials"): (1, "hr_scene_create_instanced: tri_material given without materials"),
+    ("private", "texture_range"): (1, "hr_scene_create_instanced: material texture index out of range"),
+    ("private", "texture_of_zero_width"): (1, "hr_scene_create_instanced: empty texture"),
+    ("private", "normals_on_the_first_mesh_only"): (1, "hr_scene_create_instanced: vertex normals on some meshes only"),
+    ("private", "mesh_idx"): (1, "hr_scene_create_instanced: instances[2].mesh_idx >= n_meshes"),
+    ("private", "matrix"): (1, "hr_scene_create_instanced: instances[1].model_matrix is not finite"),
+    ("shared", "material_range"): (1, "hr_scene_create_instanced_shared: a tri_material entry >= n_materials"),
+    ("shared", "no_materials"): (1, "hr_scene_create_instanced_shared: tri_material given without materials"),
+    ("shared", "texture_range"): (1, "hr_scene_create_instanced_shared: material texture index out of range"),
+    ("shared", "texture_of_zero_width"): (1, "hr_scene_create_instanced_shared: empty texture"),
+    ("shared", "normals_on_the_first_mesh_only"): (1, "hr_scene_create_instanced_shared: vertex normals on some meshes only"),
+    ("shared", "mesh_idx"): (1, "hr_scene_create_instanced_shared: instances[2].mesh_idx >= n_meshes"),
+    ("shared", "matrix"): (1, "hr_scene_create_instanced_shared: instances[1].model_matrix is not finite"),
+    ("shared_deformable", "material_range"): (1, "hr_scene_create_instanced_shared: a tri_material entry >= n_materials"),
+    ("shared_deformable", "no_materials"): (1, "hr_scene_create_instanced_shared: tri_material given without materials"),
+    ("shared_deformable", "texture_range"): (1, "hr_scene_create_instanced_shared: material texture index out of range"),
+    ("shared_deformable", "texture_of_zero_width"): (1, "hr_scene_create_instanced_shared: empty texture"),
+    ("shared_deformable", "normals_on_the_first_mesh_only"): (1, "hr_scene_create_instanced_shared: vertex normals on some meshes only"),
+    ("shared_deformable", "mesh_idx"): (1, "hr_scene_create_instanced_shared_deformable: instances[2].mesh_idx >= n_meshes"),
+    ("shared_deformable", "matrix"): (1, "hr_scene_create_instanced_shared_deformable: instances[1].model_matrix is not finite"),
+}
+
+
+def _defective(kind, defect):
+    """(creator, desc, what the desc points into) of a small textured scene with ONE defect (None: a valid one)"""
+    import ctypes as C
+    import dataclasses
+    from hybrid_rendering_amd import api
+    isd = synth.instanced_cornell(3, seed=1, textured=True)
+    meshes, inst, mt = [dataclasses.replace(m, tri_material=m.tri_material.copy()) for m in isd.meshes], list(isd.instances), isd.material_textures.copy()
+    if defect == "material_range":
+        meshes[1].tri_material[2] = len(isd.materials)
+    if defect == "texture_range":
+        mt[1, 0] = len(isd.textures)
+    if defect == "normals_on_the_first_mesh_only":
+        meshes[1:] = [dataclasses.replace(m, normals=None) for m in meshes[1:]]
+    if defect == "mesh_idx":
+        inst[2] = (inst[2][0], len(meshes), inst[2][2])
+    if defect == "matrix":
+        bad = np.array(inst[1][0], np.float32)
+        bad[5] = np.inf
+        inst[1] = (bad, inst[1][1], inst[1][2])
+    bad_isd = dataclasses.replace(isd, meshes=meshes, instances=inst, material_textures=mt)
+    L = api.lib()
+    if kind.startswith("flat"):
+        sd = dataclasses.replace(isd, material_textures=mt).flatten()
+        if defect == "material_range":
+            sd.tri_material[14] = len(isd.materials)
+        arrs = [np.ascontiguousarray(a, t) for a, t in ((sd.verts, np.float32), (sd.normals, np.float32), (sd.tri_material, np.uint32), (sd.tri_mesh_id, np.uint32),
+                                                          (sd.materials, np.float32), (sd.uvs, np.float32), (sd.tangents, np.float32), (sd.material_textures, np.int32))]
+        tex = [np.ascontiguousarray(t, np.uint8) for t in sd.textures]
+        tarr = (api.hr_texture * len(tex))(*[api.hr_texture(t.ctypes.data, t.shape[1], t.shape[0]) for t in tex])
+        v, n, m, i, mats, uv, tg, mtx = [a.ctypes.data for a in arrs]
+        d = api.hr_scene_desc(v, n, m, i, sd.n_tris, mats, len(sd.materials), uv, tg, mtx, tarr, len(tex))
+        keep = [arrs, tex, tarr]
+        fn = L.hr_scene_create_deformable if kind == "flat_deformable" else L.hr_scene_create
+        create = lambda ctx, h: fn(ctx.h, C.byref(d), C.byref(h))
+    else:
+        d, keep = api._instanced_desc(bad_isd)
+        tarr = keep[0][-1]
+        if kind == "shared_deformable":
+            flags = np.array([0, 1, 1], np.uint8)
+            keep.append(flags)
+            L.hr_scene_create_instanced_shared_deformable.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            create = lambda ctx, h: L.hr_scene_create_instanced_shared_deformable(ctx.h, C.byref(d), C.c_void_p(flags.ctypes.data), C.byref(h))
+        else:
+            fn = L.hr_scene_create_instanced_shared if kind == "shared" else L.hr_scene_create_instanced
+            create = lambda ctx, h: fn(ctx.h, C.byref(d), C.byref(h))
+    if defect == "no_materials":
+        d.materials, d.n_materials = None, 0
+    if defect == "texture_of_zero_width":
+        tarr[0].width = 0
+    return create, d, keep
+
+
+def _refusal(hr, ctx, kind, defect):
+    import ctypes as C
+    create, d, keep = _defective(kind, defect)
+    h = C.c_void_p()
+    st = create(ctx, h)
+    assert not h.value, "a refused creation hands out no scene"
+    return int(st), hr.lib().hr_last_error().decode()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_creators_refuse_bad_descs_with_their_own_words_and_leak_nothing(hr, ctx, kind):
+    """every creator, a valid small textured desc with one defect each: the status, the whole hr_last_error() string, and directly afterwards a valid
+    scene of the same kind is created and answers any-hit queries like the flat scene"""
+    import ctypes as C
+    import torch
+    rays = torch.from_numpy(_rays(2000, 3)).cuda()
+    flat = hr.Scene(ctx, synth.instanced_cornell(3, seed=1, textured=True).flatten())
+    want = flat.any_hit(rays).cpu().numpy()
+    flat.close()
+    assert 0.1 < want.mean() < 0.9
+    defects = [df for (k, df) in REFUSALS if k == kind]
+    assert len(defects) == (4 if kind.startswith("flat") else 7)
+    for defect in defects:
+        got = _refusal(hr, ctx, kind, defect)
+        print(f'    ("{kind}", "{defect}"): {got!r},')
+        assert got == REFUSALS[(kind, defect)], f"{kind}, {defect}"
+        create, d, keep = _defective(kind, None)
+        g = hr.Scene.__new__(hr.Scene)
+        g.h = C.c_void_p()
+        assert create(ctx, g.h) == 0 and g.h.value, f"{kind}: a valid scene after the refusal of {defect}"
+        assert np.array_equal(g.any_hit(rays).cpu().numpy(), want), f"{kind}: any-hit after the refusal of {defect}"
+        g.close()

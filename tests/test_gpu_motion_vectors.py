@@ -348,3 +348,34 @@ def test_errors_enqueue_nothing(hr, ctx):
     ubo = ubo_for(0)
     assert_images_equal(images(flat.gbuffer(ubo, W, H, motion=True)), images(flat.gbuffer(ubo, W, H)), "a flat scene after begin_frame")
     flat.close(); g.close()
+
+
+def test_geometric_normals_on_a_ragged_image_agree_across_the_kinds(hr, ctx):
+    """no mesh carries vertex normals (the geometric-normal branch: curvature is exactly 0) on a 61 x 37 image (lanes past the right and the bottom
+    edge leave early, the last workgroup holds fewer than four tiles): two frames of _mats motion, with and without `motion`, the shared scene equals
+    the private-copy scene in all four images, both equal a deformable flat scene over the flattened vertices in GB2 and depth"""
+    import dataclasses
+    w, h = 61, 37
+    full = synth.instanced_cornell(N_BOXES, seed=SEED)
+    isd = dataclasses.replace(full, meshes=[dataclasses.replace(m, normals=None) for m in full.meshes])
+    bare = lambda mats=None: dataclasses.replace(full.flatten(mats), normals=None)
+    g, gp, gd = hr.InstancedScene(ctx, isd, shared=True), hr.InstancedScene(ctx, isd), hr.Scene(ctx, bare(), deformable=True)
+    for f in range(2):
+        mats = _mats(full, N_BOXES, SEED, f)
+        for s in (g, gp, gd):
+            s.motion_begin_frame()
+        g.update(mats); gp.update(mats)
+        gd.update_vertices(cuda(bare(mats).verts))
+        ubo = ubo_for(f, True, w, h)
+        for motion in (False, True):
+            a, b, c = (images(s.gbuffer(ubo, w, h, motion=motion)) for s in (g, gp, gd))
+            what = f"frame {f}, motion={motion}"
+            covered = float((a["depth"] < 1.0).mean())
+            print(f"{what}: {covered:.3f} of the texels covered")
+            assert covered > 0.5, f"{what}: the scenes must cover something"
+            assert_images_equal(a, b, f"{what}: shared against private copies")
+            assert_images_equal(a, c, f"{what}: instanced against the deformable scene over the flattened vertices", keys=("gb2", "depth"))
+            for kind, img in (("shared", a), ("private", b), ("deformable", c)):
+                assert not img["gb3"][..., 1].any(), f"{what}, {kind}: curvature under geometric normals"
+    for s in (g, gp, gd):
+        s.close()

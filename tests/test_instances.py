@@ -143,3 +143,24 @@ def test_instanced_abi_without_a_gpu():
     assert L.hr_scene_create_instanced(None, None, C.byref(h)) == 1            # HR_ERR_INVALID_ARG, never an exception
     assert L.hr_scene_update_instances(None, None, None) == 1
     assert L.hr_scene_instance_count(None) == 0
+
+
+# (n_boxes, shared) -> (status, n_nodes, max_depth, node_bytes, tri_bytes) of hr_instanced_scene_footprint over synth.instanced_cornell(n_boxes)
+FOOTPRINTS = {
+    (1, False): (0, 4, 1, 320, 1152), (1, True): (0, 5, 1, 400, 1488),
+    (2, False): (0, 6, 1, 480, 1488), (2, True): (0, 6, 1, 480, 1488),
+    (8, False): (0, 18, 2, 1440, 4224), (8, True): (0, 12, 2, 960, 1488),
+    (9, False): (0, 20, 2, 1600, 4800), (9, True): (0, 13, 2, 1040, 1488),
+    (64, False): (0, 130, 3, 10400, 29760), (64, True): (0, 68, 3, 5440, 1488),
+    (65, False): (0, 132, 3, 10560, 30336), (65, True): (0, 69, 3, 5520, 1488),
+    (200, False): (0, 402, 4, 32160, 91776), (200, True): (0, 204, 4, 16320, 1488),
+}
+
+
+@pytest.mark.parametrize("n_boxes,shared", sorted(FOOTPRINTS))
+def test_top_level_shapes_through_the_footprint_call(n_boxes, shared):
+    """hr_instanced_scene_footprint (host only) runs the mesh builds, the instance table and the top-level builder of either kind: one, two, eight
+    and nine children under the root, a second and a third top level — the recorded shapes"""
+    from hybrid_rendering_amd import api
+    st, i = api.instanced_scene_footprint(synth.instanced_cornell(n_boxes), shared)
+    assert (st, i.n_nodes, i.max_depth, int(i.node_bytes), int(i.tri_bytes)) == FOOTPRINTS[(n_boxes, shared)]
