@@ -103,7 +103,19 @@ ABI_SYMBOLS = [
     "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
     "hr_scene_update_instances_device", "hr_scene_device_update_status", "hr_scene_device_update_stats",
     "hr_scene_rebuild_top_level_device", "hr_scene_set_device_rebuild_threshold", "hr_scene_device_rebuild_status", "hr_shared_top_fixed_shape", "hr_shared_top_sort_keys",
+    "hr_scene_set_instance_masks", "hr_scene_set_instance_masks_device", "hr_scene_get_instance_masks", "hr_scene_set_cull_mask", "hr_scene_get_cull_mask",
 ]
+
+# hr_ray_class (include/hr_api_post.h): the ray classes a shared scene keeps a cull mask for
+RAY_QUERY, RAY_PRIMARY, RAY_SHADOW, RAY_AO, RAY_REFLECTION, RAY_GI, RAY_CLASS_COUNT = 0, 1, 2, 3, 4, 5, 6
+# argtypes of the instance-mask entry points (include/hr_api_post.h)
+MASK_ARGTYPES = {
+    "hr_scene_set_instance_masks": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "hr_scene_set_instance_masks_device": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "hr_scene_get_instance_masks": [C.c_void_p, C.c_void_p],
+    "hr_scene_set_cull_mask": [C.c_void_p, C.c_int32, C.c_uint32],
+    "hr_scene_get_cull_mask": [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)],
+}
 
 # argtypes of the device-side instance update's entry points (include/hr_api_stages.h)
 DEVICE_UPDATE_ARGTYPES = {
@@ -501,6 +513,46 @@ class InstancedScene(Scene):
         L.hr_scene_device_rebuild_status.argtypes = DEVICE_UPDATE_ARGTYPES["hr_scene_device_rebuild_status"]
         _check(L.hr_scene_device_rebuild_status(self.h, C.byref(a), C.byref(b), C.byref(c)), "hr_scene_device_rebuild_status")
         return dict(rebuilds_done=int(a.value), launches_enqueued=int(b.value), fixed_shape=int(c.value))
+
+    def _mask_call(self, name):
+        f = getattr(lib(), name)
+        f.argtypes = MASK_ARGTYPES[name]
+        return f
+
+    def set_instance_masks(self, masks, stream=None):
+        """hr_scene_set_instance_masks / _device (shared scenes): one 8-bit mask per instance, in the order of the scene desc.  A numpy array (or
+        anything array-like on the host) is copied before the call returns; a cuda uint8 tensor [n_instances] is read when the kernel RUNS on
+        ``stream`` (default: torch's current stream) — that form may be captured, and a replay picks up the tensor's contents.  A ray walks into
+        an instance iff its mask and the cull mask of the ray's class share a bit (``set_cull_mask``); all masks start at 0xFF."""
+        import torch
+        n = int(lib().hr_scene_instance_count(self.h))
+        if isinstance(masks, torch.Tensor) and masks.is_cuda:
+            assert masks.dtype == torch.uint8 and masks.is_contiguous() and tuple(masks.shape) == (n,), "masks: cuda uint8 contiguous [n_instances]"
+            _check(self._mask_call("hr_scene_set_instance_masks_device")(self.h, _ptr(masks), _stream_ptr(stream)), "hr_scene_set_instance_masks_device")
+            return
+        m = np.ascontiguousarray(np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks))
+        assert m.shape == (n,) and (m.size == 0 or (int(m.min()) >= 0 and int(m.max()) <= 0xFF)), "masks: [n_instances] values in 0..0xFF"
+        m = np.ascontiguousarray(m, np.uint8)
+        _check(self._mask_call("hr_scene_set_instance_masks")(self.h, C.c_void_p(m.ctypes.data), _stream_ptr(stream)), "hr_scene_set_instance_masks")
+
+    def instance_masks(self) -> np.ndarray:
+        """hr_scene_get_instance_masks: the instances' masks, uint8 [n_instances] in the order of the scene desc (synchronises when a device call
+        set them since the host last knew them)"""
+        out = np.zeros(int(lib().hr_scene_instance_count(self.h)), np.uint8)
+        _check(self._mask_call("hr_scene_get_instance_masks")(self.h, C.c_void_p(out.ctypes.data)), "hr_scene_get_instance_masks")
+        return out
+
+    def set_cull_mask(self, cls: int, mask: int):
+        """hr_scene_set_cull_mask: the 8-bit cull mask of ray class ``cls`` (RAY_QUERY .. RAY_GI; 0xFF by default).  Host state, read when a pass or
+        query enqueues its launch: a graph the caller captured keeps the masks of capture time."""
+        assert 0 <= int(mask) <= 0xFFFFFFFF
+        _check(self._mask_call("hr_scene_set_cull_mask")(self.h, C.c_int32(cls), C.c_uint32(int(mask))), "hr_scene_set_cull_mask")
+        return self
+
+    def cull_mask(self, cls: int) -> int:
+        m = C.c_uint32(0)
+        _check(self._mask_call("hr_scene_get_cull_mask")(self.h, C.c_int32(cls), C.byref(m)), "hr_scene_get_cull_mask")
+        return int(m.value)
 
     def update(self, matrices, stream=None):
         """hr_scene_update_instances: matrices [n_instances][16] column-major (host); enqueued on ``stream`` (default: torch's current stream)"""

@@ -55,6 +55,7 @@ struct AOTraceArgs
     float              grid_lo[3], grid_inv_c;
     int                grid_n[3];
     const InstanceShared* inst;    // SHARED only: one record per top-level leaf (instances_shared.hip); last, so that no other member moves
+    uint32_t           cull;       // SHARED only: the scene's HR_RAY_AO cull mask (Scene2::cull)
 };
 
 // Entry-node table (round 5).  Every sample ray of a pixel stays within ray_length of its origin, so the traversals may start at the deepest
@@ -233,9 +234,9 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : 
                 dir = sample_cosine_lobe(N, r0, r1);
             }
 #if AO_COOP2
-            visible = trace_coop2<true>(active, { a.nodes, a.tris, a.inst }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry).prim != 0 && active;
+            visible = trace_coop2<true>(active, { a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry).prim != 0 && active;
 #else
-            if (active) visible = !trace_any2({ a.nodes, a.tris, a.inst }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry);
+            if (active) visible = !trace_any2({ a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry);
 #endif
         }
         else
@@ -580,7 +581,7 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     for (int i = 0; i < 16; i++) a.vpi[i] = in->ubo.view_proj_inverse[i];
     a.depth = in->cur.depth; a.gb2 = (const uint2*)in->cur.gb2; a.sobol = in->sobol; a.sr = in->scrambling_ranking;
     a.mask = (uint32_t*)p->mask.p; a.ray_slots = (uint32_t*)p->ray_slots.p;
-    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p;
+    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p; a.cull = cull_of(scene, HR_RAY_AO);
     a.stats = p->want_stats ? (unsigned long long*)((char*)p->counters.p + 16) : nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw; a.mh = p->mh;
     a.tile_y0 = p->y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(p->y1, 8) - a.tile_y0;

@@ -210,6 +210,7 @@ struct GBufArgs
     const TriGPU*   tris;
     const InstanceShared* inst;    // shared scenes only: the records of the top level's leaves
     int             w, h;
+    uint32_t        cull;          // shared scenes only: the HR_RAY_PRIMARY cull mask (Scene2::cull)
     uint32_t*       gb1;
     uint2*          gb2;
     uint2*          gb3;
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs 
     const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
     const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
     HitOf<TWO_LEVEL> hit;
-    if constexpr (TWO_LEVEL) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.inst }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
+    if constexpr (TWO_LEVEL) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.inst, a.cull }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
     else hit = trace_closest(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
     if (hit.prim < 0)
     {
@@ -772,7 +773,7 @@ hr_status hr_trace_any_hit(const hr_scene* scene, int64_t n, const float* rays, 
     if (n == 0) return HR_OK;
     if (scene->shared)
     {
-        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene), (long long)n, rays, out, (unsigned long long*)stats);
+        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out, (unsigned long long*)stats);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -788,7 +789,7 @@ hr_status hr_trace_closest_hit(const hr_scene* scene, int64_t n, const float* ra
     if (n == 0) return HR_OK;
     if (scene->shared)
     {
-        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene), (long long)n, rays, out_tuv, out_prim);
+        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out_tuv, out_prim);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -821,6 +822,7 @@ static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, 
     for (int i = 0; i < 3; i++) a.cam[i] = ubo->cam_pos[i];
     a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p;
     a.inst = sh ? (const InstanceShared*)scene->inst_shared.p : nullptr;
+    a.cull = cull_of(scene, HR_RAY_PRIMARY);
     a.normals = scene->has_normals ? (const float*)(sh ? scene->mesh_normals.p : scene->tri_normals.p) : nullptr;
     a.tri_material = scene->has_material ? (const uint32_t*)(sh ? scene->mesh_material.p : scene->tri_material.p) : nullptr;
     a.tri_mesh_id = scene->has_mesh_id && !sh ? (const uint32_t*)scene->tri_mesh_id.p : nullptr;

@@ -61,7 +61,9 @@ struct alignas(16) InstanceShared
     float    inv[9];         // column-major inverse of mat3(m) (host, double, rounded once)
     float    inv_abs_row[3]; // per object axis k: sum_j |inv(k, j)|
     float    extent;         // sum_j (|m(j, 3)| + sum_k |m(j, k)| max|p_k| over the mesh's bounds): the instance's world magnitude
-    uint32_t flags;          // bit 0: no object-space culling (the matrix has no safe inverse)
+    uint32_t flags;          // bit 0: no object-space culling (the matrix has no safe inverse).  Bits 8..15: the instance's mask
+                             // (VkAccelerationStructureInstanceKHR::mask; 0xFF at creation, hr_scene_set_instance_masks): a ray walks into the
+                             // instance iff mask & the ray's cull mask != 0.  It belongs to the INSTANCE: every writer of a record keeps it
     uint32_t first_tri;      // global index of the instance's first triangle
     uint32_t mesh_tri_base;  // index of the mesh's first triangle in the concatenated per-mesh attribute arrays
     uint32_t mesh_id;        // GB3.z of the instance's pixels
@@ -71,12 +73,15 @@ struct alignas(16) InstanceShared
     uint32_t pad[2];
 };
 static_assert(sizeof(InstanceShared) == 160, "InstanceShared must be 160 bytes");
+constexpr uint32_t kInstanceMaskShift = 8u, kInstanceMaskBits = 0xFFu << kInstanceMaskShift;   // InstanceShared::flags
 // what the two-level walk (traverse2.h) reads of a shared instanced scene
 struct Scene2
 {
     const Node8*          nodes;
     const TriGPU*         tris;
     const InstanceShared* inst;
+    uint32_t              cull;    // the ray's cull mask (hr_scene_set_cull_mask, per ray class; 0xFF: every instance), SHIFTED to the place of the
+                                   // instance mask in InstanceShared::flags: the walk's test is one AND (hr_internal.h scene2_of)
 };
 
 // deepest 8-wide tree the traversal's per-lane stack can walk (one entry per level, traverse.h LaneStack)

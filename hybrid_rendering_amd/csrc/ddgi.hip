@@ -118,10 +118,10 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
         // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
         // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if DDGI_COOP2
-        h = trace_coop2<false>(valid, { a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        h = trace_coop2<false>(valid, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
 #else
         h.prim = -1;
-        if (valid) h = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (valid) h = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
 #endif
     }
     else

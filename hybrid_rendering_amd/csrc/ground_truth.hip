@@ -80,7 +80,8 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
             adds[depth] = mk3(0.0f, 0.0f, 0.0f);
             rays++;
             HitOf<SHARED> h;
-            if constexpr (SHARED) h = trace_closest2(tc.sc, o, d, t_min, 10000.0f, s_stack, lane);
+            if constexpr (SHARED)   // the camera ray, then the bounces: their own ray classes (tc's is the visibility rays')
+                h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] }, o, d, t_min, 10000.0f, s_stack, lane);
             else h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
             if (h.prim < 0)
             {

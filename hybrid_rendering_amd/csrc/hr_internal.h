@@ -359,7 +359,7 @@ struct hr_scene
     // `uploads_done` is recorded behind them, and the next call that rewrites a mirror waits for it first (instances.hip wait_uploads)
     hipEvent_t    uploads_done = nullptr;
     bool          uploads_pending = false;
-    ~hr_scene() { if (uploads_done) (void)hipEventDestroy(uploads_done); }
+    ~hr_scene() { if (uploads_done) (void)hipEventDestroy(uploads_done); if (mask_stage) (void)hipHostFree(mask_stage); }
     int           max_rel_depth = 0;              // deepest node below an instance root (a fresh top level must leave room for it)
     std::vector<int32_t>  level_offsets;          // level_nodes[level_offsets[d] .. level_offsets[d + 1]): the nodes of depth d
     std::vector<uint32_t> inst_mesh;              // per instance: mesh index
@@ -392,6 +392,16 @@ struct hr_scene
     bool          order_replayed = false;         // a device re-build was CAPTURED: replays re-order the leaves where geometry_epoch cannot follow, so
                                                   // caches of the passes that hold top-level node indices (AO's entry table) are rebuilt at every use
     bool          mirrors_stale = false;          // a device update ran: inst_host / inst_box / top_nodes_host / shared_host lag the device
+    // instance masks and per-ray-class cull masks (instances_shared_masks.hip).  The instance masks live in the records (bvh.h InstanceShared::flags);
+    // inst_mask is the host's knowledge of them, by instance of the scene desc — stale (mirrors_stale) after hr_scene_set_instance_masks_device until
+    // shared_mirrors_refresh reads the records back.  cull_mask is host state, read when a pass or query enqueues its launch
+    std::vector<uint8_t>  inst_mask;
+    uint32_t      cull_mask[HR_RAY_CLASS_COUNT] = { 0xFFu, 0xFFu, 0xFFu, 0xFFu, 0xFFu, 0xFFu };
+    hr::DevBuf    mask_dev;                       // the host form's device staging, [n_instances] bytes; allocated by its first call
+    uint8_t*      mask_stage = nullptr;           // ... and its pinned source, guarded by uploads_done like the other staging
+    hipStream_t   mask_stream = nullptr;          // of the last hr_scene_set_instance_masks_device
+    bool          masks_on_device = false;        // ... which a read-back has to wait for
+    bool          masks_captured = false;         // ... enqueued on a capturing stream: replays rewrite the masks unseen
     // ---- deforming geometry (deform_refit.hip): trees built without spatial splits, refitted under new vertices through `deform` and node_box.
     // deform.hip: a flat scene (`deformable`); hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`.  instances_shared_deform.hip: the
     // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
@@ -406,5 +416,7 @@ struct hr_scene
 };
 
 namespace hr {
-inline Scene2 scene2_of(const hr_scene* s) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p }; }
+// the cull mask of a ray class in the place of the instance mask in a record's flags: what Scene2::cull holds
+inline uint32_t cull_of(const hr_scene* s, int ray_class) { return (s->cull_mask[ray_class] & 0xFFu) << kInstanceMaskShift; }
+inline Scene2 scene2_of(const hr_scene* s, int ray_class) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p, cull_of(s, ray_class) }; }
 } // namespace hr

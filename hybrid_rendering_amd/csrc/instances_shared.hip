@@ -113,6 +113,7 @@ void fill_record(const hr_scene* s, int i, InstanceShared& r)
     r.first_tri = h.first_tri; r.mesh_tri_base = h.mesh_tri_base; r.mesh_id = h.mesh_id; r.n_tris = h.n_tris;
     r.mesh_root = s->shared_mesh_root[k]; r.instance = (uint32_t)i;
     imath::record_terms(h.m, &s->shared_mesh_absmax[(size_t)k * 3], r.inv, r.inv_abs_row, &r.extent, &r.flags);
+    r.flags |= (uint32_t)s->inst_mask[(size_t)i] << kInstanceMaskShift;   // the instance's mask goes wherever its record goes (bvh.h)
 }
 
 void adopt_shared_top(hr_scene* s, const SharedTop& tl)
@@ -147,6 +148,7 @@ hr_status create_shared_impl(hr_ctx* ctx, const hr_instanced_scene_desc* d, hr_s
     s->ctx = ctx; s->shared = true;
     fill_instances(s, d, mt);
     s->top_cap = std::max(1, I);
+    s->inst_mask.assign((size_t)I, 0xFFu);
     uint64_t n_nodes64 = (uint64_t)s->top_cap, n_refs64 = 0, n_tris64 = 0;
     for (int k = 0; k < M; k++) { n_nodes64 += mt.blas[(size_t)k].nodes.size(); n_refs64 += mt.blas[(size_t)k].tris.size(); }
     for (int i = 0; i < I; i++) n_tris64 += s->inst_host[(size_t)i].n_tris;

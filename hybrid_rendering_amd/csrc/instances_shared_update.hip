@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(256) k_shared_records(const RecordArgs a)
             for (int k = 0; k < 16; k++) r.m[k] = m[k];
             for (int k = 0; k < 9; k++) r.inv[k] = inv[k];
             for (int k = 0; k < 3; k++) r.inv_abs_row[k] = iar[k];
-            r.extent = extent; r.flags = flags;
+            r.extent = extent; r.flags = (r.flags & kInstanceMaskBits) | flags;   // the instance's mask stays
         }
         imath::world_box(m, mt.bounds, box);
         for (int k = 0; k < 6; k++) a.inst_box[(size_t)i * 6 + k] = box[k];
@@ -473,8 +473,13 @@ namespace {
 hr_status wait_for_device_update(const hr_scene* s)
 {
     HR_HIP(hipSetDevice(s->ctx->device));
-    if (s->dev_update && !s->dev_update->captured) HR_HIP(hipStreamSynchronize(s->dev_update->last_stream));
-    else HR_HIP(hipDeviceSynchronize());
+    if (s->masks_captured || (s->masks_on_device && !s->dev_update)) HR_HIP(hipDeviceSynchronize());
+    else
+    {
+        if (s->masks_on_device) HR_HIP(hipStreamSynchronize(s->mask_stream));   // hr_scene_set_instance_masks_device: the records it wrote
+        if (s->dev_update && !s->dev_update->captured) HR_HIP(hipStreamSynchronize(s->dev_update->last_stream));
+        else HR_HIP(hipDeviceSynchronize());
+    }
     return HR_OK;
 }
 } // namespace
@@ -507,8 +512,14 @@ hr_status hr::shared_mirrors_refresh(hr_scene* s)
         HR_HIP(hipMemcpy(s->shared_leaf_inst.data(), s->dev_leaf_inst.p, I * 4, hipMemcpyDeviceToHost));
         HR_HIP(hipMemcpy(s->shared_leaf_of.data(), s->dev_leaf_of.p, I * 4, hipMemcpyDeviceToHost));
     }
-    for (size_t i = 0; i < I; i++) std::memcpy(s->inst_host[i].m, s->shared_host[(size_t)s->shared_leaf_of[i]].m, 64);
-    s->mirrors_stale = s->dev_update && s->dev_update->captured;   // sticky: a replay may rewrite the records at any time
+    for (size_t i = 0; i < I; i++)
+    {
+        const InstanceShared& r = s->shared_host[(size_t)s->shared_leaf_of[i]];
+        std::memcpy(s->inst_host[i].m, r.m, 64);
+        s->inst_mask[i] = (uint8_t)((r.flags & kInstanceMaskBits) >> kInstanceMaskShift);   // hr_scene_set_instance_masks_device wrote them unseen
+    }
+    s->masks_on_device = false;
+    s->mirrors_stale = (s->dev_update && s->dev_update->captured) || s->masks_captured;   // sticky: a replay may rewrite the records at any time
     if (s->dev_update) s->dev_update->stream_waits++;
     return HR_OK;
 }

@@ -186,10 +186,10 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
         // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
         // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if REFL_COOP2
-        hit = trace_coop2<false>(trace, { a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        hit = trace_coop2<false>(trace, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
 #else
         hit.prim = -1;
-        if (trace) hit = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (trace) hit = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
 #endif
     }
     else

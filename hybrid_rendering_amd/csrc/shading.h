@@ -459,6 +459,9 @@ struct SceneShading
     // SHARED instanced scenes (null otherwise; tri_instance / inst are null then: no per-triangle array exists): the two-level walk's Hit2 names
     // the record, the attributes are indexed by inst_shared[hit.inst].mesh_tri_base + hit.local
     const InstanceShared* inst_shared;
+    // ... and the scene's cull masks by ray class (hr_ray_class), each in the place Scene2::cull wants it: a hit-shading kernel fires its own class
+    // and HR_RAY_SHADOW (direct_lighting's light and sky rays)
+    uint32_t cull[HR_RAY_CLASS_COUNT];
 };
 // fills the members above from a scene (host)
 static inline void scene_shading_from(const hr_scene* scene, SceneShading& sh)
@@ -476,6 +479,7 @@ static inline void scene_shading_from(const hr_scene* scene, SceneShading& sh)
     sh.mat_tex      = scene->has_textures ? (const int32_t*)scene->mat_tex.p : nullptr;
     sh.tex_table    = scene->has_textures ? (const uint4*)scene->tex_table.p : nullptr;
     sh.tex_data     = scene->has_textures ? (const uint32_t*)scene->tex_data.p : nullptr;
+    for (int c = 0; c < HR_RAY_CLASS_COUNT; c++) sh.cull[c] = cull_of(scene, c);
 }
 struct SurfaceHit
 {
@@ -683,7 +687,7 @@ template <bool TWO_LEVEL> using HitOf      = typename std::conditional<TWO_LEVEL
 template <bool TWO_LEVEL>
 HR_DEV TraceCtxOf<TWO_LEVEL> make_trace_ctx(const Node8* nodes, const TriGPU* tris, const SceneShading& sh, uint32_t* wave_stack, int lane)
 {
-    if constexpr (TWO_LEVEL) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared }, wave_stack, lane };
+    if constexpr (TWO_LEVEL) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared, sh.cull[HR_RAY_SHADOW] }, wave_stack, lane };
     else return TraceCtx { nodes, tris, wave_stack, lane };
 }
 

@@ -42,6 +42,7 @@ struct TraceArgs
     const uint32_t* order;     // nullable: launch slot -> tile, heaviest tiles of the last frame first (tile_order.h)
     uint16_t*       cost;      // nullable: per tile, how long its wave lived (100 MHz ticks)
     const InstanceShared* inst; // SHARED only: one record per top-level leaf (instances_shared.hip); last, so that no other member moves
+    uint32_t        cull;       // SHARED only: the scene's HR_RAY_SHADOW cull mask (Scene2::cull)
 };
 
 // One wave = one 8x8 pixel tile = two 8x4 mask words; lane l -> pixel (l & 7, l >> 3), so the
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             if (att > 0.0f)
             {
                 fired = true;
-                if constexpr (SHARED) lit = !trace_any2({ a.nodes, a.tris, a.inst }, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
+                if constexpr (SHARED) lit = !trace_any2({ a.nodes, a.tris, a.inst, a.cull }, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
                 else
                 {
                     // Occluder cache: "is ANY triangle hit in (t_min, t_max)" is a pure function of the geometry, so testing one particular
@@ -775,7 +776,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     a.depth = in->cur.depth; a.gb2 = (const uint2*)in->cur.gb2;
     a.sobol = in->sobol; a.sr = in->scrambling_ranking;
     a.mask = (uint32_t*)p->mask.p; a.ray_slots = (uint16_t*)p->ray_slots.p;
-    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p;
+    a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p; a.cull = cull_of(scene, HR_RAY_SHADOW);
     a.stats = nullptr;
     a.timeline = nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw;

@@ -32,12 +32,14 @@ struct BoxRay
     float    idx, idy, idz;
     float    wx, wy, wz;
     uint32_t sel;
+    uint32_t keep;   // 0xff, or 0 inside an instance whose mask rejects the ray (enter_instance): test_node2 then reports no child hit
 };
 
 HR_DEV void boxray_world(BoxRay& b, const RayPre& r)
 {
     b.o = r.o; b.idx = r.idx; b.idy = r.idy; b.idz = r.idz; b.sel = r.sel;
     b.wx = 0.0f; b.wy = 0.0f; b.wz = 0.0f;
+    b.keep = 0xffu;
 }
 
 // HR_SHARED_CLAMP_REACH: a component of d' below the 1e-18 clamp is replaced by it, which moves the computed ray by up to t * 1e-18 object units along
@@ -100,7 +102,7 @@ HR_DEV NodeHits test_node2(const NodeRaw& n, const BoxRay& r, float t_near, floa
             hits |= (tn <= tf) ? (1u << (half * 4 + k)) : 0u;
         }
     }
-    h.hit8 = hits & ((1u << (q0.w >> 28)) - 1u);
+    h.hit8 = hits & ((1u << (q0.w >> 28)) - 1u) & r.keep;
     return h;
 }
 
@@ -124,9 +126,19 @@ HR_DEV uint4 load_instance_in(const InstanceShared* __restrict__ inst, uint32_t 
     return i3;
 }
 
+// Instance masks (hr_scene_set_instance_masks / hr_scene_set_cull_mask; Vulkan's rule): a ray walks into an instance iff the instance's mask — bits
+// 8..15 of the record's flags, in quad 7, which the entry holds anyway — and the ray's cull mask (Scene2::cull, shifted to the same bits) share a
+// bit.  A rejected instance does not exist for the ray.  The rejection is DATA, not control flow: the entry clears BoxRay::keep, the test of the
+// mesh's root node then reports no child hit, and both walks leave the instance through the path they take after any instance they have walked
+// to the end — their state machines (the entries parked under sp_base in trace2; the ballot, append and flush section that every lane of
+// trace_coop2 executes each iteration) are the ones of a scene without masks.  A rejected instance costs its record and one node test; a branch
+// at the entry instead saves that node and costs the trace kernels 3 to 13 % of their time when nothing is masked (docs/EXPERIMENTS.md,
+// "Instance masks").  All-0xFF masks, the default, reject nothing and change no bit of any answer.
+
 // loads record `slot`, moves the box-test ray into the instance's object space, returns the mesh root
-HR_DEV uint32_t enter_instance(const InstanceShared* __restrict__ inst, uint32_t slot, f3 o, f3 d, InstanceIn& in, BoxRay& b)
+HR_DEV uint32_t enter_instance(const Scene2& sc, uint32_t slot, f3 o, f3 d, InstanceIn& in, BoxRay& b)
 {
+    const InstanceShared* __restrict__ inst = sc.inst;
     const uint4  i3 = load_instance_in(inst, slot, in);
     const uint4* p  = reinterpret_cast<const uint4*>(inst + slot);
     const uint4  i0 = p[4], i1 = p[5], i2 = p[6], i4 = p[8];
@@ -142,6 +154,7 @@ HR_DEV uint32_t enter_instance(const InstanceShared* __restrict__ inst, uint32_t
     const float W = HR_SHARED_SLACK * (((fabsf(ow.x) + fabsf(ow.y)) + fabsf(ow.z)) + extent);
     const float dmax = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
     boxray_object(b, oo, od, mk3(W * nrm.x, W * nrm.y, W * nrm.z), mk3(nrm.x * dmax, nrm.y * dmax, nrm.z * dmax), no_cull);
+    b.keep = (i3.y & sc.cull) != 0u ? 0xffu : 0u;
     return i4.z;
 }
 
@@ -199,7 +212,7 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
             {
                 slot = pend_base + (uint32_t)__builtin_ctz(pend);
                 pend &= pend - 1u;
-                cur = (enter_instance(sc.inst, slot, o, d, in, br) << 9) | 1u;
+                cur = (enter_instance(sc, slot, o, d, in, br) << 9) | 1u;
                 inside = true;
             }
             else if (inside)
@@ -337,7 +350,7 @@ HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, 
                 {
                     slot = ipend_base + (uint32_t)__builtin_ctz(ipend);
                     ipend &= ipend - 1u;
-                    cur = (enter_instance(sc.inst, slot, o, d, in, br) << 9) | 1u;
+                    cur = (enter_instance(sc, slot, o, d, in, br) << 9) | 1u;
                     inside = true;
                 }
                 else if (inside)

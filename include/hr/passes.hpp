@@ -104,6 +104,14 @@ public:
     // call allocates: not under stream capture), then gbuffer_raycast_motion() in the place of hr_gbuffer_raycast (dynamic scenes)
     void     motion_begin_frame(Stream cmd_buf) { check(hr_scene_motion_begin_frame(m_scene, cmd_buf), "hr_scene_motion_begin_frame"); }
     void     gbuffer_raycast_motion(const hr_ubo& ubo, int32_t width, int32_t height, void* gb1, void* gb2, void* gb3, float* depth, Stream cmd_buf) const { check(hr_gbuffer_raycast_motion(m_scene, &ubo, width, height, gb1, gb2, gb3, depth, cmd_buf), "hr_gbuffer_raycast_motion"); }
+    // a shared scene only: one 8-bit mask per instance (desc order; 0xFF at creation) and one 8-bit cull mask per hr_ray_class (0xFF by default) — a
+    // ray walks into an instance iff the two share a bit.  Host masks are copied before the call returns; device masks are read when the kernel
+    // runs on cmd_buf (capturable).  Cull masks are read when a pass or query enqueues its launch
+    void     set_instance_masks(const uint8_t* masks, Stream cmd_buf) { check(hr_scene_set_instance_masks(m_scene, masks, cmd_buf), "hr_scene_set_instance_masks"); }
+    void     set_instance_masks_device(const uint8_t* device_masks, Stream cmd_buf) { check(hr_scene_set_instance_masks_device(m_scene, device_masks, cmd_buf), "hr_scene_set_instance_masks_device"); }
+    void     instance_masks(uint8_t* masks_out) const { check(hr_scene_get_instance_masks(m_scene, masks_out), "hr_scene_get_instance_masks"); }
+    void     set_cull_mask(hr_ray_class ray_class, uint32_t mask) { check(hr_scene_set_cull_mask(m_scene, (int32_t)ray_class, mask), "hr_scene_set_cull_mask"); }
+    uint32_t cull_mask(hr_ray_class ray_class) const { uint32_t m = 0xFFu; check(hr_scene_get_cull_mask(m_scene, (int32_t)ray_class, &m), "hr_scene_get_cull_mask"); return m; }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }
     uint64_t id() const { return hr_scene_id(m_scene); }   // dw::Scene::id()
     ~Scene() { hr_scene_destroy(m_scene); }

@@ -107,6 +107,15 @@ hr_status hr_scene_motion_begin_frame(hr_scene* scene, void* stream);
 hr_status hr_gbuffer_raycast_motion(const hr_scene* scene, const hr_ubo* ubo, int32_t width, int32_t height, void* gb1, void* gb2, void* gb3,
                                     float* depth, void* stream);
 
+/* ---- instance masks (Vulkan's: a ray walks into an instance iff instance mask & the ray class's cull mask != 0) -- */
+/* Shared instanced scenes only (others: HR_ERR_INVALID_ARG); all masks start at 0xFF.  The instance-mask setters are ordered on `stream`. */
+typedef enum { HR_RAY_QUERY = 0, HR_RAY_PRIMARY = 1, HR_RAY_SHADOW = 2, HR_RAY_AO = 3, HR_RAY_REFLECTION = 4, HR_RAY_GI = 5, HR_RAY_CLASS_COUNT = 6 } hr_ray_class;
+hr_status hr_scene_set_instance_masks(hr_scene* scene, const uint8_t* masks /* HOST [n_instances], desc order; copied before return */, void* stream);
+hr_status hr_scene_set_instance_masks_device(hr_scene* scene, const uint8_t* masks /* DEVICE [n_instances]; capturable */, void* stream);
+hr_status hr_scene_get_instance_masks(const hr_scene* scene, uint8_t* masks_out /* HOST; synchronises */);
+hr_status hr_scene_set_cull_mask(hr_scene* scene, int32_t ray_class, uint32_t mask /* <= 0xFF; read when a pass or query enqueues */);
+hr_status hr_scene_get_cull_mask(const hr_scene* scene, int32_t ray_class, uint32_t* mask);
+
 /* ---- self test ------------------------------------------------------------------------------------ */
 /* Evaluates the device-side arithmetic of the numerical contract on arrays so tests can
  * compare it bit for bit with a CPU replay.  which: 0 sincos(x)->(s,c)  1 exp(x)  2 log(x)  3 pow(x,y)

@@ -18,7 +18,11 @@ top-level re-builds and the mesh updates that follow exercise the read-back of t
 rejected matrix and no violated bound.
 --device-rebuild (implies --device): a device re-build of the top level (hr_scene_rebuild_top_level_device) after a random subset of the device
 updates, and a re-build threshold (hr_scene_set_device_rebuild_threshold, 1.2 to 2) on a random half of the scenes; the forced HOST re-builds
-stay in, so the scenes go back and forth between the SAH shape and the fixed one."""
+stay in, so the scenes go back and forth between the SAH shape and the fixed one.
+--masks (implies --shared; with any of the above): before every step's queries the scene takes random instance masks (through the host form or,
+every other time, from device memory) and a random RAY_QUERY cull mask, and the queries are compared with hr_scene_create over the flattened
+VISIBLE subset (triangle indices mapped back to the full scene's); the masks therefore ride through every update, re-build and read-back of the
+other switches.  They are set back to 0xFF before the passes are compared with the oracle."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,13 +40,16 @@ if MOTION:
     sys.argv.remove("--motion")
     if DEFORM:
         sys.exit("--motion compares with a private-copy scene, which cannot deform: not with --deform")
+MASKS = "--masks" in sys.argv
+if MASKS:
+    sys.argv.remove("--masks")
 DEVICE_REBUILD = "--device-rebuild" in sys.argv
 if DEVICE_REBUILD:
     sys.argv.remove("--device-rebuild")
 DEVICE = "--device" in sys.argv or DEVICE_REBUILD
 if "--device" in sys.argv:
     sys.argv.remove("--device")
-SHARED = "--shared" in sys.argv or DEFORM or DEVICE
+SHARED = "--shared" in sys.argv or DEFORM or DEVICE or MASKS
 if "--shared" in sys.argv:
     sys.argv.remove("--shared")
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -174,6 +181,16 @@ for trial in range(n):
                     if not np.array_equal(im[0][k], im[1][k]): msg.append(f"step {step}: motion G-buffer {k}: shared against private copies")
                     if k in ("gb2", "depth") and not np.array_equal(im[0][k], im[2][k]): msg.append(f"step {step}: motion G-buffer {k}: against the flattened deformable scene")
             gf = hr.Scene(ctx, flat_sd)
+            gq, keep = gf, None   # what the queries are compared with: the flattened scene, or (--masks) the flattened visible subset
+            if MASKS:
+                im = rng.choice([0, 0xFF, 1, 2, 6, 0x80], I).astype(np.uint8)
+                cm = int(rng.choice([0xFF, 0xFF, 1, 3, 6, 0x81]))
+                g.set_instance_masks(torch.from_numpy(im).cuda() if rng.rand() < 0.5 else im)
+                g.set_cull_mask(hr.RAY_QUERY, cm)
+                if not np.array_equal(g.instance_masks(), im): msg.append(f"step {step}: instance_masks() differs from what was set")
+                keep = np.flatnonzero(im & cm)
+                sub = synth.InstancedSceneData(meshes=isd.meshes, instances=[isd.instances[i] for i in keep], materials=materials)
+                gq = hr.Scene(ctx, sub.flatten(mats[keep])) if len(keep) and sub.flatten(mats[keep]).n_tris else None
             lo, hi = flat_sd.bounds()
             rays = np.zeros((20000, 8), np.float32)
             rays[:, :3] = rng.uniform(np.maximum(lo, -100) - 5, np.minimum(hi, 200) + 5, (20000, 3))
@@ -181,7 +198,18 @@ for trial in range(n):
             rays[:, 3] = np.where(rng.rand(20000) < 0.3, rng.uniform(1, 30, 20000), 1e4); rays[:, 7] = 0.01
             rd = torch.from_numpy(rays).cuda()
             a, (ta, pa) = g.any_hit(rd).cpu().numpy(), [t.cpu().numpy() for t in g.closest_hit(rd)]
-            b, (tb, pb) = gf.any_hit(rd).cpu().numpy(), [t.cpu().numpy() for t in gf.closest_hit(rd)]
+            if gq is None:   # nothing visible: every ray misses
+                b, tb, pb = np.zeros_like(a), ta, np.full_like(pa, -1)
+                if (pa >= 0).any(): msg.append(f"step {step}: a scene with no visible instance is hit")
+            else:
+                b, (tb, pb) = gq.any_hit(rd).cpu().numpy(), [t.cpu().numpy() for t in gq.closest_hit(rd)]
+            if keep is not None and gq is not None:
+                # the subset numbers its triangles densely: back to the full scene's (first_tri of the kept instance + the local index)
+                first, _, _, cnt = isd.layout()
+                ends = np.cumsum(cnt[keep].astype(np.int64))
+                j = np.searchsorted(ends, pb[pb >= 0], side="right")
+                pb = pb.copy(); pb[pb >= 0] = (first[keep][j].astype(np.int64) + (pb[pb >= 0] - (ends - cnt[keep])[j])).astype(np.int32)
+                gq.close()
             if not (np.array_equal(a, b) and np.array_equal(pa, pb) and np.array_equal(ta.view(np.uint32), tb.view(np.uint32))):
                 msg.append(f"step {step}: queries differ (any {int((a != b).sum())}, prim {int((pa != pb).sum())})")
             gi, fi_ = g.refresh_info(), gf.info
@@ -191,6 +219,8 @@ for trial in range(n):
             elif list(gi.bounds_lo) != list(fi_.bounds_lo) or list(gi.bounds_hi) != list(fi_.bounds_hi):
                 msg.append(f"step {step}: bounds differ")
             gf.close()
+        if MASKS:
+            g.set_instance_masks(np.full(I, 0xFF, np.uint8)); g.set_cull_mask(hr.RAY_QUERY, 0xFF)
         if trial % 4 == 0 and I <= 130:
             # the passes against the oracle's instanced scene on the last state
             W, H = 96, 72

@@ -25,7 +25,11 @@ warm-up: the device re-build; hr_scene_rebuild_top_level on a twin that has just
 it needs); a device update with the threshold off and with a threshold that never fires (what the predicated launches add to a frame on which
 nothing is re-built), one by one and back to back.  Then, on the scene of main() after `--frames` frames of motion through device updates: the
 shadows trace stage on the device-built top level against a fresh host SAH top level over the same matrices (masks must be equal), and the
-ratio of their half-area sums (numpy, over the nodes and records read back: top_area_np below)."""
+ratio of their half-area sums (numpy, over the nodes and records read back: top_area_np below).
+--shared --hidden FRACTION: after the figures above, that share of the movers is hidden by instance mask (hr_scene_set_instance_masks: mask 0,
+a seeded random subset) and the shadows trace stage is timed again on the same G-buffer: `shadow_trace_ms_hidden` next to
+`shadow_trace_ms_refitted` is what despawning by mask buys; the mask image must equal the one of a shared scene created from the visible
+subset."""
 import argparse, json, math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--passes", action="store_true", help="with --shared: AO / DDGI / reflections trace stages, shared against private copies")
     ap.add_argument("--device", action="store_true", help="with --shared: hr_scene_update_instances_device against the host update, per frame")
     ap.add_argument("--device-rebuild", action="store_true", help="with --shared: hr_scene_rebuild_top_level_device against the host re-build, and the trace on either tree")
+    ap.add_argument("--hidden", type=float, default=0.0, help="with --shared: hide this share of the movers by instance mask and time the shadow trace again")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--host-only", action="store_true", help="with --shared --device: time the host path alone")
     ap.add_argument("--rounds", type=int, default=3)
@@ -103,7 +108,18 @@ def main():
     gb = flat.gbuffer(ubo, W, H)
     fi = hr.frame_inputs(gb, gb, ubo, 0, 0, sob_d, sr_d)
     out = {}
-    for tag, sc in (("refitted", g), ("rebuilt", flat)):
+    runs = [("refitted", g), ("rebuilt", flat)]
+    if a.hidden > 0.0:
+        assert a.shared, "--hidden hides instances of a shared scene by mask: give --shared"
+        gone = np.sort(1 + np.random.RandomState(7).permutation(a.movers)[:int(round(a.hidden * a.movers))])
+        keep = [i for i in range(a.movers + 1) if i not in set(gone.tolist())]
+        last = instances(a.frames)
+        runs += [("hidden", g), ("subset", hr.InstancedScene(ctx, synth.InstancedSceneData(isd.meshes, [last[i] for i in keep], isd.materials), shared=True))]
+    for tag, sc in runs:
+        if tag == "hidden":   # behind the timing of the unmasked scene
+            masks = np.full(a.movers + 1, 0xFF, np.uint8)
+            masks[gone] = 0
+            g.set_instance_masks(masks)
         p = hr.RayTracedShadows(ctx, W, H)
         p.params.exact = 0
         for k in range(6):
@@ -123,6 +139,11 @@ def main():
     res["shadow_trace_ms_refitted"] = round(out["refitted"][1]["ray_trace"], 4)
     res["shadow_trace_ms_rebuilt"] = round(out["rebuilt"][1]["ray_trace"], 4)
     res["masks_equal"] = True
+    if a.hidden > 0.0:
+        assert np.array_equal(out["hidden"][0], out["subset"][0]), "masks differ between the masked scene and the scene created from the visible subset"
+        res["hidden_instances"] = int(len(gone))
+        res["shadow_trace_ms_hidden"] = round(out["hidden"][1]["ray_trace"], 4)
+        res["shadow_trace_ms_subset"] = round(out["subset"][1]["ray_trace"], 4)
     if a.shared:
         res["kind"] = "shared"
     print(json.dumps(res))
