@@ -466,7 +466,7 @@ __global__ __launch_bounds__(64 * FT_WAVES, FT_SHADOWS_EU) void kf_shadows_tempo
 
 // ------------------------------------------------------------------------------------------------------------------------
 // shadows_denoise_atrous.comp:94-174 + copy_shadow_tiles (tile class), tolerance mode.  STEP > 0: compile-time tap distance and
-// radius 1 (the reference default, fully unrolled); STEP == 0: run-time step and radius.
+// radius 1 (the reference default, fully unrolled: atrous_gather_pixel); STEP == 0: run-time step and radius.
 struct EdgeK { float kz, phi_n, inv_phi_l; bool n32; };
 HR_DEV float edge_weight_fast(const EdgeK& k, float cd, float sd, f3 cn, f3 sn, float cl, float sl)
 {
@@ -479,10 +479,118 @@ HR_DEV float edge_weight_fast(const EdgeK& k, float cd, float sd, f3 cn, f3 sn, 
     return fm::exp2f_((wL + wZ) * -1.44269504088896341f) * wN;
 }
 
+// One pixel of a live tile for kf_shadows_atrous<STEP > 0>: every load first, in one batch, then the arithmetic.  INTERIOR: the
+// workgroup's whole footprint is resident, no bounds test; else a texel that is not resident is fetched at the centre's address
+// and counts as 0 (variance) / gets weight 0 (tap).  Two whole copies of the pixel on purpose: with only the loads in the two
+// branches the compiler merges the geometry loads behind the join and waits for the value loads before it issues them.
+template <int STEP, bool N32, bool INTERIOR>
+HR_DEV void atrous_gather_pixel(const AtrousArgs& a, int x, int y, uint32_t o)
+{
+    uint32_t v_in[9], t_in[8];
+    uint2    t_nd[8];
+    bool     t_ok[8];
+    const uint32_t c   = fm::ld<uint32_t>(a.in.p, o * 4u);
+    const uint2    cnd = fm::ld<uint2>(a.nd, o * 8u);   // oct normal (fp16 x 2), mesh id | linear z (fp16 x 2)
+#pragma unroll
+    for (int k = 0; k < 9; k++)
+    {
+        const int xx = k % 3 - 1, yy = k / 3 - 1, px = x + xx, py = y + yy;
+        if (k == 4) { v_in[k] = c; continue; }
+        if (INTERIOR) v_in[k] = fm::ld<uint32_t>(a.in.p, (uint32_t)(py * a.w + px) * 4u);
+        else
+        {
+            const bool     res = px >= 0 && px < a.w && py >= a.y0 && py < a.y1;   // a texel that is not resident is 0 (ImgRG16F::raw)
+            const uint32_t vv  = fm::ld<uint32_t>(a.in.p, (res ? (uint32_t)(py * a.w + px) : o) * 4u);
+            v_in[k] = res ? vv : 0u;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 8; t++)
+    {
+        const int k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
+        const int px = x + xx * STEP, py = y + yy * STEP;
+        // a tap outside the image is skipped; one outside the resident rows of a band reads zeros, whose weight is 0 (halo
+        // rows only): both get weight 0 below
+        const bool     res = INTERIOR || (px >= 0 && py >= 0 && px < a.w && py < a.h && py >= a.y0 && py < a.y1);
+        const uint32_t so  = res ? (uint32_t)(py * a.w + px) : o;
+        t_ok[t] = res;
+        t_in[t] = fm::ld<uint32_t>(a.in.p, so * 4u);
+        t_nd[t] = fm::ld<uint2>(a.nd, so * 8u);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // nothing of the arithmetic (and none of its waits) in front of a load
+    // compute_variance_center (:65-88): 3x3 gaussian of the variance channel, unit taps
+    float var = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; k++)
+    {
+        const int   xx = k % 3 - 1, yy = k / 3 - 1;
+        const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
+        var += fm::hi(v_in[k]) * kw;
+    }
+    const float cz = fm::hi(cnd.y);
+    const f3    cn = fm::oct_unit(cnd.x);
+    const float cv = fm::lo(c);
+    EdgeK ek;
+    ek.kz        = 1.44269504088896341f * fm::rcp(a.sigma_depth);
+    ek.phi_n     = a.phi_normal;
+    ek.n32       = N32;
+    ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
+    float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
+#pragma unroll
+    for (int t = 0; t < 8; t++)
+    {
+        const int   k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
+        const float kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
+        const float sv = fm::lo(t_in[t]);
+        float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(t_nd[t].y), cn, fm::oct_unit(t_nd[t].x), cv, sv), kk);
+        if (!t_ok[t]) wv = 0.0f;
+        sum_w += wv;
+        sum_v += wv * sv;
+        sum_var += (wv * wv) * fm::hi(t_in[t]);
+    }
+    const float iw = fm::rcp(sum_w);
+    float ov = sum_v * iw;
+    const float ovar = sum_var * (iw * iw);
+    if (a.power != 0.0f) ov = fm::powf_(fm::fmax_(ov, 0.0f), a.power);
+    const uint32_t result = cz < 0.0f ? c : fm::pack2(ov, ovar);   // a sky centre passes through: its taps were fetched for nothing
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out) + o * 4u) = result;
+    if (a.out2) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) = result;
+}
+
 template <int STEP, bool N32>
 __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
 {
     const uint2 BLK = block_xy<0>();
+    if constexpr (STEP > 0)
+    {
+        // Radius 1, compile-time tap distance: ONE vector round trip per live wave (it was three: tile class -> centre -> taps).  The
+        // classes of the workgroup's four tiles (32 x 8 pixels = four tiles of one tile row; a.y0 is a multiple of 8) come through a
+        // wave-uniform fetch — the two aligned dwords that hold the four bytes, shifted: the class image is readable 8 bytes past its
+        // last tile — and every texel the pixel needs (centre, 3x3 variance, 8 taps: value + geometry record) is then requested at
+        // once, at addresses that are resident whatever the centre turns out to be; a sky centre (linear z < 0: rare inside a live
+        // tile) throws its taps away afterwards.
+        const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+        const int fx0 = (int)BLK.x * 32, fy0 = a.y0 + (int)BLK.y * 8;
+        if (fx0 >= a.w) return;   // a padding column of the launch (block_map.h grid_cols)
+        const uint32_t  tb   = (uint32_t)(fy0 >> 3) * (uint32_t)a.tiles_x + (uint32_t)(fx0 >> 3);
+        const uint32_t* tc   = reinterpret_cast<const uint32_t*>(a.tile_class) + (tb >> 2);
+        const uint32_t  cls4 = (uint32_t)(((uint64_t)tc[0] | ((uint64_t)tc[1] << 32)) >> ((tb & 3u) * 8u));
+        const int x = fx0 + lx, y = fy0 + ly;
+        if (x >= a.w || y >= a.y1) return;
+        const uint32_t o = (uint32_t)(y * a.w + x);
+        if (!((cls4 >> ((lx >> 3) * 8)) & 0xffu))
+        {
+            *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out) + o * 4u) = 0u; // shadows_denoise_copy_shadow_tiles.comp:35
+            if (a.out2) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) = 0u;
+            return;
+        }
+        // a workgroup whose whole footprint lies inside the resident rows needs no bounds test at all (uniform branch)
+        const bool interior = fx0 - STEP >= 0 && fx0 + 31 + STEP < a.w && fy0 - STEP >= (a.y0 > 0 ? a.y0 : 0) && fy0 + 7 + STEP < (a.y1 < a.h ? a.y1 : a.h);
+        if (interior) atrous_gather_pixel<STEP, N32, true>(a, x, y, o);
+        else atrous_gather_pixel<STEP, N32, false>(a, x, y, o);
+        return;
+    }
+    // STEP == 0: run-time tap distance and radius
     const int x = BLK.x * 32 + (threadIdx.x & 31);
     const int y = a.y0 + BLK.y * 8 + (threadIdx.x >> 5);
     if (x >= a.w || y >= a.y1) return;
@@ -495,8 +603,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
         if (out2p) *out2p = 0u;
         return;
     }
-    const int step = STEP > 0 ? STEP : a.step;
-    const int R    = STEP > 0 ? 1 : a.radius;
+    const int step = a.step, R = a.radius;
     // a workgroup whose whole footprint lies inside the resident rows needs no bounds test at all (uniform branch)
     const int  fx0 = (int)BLK.x * 32, fy0 = a.y0 + (int)BLK.y * 8;
     const int  reach = step * R > 1 ? step * R : 1;
@@ -537,73 +644,24 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
         ek.n32       = N32;
         ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
         float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
-        if (STEP > 0)
-        {
-            uint32_t t_in[8];
-            uint2    t_nd[8];
-            bool     t_ok[8];
-            if (interior)
+        for (int yy = -R; yy <= R; yy++)
+            for (int xx = -R; xx <= R; xx++)
             {
-#pragma unroll
-                for (int t = 0; t < 8; t++)
-                {
-                    const int      k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-                    const uint32_t so = (uint32_t)((y + yy * STEP) * a.w + (x + xx * STEP));
-                    t_ok[t] = true;
-                    t_in[t] = fm::ld<uint32_t>(a.in.p, so * 4u);
-                    t_nd[t] = fm::ld<uint2>(a.nd, so * 8u);
-                }
-            }
-            else
-            {
-#pragma unroll
-                for (int t = 0; t < 8; t++)
-                {
-                    const int k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-                    const int px = x + xx * STEP, py = y + yy * STEP;
-                    // a tap outside the image is skipped; one outside the resident rows of a band reads zeros, whose weight is 0 (halo
-                    // rows only): both get weight 0 below
-                    const bool     res = px >= 0 && py >= 0 && px < a.w && py < a.h && py >= a.y0 && py < a.y1;
-                    const uint32_t so  = res ? (uint32_t)(py * a.w + px) : o;
-                    t_ok[t] = res;
-                    t_in[t] = fm::ld<uint32_t>(a.in.p, so * 4u);
-                    t_nd[t] = fm::ld<uint2>(a.nd, so * 8u);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 8; t++)
-            {
-                const int   k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-                const float kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
-                const float sv = fm::lo(t_in[t]);
-                float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(t_nd[t].y), cn, fm::oct_unit(t_nd[t].x), cv, sv), kk);
-                if (!t_ok[t]) wv = 0.0f;
+                const int px = x + xx * step, py = y + yy * step;
+                if (px < 0 || py < 0 || px >= a.w || py >= a.h || (xx == 0 && yy == 0)) continue;
+                const int   axx = xx < 0 ? -xx : xx, ayy = yy < 0 ? -yy : yy;
+                const float kx = axx == 0 ? 1.0f : (axx == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
+                const float ky = ayy == 0 ? 1.0f : (ayy == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
+                if (py < a.y0 || py >= a.y1) continue;   // outside the resident rows of a band: zeros, weight 0
+                const uint32_t so = (uint32_t)(py * a.w + px);
+                const uint32_t s  = fm::ld<uint32_t>(a.in.p, so * 4u);
+                const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
+                const float sv = fm::lo(s);
+                const float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(nd.y), cn, fm::oct_unit(nd.x), cv, sv), kx * ky);
                 sum_w += wv;
                 sum_v += wv * sv;
-                sum_var += (wv * wv) * fm::hi(t_in[t]);
+                sum_var += (wv * wv) * fm::hi(s);
             }
-        }
-        else
-        {
-            for (int yy = -R; yy <= R; yy++)
-                for (int xx = -R; xx <= R; xx++)
-                {
-                    const int px = x + xx * step, py = y + yy * step;
-                    if (px < 0 || py < 0 || px >= a.w || py >= a.h || (xx == 0 && yy == 0)) continue;
-                    const int   axx = xx < 0 ? -xx : xx, ayy = yy < 0 ? -yy : yy;
-                    const float kx = axx == 0 ? 1.0f : (axx == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
-                    const float ky = ayy == 0 ? 1.0f : (ayy == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
-                    if (py < a.y0 || py >= a.y1) continue;   // outside the resident rows of a band: zeros, weight 0
-                    const uint32_t so = (uint32_t)(py * a.w + px);
-                    const uint32_t s  = fm::ld<uint32_t>(a.in.p, so * 4u);
-                    const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
-                    const float sv = fm::lo(s);
-                    const float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(nd.y), cn, fm::oct_unit(nd.x), cv, sv), kx * ky);
-                    sum_w += wv;
-                    sum_v += wv * sv;
-                    sum_var += (wv * wv) * fm::hi(s);
-                }
-        }
         const float iw = fm::rcp(sum_w);
         float ov = sum_v * iw;
         const float ovar = sum_var * (iw * iw);

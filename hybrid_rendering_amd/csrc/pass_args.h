@@ -62,7 +62,7 @@ struct AtrousArgs
 {
     ImgRG16F       in;
     const float4*  nd;      // decoded normal + linear z of every pixel (k_shadows_temporal)
-    const uint8_t* tile_class;
+    const uint8_t* tile_class;   // readable 8 bytes past its last tile (kf_shadows_atrous fetches a workgroup's four classes as aligned dwords)
     uint32_t*      out;
     uint32_t*      out2;    // feedback copy (prev_image) or nullptr
     int            w, h, y0, y1, tiles_x;

@@ -653,7 +653,8 @@ hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height
     A(atrous[0], px * 4)
     A(atrous[1], px * 4)
     A(upsample, (size_t)full_width * full_height * 2)
-    A(tile_class, (size_t)p->tiles_x * p->tiles_y)
+    // + 8 readable bytes: kf_shadows_atrous fetches the classes of a workgroup's four tiles as the two aligned dwords that hold them
+    A(tile_class, (((size_t)p->tiles_x * p->tiles_y + 3) & ~(size_t)3) + 8)
     A(nd, px * 16)
     A(counters, 64)
     A(ray_slots, (size_t)p->tiles_x * p->tiles_y * 2)
