@@ -104,6 +104,7 @@ ABI_SYMBOLS = [
     "hr_scene_update_instances_device", "hr_scene_device_update_status", "hr_scene_device_update_stats",
     "hr_scene_rebuild_top_level_device", "hr_scene_set_device_rebuild_threshold", "hr_scene_device_rebuild_status", "hr_shared_top_fixed_shape", "hr_shared_top_sort_keys",
     "hr_scene_set_instance_masks", "hr_scene_set_instance_masks_device", "hr_scene_get_instance_masks", "hr_scene_set_cull_mask", "hr_scene_get_cull_mask",
+    "hr_scene_set_alpha_cutoffs", "hr_scene_get_alpha_cutoffs", "hr_scene_set_ray_class_opaque", "hr_scene_get_ray_class_opaque",
 ]
 
 # hr_ray_class (include/hr_api_post.h): the ray classes a shared scene keeps a cull mask for
@@ -115,6 +116,14 @@ MASK_ARGTYPES = {
     "hr_scene_get_instance_masks": [C.c_void_p, C.c_void_p],
     "hr_scene_set_cull_mask": [C.c_void_p, C.c_int32, C.c_uint32],
     "hr_scene_get_cull_mask": [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)],
+}
+
+# argtypes of the cutout-material entry points (include/hr_api_post.h)
+CUTOUT_ARGTYPES = {
+    "hr_scene_set_alpha_cutoffs": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "hr_scene_get_alpha_cutoffs": [C.c_void_p, C.c_void_p],
+    "hr_scene_set_ray_class_opaque": [C.c_void_p, C.c_int32, C.c_int32],
+    "hr_scene_get_ray_class_opaque": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
 }
 
 # argtypes of the device-side instance update's entry points (include/hr_api_stages.h)
@@ -216,7 +225,7 @@ class Scene:
     ``update_vertices`` replaces on the GPU (the BVH is refitted; ``refit_cost`` / ``rebuild`` for when the refitted tree has gone bad)."""
 
     def __init__(self, ctx: Context, sd, deformable: bool = False):
-        self.ctx, self.deformable = ctx, bool(deformable)
+        self.ctx, self.deformable, self.n_materials = ctx, bool(deformable), len(sd.materials)
         self._keep = [np.ascontiguousarray(sd.verts, np.float32), None if sd.normals is None else np.ascontiguousarray(sd.normals, np.float32),
                       np.ascontiguousarray(sd.tri_material, np.uint32), np.ascontiguousarray(sd.tri_mesh_id, np.uint32),
                       np.ascontiguousarray(sd.materials, np.float32)]
@@ -302,6 +311,48 @@ class Scene:
         _check(lib().hr_trace_closest_hit(self.h, C.c_int64(rays.shape[0]), _ptr(rays), _ptr(tuv), _ptr(prim), _stream_ptr(stream)), "hr_trace_closest_hit")
         return tuv, prim
 
+    # ---- alpha-tested cutout materials.  Flat, deformable and shared instanced scenes; a private-copy instanced scene raises
+    # HRError (HR_ERR_UNSUPPORTED).  Bad arguments are refused here, before the library is touched.
+    def _cutout_call(self, name):
+        f = getattr(lib(), name)
+        f.argtypes = CUTOUT_ARGTYPES[name]
+        return f
+
+
+    def set_alpha_cutoffs(self, cutoffs, stream=None):
+        """hr_scene_set_alpha_cutoffs: one cutoff per material (host, copied before the call returns; <= 0: opaque, the default).  A hit on a
+        triangle of material m whose albedo texture's alpha at the hit is below cutoffs[m] does not exist for the ray.  A cutoff above 0 needs an
+        albedo texture on the material and uvs in the scene.  Ordered on ``stream`` (default: torch's current stream)."""
+        c = np.asarray(cutoffs)
+        if c.ndim != 1 or c.shape[0] != self.n_materials:
+            raise ValueError(f"cutoffs: one value per material ({self.n_materials}), got shape {c.shape}")
+        c = np.ascontiguousarray(c, np.float32)
+        if not np.all(np.isfinite(c)):
+            raise ValueError("cutoffs: every value must be finite")
+        _check(self._cutout_call("hr_scene_set_alpha_cutoffs")(self.h, C.c_void_p(c.ctypes.data), _stream_ptr(stream)), "hr_scene_set_alpha_cutoffs")
+        return self
+
+    def alpha_cutoffs(self) -> np.ndarray:
+        """hr_scene_get_alpha_cutoffs: float32 [n_materials] as last set (zeros before the first call)"""
+        out = np.zeros(self.n_materials, np.float32)
+        _check(self._cutout_call("hr_scene_get_alpha_cutoffs")(self.h, C.c_void_p(out.ctypes.data)), "hr_scene_get_alpha_cutoffs")
+        return out
+
+    def set_ray_class_opaque(self, cls: int, force_opaque: bool = True):
+        """hr_scene_set_ray_class_opaque: rays of class ``cls`` (RAY_QUERY .. RAY_GI) skip the alpha test (gl_RayFlagsOpaqueEXT: the reference's
+        behaviour) or, the default, run it.  Host state, read when a pass or query enqueues its launch."""
+        if not (isinstance(cls, (int, np.integer)) and 0 <= int(cls) < RAY_CLASS_COUNT):
+            raise ValueError(f"ray class {cls!r} is outside [0, {RAY_CLASS_COUNT})")
+        _check(self._cutout_call("hr_scene_set_ray_class_opaque")(self.h, C.c_int32(int(cls)), C.c_int32(1 if force_opaque else 0)), "hr_scene_set_ray_class_opaque")
+        return self
+
+    def ray_class_opaque(self, cls: int) -> bool:
+        if not (isinstance(cls, (int, np.integer)) and 0 <= int(cls) < RAY_CLASS_COUNT):
+            raise ValueError(f"ray class {cls!r} is outside [0, {RAY_CLASS_COUNT})")
+        v = C.c_int32(0)
+        _check(self._cutout_call("hr_scene_get_ray_class_opaque")(self.h, C.c_int32(int(cls)), C.byref(v)), "hr_scene_get_ray_class_opaque")
+        return bool(v.value)
+
     def motion_begin_frame(self, stream=None):
         """hr_scene_motion_begin_frame: remember the geometry as "previous frame" — once per frame, BEFORE that frame's update calls, on their
         stream.  The first call allocates (not under stream capture); a plain hr_scene_create scene takes it as a no-op."""
@@ -372,7 +423,7 @@ class InstancedScene(Scene):
     spatial splits and ``update_meshes`` replaces its vertices on the GPU (``mesh_refit_cost`` for when its refitted tree has gone bad)."""
 
     def __init__(self, ctx: Context, isd, shared: bool = False, deformable=None):
-        self.ctx, self.isd, self.shared = ctx, isd, bool(shared)
+        self.ctx, self.isd, self.shared, self.n_materials = ctx, isd, bool(shared), len(isd.materials)
         d, self._keep = _instanced_desc(isd)
         self.h = C.c_void_p()
         if deformable is not None:

@@ -213,7 +213,9 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
     roughnessFactor) + emissiveFactor.  One mesh id per (node, primitive).  The reference loads meshes/*.gltf through assimp
     (common.cpp:347-488).  TEXCOORD_0, TANGENT and the PNG images behind baseColorTexture / normalTexture /
     metallicRoughnessTexture (roughness = G, metallic = B) become SceneData.uvs / tangents / material_textures / textures
-    (the hit shaders' fetch_* inputs); images in other encodings (JPEG) are skipped, the factor then applies."""
+    (the hit shaders' fetch_* inputs); images in other encodings (JPEG) are skipped, the factor then applies.
+    alphaMode MASK fills alpha_cutoffs[m] with alphaCutoff (default 0.5) divided by a baseColorFactor alpha other than 1; OPAQUE and BLEND give 0.
+    Nothing applies the array by itself: pass it to Scene.set_alpha_cutoffs."""
     import base64
     import json
     raw = open(path, "rb").read()
@@ -279,7 +281,7 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
                 image_slot[src] = -1
         return image_slot[src]
 
-    mats, mat_tex = [], []
+    mats, mat_tex, cutoffs = [], [], []
     for m in doc.get("materials", []):
         pbr = m.get("pbrMetallicRoughness", {})
         bc = pbr.get("baseColorFactor", [1, 1, 1, 1])
@@ -288,9 +290,15 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
         bct, nrm = texture_slot(pbr.get("baseColorTexture")), texture_slot(m.get("normalTexture"))
         mr = texture_slot(pbr.get("metallicRoughnessTexture"))
         mat_tex.append([bct, nrm, mr, mr, 1, 2])
+        # alphaMode MASK: texel alpha * baseColorFactor alpha < alphaCutoff is cut away; the back end compares the texel alone, so the factor is folded in
+        cut = float(m.get("alphaCutoff", 0.5)) if m.get("alphaMode", "OPAQUE") == "MASK" else 0.0
+        if cut > 0.0 and float(bc[3]) != 1.0:
+            cut = cut / float(bc[3]) if float(bc[3]) > 0.0 else float(np.finfo(np.float32).max)
+        cutoffs.append(cut)
     default_mat = len(mats)
     mats.append([0.8, 0.8, 0.8, 0.0, 0.5, 0.0, 0.0, 0.0])
     mat_tex.append([-1, -1, -1, -1, 1, 2])
+    cutoffs.append(0.0)
 
     verts, norms, tmat, tmesh, uvs, tans = [], [], [], [], [], []
     mesh_id = [0]
@@ -393,7 +401,8 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
         if not inst:
             raise ValueError(f"{path}: no triangle primitives")
         return InstancedSceneData(meshes=meshes, instances=inst, materials=np.asarray(mats, np.float32), name=os.path.basename(path),
-                                  material_textures=np.asarray(mat_tex, np.int32) if textures else None, textures=textures if textures else None)
+                                  material_textures=np.asarray(mat_tex, np.int32) if textures else None, textures=textures if textures else None,
+                                  alpha_cutoffs=np.asarray(cutoffs, np.float32))
     if not verts:
         raise ValueError(f"{path}: no triangle primitives")
     sd = SceneData(verts=np.ascontiguousarray(np.concatenate(verts), np.float32), normals=np.ascontiguousarray(np.concatenate(norms), np.float32),
@@ -404,6 +413,7 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
         sd.tangents = np.ascontiguousarray(np.concatenate(tans), np.float32)
         sd.material_textures = np.asarray(mat_tex, np.int32)
         sd.textures = textures
+    sd.alpha_cutoffs = np.asarray(cutoffs, np.float32)
     return sd
 
 

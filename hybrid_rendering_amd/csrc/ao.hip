@@ -8,6 +8,7 @@
 #include "hr_internal.h"
 #include "reproject.h"
 #include "traverse2.h"
+#include "cutout_host.h"
 #include "mask_window.h"
 #include "upsample.h"
 #include "pass_args.h"
@@ -118,6 +119,9 @@ extern "C" int hr_debug_divergence_ao(uint64_t* out, int reset)
 #ifndef AO_TRACE_SHARED_EU
 #define AO_TRACE_SHARED_EU 4   // SHARED: the two-level walk keeps the instance's matrix and both box-test rays live: under the bound of 6 it spills
 #endif
+#ifndef AO_TRACE_CUTOUT_EU
+#define AO_TRACE_CUTOUT_EU 4   // CUTOUT instantiations, flat and SHARED
+#endif
 // one sample's visibility bits of the tile -> the two 8x4 mask words of plane `m`
 HR_DEV void ao_store_mask_rows(const AOTraceArgs& a, uint32_t* m, int tx, int ty, unsigned long long bits)
 {
@@ -129,10 +133,13 @@ HR_DEV void ao_store_mask_rows(const AOTraceArgs& a, uint32_t* m, int tx, int ty
 // two-level walk of traverse2.h.  The entry node is a TOP-LEVEL node there: entry_node_for_box stops at the first node with a leaf — an
 // instance — among the children that overlap the ball, and k_ao_entry_grid builds the pass's table with it, so both stay above the mesh trees.
 // <STATS, false> is the kernel as it was.
-template <bool STATS, bool SHARED = false>
-__global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : AO_TRACE_EU) void k_ao_trace(AOTraceArgs a)
+// CUTOUT: the walks run the alpha test (cutout.h) through `cv`; the host picks it iff cutout_on(scene, HR_RAY_AO).  Its register bound is its own
+// (AO_TRACE_CUTOUT_EU): the uv and texel addressing do not fit under the opaque kernel's.
+template <bool STATS, bool SHARED = false, bool CUTOUT = false>
+__global__ __launch_bounds__(64 * AO_TRACE_WAVES, CUTOUT ? AO_TRACE_CUTOUT_EU : SHARED ? AO_TRACE_SHARED_EU : AO_TRACE_EU) void k_ao_trace(AOTraceArgs a, CutoutView cv)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(STATS && CUTOUT) && !(CUTOUT && AO_SEQ), "no statistics or -DAO_SEQ build of the cutout walks");
     static_assert(!(SHARED && AO_SEQ), "-DAO_SEQ walks one level: it cannot trace a shared instanced scene");
     __shared__ uint32_t s_stack[AO_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if AO_COOP && !AO_SEQ
@@ -234,9 +241,9 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : 
                 dir = sample_cosine_lobe(N, r0, r1);
             }
 #if AO_COOP2
-            visible = trace_coop2<true>(active, { a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry).prim != 0 && active;
+            visible = trace_coop2<true, CUTOUT>(active, { a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry, cv).prim != 0 && active;
 #else
-            if (active) visible = !trace_any2({ a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry);
+            if (active) visible = !trace_any2<CUTOUT>({ a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry, cv);
 #endif
         }
         else
@@ -250,7 +257,7 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : 
                 const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
                 dir = sample_cosine_lobe(N, r0, r1);
             }
-            visible = trace_coop<true, AO_ORDER>(active, a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry).prim != 0 && active;
+            visible = trace_coop<true, AO_ORDER, CUTOUT>(active, a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry, nullptr, cv).prim != 0 && active;
         }
         else
 #endif
@@ -259,7 +266,9 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, SHARED ? AO_TRACE_SHARED_EU : 
             const int   idx = (int)a.num_frames * a.spp + s;
             const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
             const f3    dir = sample_cosine_lobe(N, r0, r1);
-            visible         = !trace_any<STATS, AO_ORDER>(a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, nn, nt, entry HR_DIV(, &dv));
+            DivCounters* dvp = nullptr;
+            HR_DIV(dvp = &dv;)
+            visible         = !trace_any<STATS, AO_ORDER, CUTOUT>(a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, nn, nt, entry, dvp, nullptr, cv);
         }
         const unsigned long long bits = __ballot(visible);
         if (lane == 0) ao_store_mask_rows(a, a.mask + (size_t)s * a.mh * a.mw, tx, ty, bits);
@@ -567,6 +576,9 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     HR_REJECT_SHARED(scene, "hr_ao_ray_trace");
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     HR_REJECT_SHARED_DEV(scene, "hr_ao_ray_trace", p->want_stats);
+    HR_REJECT_CUTOUT(scene, HR_RAY_AO, "hr_ao_ray_trace", p->want_stats);
+    const bool       cutout = cutout_on(scene, HR_RAY_AO);
+    const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     if (p->first_frame)
@@ -642,13 +654,13 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     }
     if (p->want_stats)
     {
-        hipLaunchKernelGGL(k_ao_trace<true>, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
+        hipLaunchKernelGGL(k_ao_trace<true>, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a, cv);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
     int ev = p->prof.begin("ray_trace", st, px * 12 + px * prm->spp / 8);
-    if (scene->shared) hipLaunchKernelGGL((k_ao_trace<false, true>), dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(k_ao_trace<false>, dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a);
+    if (scene->shared) hipLaunchKernelGGL((cutout ? k_ao_trace<false, true, true> : k_ao_trace<false, true>), dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a, cv);
+    else hipLaunchKernelGGL((cutout ? k_ao_trace<false, false, true> : k_ao_trace<false>), dim3(cdiv(n_tiles, AO_TRACE_WAVES)), dim3(64 * AO_TRACE_WAVES), 0, st, a, cv);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     if (a.cost)

@@ -8,6 +8,7 @@
 #include "traverse.h"
 #include "traverse2.h"
 #include "shading.h"
+#include "cutout_host.h"
 #include "selftest.h"
 #include <cstring>
 #include <cmath>
@@ -111,8 +112,9 @@ extern "C" int32_t hr_markers_log(char* out, int32_t capacity)
 }
 
 // ------------------------------------------------------------------------------------------------
-// raw ray queries
-__global__ __launch_bounds__(256) void k_any_hit_batch(const Node8* nodes, const TriGPU* tris, long long n, const float* rays, uint8_t* out, unsigned long long* stats)
+// raw ray queries.  CUTOUT (all four kernels): the walks run the alpha test (cutout.h) through `cv`; the host picks it iff cutout_on(scene, HR_RAY_QUERY)
+template <bool CUTOUT>
+__global__ __launch_bounds__(256) void k_any_hit_batch(const Node8* nodes, const TriGPU* tris, long long n, const float* rays, uint8_t* out, unsigned long long* stats, CutoutView cv)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     __shared__ CoopWave s_coop[4];
@@ -122,16 +124,16 @@ __global__ __launch_bounds__(256) void k_any_hit_batch(const Node8* nodes, const
     // the counting query walks per lane (trace_any); the plain one is the wave-cooperative walk the AO pass uses (trace_coop)
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (i < n) { a = ((const float4*)rays)[i * 2]; b = ((const float4*)rays)[i * 2 + 1]; }
-    if (stats)
+    if (!CUTOUT && stats)
     {
         if (i < n) out[i] = trace_any<true>(nodes, tris, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, nn, nt) ? 1 : 0;
     }
     else
     {
-        const bool occ = trace_coop<true>(i < n, nodes, tris, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], s_coop[wave], lane).prim == 0;
+        const bool occ = trace_coop<true, HR_ANY_ORDER, CUTOUT>(i < n, nodes, tris, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv).prim == 0;
         if (i < n) out[i] = occ ? 1 : 0;
     }
-    if (stats)
+    if (!CUTOUT && stats)
     {
         for (int o = 32; o > 0; o >>= 1) { nn += __shfl_down(nn, o); nt += __shfl_down(nt, o); }
         if (lane == 0)
@@ -142,7 +144,8 @@ __global__ __launch_bounds__(256) void k_any_hit_batch(const Node8* nodes, const
     }
 }
 
-__global__ __launch_bounds__(256) void k_closest_hit_batch(const Node8* nodes, const TriGPU* tris, long long n, const float* rays, float* out_tuv, int32_t* out_prim)
+template <bool CUTOUT>
+__global__ __launch_bounds__(256) void k_closest_hit_batch(const Node8* nodes, const TriGPU* tris, long long n, const float* rays, float* out_tuv, int32_t* out_prim, CutoutView cv)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     __shared__ CoopWave s_coop[4];
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void k_closest_hit_batch(const Node8* nodes, c
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (i < n) { a = ((const float4*)rays)[i * 2]; b = ((const float4*)rays)[i * 2 + 1]; }
     // the walk the DDGI and reflection passes use (trace_coop); lanes past the end of the batch only serve as triangle-test lanes
-    const HitRec h = trace_coop<false>(i < n, nodes, tris, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], s_coop[wave], lane);
+    const HitRec h = trace_coop<false, HR_ORDER_NEAR, CUTOUT>(i < n, nodes, tris, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv);
     if (i >= n) return;
     out_tuv[i * 3 + 0] = h.t;
     out_tuv[i * 3 + 1] = h.u;
@@ -160,7 +163,8 @@ __global__ __launch_bounds__(256) void k_closest_hit_batch(const Node8* nodes, c
 }
 
 // ---- shared instanced scenes: the queries through traverse2.h.  Kept apart from the two above: another walk (trace_coop's helper lanes there) is behaviour
-__global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, const float* rays, uint8_t* out, unsigned long long* stats)
+template <bool CUTOUT>
+__global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, const float* rays, uint8_t* out, unsigned long long* stats, CutoutView cv)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -169,9 +173,10 @@ __global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, 
     if (i < n)
     {
         const float4 a = ((const float4*)rays)[i * 2], b = ((const float4*)rays)[i * 2 + 1];
-        out[i] = trace2<true, true>(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, &nn, &nt).prim == 0 ? 1 : 0;
+        if constexpr (CUTOUT) out[i] = trace_any2<true>(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, 0u, cv) ? 1 : 0;
+        else out[i] = trace2<true, true>(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, &nn, &nt).prim == 0 ? 1 : 0;
     }
-    if (stats)
+    if (!CUTOUT && stats)
     {
         for (int o = 32; o > 0; o >>= 1) { nn += __shfl_down(nn, o); nt += __shfl_down(nt, o); }
         if (lane == 0)
@@ -182,14 +187,15 @@ __global__ __launch_bounds__(256) void k_any_hit_batch2(Scene2 sc, long long n, 
     }
 }
 
-__global__ __launch_bounds__(256) void k_closest_hit_batch2(Scene2 sc, long long n, const float* rays, float* out_tuv, int32_t* out_prim)
+template <bool CUTOUT>
+__global__ __launch_bounds__(256) void k_closest_hit_batch2(Scene2 sc, long long n, const float* rays, float* out_tuv, int32_t* out_prim, CutoutView cv)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long i    = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float4 a = ((const float4*)rays)[i * 2], b = ((const float4*)rays)[i * 2 + 1];
-    const Hit2 h = trace_closest2(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane);
+    const Hit2 h = trace_closest2<CUTOUT>(sc, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), b.w, a.w, s_stack[wave], lane, cv);
     out_tuv[i * 3 + 0] = h.t;
     out_tuv[i * 3 + 1] = h.u;
     out_tuv[i * 3 + 2] = h.v;
@@ -289,8 +295,8 @@ HR_DEV void gb_transform_triangle(const float* m, const float* p, float* out)
     }
 }
 
-template <bool MOTION, bool TWO_LEVEL>
-__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs mo)
+template <bool MOTION, bool TWO_LEVEL, bool CUTOUT>
+__global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs mo, CutoutView cv)
 {
     __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -304,8 +310,8 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs 
     const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
     const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
     HitOf<TWO_LEVEL> hit;
-    if constexpr (TWO_LEVEL) hit = trace_closest2(Scene2 { a.nodes, a.tris, a.inst, a.cull }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
-    else hit = trace_closest(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane);
+    if constexpr (TWO_LEVEL) hit = trace_closest2<CUTOUT>(Scene2 { a.nodes, a.tris, a.inst, a.cull }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane, cv);
+    else hit = trace_closest<false, CUTOUT>(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane, nullptr, nullptr, nullptr, cv);
     if (hit.prim < 0)
     {
         a.gb1[i]   = 0u;
@@ -770,15 +776,18 @@ hr_status hr_scene_destroy(hr_scene* scene)
 hr_status hr_trace_any_hit(const hr_scene* scene, int64_t n, const float* rays, uint8_t* out, uint64_t* stats, void* stream)
 {
     HR_CHECK_ARG(scene && n >= 0 && (n == 0 || (rays && out)));
+    HR_REJECT_CUTOUT(scene, HR_RAY_QUERY, "hr_trace_any_hit", stats != nullptr);
     if (n == 0) return HR_OK;
+    const bool       cutout = cutout_on(scene, HR_RAY_QUERY);
+    const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
     if (scene->shared)
     {
-        hipLaunchKernelGGL(k_any_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out, (unsigned long long*)stats);
+        hipLaunchKernelGGL(cutout ? k_any_hit_batch2<true> : k_any_hit_batch2<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out, (unsigned long long*)stats, cv);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
-    hipLaunchKernelGGL(k_any_hit_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
-                       (const TriGPU*)scene->tris.p, (long long)n, rays, out, (unsigned long long*)stats);
+    hipLaunchKernelGGL(cutout ? k_any_hit_batch<true> : k_any_hit_batch<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
+                       (const TriGPU*)scene->tris.p, (long long)n, rays, out, (unsigned long long*)stats, cv);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }
@@ -787,14 +796,16 @@ hr_status hr_trace_closest_hit(const hr_scene* scene, int64_t n, const float* ra
 {
     HR_CHECK_ARG(scene && n >= 0 && (n == 0 || (rays && out_tuv && out_prim)));
     if (n == 0) return HR_OK;
+    const bool       cutout = cutout_on(scene, HR_RAY_QUERY);
+    const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
     if (scene->shared)
     {
-        hipLaunchKernelGGL(k_closest_hit_batch2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out_tuv, out_prim);
+        hipLaunchKernelGGL(cutout ? k_closest_hit_batch2<true> : k_closest_hit_batch2<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene2_of(scene, HR_RAY_QUERY), (long long)n, rays, out_tuv, out_prim, cv);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
-    hipLaunchKernelGGL(k_closest_hit_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
-                       (const TriGPU*)scene->tris.p, (long long)n, rays, out_tuv, out_prim);
+    hipLaunchKernelGGL(cutout ? k_closest_hit_batch<true> : k_closest_hit_batch<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const Node8*)scene->nodes.p,
+                       (const TriGPU*)scene->tris.p, (long long)n, rays, out_tuv, out_prim, cv);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }
@@ -831,8 +842,12 @@ static hr_status gbuffer_raycast_impl(const hr_scene* scene, const hr_ubo* ubo, 
     a.w = w; a.h = h;
     a.gb1 = (uint32_t*)gb1; a.gb2 = (uint2*)gb2; a.gb3 = (uint2*)gb3; a.depth = depth;
     const int tiles = ((w + 7) / 8) * ((h + 7) / 8);
-    void (*const kernel[2][2])(GBufArgs, MotionArgs) = { { k_gbuffer_raycast<false, false>, k_gbuffer_raycast<false, true> }, { k_gbuffer_raycast<true, false>, k_gbuffer_raycast<true, true> } };
-    hipLaunchKernelGGL(kernel[motion][sh], dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo);
+    // a private-copy instanced scene never enables cutouts (cutout.hip scene_check)
+    const bool       cutout = cutout_on(scene, HR_RAY_PRIMARY);
+    const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
+    void (*const kernel[2][2][2])(GBufArgs, MotionArgs, CutoutView) = { { { k_gbuffer_raycast<false, false, false>, k_gbuffer_raycast<false, false, true> }, { k_gbuffer_raycast<false, true, false>, k_gbuffer_raycast<false, true, true> } },
+                                                                        { { k_gbuffer_raycast<true, false, false>, k_gbuffer_raycast<true, false, true> }, { k_gbuffer_raycast<true, true, false>, k_gbuffer_raycast<true, true, true> } } };
+    hipLaunchKernelGGL(kernel[motion][sh][cutout], dim3((tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, mo, cv);
     HR_HIP(hipGetLastError());
     return HR_OK;
 }

@@ -5,6 +5,7 @@
 //   sample_probe_grid() :943-986, gi_sample_probe_grid.comp:75-99                                -> k_ddgi_sample
 #include "hr_internal.h"
 #include "shading.h"
+#include "cutout_host.h"
 #include "pass_args.h"
 #ifdef HR_DEV_PATHS
 #include "trace_queue.h"
@@ -83,10 +84,16 @@ extern "C" int hr_debug_divergence_ddgi(uint64_t* out, int reset)
 #ifndef DDGI_TRACE_SHARED_EU
 #define DDGI_TRACE_SHARED_EU 4   // SHARED: under the single-level kernel's bound of 6 the two-level walk spills (docs/EXPERIMENTS.md)
 #endif
-template <bool STATS, bool SHARED = false>
-__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a)
+// CUTOUT: the probe rays (class HR_RAY_GI, through cv_gi) and the hit shader's visibility rays (class HR_RAY_SHADOW, through cv_shadow) run the alpha
+// test of cutout.h; the host picks it iff either class has cutouts on, and hands the other a view without a table (cutout_accept takes everything).
+#ifndef DDGI_TRACE_CUTOUT_EU
+#define DDGI_TRACE_CUTOUT_EU 4   // CUTOUT instantiations, flat and SHARED: the uv and texel addressing do not fit under the opaque kernel's bound
+#endif
+template <bool STATS, bool SHARED = false, bool CUTOUT = false>
+__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_EU : SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(STATS && CUTOUT) && !(CUTOUT && DDGI_SEQ), "no statistics or -DDDGI_SEQ build of the cutout walks");
     static_assert(!(SHARED && DDGI_SEQ), "-DDDGI_SEQ walks one level: it cannot trace a shared instanced scene");
     __shared__ uint32_t s_stack[DDGI_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if DDGI_COOP
@@ -118,16 +125,17 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
         // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
         // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if DDGI_COOP2
-        h = trace_coop2<false>(valid, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        h = trace_coop2<false, CUTOUT>(valid, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane, 0u, cv_gi);
 #else
         h.prim = -1;
-        if (valid) h = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (valid) h = trace_closest2<CUTOUT>({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_gi);
 #endif
     }
     else
     {
 #if DDGI_COOP
-        if (!STATS) h = trace_coop<false>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+        if constexpr (CUTOUT) h = trace_coop<false, HR_ORDER_NEAR, true>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv_gi);
+        else if (!STATS) h = trace_coop<false>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
         else
         {
             h.prim = -1;
@@ -137,7 +145,7 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
         h.prim = -1;
         DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
         HR_DIV(dvp_ptr = &dvp;)
-        if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
+        if (valid) h = trace_closest<STATS, CUTOUT>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t, cv_gi);
 #endif
     }
     if (valid)
@@ -158,6 +166,7 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
             const float r2x = next_float(rng), r2y = next_float(rng);
             TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            if constexpr (CUTOUT) tc.cv = cv_shadow;
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
 #if DDGI_SEQ && !defined(HR_DEV_PATHS)
 #error "-DDDGI_SEQ=1 is an A/B path: build with -DHR_DEV_PATHS"
@@ -175,7 +184,7 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, SHARED ? DDGI_TRACE_SHARED_E
             f3 Lo = o1 ? mk3(0.0f, 0.0f, 0.0f) : ds.P1;
             if (!o2) Lo = add3(Lo, ds.P2);
 #else
-            f3 Lo = direct_lighting<STATS>(tc, a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky, rays);
+            f3 Lo = direct_lighting<STATS, CUTOUT>(tc, a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
 #endif
 #ifndef HR_ABL_DDGI_NO_IRRADIANCE
@@ -633,6 +642,8 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
     HR_CHECK_ARG(p && scene && in && env && prm && env->sky && env->sky_size > 0);
     HR_REJECT_SHARED(scene, "hr_ddgi_ray_trace");
     HR_REJECT_SHARED_DEV(scene, "hr_ddgi_ray_trace", p->want_stats || p->wavefront);   // no wavefront form of the two-level kernel either
+    HR_REJECT_CUTOUT(scene, HR_RAY_GI, "hr_ddgi_ray_trace", p->want_stats || p->wavefront);
+    HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_ddgi_ray_trace", p->want_stats || p->wavefront);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong
@@ -658,7 +669,7 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
         HR_HIP(hipMemsetAsync((char*)p->counters.p + 8, 0, 24, st));
         a.stats = (unsigned long long*)((char*)p->counters.p + 8);
         const int tb = 64 * DDGI_TRACE_WAVES;
-        hipLaunchKernelGGL(k_ddgi_trace<true>, dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
+        hipLaunchKernelGGL(k_ddgi_trace<true>, dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, CutoutView(), CutoutView());
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -688,8 +699,11 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
 #endif
     {
         const int tb = 64 * DDGI_TRACE_WAVES;
-        if (scene->shared) hipLaunchKernelGGL((k_ddgi_trace<false, true>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
-        else hipLaunchKernelGGL((k_ddgi_trace<false, false>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a);
+        // one CUTOUT instantiation for the two classes the kernel fires; a class that is forced opaque gets a view without a table
+        const bool       cut_gi = cutout_on(scene, HR_RAY_GI), cut_shadow = cutout_on(scene, HR_RAY_SHADOW), cutout = cut_gi || cut_shadow;
+        const CutoutView cv_gi = cut_gi ? cutout_view_of(scene) : CutoutView(), cv_shadow = cut_shadow ? cutout_view_of(scene) : CutoutView();
+        if (scene->shared) hipLaunchKernelGGL((cutout ? k_ddgi_trace<false, true, true> : k_ddgi_trace<false, true>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow);
+        else hipLaunchKernelGGL((cutout ? k_ddgi_trace<false, false, true> : k_ddgi_trace<false, false>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow);
     }
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());

@@ -7,6 +7,7 @@
 // that call (SURVEY §8f row 3's optional extension): up to max_ray_bounces path segments with Russian roulette.
 #include "hr_internal.h"
 #include "shading.h"
+#include "cutout_host.h"
 
 using namespace hr;
 
@@ -46,8 +47,10 @@ HR_DEV f3 sample_specular_ggx_lobe(f3 n, float alpha, float xi_x, float xi_y)
 
 // INDIRECT = false is the reference as shipped (one invocation per pixel: no payload chain to keep)
 // SHARED: every bounce and every visibility ray over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of traverse2.h
-template <bool INDIRECT, bool SHARED = false>
-__global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
+// CUTOUT: the camera ray (class HR_RAY_PRIMARY, cv_primary), the bounces (HR_RAY_GI, cv_gi) and the visibility rays (HR_RAY_SHADOW, cv_shadow) run the
+// alpha test of cutout.h; the host picks it iff any of the three classes has cutouts on, and hands the others a view without a table.
+template <bool INDIRECT, bool SHARED = false, bool CUTOUT = false>
+__global__ __launch_bounds__(64) void k_ground_truth(GTArgs a, CutoutView cv_primary, CutoutView cv_gi, CutoutView cv_shadow)
 {
     __shared__ uint32_t s_stack[HR_STACK_ENTRIES * 64];
     const int lane = threadIdx.x;
@@ -75,12 +78,20 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
         int      depth = 0;
         uint32_t nn = 0, nt = 0;
         TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack, lane);
+        if constexpr (CUTOUT) tc.cv = cv_shadow;
         for (;; depth++)
         {
             adds[depth] = mk3(0.0f, 0.0f, 0.0f);
             rays++;
             HitOf<SHARED> h;
-            if constexpr (SHARED)   // the camera ray, then the bounces: their own ray classes (tc's is the visibility rays')
+            if constexpr (CUTOUT)
+            {
+                const CutoutView cv = depth == 0 ? cv_primary : cv_gi;
+                if constexpr (SHARED)
+                    h = trace_closest2<true>(Scene2 { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] }, o, d, t_min, 10000.0f, s_stack, lane, cv);
+                else h = trace_closest<false, true>(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane, nullptr, nullptr, nullptr, cv);
+            }
+            else if constexpr (SHARED)   // the camera ray, then the bounces: their own ray classes (tc's is the visibility rays')
                 h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] }, o, d, t_min, 10000.0f, s_stack, lane);
             else h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
             if (h.prim < 0)
@@ -107,7 +118,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
                 if (attenuation > 0.0f)
                 {
                     rays++;
-                    attenuation = attenuation * (visibility_ray_occluded<false>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
+                    attenuation = attenuation * (visibility_ray_occluded<false, CUTOUT>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
                 }
                 const f3 brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
                 Lo = add3(Lo, mul3(scale3(mul3(T, brdf), attenuation), Li));
@@ -117,7 +128,7 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a)
                 f3       Li = a.sky.fetch(Wi);
                 const f3 Wh = normalize3(add3(Wo, Wi));
                 rays++;
-                Li = scale3(Li, visibility_ray_occluded<false>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
+                Li = scale3(Li, visibility_ray_occluded<false, CUTOUT>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
                 const f3 brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
                 Lo = add3(Lo, mul3(mul3(T, brdf), Li));
             }
@@ -254,13 +265,13 @@ hr_status hr_ground_truth_render(hr_ground_truth* p, const hr_scene* scene, cons
     const int tiles_y = cdiv(p->y1, 8) - a.tile_y0;
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
     int ev = p->prof.begin("path_trace", st, px * 16);
-    if (scene->shared)
-    {
-        if (a.trace_indirect) hipLaunchKernelGGL((k_ground_truth<true, true>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_ground_truth<false, true>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
-    }
-    else if (a.trace_indirect) hipLaunchKernelGGL((k_ground_truth<true, false>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_ground_truth<false, false>), dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a);
+    // one CUTOUT instantiation for the three classes the kernel fires; a class that is forced opaque gets a view without a table
+    const bool cut_primary = cutout_on(scene, HR_RAY_PRIMARY), cut_gi = cutout_on(scene, HR_RAY_GI), cut_shadow = cutout_on(scene, HR_RAY_SHADOW);
+    const CutoutView off = CutoutView(), on = (cut_primary || cut_gi || cut_shadow) ? cutout_view_of(scene) : off;
+    void (*const kernel[2][2][2])(GTArgs, CutoutView, CutoutView, CutoutView) = { { { k_ground_truth<false, false, false>, k_ground_truth<false, false, true> }, { k_ground_truth<false, true, false>, k_ground_truth<false, true, true> } },
+                                                                                  { { k_ground_truth<true, false, false>, k_ground_truth<true, false, true> }, { k_ground_truth<true, true, false>, k_ground_truth<true, true, true> } } };
+    hipLaunchKernelGGL(kernel[a.trace_indirect ? 1 : 0][scene->shared ? 1 : 0][cut_primary || cut_gi || cut_shadow], dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a,
+                       cut_primary ? on : off, cut_gi ? on : off, cut_shadow ? on : off);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     p->ping_pong = !p->ping_pong;

@@ -99,6 +99,10 @@ hr_status scene_create_flat(hr_ctx* ctx, const hr_scene_desc* d, hr_scene** out,
 // deform.hip: what a refit needs, for a scene that holds the uploaded tree `b` (deform_refit.h deform_refit_adopt of one mesh); the exact bounds of the last hr_scene_update_vertices, read back on demand
 hr_status deformable_scene_adopt(hr_scene* s, const BuiltBVH& b);
 hr_status deformable_scene_refresh_bounds(const hr_scene* scene);
+// cutout.hip.  HR_REJECT_CUTOUT: the instrumented and developer variants of a trace (`wanted`) have no CUTOUT instantiation — they refuse a scene whose
+// cutouts are enabled for the call's ray class, before anything is enqueued or any state of the pass changes; with every cutoff 0 they run as ever
+bool      reject_cutout_dev_switches(const hr_scene* s, int ray_class, const char* call, bool wanted);
+#define HR_REJECT_CUTOUT(scene, ray_class, call, wanted) do { if (::hr::reject_cutout_dev_switches(scene, ray_class, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
 
 struct DevBuf
 {
@@ -359,7 +363,13 @@ struct hr_scene
     // `uploads_done` is recorded behind them, and the next call that rewrites a mirror waits for it first (instances.hip wait_uploads)
     hipEvent_t    uploads_done = nullptr;
     bool          uploads_pending = false;
-    ~hr_scene() { if (uploads_done) (void)hipEventDestroy(uploads_done); if (mask_stage) (void)hipHostFree(mask_stage); }
+    ~hr_scene()
+    {
+        if (uploads_done) (void)hipEventDestroy(uploads_done);
+        if (mask_stage) (void)hipHostFree(mask_stage);
+        if (cutoff_copied) (void)hipEventDestroy(cutoff_copied);
+        if (cutoff_stage) (void)hipHostFree(cutoff_stage);
+    }
     int           max_rel_depth = 0;              // deepest node below an instance root (a fresh top level must leave room for it)
     std::vector<int32_t>  level_offsets;          // level_nodes[level_offsets[d] .. level_offsets[d + 1]): the nodes of depth d
     std::vector<uint32_t> inst_mesh;              // per instance: mesh index
@@ -402,6 +412,16 @@ struct hr_scene
     hipStream_t   mask_stream = nullptr;          // of the last hr_scene_set_instance_masks_device
     bool          masks_on_device = false;        // ... which a read-back has to wait for
     bool          masks_captured = false;         // ... enqueued on a capturing stream: replays rewrite the masks unseen
+    // ---- alpha-tested cutout materials (cutout.hip, cutout.h).  alpha_cutoffs / class_opaque are host state, read when a pass or query
+    // enqueues: a launch takes its CUTOUT instantiation iff cutout_enabled && !class_opaque[its ray class].  cutout_tab is keyed on the attribute
+    // index (original triangle, or the mesh's offset + local triangle), so no update, refit or re-build of the scene touches it
+    std::vector<float>    alpha_cutoffs;          // per material as last set; empty: never set (all opaque)
+    bool          cutout_enabled = false;         // some cutoff is above 0
+    int32_t       class_opaque[HR_RAY_CLASS_COUNT] = { 0, 0, 0, 0, 0, 0 };
+    std::vector<int32_t>  mat_albedo_host;        // per material: its albedo texture (-1 none); filled at creation with mat_tex (scene_create.h), empty without textures
+    hr::DevBuf    cutoff_dev, cutout_tab;         // [n_materials] floats; per attribute index { albedo texture + 1 or 0, cutoff bits }; allocated by the first setter call
+    float*        cutoff_stage = nullptr;         // pinned source of the copy into cutoff_dev; the next call waits for cutoff_copied before it rewrites it
+    hipEvent_t    cutoff_copied = nullptr;
     // ---- deforming geometry (deform_refit.hip): trees built without spatial splits, refitted under new vertices through `deform` and node_box.
     // deform.hip: a flat scene (`deformable`); hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`.  instances_shared_deform.hip: the
     // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
@@ -418,5 +438,7 @@ struct hr_scene
 namespace hr {
 // the cull mask of a ray class in the place of the instance mask in a record's flags: what Scene2::cull holds
 inline uint32_t cull_of(const hr_scene* s, int ray_class) { return (s->cull_mask[ray_class] & 0xFFu) << kInstanceMaskShift; }
+// does a launch of `ray_class` over the scene take its CUTOUT instantiation?
+inline bool cutout_on(const hr_scene* s, int ray_class) { return s->cutout_enabled && !s->class_opaque[ray_class]; }
 inline Scene2 scene2_of(const hr_scene* s, int ray_class) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p, cull_of(s, ray_class) }; }
 } // namespace hr

@@ -9,6 +9,7 @@
 #include "hr_internal.h"
 #include "reproject.h"
 #include "shading.h"
+#include "cutout_host.h"
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
@@ -121,10 +122,13 @@ extern "C" int hr_debug_divergence_refl(uint64_t* out, int reset)
 // The trace image is bit-exact in tolerance mode too.
 // SHARED: the reflection rays and the hit shader's light rays over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of
 // traverse2.h, one ray per lane, hit shading from the Hit2 (shading.h); both arithmetic modes launch it.  <STATS, false> is the kernel as it was.
-template <bool STATS, bool SHARED = false>
-__global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace(ReflTraceArgs a)
+// CUTOUT: the reflection rays (class HR_RAY_REFLECTION, through cv_refl) and the hit shader's light rays (class HR_RAY_SHADOW, through cv_shadow) run the
+// alpha test of cutout.h; the host picks it iff either class has cutouts on, and hands the other a view without a table (cutout_accept takes everything).
+template <bool STATS, bool SHARED = false, bool CUTOUT = false>
+__global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace(ReflTraceArgs a, CutoutView cv_refl, CutoutView cv_shadow)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     __shared__ uint32_t s_stack[REFL_TRACE_WAVES][HR_STACK_ENTRIES * 64];
 #if REFL_COOP
     __shared__ CoopWave s_coop[REFL_TRACE_WAVES];
@@ -186,16 +190,17 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
         // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
         // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
 #if REFL_COOP2
-        hit = trace_coop2<false>(trace, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane);
+        hit = trace_coop2<false, CUTOUT>(trace, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane, 0u, cv_refl);
 #else
         hit.prim = -1;
-        if (trace) hit = trace_closest2({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane);
+        if (trace) hit = trace_closest2<CUTOUT>({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_refl);
 #endif
     }
     else
     {
 #if REFL_COOP
-        if (!STATS) hit = trace_coop<false>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
+        if constexpr (CUTOUT) hit = trace_coop<false, HR_ORDER_NEAR, true>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv_refl);
+        else if (!STATS) hit = trace_coop<false>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
         else
         {
             hit.prim = -1;
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
         hit.prim = -1;
         DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
         HR_DIV(dvp_ptr = &dvp;)
-        if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t);
+        if (trace) hit = trace_closest<STATS, CUTOUT>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t, cv_refl);
 #endif
     }
     if (trace)
@@ -218,9 +223,10 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
             const f3 F0  = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
             const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
             TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
+            if constexpr (CUTOUT) tc.cv = cv_shadow;
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
             CubeMap  none { nullptr, 0 };
-            hLo = direct_lighting<STATS>(tc, a.light, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), false, 0.0f, 0.0f, none, rays);
+            hLo = direct_lighting<STATS, CUTOUT>(tc, a.light, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), false, 0.0f, 0.0f, none, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
             if (a.sample_gi == 1)
             {
@@ -583,6 +589,8 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
     if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
     HR_REJECT_SHARED_DEV(scene, "hr_reflections_ray_trace", p->want_stats);
+    HR_REJECT_CUTOUT(scene, HR_RAY_REFLECTION, "hr_reflections_ray_trace", p->want_stats);
+    HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_reflections_ray_trace", p->want_stats);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int pp = in->ping_pong ? 1 : 0;
@@ -628,13 +636,16 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
         // instrumented build of the same kernel (hr_reflections_trace_stats): counters + 8 .. 32
         HR_HIP(hipMemsetAsync((char*)p->counters.p + 8, 0, 24, st));
         a.stats = (unsigned long long*)((char*)p->counters.p + 8);
-        hipLaunchKernelGGL((k_refl_trace<true>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
+        hipLaunchKernelGGL((k_refl_trace<true>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a, CutoutView(), CutoutView());
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
     int ev = p->prof.begin("ray_trace", st, px * 28);
-    if (scene->shared) hipLaunchKernelGGL((k_refl_trace<false, true>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
-    else hipLaunchKernelGGL((k_refl_trace<false, false>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a);
+    // one CUTOUT instantiation for the two classes the kernel fires; a class that is forced opaque gets a view without a table
+    const bool       cut_refl = cutout_on(scene, HR_RAY_REFLECTION), cut_shadow = cutout_on(scene, HR_RAY_SHADOW), cutout = cut_refl || cut_shadow;
+    const CutoutView cv_refl = cut_refl ? cutout_view_of(scene) : CutoutView(), cv_shadow = cut_shadow ? cutout_view_of(scene) : CutoutView();
+    if (scene->shared) hipLaunchKernelGGL((cutout ? k_refl_trace<false, true, true> : k_refl_trace<false, true>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a, cv_refl, cv_shadow);
+    else hipLaunchKernelGGL((cutout ? k_refl_trace<false, false, true> : k_refl_trace<false, false>), dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a, cv_refl, cv_shadow);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     if (a.cost)

@@ -59,6 +59,8 @@ hr_status stage_materials(hr_scene* s, const Desc* d, const char* who)
     }
     for (int i = 0; i < d->n_materials * 4; i++)
         if (d->material_textures[(i / 4) * 6 + (i % 4)] >= d->n_textures) { set_last_error(std::string(who) + ": material texture index out of range"); return HR_ERR_INVALID_ARG; }
+    s->mat_albedo_host.resize((size_t)d->n_materials);   // what hr_scene_set_alpha_cutoffs validates against (cutout.hip)
+    for (int m = 0; m < d->n_materials; m++) s->mat_albedo_host[(size_t)m] = d->material_textures[m * 6];
     HR_TRY(upload(s->mat_tex, d->material_textures, (size_t)d->n_materials * 24));
     HR_TRY(upload(s->tex_table, table.data(), table.size() * 4));
     HR_TRY(upload(s->tex_data, texels.data(), texels.size()));

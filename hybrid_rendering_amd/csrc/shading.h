@@ -491,23 +491,7 @@ struct SurfaceHit
 // tests/test_ref_shaders.py::test_textured_materials_in_hit_shaders).  out[4] = r, g, b, a.
 HR_DEV void sample_texture(const SceneShading& s, int tex, float u, float v, float* out)
 {
-    const uint4 t  = s.tex_table[tex];
-    const int   w  = (int)t.y, h = (int)t.z;
-    const float px = u * (float)w - 0.5f, py = v * (float)h - 0.5f;
-    const float fx0 = floorf(px), fy0 = floorf(py);
-    const float fx = px - fx0, fy = py - fy0;
-    int x0 = (int)fx0 % w, x1 = ((int)fx0 + 1) % w, y0 = (int)fy0 % h, y1 = ((int)fy0 + 1) % h;
-    x0 = x0 < 0 ? x0 + w : x0; x1 = x1 < 0 ? x1 + w : x1; y0 = y0 < 0 ? y0 + h : y0; y1 = y1 < 0 ? y1 + h : y1;
-    const uint32_t* base = s.tex_data + t.x;
-    const uint32_t t00 = base[(size_t)y0 * w + x0], t10 = base[(size_t)y0 * w + x1], t01 = base[(size_t)y1 * w + x0], t11 = base[(size_t)y1 * w + x1];
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-    {
-        const float a = __fdiv_rn((float)((t00 >> (8 * c)) & 0xffu), 255.0f), b = __fdiv_rn((float)((t10 >> (8 * c)) & 0xffu), 255.0f);
-        const float e = __fdiv_rn((float)((t01 >> (8 * c)) & 0xffu), 255.0f), g = __fdiv_rn((float)((t11 >> (8 * c)) & 0xffu), 255.0f);
-        const float top = a * (1.0f - fx) + b * fx, bot = e * (1.0f - fx) + g * fx;
-        out[c] = top * (1.0f - fy) + bot * fy;
-    }
+    sample_texture_channels<0, 4>(s.tex_table, s.tex_data, tex, u, v, out);   // cutout.h: one body for the hit shading and the alpha test
 }
 // interpolated_vertex + transform_vertex (identity model) + fetch_albedo / fetch_roughness / fetch_metallic / fetch_normal
 // (scene_descriptor_set.glsl:133-220).  Quirk kept: the hit shaders call fetch_normal(material, tangent, TANGENT, normal, uv)
@@ -660,6 +644,7 @@ struct TraceCtx
     int           lane;
     DivCounters*  dv = nullptr;   // developer instrumentation (traverse.h)
     uint32_t      nn = 0, nt = 0; // direct_lighting<true>: node steps / triangle tests of the light and sky rays (hr_*_trace_stats)
+    CutoutView    cv = CutoutView();   // CUTOUT kernels: what the visibility rays' alpha test reads (class HR_RAY_SHADOW)
 };
 // the same over a shared instanced scene: the visibility rays take the two-level any-hit walk (no statistics build exists for it)
 struct TraceCtx2
@@ -668,17 +653,20 @@ struct TraceCtx2
     uint32_t* wave_stack;
     int       lane;
     uint32_t  nn = 0, nt = 0;
+    CutoutView cv = CutoutView();
 };
-template <bool STATS>
+template <bool STATS, bool CUTOUT = false>
 HR_DEV bool visibility_ray_occluded(TraceCtx& tc, f3 o, f3 d, float t_min, float t_max, uint32_t& nn, uint32_t& nt)
 {
-    return trace_any<STATS>(tc.nodes, tc.tris, o, d, t_min, t_max, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv);
+    if constexpr (CUTOUT) return trace_any<STATS, HR_ANY_ORDER, true>(tc.nodes, tc.tris, o, d, t_min, t_max, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv, nullptr, tc.cv);
+    else return trace_any<STATS>(tc.nodes, tc.tris, o, d, t_min, t_max, tc.wave_stack, tc.lane, nn, nt, 0u, tc.dv);
 }
-template <bool STATS>
+template <bool STATS, bool CUTOUT = false>
 HR_DEV bool visibility_ray_occluded(TraceCtx2& tc, f3 o, f3 d, float t_min, float t_max, uint32_t&, uint32_t&)
 {
     static_assert(!STATS, "no statistics build of the two-level walk");
-    return trace_any2(tc.sc, o, d, t_min, t_max, tc.wave_stack, tc.lane);
+    if constexpr (CUTOUT) return trace_any2<true>(tc.sc, o, d, t_min, t_max, tc.wave_stack, tc.lane, 0u, tc.cv);
+    else return trace_any2(tc.sc, o, d, t_min, t_max, tc.wave_stack, tc.lane);
 }
 
 // what a kernel templated on TWO_LEVEL (a shared instanced scene) walks with and gets back
@@ -692,7 +680,7 @@ HR_DEV TraceCtxOf<TWO_LEVEL> make_trace_ctx(const Node8* nodes, const TriGPU* tr
 }
 
 // direct_lighting (lighting.glsl:117-196); Ctx: TraceCtx or TraceCtx2
-template <bool STATS = false, class Ctx = TraceCtx>
+template <bool STATS = false, bool CUTOUT = false, class Ctx = TraceCtx>
 HR_DEV f3 direct_lighting(Ctx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 F0, f3 diffuse_color, float roughness, f3 T,
                           bool sample_sky, float r2x, float r2y, const CubeMap& sky, uint32_t& rays)
 {
@@ -707,7 +695,7 @@ HR_DEV f3 direct_lighting(Ctx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 
         if (attenuation > 0.0f)
         {
             rays++;
-            attenuation = attenuation * (visibility_ray_occluded<STATS>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
+            attenuation = attenuation * (visibility_ray_occluded<STATS, CUTOUT>(tc, ray_origin, Wi, 0.01f, t_max, nn, nt) ? 0.0f : 1.0f);
         }
 #endif
         const f3 brdf = evaluate_uber_brdf(diffuse_color, roughness, N, F0, Wo, Wh, Wi);
@@ -720,7 +708,7 @@ HR_DEV f3 direct_lighting(Ctx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 
         const f3 Wh = normalize3(add3(Wo, Wi));
 #ifndef HR_ABL_NO_SECONDARY
         rays++;
-        Li = scale3(Li, visibility_ray_occluded<STATS>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
+        Li = scale3(Li, visibility_ray_occluded<STATS, CUTOUT>(tc, ray_origin, Wi, 0.01f, 10000.0f, nn, nt) ? 0.0f : 1.0f);
 #endif
         const f3 brdf = evaluate_uber_brdf(diffuse_color, roughness, N, F0, Wo, Wh, Wi);
         Lo = add3(Lo, mul3(mul3(T, brdf), Li));

@@ -10,6 +10,7 @@
 #include "traverse.h"
 #include "traverse2.h"
 #include "shading.h"
+#include "cutout_host.h"
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
@@ -55,10 +56,13 @@ struct TraceArgs
 // SHARED: over a shared instanced scene (instances_shared.hip) — the same pixel -> ray set-up, the two-level walk of traverse2.h.  The occluder
 // cache is off there (it stores an index into a world-space `tris`; the mask does not depend on it), and so are the developer switches and the
 // timeline, which the host refuses on such a scene.  <STATS, false> is the kernel as it was.
-template <bool STATS, bool SHARED = false>
-__global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_trace(TraceArgs a)
+// CUTOUT: the walk and the occluder cache's early test run the alpha test (cutout.h) through `cv`, so only an ACCEPTED triangle answers or is cached;
+// the host picks it iff cutout_on(scene, HR_RAY_SHADOW).  `cv` is unset and unread otherwise.
+template <bool STATS, bool SHARED = false, bool CUTOUT = false>
+__global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_trace(TraceArgs a, CutoutView cv)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     __shared__ uint32_t s_stack[TRACE_WAVES][HR_STACK_ENTRIES * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * TRACE_WAVES + wave;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
             if (att > 0.0f)
             {
                 fired = true;
-                if constexpr (SHARED) lit = !trace_any2({ a.nodes, a.tris, a.inst, a.cull }, ro, Wi, 0.01f, t_max, s_stack[wave], lane);
+                if constexpr (SHARED) lit = !trace_any2<CUTOUT>({ a.nodes, a.tris, a.inst, a.cull }, ro, Wi, 0.01f, t_max, s_stack[wave], lane, 0u, cv);
                 else
                 {
                     // Occluder cache: "is ANY triangle hit in (t_min, t_max)" is a pure function of the geometry, so testing one particular
@@ -118,7 +122,9 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
                         {
                             const RayPre rp = ray_prepare(ro, Wi);
                             float t, u, v;
-                            occluded = ray_tri_raw<false>(rp, load_tri_raw(a.tris, c), 0.01f, t_max, t, u, v);
+                            const TriRaw tc = load_tri_raw(a.tris, c);
+                            occluded = ray_tri_raw<CUTOUT>(rp, tc, 0.01f, t_max, t, u, v);
+                            if (CUTOUT) occluded = occluded && cutout_accept(cv, tc.a.w, u, v);
                             if (STATS) nt++;
                             hit_tri = c;
                         }
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
                     else if (!occluded)
                     {
                         hit_tri = 0xffffffffu;
-                        occluded = trace_any<STATS>(a.nodes, a.tris, ro, Wi, 0.01f, t_max, s_stack[wave], lane, nn, nt, 0u, nullptr, &hit_tri);
+                        occluded = trace_any<STATS, HR_ANY_ORDER, CUTOUT>(a.nodes, a.tris, ro, Wi, 0.01f, t_max, s_stack[wave], lane, nn, nt, 0u, nullptr, &hit_tri, cv);
                     }
                     if (!a.debug_skip_traversal) lit = !occluded;
                     if (a.occluder && kind == 1 && hit_tri != occ_pre) a.occluder[pix] = hit_tri;
@@ -761,6 +767,9 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
     // statistics, timelines, the persistent-wave A/B kernel and the debug switches
     HR_REJECT_SHARED_DEV(scene, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
+    HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
+    const bool       cutout = cutout_on(scene, HR_RAY_SHADOW);
+    const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     // clear_images() (ray_traced_shadows.cpp:938-968): first frame zeroes the feedback image and the
@@ -795,7 +804,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     if (scene->shared)
     {
         int ev = p->prof.begin("ray_trace", st, px * 12 + px / 8);
-        hipLaunchKernelGGL((k_shadows_trace<false, true>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
+        hipLaunchKernelGGL((cutout ? k_shadows_trace<false, true, true> : k_shadows_trace<false, true>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
         p->prof.end(ev, st);
         HR_HIP(hipGetLastError());
         if (a.cost && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;
@@ -811,7 +820,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
         if (p->persistent_waves) hipLaunchKernelGGL(k_shadows_trace_pw<true>, dim3(cdiv(n_tiles, PW_TILES)), dim3(256), 0, st, a);
         else
 #endif
-        hipLaunchKernelGGL(k_shadows_trace<true>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
+        hipLaunchKernelGGL(k_shadows_trace<true>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
         HR_HIP(hipGetLastError());
         return HR_OK;
     }
@@ -823,8 +832,8 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
         hr_status bs = buf.alloc((size_t)n_tiles * 32);
         if (bs != HR_OK) return bs;
         a.timeline = (unsigned long long*)buf.p;
-        if (p->dbg_timeline_stats) hipLaunchKernelGGL(k_shadows_trace<true>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
-        else hipLaunchKernelGGL(k_shadows_trace<false>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
+        if (p->dbg_timeline_stats) hipLaunchKernelGGL(k_shadows_trace<true>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
+        else hipLaunchKernelGGL(k_shadows_trace<false>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
         HR_HIP(hipStreamSynchronize(st));
         std::vector<unsigned long long> host((size_t)n_tiles * 4);
         HR_HIP(hipMemcpy(host.data(), buf.p, host.size() * 8, hipMemcpyDeviceToHost));
@@ -836,7 +845,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     if (p->persistent_waves) hipLaunchKernelGGL(k_shadows_trace_pw<false>, dim3(cdiv(n_tiles, PW_TILES)), dim3(256), 0, st, a);
     else
 #endif
-    hipLaunchKernelGGL(k_shadows_trace<false>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a);
+    hipLaunchKernelGGL((cutout ? k_shadows_trace<false, false, true> : k_shadows_trace<false>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
     if (a.cost && !p->persistent_waves && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;

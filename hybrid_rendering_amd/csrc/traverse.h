@@ -14,6 +14,7 @@
 #pragma once
 #include "bvh.h"
 #include "device_math.h"
+#include "cutout.h"
 
 namespace hr {
 
@@ -367,11 +368,14 @@ HR_DEV uint32_t entry_node_for_box(const Node8* __restrict__ nodes, f3 lo, f3 hi
 
 // hit_tri (optional): index into `tris` of the triangle that occluded the ray (untouched on a miss) — the next frame's first guess
 // (shadow trace: occluder cache).
-template <bool STATS, int ORDER = HR_ANY_ORDER>
+// CUTOUT (here and in every walk below): a triangle that passes the watertight test counts only if cutout_accept (cutout.h) takes it at the
+// test's barycentrics; `cv` is what that reads.  With CUTOUT = false `cv` is neither set nor read and the code is the walk's without it.
+template <bool STATS, int ORDER = HR_ANY_ORDER, bool CUTOUT = false>
 HR_DEV bool trace_any(const Node8* __restrict__ nodes, const TriGPU* __restrict__ tris, f3 o, f3 d, float t_min, float t_max,
                       uint32_t* wave_stack, int lane, uint32_t& n_nodes, uint32_t& n_tris, uint32_t entry = 0u, DivCounters* dv = nullptr,
-                      uint32_t* hit_tri = nullptr)
+                      uint32_t* hit_tri = nullptr, const CutoutView& cv = CutoutView())
 {
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     if (entry == HR_NO_ENTRY) return false;
     RayPre    r = ray_prepare(o, d);
     uint32_t  spill_array[HR_SPILL_ENTRIES];
@@ -398,8 +402,10 @@ HR_DEV bool trace_any(const Node8* __restrict__ nodes, const TriGPU* __restrict_
             const TriRaw ta = load_tri_raw(tris, h.tri_base + i0), tb = load_tri_raw(tris, h.tri_base + i1);
             if (STATS) n_tris += two ? 2u : 1u;
             float t, u, v;
-            const bool ha = ray_tri_raw_uniform<false>(r, pcode, ta, t_min, t_max, t, u, v);
-            const bool hb = ray_tri_raw_uniform<false>(r, pcode, tb, t_min, t_max, t, u, v);
+            bool ha = ray_tri_raw_uniform<CUTOUT>(r, pcode, ta, t_min, t_max, t, u, v);
+            if (CUTOUT) ha = ha && cutout_accept(cv, ta.a.w, u, v);
+            bool hb = ray_tri_raw_uniform<CUTOUT>(r, pcode, tb, t_min, t_max, t, u, v);
+            if (CUTOUT) hb = hb && cutout_accept(cv, tb.a.w, u, v);
             if (ha || hb) { hit = true; if (hit_tri) *hit_tri = h.tri_base + (ha ? i0 : i1); break; }
         }
         if (hit) break;
@@ -573,10 +579,12 @@ struct HitRec
 // Closest hit: smallest t, ties broken by the smallest original triangle index (so the answer
 // does not depend on traversal order).
 // STATS: count node steps / triangle tests into *n_nodes / *n_tris (the instrumented builds behind hr_*_trace_stats).
-template <bool STATS = false>
+template <bool STATS = false, bool CUTOUT = false>
 HR_DEV HitRec trace_closest(const Node8* __restrict__ nodes, const TriGPU* __restrict__ tris, f3 o, f3 d, float t_min, float t_max,
-                            uint32_t* wave_stack, int lane, DivCounters* dv = nullptr, uint32_t* n_nodes = nullptr, uint32_t* n_tris = nullptr)
+                            uint32_t* wave_stack, int lane, DivCounters* dv = nullptr, uint32_t* n_nodes = nullptr, uint32_t* n_tris = nullptr,
+                            const CutoutView& cv = CutoutView())
 {
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     RayPre    r = ray_prepare(o, d);
     uint32_t  spill_array[HR_SPILL_ENTRIES];
     LaneStack st;
@@ -599,7 +607,7 @@ HR_DEV HitRec trace_closest(const Node8* __restrict__ nodes, const TriGPU* __res
             const TriRaw tri = load_tri_raw(tris, h.tri_base + i);
             if (STATS) (*n_tris)++;
             float t, u, v;
-            if (ray_tri_raw<true>(r, tri, t_min, t_max, t, u, v))
+            if (ray_tri_raw<true>(r, tri, t_min, t_max, t, u, v) && (!CUTOUT || cutout_accept(cv, tri.a.w, u, v)))
             {
                 const int32_t prim = (int32_t)tri.a.w;
                 if (best.prim < 0 || t < best.t || (t == best.t && prim < best.prim)) { best.t = t; best.u = u; best.v = v; best.prim = prim; }
@@ -637,8 +645,9 @@ constexpr uint32_t kCoopMaxTriangles = 1u << 26;
 HR_DEV uint32_t float_ordered(float f) { const uint32_t b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
 HR_DEV float    ordered_float(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
-template <bool ANY>
-HR_DEV void coop_flush(CoopWave& cw, const TriGPU* __restrict__ tris, const RayPre& r, float t_min, float t_max, uint32_t rank, uint32_t head, uint32_t n, int lane)
+template <bool ANY, bool CUTOUT = false>
+HR_DEV void coop_flush(CoopWave& cw, const TriGPU* __restrict__ tris, const RayPre& r, float t_min, float t_max, uint32_t rank, uint32_t head, uint32_t n, int lane,
+                       const CutoutView& cv = CutoutView())
 {
     const bool     mine  = rank < n;
     const uint32_t job   = mine ? cw.jobs[(head + rank) & (HR_COOP_RING - 1)] : ((uint32_t)lane << 26);
@@ -655,8 +664,9 @@ HR_DEV void coop_flush(CoopWave& cw, const TriGPU* __restrict__ tris, const RayP
     if (mine)
     {
         const TriRaw tr = load_tri_raw(tris, job & (kCoopMaxTriangles - 1u));
-        hit  = ray_tri_raw<!ANY>(q, tr, q_min, q_max, t, u, v);
+        hit  = ray_tri_raw<!ANY || CUTOUT>(q, tr, q_min, q_max, t, u, v);
         prim = tr.a.w;
+        if (CUTOUT) hit = hit && cutout_accept(cv, prim, u, v);   // the lane that tests the job decides, before key[owner] hears of it
     }
     if (ANY)
     {
@@ -674,9 +684,9 @@ HR_DEV void coop_flush(CoopWave& cw, const TriGPU* __restrict__ tris, const RayP
 
 // Closest hit (ANY = false: smallest t, ties to the smallest original triangle index — trace_closest's answer bit for bit) or
 // any-hit (ANY = true: HitRec.prim = 0 if occluded, -1 if not; t, u, v unset).
-template <bool ANY, int ORDER = (ANY ? HR_ANY_ORDER : HR_ORDER_NEAR)>
+template <bool ANY, int ORDER = (ANY ? HR_ANY_ORDER : HR_ORDER_NEAR), bool CUTOUT = false>
 HR_DEV HitRec trace_coop(bool active, const Node8* __restrict__ nodes, const TriGPU* __restrict__ tris, f3 o, f3 d, float t_min, float t_max,
-                         uint32_t* wave_stack, CoopWave& cw, int lane, uint32_t entry = 0u, DivCounters* dv = nullptr)
+                         uint32_t* wave_stack, CoopWave& cw, int lane, uint32_t entry = 0u, DivCounters* dv = nullptr, const CutoutView& cv = CutoutView())
 {
     const unsigned long long exec  = __ballot(1);
     const uint32_t           nproc = (uint32_t)__popcll(exec), rank = lanes_below(exec);
@@ -728,7 +738,7 @@ HR_DEV HitRec trace_coop(bool active, const Node8* __restrict__ nodes, const Tri
             const uint32_t n = count < nproc ? count : nproc;
             wave_fence();
             HR_DIV(if (dv) div_count(dv->lane_pairs, dv->wave_pairs);)
-            coop_flush<ANY>(cw, tris, r, t_min, t_max, rank, head, n, lane);
+            coop_flush<ANY, CUTOUT>(cw, tris, r, t_min, t_max, rank, head, n, lane, cv);
             head += n; count -= n;
             flushed = true;
         }

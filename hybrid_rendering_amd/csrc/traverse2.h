@@ -111,6 +111,7 @@ struct InstanceIn
 {
     float    m[12];   // columns 0..3, rows x y z
     uint32_t first_tri;
+    uint32_t mesh_tri_base;   // the attribute index of the mesh's first triangle: what cutout_accept is keyed on (read by CUTOUT walks only)
 };
 
 // matrix and first_tri of record `slot` (quads 0..3 and 7 of the record); returns quad 7: extent, flags, first_tri
@@ -122,7 +123,7 @@ HR_DEV uint4 load_instance_in(const InstanceShared* __restrict__ inst, uint32_t 
     in.m[3] = __uint_as_float(c1.x); in.m[4] = __uint_as_float(c1.y); in.m[5]  = __uint_as_float(c1.z);
     in.m[6] = __uint_as_float(c2.x); in.m[7] = __uint_as_float(c2.y); in.m[8]  = __uint_as_float(c2.z);
     in.m[9] = __uint_as_float(c3.x); in.m[10] = __uint_as_float(c3.y); in.m[11] = __uint_as_float(c3.z);
-    in.first_tri = i3.z;
+    in.first_tri = i3.z; in.mesh_tri_base = i3.w;
     return i3;
 }
 
@@ -186,10 +187,12 @@ struct Hit2
 // entry: the TOP-LEVEL node the walk starts from (0 = the root; HR_NO_ENTRY: nothing to walk, a miss).  entry_node_for_box (traverse.h) over a
 // shared scene's `nodes` yields one: it descends through internal children only and stops at the first node with a leaf — an instance — among
 // the overlapping children, so it never leaves the top level.  Any valid entry gives the root's answer.
-template <bool ANY, bool STATS = false>
+// CUTOUT: traverse.h trace_any; the attribute index is the mesh's offset + the local triangle, the barycentrics are the world-space test's.
+template <bool ANY, bool STATS = false, bool CUTOUT = false>
 HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t* n_nodes = nullptr, uint32_t* n_tris = nullptr,
-                   uint32_t entry = 0u)
+                   uint32_t entry = 0u, const CutoutView& cv = CutoutView())
 {
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     constexpr int ORDER = ANY ? HR_ANY_ORDER : HR_ORDER_NEAR;
     const RayPre rw = ray_prepare(o, d);   // world space: the top level's boxes and every triangle test
     BoxRay   br;
@@ -249,7 +252,7 @@ HR_DEV Hit2 trace2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint3
             f3 v0, v1, v2;
             instance_tri(in, q, v0, v1, v2);
             float t, u, v;
-            if (ray_tri<!ANY>(rw, v0, v1, v2, t_min, t_max, t, u, v))
+            if (ray_tri<!ANY || CUTOUT>(rw, v0, v1, v2, t_min, t_max, t, u, v) && (!CUTOUT || cutout_accept(cv, (size_t)in.mesh_tri_base + q.a.w, u, v)))
             {
                 if (ANY) { best.prim = 0; best.inst = slot; best.local = q.a.w; return best; }
                 const int32_t prim = (int32_t)(in.first_tri + q.a.w);
@@ -274,8 +277,9 @@ struct CoopWave2
     uint2              where[64];            // closest: record, mesh-local triangle of the winner
 };
 
-template <bool ANY>
-HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float t_min, float t_max, uint32_t rank, uint32_t head, uint32_t n, int lane)
+template <bool ANY, bool CUTOUT = false>
+HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float t_min, float t_max, uint32_t rank, uint32_t head, uint32_t n, int lane,
+                        const CutoutView& cv = CutoutView())
 {
     const bool  mine  = rank < n;
     const uint2 job   = mine ? cw.jobs[(head + rank) & (HR_COOP_RING - 1)] : make_uint2(0u, (uint32_t)lane << 26);
@@ -297,9 +301,10 @@ HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float 
         const TriRaw tr = load_tri_raw(sc.tris, job.x);
         f3 v0, v1, v2;
         instance_tri(in, tr, v0, v1, v2);
-        hit   = ray_tri<!ANY>(q, v0, v1, v2, q_min, q_max, t, u, v);
+        hit   = ray_tri<!ANY || CUTOUT>(q, v0, v1, v2, q_min, q_max, t, u, v);
         local = tr.a.w;
         prim  = in.first_tri + local;
+        if (CUTOUT) hit = hit && cutout_accept(cv, (size_t)in.mesh_tri_base + local, u, v);   // before key[owner] hears of the hit
     }
     if (ANY)
     {
@@ -317,8 +322,9 @@ HR_DEV void coop_flush2(CoopWave2& cw, const Scene2& sc, const RayPre& r, float 
 
 // trace2's answer bit for bit (ANY: Hit2.prim = 0 if occluded, -1 if not; t, u, v, inst, local unset).  The caller keeps the wave converged
 // around the call; lanes without a ray pass active = false.
-template <bool ANY>
-HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, CoopWave2& cw, int lane, uint32_t entry = 0u)
+template <bool ANY, bool CUTOUT = false>
+HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, CoopWave2& cw, int lane, uint32_t entry = 0u,
+                        const CutoutView& cv = CutoutView())
 {
     constexpr int ORDER = ANY ? HR_ANY_ORDER : HR_ORDER_NEAR;
     const unsigned long long exec  = __ballot(1);
@@ -399,7 +405,7 @@ HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, 
         {
             const uint32_t n = count < nproc ? count : nproc;
             wave_fence();
-            coop_flush2<ANY>(cw, sc, rw, t_min, t_max, rank, head, n, lane);
+            coop_flush2<ANY, CUTOUT>(cw, sc, rw, t_min, t_max, rank, head, n, lane, cv);
             head += n; count -= n;
             flushed = true;
         }
@@ -424,7 +430,9 @@ HR_DEV Hit2 trace_coop2(bool active, const Scene2& sc, f3 o, f3 d, float t_min, 
     return best;
 }
 
-HR_DEV bool   trace_any2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t entry = 0u) { return trace2<true>(sc, o, d, t_min, t_max, wave_stack, lane, nullptr, nullptr, entry).prim == 0; }
-HR_DEV Hit2   trace_closest2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane) { return trace2<false>(sc, o, d, t_min, t_max, wave_stack, lane); }
+template <bool CUTOUT = false>
+HR_DEV bool   trace_any2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t entry = 0u, const CutoutView& cv = CutoutView()) { return trace2<true, false, CUTOUT>(sc, o, d, t_min, t_max, wave_stack, lane, nullptr, nullptr, entry, cv).prim == 0; }
+template <bool CUTOUT = false>
+HR_DEV Hit2   trace_closest2(const Scene2& sc, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, const CutoutView& cv = CutoutView()) { return trace2<false, false, CUTOUT>(sc, o, d, t_min, t_max, wave_stack, lane, nullptr, nullptr, 0u, cv); }
 
 } // namespace hr

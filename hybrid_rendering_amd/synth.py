@@ -37,6 +37,7 @@ class SceneData:
     tangents: np.ndarray = None           # [n,3,3] float32 (normal-mapped materials only)
     material_textures: np.ndarray = None  # [m,6] int32: albedo, normal, roughness, metallic texture (-1 none), roughness channel, metallic channel
     textures: list = None                 # list of [h,w,4] uint8 (RGBA8 UNORM)
+    alpha_cutoffs: np.ndarray = None      # [m] float32 for Scene.set_alpha_cutoffs (0: opaque); nothing applies it by itself
 
     @property
     def n_tris(self) -> int:
@@ -58,6 +59,7 @@ class InstancedSceneData:
     name: str = "instanced"
     material_textures: np.ndarray = None
     textures: list = None
+    alpha_cutoffs: np.ndarray = None      # [m] float32 for Scene.set_alpha_cutoffs (0: opaque); nothing applies it by itself
 
     def matrices(self) -> np.ndarray:
         return np.ascontiguousarray(np.stack([np.asarray(m, np.float32).reshape(16) for m, _, _ in self.instances]), np.float32)
@@ -337,6 +339,47 @@ def with_textures(sd: SceneData, seed: int = 5) -> SceneData:
     return SceneData(sd.verts, sd.normals, sd.tri_material, sd.tri_mesh_id, sd.materials, sd.name + "_textured", dict(sd.meta),
                      uvs=np.ascontiguousarray(uvs), tangents=np.ascontiguousarray(t), material_textures=mt,
                      textures=[np.ascontiguousarray(alb), np.ascontiguousarray(nmap), np.ascontiguousarray(rm)])
+
+
+FOLIAGE_MATERIAL = 11   # sponza_like's foliage cards
+
+
+def leaf_texture(size: int = 64, seed: int = 21) -> np.ndarray:
+    """[size, size, 4] uint8: a leaf on a transparent ground — an ellipse along the diagonal with a serrated rim and a midrib, alpha 255 inside
+    and 0 outside with a two-texel ramp between, so that the bilinear alpha crosses a cutoff of 0.5 along the outline"""
+    rng = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float32)
+    u, v = (xx + 0.5) / size - 0.5, (yy + 0.5) / size - 0.5
+    a, b = (u + v) * np.float32(0.7071), (v - u) * np.float32(0.7071)        # along / across the leaf
+    rim = 0.16 * np.sqrt(np.maximum(1.0 - (a / 0.62) ** 2, 0.0)) * (1.0 + 0.12 * np.sin(a * 60.0))
+    inside = (rim - np.abs(b)) * size / 2.0                                  # signed distance to the outline, in texels
+    tex = np.zeros((size, size, 4), np.uint8)
+    tex[..., 0] = np.clip(40 + 30 * np.abs(b) / 0.16 + rng.randint(-8, 8, (size, size)), 0, 255)
+    tex[..., 1] = np.clip(150 - 60 * (np.abs(b) < 0.012) + rng.randint(-12, 12, (size, size)), 0, 255)
+    tex[..., 2] = np.clip(35 + rng.randint(-8, 8, (size, size)), 0, 255)
+    tex[..., 3] = np.clip(inside * 127.5 + 127.5, 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(tex)
+
+
+def with_leaf_cutout(sd: SceneData, material: int = FOLIAGE_MATERIAL, cutoff: float = 0.5) -> SceneData:
+    """`sd` with `material` turned into a cutout: per-card texture coordinates (a card of _Builder.cards is the two triangles p0 p1 p2 / p0 p2 p3 of
+    a rectangle; the half with its right angle at the second vertex gets (0,0) (1,0) (1,1), the other (0,0) (1,1) (0,1)), leaf_texture() as the
+    material's albedo texture and alpha_cutoffs[material] = cutoff.  Every other material stays untextured.  Pass alpha_cutoffs to
+    Scene.set_alpha_cutoffs."""
+    n, m = sd.n_tris, len(sd.materials)
+    uvs = np.zeros((n, 3, 2), np.float32)
+    sel = np.flatnonzero(np.asarray(sd.tri_material) == material)
+    v = sd.verts[sel].astype(np.float64)
+    at1 = np.abs(np.sum((v[:, 0] - v[:, 1]) * (v[:, 2] - v[:, 1]), -1))
+    at2 = np.abs(np.sum((v[:, 0] - v[:, 2]) * (v[:, 1] - v[:, 2]), -1))
+    uvs[sel] = np.where((at1 <= at2)[:, None, None], np.float32([[0, 0], [1, 0], [1, 1]]), np.float32([[0, 0], [1, 1], [0, 1]]))
+    mt = np.full((m, 6), -1, np.int32)
+    mt[:, 4], mt[:, 5] = 1, 2
+    mt[material, 0] = 0
+    cut = np.zeros(m, np.float32)
+    cut[material] = cutoff
+    return SceneData(sd.verts, sd.normals, sd.tri_material, sd.tri_mesh_id, sd.materials, sd.name + "_cutout", dict(sd.meta), uvs=uvs, tangents=None,
+                     material_textures=mt, textures=[leaf_texture()], alpha_cutoffs=cut)
 
 
 # --------------------------------------------------------------------------- scenes

@@ -112,6 +112,13 @@ public:
     void     instance_masks(uint8_t* masks_out) const { check(hr_scene_get_instance_masks(m_scene, masks_out), "hr_scene_get_instance_masks"); }
     void     set_cull_mask(hr_ray_class ray_class, uint32_t mask) { check(hr_scene_set_cull_mask(m_scene, (int32_t)ray_class, mask), "hr_scene_set_cull_mask"); }
     uint32_t cull_mask(hr_ray_class ray_class) const { uint32_t m = 0xFFu; check(hr_scene_get_cull_mask(m_scene, (int32_t)ray_class, &m), "hr_scene_get_cull_mask"); return m; }
+    // alpha-tested cutout materials (every kind but the private-copy instanced one): one cutoff per material (host, copied before the call returns;
+    // <= 0: opaque, the default) — a hit whose albedo alpha is below its material's cutoff does not exist for the ray.  set_ray_class_opaque(c, true):
+    // rays of class c skip the test (gl_RayFlagsOpaqueEXT, the reference's behaviour); read when a pass or query enqueues its launch
+    void     set_alpha_cutoffs(const float* cutoffs, Stream cmd_buf) { check(hr_scene_set_alpha_cutoffs(m_scene, cutoffs, cmd_buf), "hr_scene_set_alpha_cutoffs"); }
+    void     alpha_cutoffs(float* cutoffs_out) const { check(hr_scene_get_alpha_cutoffs(m_scene, cutoffs_out), "hr_scene_get_alpha_cutoffs"); }
+    void     set_ray_class_opaque(hr_ray_class ray_class, bool force_opaque) { check(hr_scene_set_ray_class_opaque(m_scene, (int32_t)ray_class, force_opaque ? 1 : 0), "hr_scene_set_ray_class_opaque"); }
+    bool     ray_class_opaque(hr_ray_class ray_class) const { int32_t v = 0; check(hr_scene_get_ray_class_opaque(m_scene, (int32_t)ray_class, &v), "hr_scene_get_ray_class_opaque"); return v != 0; }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }
     uint64_t id() const { return hr_scene_id(m_scene); }   // dw::Scene::id()
     ~Scene() { hr_scene_destroy(m_scene); }

@@ -115,6 +115,9 @@ hr_status hr_scene_set_instance_masks_device(hr_scene* scene, const uint8_t* mas
 hr_status hr_scene_get_instance_masks(const hr_scene* scene, uint8_t* masks_out /* HOST; synchronises */);
 hr_status hr_scene_set_cull_mask(hr_scene* scene, int32_t ray_class, uint32_t mask /* <= 0xFF; read when a pass or query enqueues */);
 hr_status hr_scene_get_cull_mask(const hr_scene* scene, int32_t ray_class, uint32_t* mask);
+/* ---- alpha-tested cutout materials: a hit whose albedo alpha < its material's cutoff does not exist for the ray.  Private-copy instanced scenes: HR_ERR_UNSUPPORTED -- */
+hr_status hr_scene_set_alpha_cutoffs(hr_scene* scene, const float* cutoffs /* HOST [n_materials], copied before return; <= 0 = opaque (the default) */, void* stream); hr_status hr_scene_get_alpha_cutoffs(const hr_scene* scene, float* cutoffs_out /* HOST [n_materials] */);
+hr_status hr_scene_set_ray_class_opaque(hr_scene* scene, int32_t ray_class, int32_t force_opaque /* 1: the class skips the test (gl_RayFlagsOpaqueEXT); 0: default; read at enqueue */); hr_status hr_scene_get_ray_class_opaque(const hr_scene* scene, int32_t ray_class, int32_t* force_opaque);
 
 /* ---- self test ------------------------------------------------------------------------------------ */
 /* Evaluates the device-side arithmetic of the numerical contract on arrays so tests can
