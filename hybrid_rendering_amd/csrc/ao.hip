@@ -13,6 +13,7 @@
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
+#include "pass_core.h"
 
 using namespace hr;
 
@@ -444,29 +445,12 @@ __global__ __launch_bounds__(256) void k_ao_blur(AOBlurArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-struct hr_ao
+struct hr_ao : PassCore
 {
-    hr_ctx* ctx = nullptr;
-    int     full_w = 0, full_h = 0, w = 0, h = 0, scale = 0, y0 = 0, y1 = 0, band_y0 = 0, band_y1 = 0;
-    int     mw = 0, mh = 0, tiles_x = 0, tiles_y = 0, max_spp = 4;
-    DevBuf  mask, color[2], length[2], blur[2], upsample, tile_class, counters, ray_slots, geo[2];
-    bool    first_frame = true, last_denoise = true, want_stats = false;
-    bool    fuse = true;   // tolerance mode: both blur passes in one launch (developer A/B switch HR_FUSE=0, read once at create)
+    int     max_spp = 4;
+    DevBuf  mask, color[2], length[2], blur[2];
+    DevBuf  geo[2];    // tolerance mode: the two slots of geometry records {oct normal, mesh id | AO} (pass_core.h GeoRecords), allocated iff records.history
     int     last_pp = 0;
-    StageProfiler prof;
-    hipStream_t   last_stream = nullptr;
-    // Tolerance mode: the temporal kernel also writes an 8-byte record per pixel {oct normal, mesh id | AO} — copies of the current
-    // G-buffer's words and of its own output — into geo[geo_parity].  When the caller hands back, as in->prev, the images it passed as
-    // in->cur in the previous call (the reference's ping-pong, g_buffer.cpp:208-211) and alternates ping_pong, those records ARE the
-    // previous G-buffer + the AO history, and the next frame reprojects from them: 2 images + the history length, 9 gathers per pixel
-    // instead of 5 images, 17 gathers with half of every G-buffer line unused.
-    bool          geo_history = true;   // developer A/B switch HR_GEO_HISTORY=0 (read once at create)
-    bool          geo_valid = false;
-    bool          dbg_require_geo = false;   // HR_DEBUG_REQUIRE_GEO (tests)
-    int           geo_parity = 0, geo_pp = -1;
-    const void*   geo_gb2 = nullptr;
-    const void*   geo_gb3 = nullptr;
-    TileOrder     tile_order;           // heaviest-first launch order of the trace kernel (tile_order.h)
     // entry-node table of the trace kernel (AoEntryGrid above): built for (scene, ray_length), rebuilt in-stream when either changes
     DevBuf        entry_grid;
     bool          grid_enabled = true;  // developer A/B switch HR_AO_ENTRY_GRID=0 (read once at create)
@@ -487,40 +471,21 @@ void hr_ao_default_params(hr_ao_params* p)
 
 hr_status hr_ao_create(hr_ctx* ctx, int32_t full_width, int32_t full_height, hr_scale scale, const hr_band* band, hr_ao** out)
 {
-    HR_CHECK_ARG(ctx && out && full_width > 0 && full_height > 0 && (int)scale >= 0 && (int)scale <= 2);
-    HR_HIP(hipSetDevice(ctx->device));
-    hr_ao* p = new hr_ao();
-    p->ctx = ctx; p->full_w = full_width; p->full_h = full_height; p->scale = (int)scale;
-    if (const char* e = getenv("HR_FUSE")) p->fuse = atoi(e) != 0;
-    if (const char* e = getenv("HR_GEO_HISTORY")) p->geo_history = atoi(e) != 0;
-    if (const char* e = getenv("HR_DEBUG_REQUIRE_GEO")) p->dbg_require_geo = atoi(e) != 0;   // test switch, see hr_shadows
+    hr_ao*    p = nullptr;
+    hr_status s = pass_new(&p, ctx, full_width, full_height, scale, band, out, BandRule::AoReflections, "ao");
+    if (s != HR_OK) return s;
     if (const char* e = getenv("HR_AO_ENTRY_GRID")) p->grid_enabled = atoi(e) != 0;
-    if (const char* e = getenv("HR_TILE_ORDER")) p->tile_order.enabled = atoi(e) != 0;
-    p->tile_order.tag = "ao";
-    p->w = full_width >> (int)scale; p->h = full_height >> (int)scale;
-    p->y0 = 0; p->y1 = p->h;
-    if (band && band->band_y1 > band->band_y0)
-    {
-        p->band_y0 = band->band_y0; p->band_y1 = band->band_y1;
-        p->y0 = band->band_y0 - band->halo < 0 ? 0 : band->band_y0 - band->halo;
-        p->y1 = band->band_y1 + band->halo > p->h ? p->h : band->band_y1 + band->halo;
-        if ((p->y0 & 7) || ((p->y1 & 7) && p->y1 != p->h)) { set_last_error("band rows must be multiples of 8"); delete p; return HR_ERR_INVALID_ARG; }
-    }
-    p->mw = cdiv(p->w, 8); p->mh = cdiv(p->h, 4); p->tiles_x = cdiv(p->w, 8); p->tiles_y = cdiv(p->h, 8);
     const size_t px = (size_t)p->w * p->h;
-    hr_status s;
-#define A(buf, n) if ((s = p->buf.alloc(n)) != HR_OK) { delete p; return s; }
-    A(mask, (size_t)p->max_spp * p->mw * p->mh * 4)
-    A(color[0], px * 2) A(color[1], px * 2) A(length[0], px * 2) A(length[1], px * 2)
-    A(blur[0], px * 2) A(blur[1], px * 2)
-    A(upsample, (size_t)full_width * full_height * 2)
-    A(tile_class, (size_t)p->tiles_x * p->tiles_y)
-    A(counters, 64)
-    A(ray_slots, (size_t)p->tiles_x * p->tiles_y * 4)
-    if (p->geo_history) { A(geo[0], px * 8) A(geo[1], px * 8) }   // (round 5: bands too — see hr_ao_temporal)
-    if (p->grid_enabled) { A(entry_grid, (size_t)kAoGridCells * 4) }
-#undef A
-    if ((s = p->tile_order.init(p->tiles_x * (cdiv(p->y1, 8) - p->y0 / 8))) != HR_OK) { delete p; return s; }
+    HR_PASS_ALLOC(mask, (size_t)p->max_spp * p->mw * p->mh * 4)
+    HR_PASS_ALLOC(color[0], px * 2) HR_PASS_ALLOC(color[1], px * 2) HR_PASS_ALLOC(length[0], px * 2) HR_PASS_ALLOC(length[1], px * 2)
+    HR_PASS_ALLOC(blur[0], px * 2) HR_PASS_ALLOC(blur[1], px * 2)
+    HR_PASS_ALLOC(upsample, (size_t)full_width * full_height * 2)
+    HR_PASS_ALLOC(tile_class, (size_t)p->tiles_x * p->tiles_y)
+    HR_PASS_ALLOC(counters, 64)
+    HR_PASS_ALLOC(ray_slots, (size_t)p->tiles_x * p->tiles_y * 4)
+    if (p->records.history) { HR_PASS_ALLOC(geo[0], px * 8) HR_PASS_ALLOC(geo[1], px * 8) }   // (round 5: bands too — see hr_ao_temporal)
+    if (p->grid_enabled) { HR_PASS_ALLOC(entry_grid, (size_t)kAoGridCells * 4) }
+    if ((s = p->tile_order.init(p->resident_tiles())) != HR_OK) { delete p; return s; }
     HR_HIP(hipMemset(p->counters.p, 0, 64));
     HR_HIP(hipMemset(p->ray_slots.p, 0, p->ray_slots.bytes));
     HR_HIP(hipMemset(p->mask.p, 0, p->mask.bytes));
@@ -528,53 +493,27 @@ hr_status hr_ao_create(hr_ctx* ctx, int32_t full_width, int32_t full_height, hr_
     return HR_OK;
 }
 
-hr_status hr_ao_destroy(hr_ao* p)
-{
-    if (!p) return HR_OK;
-    (void)hipSetDevice(p->ctx->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return HR_OK;
-}
+hr_status hr_ao_destroy(hr_ao* p) { return pass_destroy(p); }
 // Also forgets the entry-node table: it is marked built when its kernel is ENQUEUED, and this is the path a frame whose capture / launch
 // failed takes (frame.hip reset_after_failed_frame) — the table may never have been written.
 hr_status hr_ao_reset_history(hr_ao* p)
 {
     HR_CHECK_ARG(p);
-    p->first_frame = true; p->geo_valid = false; p->tile_order.invalidate();
     p->grid_scene = 0; p->grid_ray_length = -1.0f;
-    return HR_OK;
+    return pass_reset_history(p);
 }
-hr_status hr_ao_history_apron_exceeded(hr_ao* p, int32_t* exceeded)   // see hr_shadows_history_apron_exceeded
-{
-    HR_CHECK_ARG(p && exceeded);
-    uint32_t v = 0;
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    HR_HIP(hipMemcpy(&v, (char*)p->counters.p + 48, 4, hipMemcpyDeviceToHost));
-    if (v) HR_HIP(hipMemset((char*)p->counters.p + 48, 0, 4));
-    *exceeded = v ? 1 : 0;
-    return HR_OK;
-}
-
-hr_status hr_ao_set_profiling(hr_ao* p, int32_t e) { HR_CHECK_ARG(p); p->prof.enabled = e != 0; return HR_OK; }
-hr_status hr_ao_get_stage_times(hr_ao* p, hr_stage_times* out) { HR_CHECK_ARG(p && out); p->prof.collect(out); return HR_OK; }
-hr_status hr_ao_ray_count(hr_ao* p, uint64_t* rays)
-{
-    HR_CHECK_ARG(p && rays);
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    std::vector<uint32_t> slots((size_t)p->tiles_x * p->tiles_y);
-    HR_HIP(hipMemcpy(slots.data(), p->ray_slots.p, slots.size() * 4, hipMemcpyDeviceToHost));
-    uint64_t total = 0;
-    for (uint32_t v : slots) total += v;
-    *rays = total;
-    return HR_OK;
-}
+hr_status hr_ao_history_apron_exceeded(hr_ao* p, int32_t* exceeded) { return pass_history_apron_exceeded(p, exceeded); }
+hr_status hr_ao_set_profiling(hr_ao* p, int32_t e) { return pass_set_profiling(p, e); }
+hr_status hr_ao_get_stage_times(hr_ao* p, hr_stage_times* out) { return pass_get_stage_times(p, out); }
+hr_status hr_ao_ray_count(hr_ao* p, uint64_t* rays) { return pass_ray_count<uint32_t>(p, rays); }
+hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles) { return pass_launch_order(p, out, n_tiles); }
 
 hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_ao_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && in && prm && prm->spp >= 1 && prm->spp <= p->max_spp);
     HR_REJECT_SHARED(scene, "hr_ao_ray_trace");
-    HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
+    { const hr_status cs = check_inputs(p, in, false); if (cs != HR_OK) return cs; }
+    HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
     HR_REJECT_SHARED_DEV(scene, "hr_ao_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_AO, "hr_ao_ray_trace", p->want_stats);
     const bool       cutout = cutout_on(scene, HR_RAY_AO);
@@ -596,7 +535,7 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     a.nodes = (const Node8*)scene->nodes.p; a.tris = (const TriGPU*)scene->tris.p; a.inst = (const InstanceShared*)scene->inst_shared.p; a.cull = cull_of(scene, HR_RAY_AO);
     a.stats = p->want_stats ? (unsigned long long*)((char*)p->counters.p + 16) : nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw; a.mh = p->mh;
-    a.tile_y0 = p->y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(p->y1, 8) - a.tile_y0;
+    a.tile_y0 = p->tile_y0(); a.tiles_x = p->tiles_x; a.tiles_y = p->resident_tiles_y();
     a.bias = prm->bias; a.ray_length = prm->ray_length; a.num_frames = in->num_frames; a.spp = prm->spp;
     const int n_tiles = a.tiles_x * a.tiles_y;
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
@@ -671,12 +610,6 @@ hr_status hr_ao_ray_trace(hr_ao* p, const hr_scene* scene, const hr_frame_inputs
     return HR_OK;
 }
 
-hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles)
-{
-    HR_CHECK_ARG(p);
-    return p->tile_order.read(out, n_tiles, p->last_stream);
-}
-
 hr_status hr_ao_trace_stats(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_ao_params* prm, uint64_t* out3, void* stream)
 {
     HR_CHECK_ARG(p && out3);
@@ -711,10 +644,10 @@ hr_status hr_ao_temporal(hr_ao* p, const hr_frame_inputs* in, const hr_ao_params
     a.hist = ImgR16F { (const uint16_t*)p->color[!pp].p, w, y0, y1 };
     a.hist_len = ImgR16F { (const uint16_t*)p->length[!pp].p, w, y0, y1 };
     a.out = (uint16_t*)p->color[pp].p; a.out_len = (uint16_t*)p->length[pp].p; a.tile_class = (uint8_t*)p->tile_class.p;
-    a.apron_flag = (y0 > 0 || y1 < p->h) ? (uint32_t*)((char*)p->counters.p + 48) : nullptr;   // row bands only
+    a.apron_flag = p->apron_flag();
     a.band_y0 = p->band_y0; a.band_y1 = p->band_y1;
     a.w = w; a.h = p->h; a.y0 = y0; a.y1 = y1;
-    a.tile_y0 = y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(y1, 8) - a.tile_y0;
+    a.tile_y0 = p->tile_y0(); a.tiles_x = p->tiles_x; a.tiles_y = p->resident_tiles_y();
     a.alpha = prm->alpha;
     a.geo_hist = nullptr; a.geo_out = nullptr; a.geo_band = 0;
     if (!prm->exact && p->geo[0].p)
@@ -723,15 +656,13 @@ hr_status hr_ao_temporal(hr_ao* p, const hr_frame_inputs* in, const hr_ao_params
         // with the R16F image): the rows next to a band boundary hold the neighbour's AO history after the per-frame exchange
         // (hr_ao_exchange_history), the record's AO half there is this GPU's own redundant result.  The geometry half is a copy of the
         // G-buffer either way, and a band computes — and so records — every row it reads history from (history_halo == halo for AO).
-        a.geo_band = (y0 > 0 || y1 < p->h) ? 1 : 0;
-        const bool had_records = p->geo_valid;
-        if (p->geo_valid && !p->first_frame && pp != p->geo_pp && in->prev.gb2 == p->geo_gb2 && in->prev.gb3 == p->geo_gb3 && in->prev.gb2 != in->cur.gb2 && in->prev.gb3 != in->cur.gb3) a.geo_hist = p->geo[p->geo_parity].p;
-        p->geo_parity ^= 1;
-        a.geo_out = p->geo[p->geo_parity].p;
-        p->geo_valid = true; p->geo_pp = pp; p->geo_gb2 = in->cur.gb2; p->geo_gb3 = in->cur.gb3;
-        if (p->dbg_require_geo && had_records && !a.geo_hist) { hr::set_last_error("hr_ao_temporal: HR_DEBUG_REQUIRE_GEO is set and the record path was not taken"); return HR_ERR_INVALID_ARG; }
+        a.geo_band = p->banded() ? 1 : 0;
+        const GeoRecords::Step g = p->records.advance(in->cur.gb2, in->cur.gb3, in->prev.gb2, in->prev.gb3, p->first_frame, pp);
+        if (g.read >= 0) a.geo_hist = p->geo[g.read].p;
+        a.geo_out = p->geo[g.write].p;
+        if (g.require_failed) return geo_require_error("hr_ao_temporal");
     }
-    else p->geo_valid = false;
+    else p->records.invalidate();
     p->last_pp = pp;
     const uint64_t px = (uint64_t)w * (y1 - y0);
     a.sort = TileSortArgs { nullptr, nullptr, 0, 0, 0, 0 };
@@ -796,28 +727,14 @@ static hr_status ao_blur_xy(hr_ao* p, const hr_frame_inputs* in, const hr_ao_par
     return HR_OK;
 }
 
-hr_status hr_ao_upsample(hr_ao* p, const hr_frame_inputs* in, const hr_ao_params* prm, void* stream_)
+hr_status hr_ao_upsample(hr_ao* p, const hr_frame_inputs* in, const hr_ao_params* prm, void* stream)
 {
     HR_CHECK_ARG(p && in && prm);
-    if (p->scale == 0) return HR_OK;
-    HR_CHECK_ARG(in->cur_full.gb2 && in->cur_full.gb3 && in->cur_full.width == p->full_w && in->cur_full.height == p->full_h);
-    hipStream_t st = (hipStream_t)stream_;
-    p->last_stream = st;
-    UpsampleArgs a;
-    a.W = p->full_w; a.H = p->full_h; a.w = p->w; a.h = p->h;
-    a.G2 = (const uint2*)in->cur_full.gb2; a.G3 = (const uint2*)in->cur_full.gb3;
-    a.g2 = (const uint2*)in->cur.gb2; a.g3 = (const uint2*)in->cur.gb3;
-    a.in = p->blur[1].p; a.in_channels = 1; a.channels = 1; a.out = p->upsample.p; a.sky_value = 1.0f; a.power = prm->power;
     const uint64_t PX = (uint64_t)p->full_w * p->full_h, px = (uint64_t)p->w * p->h;
-    int ev = p->prof.begin("upsample", st, PX * 18 + px * 18);
-    if (prm->exact) launch_upsample(a, st);
-    else launch_upsample_fast(a, st);
-    p->prof.end(ev, st);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return pass_upsample(p, in, prm->exact != 0, p->blur[1].p, 1, 1, 1.0f, prm->power, PX * 18 + px * 18, stream);
 }
 
-// Everything of RayTracedAO::render after the ray trace (ray_traced_ao.cpp:102-111); see hr_shadows_denoise
+// Everything of RayTracedAO::render after the ray trace (ray_traced_ao.cpp:102-111), for a caller that overlaps work with the trace
 hr_status hr_ao_denoise(hr_ao* p, const hr_frame_inputs* in, const hr_ao_params* prm, void* stream)
 {
     HR_CHECK_ARG(p && in && prm);
@@ -852,11 +769,6 @@ hr_status hr_ao_render(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* i
     hr_status s = hr_ao_ray_trace(p, scene, in, prm, stream);
     if (s != HR_OK) return s;
     return hr_ao_denoise(p, in, prm, stream);
-}
-
-static void fill_view(hr_image_view* v, void* data, int w, int h, int bpp, hr_format f)
-{
-    v->data = data; v->width = w; v->height = h; v->row_pitch_bytes = w * bpp; v->format = f;
 }
 
 // 0 mask (plane 0..spp-1 stacked vertically), 1/2 AO colour[0/1], 3/4 history length[0/1], 5/6 blur[0/1], 7 upsample, 8 tile classes

@@ -794,11 +794,6 @@ hr_status hr_ddgi_render(hr_ddgi* p, const hr_scene* scene, const hr_frame_input
     return hr_ddgi_end_frame(p);
 }
 
-static void fill_view(hr_image_view* v, void* data, int w, int h, int bpp, hr_format f)
-{
-    v->data = data; v->width = w; v->height = h; v->row_pitch_bytes = w * bpp; v->format = f;
-}
-
 hr_status hr_ddgi_image(hr_ddgi* p, int32_t which, hr_image_view* v)
 {
     HR_CHECK_ARG(p && v);

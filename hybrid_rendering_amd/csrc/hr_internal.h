@@ -155,6 +155,12 @@ struct DevBuf
     DevBuf& operator=(const DevBuf&) = delete;
 };
 
+// a tightly packed image of `bpp` bytes per texel as an hr_*_image / hr_*_output view
+inline void fill_view(hr_image_view* v, void* data, int w, int h, int bpp, hr_format f)
+{
+    v->data = data; v->width = w; v->height = h; v->row_pitch_bytes = w * bpp; v->format = f;
+}
+
 // What the refit of split-free trees under new vertices keeps (deform_refit.hip) for a scene from hr_scene_create_deformable (one flagged mesh:
 // the scene) or hr_scene_create_instanced_shared_deformable.  Everything is indexed by mesh; an unflagged mesh has no levels, no partials and -1
 // in tri_ref.

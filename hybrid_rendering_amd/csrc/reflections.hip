@@ -13,6 +13,7 @@
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
+#include "pass_core.h"
 
 using namespace hr;
 
@@ -476,29 +477,13 @@ __global__ __launch_bounds__(256) void k_refl_atrous(ReflAtrousArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-struct hr_reflections
+struct hr_reflections : PassCore
 {
-    hr_ctx* ctx = nullptr;
-    int     full_w = 0, full_h = 0, w = 0, h = 0, scale = 0, y0 = 0, y1 = 0, band_y0 = 0, band_y1 = 0, tiles_x = 0, tiles_y = 0;
-    DevBuf  trace, color[2], moments[2], prev_image, atrous[2], upsample, tile_class, counters, ray_slots, geo[2];
-    bool    first_frame = true, last_denoise = true, want_stats = false;
+    DevBuf  trace, color[2], moments[2], prev_image, atrous[2];
+    DevBuf  geo[2];    // tolerance mode: the two slots of geometry records {oct normal, mesh id | linear z} (pass_core.h GeoRecords), allocated iff records.history
     int     read_idx = 0, last_pp = 0;
     bool    last_blur_as_input = false;   // which image the NEXT frame's temporal stage reads as colour history (hr_reflections_image 10)
-    bool    fuse = true;   // tolerance mode: a-trous iterations 0 + 1 in one launch (developer A/B switch HR_FUSE=0, read once at create)
-    StageProfiler prof;
-    hipStream_t   last_stream = nullptr;
-    // Tolerance mode: the temporal kernel writes an 8-byte geometry record per pixel {oct normal, mesh id | linear z} (copies of the
-    // current G-buffer's words) into geo[geo_parity]: this frame's a-trous taps read it instead of two half-used G-buffer lines, and —
-    // when the caller hands back as in->prev the images it passed as in->cur (the reference's ping-pong, g_buffer.cpp:208-211) — so does
-    // the next frame's reprojection (see hr_shadows).
-    bool          geo_history = true;   // developer A/B switch HR_GEO_HISTORY=0 (read once at create)
-    bool          geo_valid = false;
-    bool          dbg_require_geo = false;   // HR_DEBUG_REQUIRE_GEO (tests)
-    int           geo_parity = 0;
-    const void*   geo_gb2 = nullptr;
-    const void*   geo_gb3 = nullptr;
     const void*   geo_cur = nullptr;    // this frame's records (a-trous stages), nullptr in the parity mode / for bands
-    TileOrder     tile_order;           // heaviest-first launch order of the trace kernel (tile_order.h)
 };
 
 bool hr::profiling_enabled(const hr_reflections* p) { return p && p->prof.enabled; }
@@ -515,78 +500,37 @@ void hr_reflections_default_params(hr_reflections_params* p)
 
 hr_status hr_reflections_create(hr_ctx* ctx, int32_t full_width, int32_t full_height, hr_scale scale, const hr_band* band, hr_reflections** out)
 {
-    HR_CHECK_ARG(ctx && out && full_width > 0 && full_height > 0 && (int)scale >= 0 && (int)scale <= 2);
-    HR_HIP(hipSetDevice(ctx->device));
-    hr_reflections* p = new hr_reflections();
-    p->ctx = ctx; p->full_w = full_width; p->full_h = full_height; p->scale = (int)scale;
-    if (const char* e = getenv("HR_FUSE")) p->fuse = atoi(e) != 0;
-    if (const char* e = getenv("HR_GEO_HISTORY")) p->geo_history = atoi(e) != 0;
-    if (const char* e = getenv("HR_DEBUG_REQUIRE_GEO")) p->dbg_require_geo = atoi(e) != 0;   // test switch, see hr_shadows
-    if (const char* e = getenv("HR_TILE_ORDER")) p->tile_order.enabled = atoi(e) != 0;
-    p->tile_order.tag = "reflections";
-    p->w = full_width >> (int)scale; p->h = full_height >> (int)scale; p->y0 = 0; p->y1 = p->h;
-    if (band && band->band_y1 > band->band_y0)
-    {
-        p->band_y0 = band->band_y0; p->band_y1 = band->band_y1;
-        p->y0 = band->band_y0 - band->halo < 0 ? 0 : band->band_y0 - band->halo;
-        p->y1 = band->band_y1 + band->halo > p->h ? p->h : band->band_y1 + band->halo;
-        if ((p->y0 & 7) || ((p->y1 & 7) && p->y1 != p->h)) { set_last_error("band rows must be multiples of 8"); delete p; return HR_ERR_INVALID_ARG; }
-    }
-    p->tiles_x = cdiv(p->w, 8); p->tiles_y = cdiv(p->h, 8);
+    hr_reflections* p = nullptr;
+    hr_status       s = pass_new(&p, ctx, full_width, full_height, scale, band, out, BandRule::AoReflections, "reflections");
+    if (s != HR_OK) return s;
     const size_t px = (size_t)p->w * p->h;
-    hr_status s;
-#define A(buf, n) if ((s = p->buf.alloc(n)) != HR_OK) { delete p; return s; }
-    A(trace, px * 8) A(color[0], px * 8) A(color[1], px * 8) A(moments[0], px * 8) A(moments[1], px * 8) A(prev_image, px * 8)
-    A(atrous[0], px * 8) A(atrous[1], px * 8) A(upsample, (size_t)full_width * full_height * 8) A(tile_class, (size_t)p->tiles_x * p->tiles_y) A(counters, 64) A(ray_slots, (size_t)p->tiles_x * p->tiles_y * 4)
-    if (p->geo_history) { A(geo[0], px * 8) A(geo[1], px * 8) }   // (round 5: bands too — a band computes, and so records, every row it reads history from: history_halo == halo)
-#undef A
-    if ((s = p->tile_order.init(p->tiles_x * (cdiv(p->y1, 8) - p->y0 / 8))) != HR_OK) { delete p; return s; }
+    HR_PASS_ALLOC(trace, px * 8) HR_PASS_ALLOC(color[0], px * 8) HR_PASS_ALLOC(color[1], px * 8) HR_PASS_ALLOC(moments[0], px * 8) HR_PASS_ALLOC(moments[1], px * 8)
+    HR_PASS_ALLOC(prev_image, px * 8) HR_PASS_ALLOC(atrous[0], px * 8) HR_PASS_ALLOC(atrous[1], px * 8)
+    HR_PASS_ALLOC(upsample, (size_t)full_width * full_height * 8) HR_PASS_ALLOC(tile_class, (size_t)p->tiles_x * p->tiles_y) HR_PASS_ALLOC(counters, 64)
+    HR_PASS_ALLOC(ray_slots, (size_t)p->tiles_x * p->tiles_y * 4)
+    if (p->records.history) { HR_PASS_ALLOC(geo[0], px * 8) HR_PASS_ALLOC(geo[1], px * 8) }   // (round 5: bands too — a band computes, and so records, every row it reads history from: history_halo == halo)
+    if ((s = p->tile_order.init(p->resident_tiles())) != HR_OK) { delete p; return s; }
     HR_HIP(hipMemset(p->counters.p, 0, 64));
     HR_HIP(hipMemset(p->ray_slots.p, 0, p->ray_slots.bytes));
     *out = p;
     return HR_OK;
 }
 
-hr_status hr_reflections_destroy(hr_reflections* p)
-{
-    if (!p) return HR_OK;
-    (void)hipSetDevice(p->ctx->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return HR_OK;
-}
-hr_status hr_reflections_reset_history(hr_reflections* p) { HR_CHECK_ARG(p); p->first_frame = true; p->geo_valid = false; p->tile_order.invalidate(); return HR_OK; }
-hr_status hr_reflections_history_apron_exceeded(hr_reflections* p, int32_t* exceeded)   // see hr_shadows_history_apron_exceeded
-{
-    HR_CHECK_ARG(p && exceeded);
-    uint32_t v = 0;
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    HR_HIP(hipMemcpy(&v, (char*)p->counters.p + 48, 4, hipMemcpyDeviceToHost));
-    if (v) HR_HIP(hipMemset((char*)p->counters.p + 48, 0, 4));
-    *exceeded = v ? 1 : 0;
-    return HR_OK;
-}
-
-hr_status hr_reflections_set_profiling(hr_reflections* p, int32_t e) { HR_CHECK_ARG(p); p->prof.enabled = e != 0; return HR_OK; }
-hr_status hr_reflections_get_stage_times(hr_reflections* p, hr_stage_times* out) { HR_CHECK_ARG(p && out); p->prof.collect(out); return HR_OK; }
-hr_status hr_reflections_ray_count(hr_reflections* p, uint64_t* rays)
-{
-    HR_CHECK_ARG(p && rays);
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    std::vector<uint32_t> slots((size_t)p->tiles_x * p->tiles_y);
-    HR_HIP(hipMemcpy(slots.data(), p->ray_slots.p, slots.size() * 4, hipMemcpyDeviceToHost));
-    uint64_t total = 0;
-    for (uint32_t v : slots) total += v;
-    *rays = total;
-    return HR_OK;
-}
+hr_status hr_reflections_destroy(hr_reflections* p) { return pass_destroy(p); }
+hr_status hr_reflections_reset_history(hr_reflections* p) { return pass_reset_history(p); }
+hr_status hr_reflections_history_apron_exceeded(hr_reflections* p, int32_t* exceeded) { return pass_history_apron_exceeded(p, exceeded); }
+hr_status hr_reflections_set_profiling(hr_reflections* p, int32_t e) { return pass_set_profiling(p, e); }
+hr_status hr_reflections_get_stage_times(hr_reflections* p, hr_stage_times* out) { return pass_get_stage_times(p, out); }
+hr_status hr_reflections_ray_count(hr_reflections* p, uint64_t* rays) { return pass_ray_count<uint32_t>(p, rays); }
 
 hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_environment* env, hr_ddgi* ddgi,
                                    const hr_reflections_params* prm, void* stream_)
 {
     HR_CHECK_ARG(p && scene && in && env && ddgi && prm && env->sky && env->sky_size > 0);
     HR_REJECT_SHARED(scene, "hr_reflections_ray_trace");
-    HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->cur.width == p->w && in->cur.height == p->h && in->sobol && in->scrambling_ranking);
+    hr_status s = check_inputs(p, in, false);
+    if (s != HR_OK) return s;
+    HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
     if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
     HR_REJECT_SHARED_DEV(scene, "hr_reflections_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_REFLECTION, "hr_reflections_ray_trace", p->want_stats);
@@ -603,8 +547,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
         p->first_frame = false;
     }
     ReflTraceArgs a;
-    hr_status s = hr_ddgi_get_uniforms(ddgi, &a.d);
-    if (s != HR_OK) return s;
+    if ((s = hr_ddgi_get_uniforms(ddgi, &a.d)) != HR_OK) return s;
     hr_image_view iv, dv;
     if ((s = hr_ddgi_current_read(ddgi, &iv, &dv)) != HR_OK) return s;
     a.irr = AtlasRGBA { (const uint2*)iv.data, iv.width, iv.height };
@@ -621,7 +564,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     a.env.lut = (const uint32_t*)env->brdf_lut; a.env.lut_size = env->brdf_lut_size;
     a.out = (uint2*)p->trace.p; a.ray_slots = (uint32_t*)p->ray_slots.p + (size_t)(p->y0 / 8) * p->tiles_x;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1;
-    a.tile_y0 = p->y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(p->y1, 8) - a.tile_y0;
+    a.tile_y0 = p->tile_y0(); a.tiles_x = p->tiles_x; a.tiles_y = p->resident_tiles_y();
     a.bias = prm->bias; a.trim = prm->trim; a.num_frames = in->num_frames;
     a.sample_gi = prm->sample_gi ? 1 : 0; a.approximate_with_ddgi = prm->approximate_with_ddgi ? 1 : 0;
     a.gi_intensity = prm->gi_intensity; a.rough_ddgi_intensity = prm->rough_ddgi_intensity; a.ibl_intensity = prm->ibl_indirect_specular_intensity;
@@ -676,8 +619,9 @@ hr_status hr_reflections_trace_stats(hr_reflections* p, const hr_scene* scene, c
 
 hr_status hr_reflections_temporal(hr_reflections* p, const hr_frame_inputs* in, const hr_reflections_params* prm, void* stream_)
 {
-    HR_CHECK_ARG(p && in && prm && in->cur.depth && in->cur.gb2 && in->cur.gb3 && in->prev.depth && in->prev.gb2 && in->prev.gb3);
-    HR_CHECK_ARG(in->cur.width == p->w && in->prev.width == p->w && in->cur.height == p->h && in->prev.height == p->h);
+    HR_CHECK_ARG(p && in && prm);
+    const hr_status cs = check_inputs(p, in, true);
+    if (cs != HR_OK) return cs;
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int pp = in->ping_pong ? 1 : 0, w = p->w, y0 = p->y0, y1 = p->y1;
@@ -691,7 +635,7 @@ hr_status hr_reflections_temporal(hr_reflections* p, const hr_frame_inputs* in, 
     a.depth = ImgR32F { in->cur.depth, w, y0, y1 }; a.pdepth = ImgR32F { in->prev.depth, w, y0, y1 };
     a.out = (uint2*)p->color[pp].p; a.out_moments = (uint2*)p->moments[pp].p; a.tile_class = (uint8_t*)p->tile_class.p;
     a.w = w; a.h = p->h; a.y0 = y0; a.y1 = y1; a.tiles_x = p->tiles_x;
-    a.apron_flag = (y0 > 0 || y1 < p->h) ? (uint32_t*)((char*)p->counters.p + 48) : nullptr;   // row bands only
+    a.apron_flag = p->apron_flag();
     a.band_y0 = p->band_y0; a.band_y1 = p->band_y1;
     a.alpha = prm->alpha; a.moments_alpha = prm->moments_alpha; a.approximate_with_ddgi = prm->approximate_with_ddgi ? 1 : 0;
     const float* cd = prm->camera_delta;
@@ -699,15 +643,13 @@ hr_status hr_reflections_temporal(hr_reflections* p, const hr_frame_inputs* in, 
     a.geo_hist = nullptr; a.geo_out = nullptr; p->geo_cur = nullptr;
     if (!prm->exact && p->geo[0].p)
     {
-        const bool had_records = p->geo_valid;
-        if (p->geo_valid && !p->first_frame && in->prev.gb2 == p->geo_gb2 && in->prev.gb3 == p->geo_gb3 && in->prev.gb2 != in->cur.gb2 && in->prev.gb3 != in->cur.gb3) a.geo_hist = p->geo[p->geo_parity].p;
-        p->geo_parity ^= 1;
-        a.geo_out = p->geo[p->geo_parity].p;
+        const GeoRecords::Step g = p->records.advance(in->cur.gb2, in->cur.gb3, in->prev.gb2, in->prev.gb3, p->first_frame);
+        if (g.read >= 0) a.geo_hist = p->geo[g.read].p;
+        a.geo_out = p->geo[g.write].p;
         p->geo_cur = a.geo_out;
-        p->geo_valid = true; p->geo_gb2 = in->cur.gb2; p->geo_gb3 = in->cur.gb3;
-        if (p->dbg_require_geo && had_records && !a.geo_hist) { hr::set_last_error("hr_reflections_temporal: HR_DEBUG_REQUIRE_GEO is set and the record path was not taken"); return HR_ERR_INVALID_ARG; }
+        if (g.require_failed) return geo_require_error("hr_reflections_temporal");
     }
-    else p->geo_valid = false;
+    else p->records.invalidate();
     p->last_pp = pp;
     p->last_blur_as_input = prm->blur_as_input != 0;
     const uint64_t px = (uint64_t)w * (y1 - y0);
@@ -781,27 +723,14 @@ static hr_status reflections_atrous01(hr_reflections* p, const hr_frame_inputs* 
     return HR_OK;
 }
 
-hr_status hr_reflections_upsample(hr_reflections* p, const hr_frame_inputs* in, const hr_reflections_params* prm, void* stream_)
+hr_status hr_reflections_upsample(hr_reflections* p, const hr_frame_inputs* in, const hr_reflections_params* prm, void* stream)
 {
     HR_CHECK_ARG(p && in && prm);
-    if (p->scale == 0) return HR_OK;
-    HR_CHECK_ARG(in->cur_full.gb2 && in->cur_full.gb3 && in->cur_full.width == p->full_w && in->cur_full.height == p->full_h);
-    hipStream_t st = (hipStream_t)stream_;
-    p->last_stream = st;
-    UpsampleArgs a;
-    a.W = p->full_w; a.H = p->full_h; a.w = p->w; a.h = p->h;
-    a.G2 = (const uint2*)in->cur_full.gb2; a.G3 = (const uint2*)in->cur_full.gb3; a.g2 = (const uint2*)in->cur.gb2; a.g3 = (const uint2*)in->cur.gb3;
-    a.in = p->atrous[p->read_idx].p; a.in_channels = 4; a.channels = 4; a.out = p->upsample.p; a.sky_value = 0.0f; a.power = 0.0f;
     const uint64_t PX = (uint64_t)p->full_w * p->full_h, px = (uint64_t)p->w * p->h;
-    int ev = p->prof.begin("upsample", st, PX * 24 + px * 24);
-    if (prm->exact) launch_upsample(a, st);
-    else launch_upsample_fast(a, st);
-    p->prof.end(ev, st);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return pass_upsample(p, in, prm->exact != 0, p->atrous[p->read_idx].p, 4, 4, 0.0f, 0.0f, PX * 24 + px * 24, stream);
 }
 
-// Everything of RayTracedReflections::render after the ray trace (ray_traced_reflections.cpp:113-122); see hr_shadows_denoise
+// Everything of RayTracedReflections::render after the ray trace (ray_traced_reflections.cpp:113-122), for a caller that overlaps work with the trace
 hr_status hr_reflections_denoise(hr_reflections* p, const hr_frame_inputs* in, const hr_reflections_params* prm, void* stream)
 {
     HR_CHECK_ARG(p && in && prm);
@@ -833,11 +762,6 @@ hr_status hr_reflections_render(hr_reflections* p, const hr_scene* scene, const 
     hr_status s = hr_reflections_ray_trace(p, scene, in, env, ddgi, prm, stream);
     if (s != HR_OK) return s;
     return hr_reflections_denoise(p, in, prm, stream);
-}
-
-static void fill_view(hr_image_view* v, void* data, int w, int h, int bpp, hr_format f)
-{
-    v->data = data; v->width = w; v->height = h; v->row_pitch_bytes = w * bpp; v->format = f;
 }
 
 hr_status hr_reflections_image(hr_reflections* p, int32_t which, hr_image_view* v)

@@ -14,6 +14,7 @@
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
+#include "pass_core.h"
 
 using namespace hr;
 
@@ -554,25 +555,13 @@ __global__ __launch_bounds__(256) void k_shadows_atrous(AtrousArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-struct hr_shadows
+struct hr_shadows : PassCore
 {
-    hr_ctx* ctx = nullptr;
-    int     full_w = 0, full_h = 0, w = 0, h = 0, scale = 0;
-    int     y0 = 0, y1 = 0;           // resident rows (band + halo)
-    int     band_y0 = 0, band_y1 = 0;
-    int     ry0 = 0, ry1 = 0;         // rows whose history / G-buffer may be read (band + history halo)
-    int     mw = 0, mh = 0, tiles_x = 0, tiles_y = 0;
-    DevBuf  mask, temporal_out, moments[2], prev_image, atrous[2], upsample, tile_class, counters, nd, ray_slots, occluder;
+    DevBuf  mask, temporal_out, moments[2], prev_image, atrous[2], nd, occluder;
     bool    occluder_cache = true;    // developer A/B switch HR_SHADOW_CACHE=0 (read once at create)
-    bool    first_frame = true;
     int     read_idx = 0;             // ATrous::read_idx
-    bool    last_denoise = true;
     int     last_ping_pong = 0;
-    StageProfiler prof;
-    hipStream_t   last_stream = nullptr;
-    bool          want_stats = false;
     int           latched_exact = -1;       // arithmetic mode of the last temporal stage: the `nd` side image it wrote has a mode-specific layout
-    bool          fuse = true;              // tolerance mode: a-trous iterations 0 + 1 in one launch (developer A/B switch HR_FUSE=0)
     bool          persistent_waves = false; // HR_TRACE_KERNEL=queue selects the persistent-wave ray-queue kernel (A/B measurements)
     // developer switches (tools/timeline.py, tools/passbench.py), read from the environment ONCE in hr_shadows_create — the
     // render path never calls getenv
@@ -580,20 +569,8 @@ struct hr_shadows
     bool          dbg_skip_traversal = false, dbg_skip_reproject = false, dbg_timeline_stats = false;
     std::string   dbg_timeline;             // HR_DEBUG_TIMELINE=<file>
     uint64_t      last_wave_max_steps = 0; // sum over waves of the slowest lane's (node + triangle) steps
-    // Tolerance mode: the temporal kernel writes an 8-byte geometry record per pixel {oct normal, mesh id | linear z} — copies of the
-    // current G-buffer's words — for the a-trous taps; the two halves of `nd` alternate, so last frame's records are still there when
-    // the next frame reprojects.  They stand for the caller's PREVIOUS G-buffer exactly when the caller hands back, as in->prev, the
-    // images it passed as in->cur in the previous call (the reference's ping-pong, g_buffer.cpp:208-211): then the reprojection reads
-    // them (4 images, 16 gathers per pixel, full cache lines) instead of prev GB2 / GB3 (5 images, 21 gathers, half of every line).
-    // A previous G-buffer that ALIASES the current one (one buffer rewritten in place) is read as the caller passed it.
-    bool          geo_history = true;       // developer A/B switch HR_GEO_HISTORY=0 (read once at create)
-    bool          geo_valid = false;        // `nd` half geo_parity holds the records of the last frame this pass rendered
-    bool          dbg_require_geo = false;  // HR_DEBUG_REQUIRE_GEO (tests): from the second frame on, a tolerance-mode temporal stage must take the record path
-    int           geo_parity = 0;
-    const void*   geo_gb2 = nullptr;        // in->cur.gb2 / gb3 of that frame
-    const void*   geo_gb3 = nullptr;
+    // tolerance mode: the geometry records (pass_core.h GeoRecords) alternate between the two halves of `nd`; the parity mode's float4 layout covers both
     void*         nd_cur = nullptr;         // the side image of the frame in flight (a-trous stages)
-    TileOrder     tile_order;               // heaviest-first launch order of the trace kernel (tile_order.h)
 };
 
 bool hr::profiling_enabled(const hr_shadows* p) { return p && p->prof.enabled; }
@@ -609,64 +586,35 @@ void hr_shadows_default_params(hr_shadows_params* p)
 
 hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height, hr_scale scale, const hr_band* band, hr_shadows** out)
 {
-    HR_CHECK_ARG(ctx && out && full_width > 0 && full_height > 0 && (int)scale >= 0 && (int)scale <= 2);
-    HR_HIP(hipSetDevice(ctx->device));
-    hr_shadows* p = new hr_shadows();
-    p->ctx = ctx; p->full_w = full_width; p->full_h = full_height; p->scale = (int)scale;
+    hr_shadows* p = nullptr;
+    hr_status   s = pass_new(&p, ctx, full_width, full_height, scale, band, out, BandRule::Shadows, "shadows");
+    if (s != HR_OK) return s;
 #ifdef HR_DEV_PATHS
     { const char* e = getenv("HR_TRACE_KERNEL"); p->persistent_waves = (e && std::string(e) == "queue"); }
 #endif
     if (const char* e = getenv("HR_DEBUG_ONLY_TILE")) sscanf(e, "%d,%d", &p->dbg_only_tx, &p->dbg_only_ty);
-    if (const char* e = getenv("HR_FUSE")) p->fuse = atoi(e) != 0;
     if (const char* e = getenv("HR_SHADOW_CACHE")) p->occluder_cache = atoi(e) != 0;
-    if (const char* e = getenv("HR_GEO_HISTORY")) p->geo_history = atoi(e) != 0;
-    if (const char* e = getenv("HR_DEBUG_REQUIRE_GEO")) p->dbg_require_geo = atoi(e) != 0;   // test switch: a temporal stage that cannot reproject from the records fails
-    if (const char* e = getenv("HR_TILE_ORDER")) p->tile_order.enabled = atoi(e) != 0;
-    p->tile_order.tag = "shadows";
     p->tile_order.min_spread = HR_ORDER_COHERENT_SPREAD;   // rays towards one light: coherent
     p->dbg_skip_traversal = getenv("HR_DEBUG_SKIP_TRAVERSAL") != nullptr;
     p->dbg_skip_reproject = getenv("HR_DEBUG_SKIP_REPROJECT") != nullptr;
     p->dbg_timeline_stats = getenv("HR_DEBUG_TIMELINE_STATS") != nullptr;
     if (const char* e = getenv("HR_DEBUG_TIMELINE")) p->dbg_timeline = e;
-    // m_width = extent / 2^scale (ray_traced_shadows.cpp:80-83: float divide then truncation)
-    p->w = full_width >> (int)scale; p->h = full_height >> (int)scale;
-    p->y0 = 0; p->y1 = p->h; p->band_y0 = 0; p->band_y1 = p->h; p->ry0 = 0; p->ry1 = p->h;
-    if (band && band->band_y1 > band->band_y0)
-    {
-        if (band->band_y0 < 0 || band->band_y1 > p->h || (band->band_y0 & 7) || ((band->band_y1 & 7) && band->band_y1 != p->h) || band->halo < 0 || (band->halo & 7))
-        {
-            set_last_error("band rows must be multiples of 8 inside the pass image; halo a multiple of 8");
-            delete p;
-            return HR_ERR_INVALID_ARG;
-        }
-        p->band_y0 = band->band_y0; p->band_y1 = band->band_y1;
-        p->y0 = band->band_y0 - band->halo < 0 ? 0 : band->band_y0 - band->halo;
-        p->y1 = band->band_y1 + band->halo > p->h ? p->h : band->band_y1 + band->halo;
-        const int hh = band->history_halo > band->halo ? band->history_halo : band->halo;
-        p->ry0 = band->band_y0 - hh < 0 ? 0 : band->band_y0 - hh;
-        p->ry1 = band->band_y1 + hh > p->h ? p->h : band->band_y1 + hh;
-    }
-    p->mw = cdiv(p->w, 8); p->mh = cdiv(p->h, 4);
-    p->tiles_x = cdiv(p->w, 8); p->tiles_y = cdiv(p->h, 8);
     const size_t px = (size_t)p->w * p->h; // full-frame sized (bands index with absolute rows)
-    hr_status s;
-#define A(buf, n) if ((s = p->buf.alloc(n)) != HR_OK) { delete p; return s; }
-    A(mask, (size_t)p->mw * p->mh * 4)
-    A(temporal_out, px * 4)
-    A(moments[0], px * 8)
-    A(moments[1], px * 8)
-    A(prev_image, px * 4)
-    A(atrous[0], px * 4)
-    A(atrous[1], px * 4)
-    A(upsample, (size_t)full_width * full_height * 2)
+    HR_PASS_ALLOC(mask, (size_t)p->mw * p->mh * 4)
+    HR_PASS_ALLOC(temporal_out, px * 4)
+    HR_PASS_ALLOC(moments[0], px * 8)
+    HR_PASS_ALLOC(moments[1], px * 8)
+    HR_PASS_ALLOC(prev_image, px * 4)
+    HR_PASS_ALLOC(atrous[0], px * 4)
+    HR_PASS_ALLOC(atrous[1], px * 4)
+    HR_PASS_ALLOC(upsample, (size_t)full_width * full_height * 2)
     // + 8 readable bytes: kf_shadows_atrous fetches the classes of a workgroup's four tiles as the two aligned dwords that hold them
-    A(tile_class, (((size_t)p->tiles_x * p->tiles_y + 3) & ~(size_t)3) + 8)
-    A(nd, px * 16)
-    A(counters, 64)
-    A(ray_slots, (size_t)p->tiles_x * p->tiles_y * 2)
-    A(occluder, px * 4)
-#undef A
-    if ((s = p->tile_order.init(p->tiles_x * (cdiv(p->y1, 8) - p->y0 / 8))) != HR_OK) { delete p; return s; }
+    HR_PASS_ALLOC(tile_class, (((size_t)p->tiles_x * p->tiles_y + 3) & ~(size_t)3) + 8)
+    HR_PASS_ALLOC(nd, px * 16)
+    HR_PASS_ALLOC(counters, 64)
+    HR_PASS_ALLOC(ray_slots, (size_t)p->tiles_x * p->tiles_y * 2)
+    HR_PASS_ALLOC(occluder, px * 4)
+    if ((s = p->tile_order.init(p->resident_tiles())) != HR_OK) { delete p; return s; }
     HR_HIP(hipMemset(p->occluder.p, 0xff, p->occluder.bytes));   // no cached occluder
     HR_HIP(hipMemset(p->counters.p, 0, 64));
     HR_HIP(hipMemset(p->ray_slots.p, 0, p->ray_slots.bytes));
@@ -676,63 +624,13 @@ hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height
     return HR_OK;
 }
 
-hr_status hr_shadows_destroy(hr_shadows* p)
-{
-    if (!p) return HR_OK;
-    (void)hipSetDevice(p->ctx->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return HR_OK;
-}
-
-hr_status hr_shadows_reset_history(hr_shadows* p)
-{
-    HR_CHECK_ARG(p);
-    p->first_frame = true;
-    p->geo_valid = false;
-    p->tile_order.invalidate();   // costs of a frame that may never have run are not sorted (the launch list itself is always a permutation)
-    return HR_OK;
-}
-
-// Row bands: did any history tap of the frames rendered since the last call fall on an image row this GPU does not hold (per-frame
-// motion beyond hr_band.history_halo)?  Such taps were treated as disoccluded — the image stays valid but is no longer identical to
-// the single-GPU one; the integrator widens history_halo (or re-creates the band) when this fires.  Synchronises the stream.
-hr_status hr_shadows_history_apron_exceeded(hr_shadows* p, int32_t* exceeded)
-{
-    HR_CHECK_ARG(p && exceeded);
-    uint32_t v = 0;
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    HR_HIP(hipMemcpy(&v, (char*)p->counters.p + 48, 4, hipMemcpyDeviceToHost));
-    if (v) HR_HIP(hipMemset((char*)p->counters.p + 48, 0, 4));
-    *exceeded = v ? 1 : 0;
-    return HR_OK;
-}
-
-hr_status hr_shadows_set_profiling(hr_shadows* p, int32_t enable)
-{
-    HR_CHECK_ARG(p);
-    p->prof.enabled = enable != 0;
-    return HR_OK;
-}
-
-hr_status hr_shadows_get_stage_times(hr_shadows* p, hr_stage_times* out)
-{
-    HR_CHECK_ARG(p && out);
-    p->prof.collect(out);
-    return HR_OK;
-}
-
-hr_status hr_shadows_ray_count(hr_shadows* p, uint64_t* rays)
-{
-    HR_CHECK_ARG(p && rays);
-    HR_HIP(hipStreamSynchronize(p->last_stream));
-    std::vector<uint16_t> slots((size_t)p->tiles_x * p->tiles_y);
-    HR_HIP(hipMemcpy(slots.data(), p->ray_slots.p, slots.size() * 2, hipMemcpyDeviceToHost));
-    uint64_t total = 0;
-    for (uint16_t v : slots) total += v;
-    *rays = total;
-    return HR_OK;
-}
+hr_status hr_shadows_destroy(hr_shadows* p) { return pass_destroy(p); }
+hr_status hr_shadows_reset_history(hr_shadows* p) { return pass_reset_history(p); }
+hr_status hr_shadows_history_apron_exceeded(hr_shadows* p, int32_t* exceeded) { return pass_history_apron_exceeded(p, exceeded); }
+hr_status hr_shadows_set_profiling(hr_shadows* p, int32_t enable) { return pass_set_profiling(p, enable); }
+hr_status hr_shadows_get_stage_times(hr_shadows* p, hr_stage_times* out) { return pass_get_stage_times(p, out); }
+hr_status hr_shadows_ray_count(hr_shadows* p, uint64_t* rays) { return pass_ray_count<uint16_t>(p, rays); }
+hr_status hr_shadows_launch_order(hr_shadows* p, uint32_t* out, int32_t* n_tiles) { return pass_launch_order(p, out, n_tiles); }
 
 hr_status hr_shadows_tile_ray_counts(hr_shadows* p, uint16_t* out, int32_t* tiles_x, int32_t* tiles_y)
 {
@@ -742,20 +640,6 @@ hr_status hr_shadows_tile_ray_counts(hr_shadows* p, uint16_t* out, int32_t* tile
     if (!out) return HR_OK;
     HR_HIP(hipStreamSynchronize(p->last_stream));
     HR_HIP(hipMemcpy(out, p->ray_slots.p, (size_t)p->tiles_x * p->tiles_y * 2, hipMemcpyDeviceToHost));
-    return HR_OK;
-}
-
-hr_status hr_shadows_launch_order(hr_shadows* p, uint32_t* out, int32_t* n_tiles)
-{
-    HR_CHECK_ARG(p);
-    return p->tile_order.read(out, n_tiles, p->last_stream);
-}
-
-static hr_status check_inputs(const hr_shadows* p, const hr_frame_inputs* in, bool need_prev)
-{
-    HR_CHECK_ARG(in->cur.depth && in->cur.gb2 && in->cur.gb3);
-    HR_CHECK_ARG(in->cur.width == p->w && in->cur.height == p->h);
-    if (need_prev) HR_CHECK_ARG(in->prev.depth && in->prev.gb2 && in->prev.gb3 && in->prev.width == p->w && in->prev.height == p->h);
     return HR_OK;
 }
 
@@ -790,7 +674,7 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     a.stats = nullptr;
     a.timeline = nullptr;
     a.w = p->w; a.h = p->h; a.y0 = p->y0; a.y1 = p->y1; a.mw = p->mw;
-    a.tile_y0 = p->y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(p->y1, 8) - a.tile_y0;
+    a.tile_y0 = p->tile_y0(); a.tiles_x = p->tiles_x; a.tiles_y = p->resident_tiles_y();
     a.bias = prm->bias; a.num_frames = in->num_frames;
     a.occluder = p->occluder_cache ? (uint32_t*)p->occluder.p : nullptr;
     a.n_tri_refs = (uint32_t)(scene->tris.bytes / sizeof(TriGPU));
@@ -923,23 +807,20 @@ hr_status hr_shadows_temporal(hr_shadows* p, const hr_frame_inputs* in, const hr
         // (round 5: bands too — the records of the rows a band reads history from but does not compute, hr_band.history_halo beyond
         // hr_band.halo, are copies of the current G-buffer as well, written by a few extra workgroups of the temporal launch: GeoApronArgs)
         const size_t half = (size_t)p->w * p->h * 8;
-        const bool   had_records = p->geo_history && p->geo_valid;
-        if (p->geo_history && p->geo_valid && !p->first_frame && in->prev.gb2 == p->geo_gb2 && in->prev.gb3 == p->geo_gb3 && in->prev.gb2 != in->cur.gb2 && in->prev.gb3 != in->cur.gb3)
-            a.geo_hist = (const char*)p->nd.p + (size_t)p->geo_parity * half;
-        p->geo_parity ^= 1;
-        a.nd = (float4*)((char*)p->nd.p + (size_t)p->geo_parity * half);
-        p->geo_valid = true; p->geo_gb2 = in->cur.gb2; p->geo_gb3 = in->cur.gb3;
-        if (p->geo_history && (ry0 < y0 || ry1 > y1))
+        const GeoRecords::Step g = p->records.advance(in->cur.gb2, in->cur.gb3, in->prev.gb2, in->prev.gb3, p->first_frame);
+        if (g.read >= 0) a.geo_hist = (const char*)p->nd.p + (size_t)g.read * half;
+        a.nd = (float4*)((char*)p->nd.p + (size_t)g.write * half);
+        if (p->records.history && (ry0 < y0 || ry1 > y1))
             a.apron = GeoApronArgs { in->cur.gb2, in->cur.gb3, a.nd, w, ry0, y0, y1, ry1, -1 };
-        if (p->dbg_require_geo && had_records && !a.geo_hist) { set_last_error("hr_shadows_temporal: HR_DEBUG_REQUIRE_GEO is set and the record path was not taken"); return HR_ERR_INVALID_ARG; }
+        if (g.require_failed) return geo_require_error("hr_shadows_temporal");
     }
-    else p->geo_valid = false;   // the parity mode's float4 layout covers both halves
+    else p->records.invalidate();   // the parity mode's float4 layout covers both halves
     p->nd_cur = a.nd;
     a.w = w; a.h = p->h; a.y0 = y0; a.y1 = y1;
-    a.tile_y0 = y0 / 8; a.tiles_x = p->tiles_x; a.tiles_y = cdiv(y1, 8) - a.tile_y0;
+    a.tile_y0 = p->tile_y0(); a.tiles_x = p->tiles_x; a.tiles_y = p->resident_tiles_y();
     a.alpha = prm->alpha; a.moments_alpha = prm->moments_alpha;
     a.debug_skip_reproject = p->dbg_skip_reproject ? 1 : 0;
-    a.apron_flag = (p->y0 > 0 || p->y1 < p->h) ? (uint32_t*)((char*)p->counters.p + 48) : nullptr;   // row bands only
+    a.apron_flag = p->apron_flag();
     a.band_y0 = p->band_y0; a.band_y1 = p->band_y1;
     p->last_ping_pong = in->ping_pong ? 1 : 0;
     const uint64_t px = (uint64_t)w * (y1 - y0);
@@ -1036,26 +917,11 @@ static hr_status shadows_atrous01(hr_shadows* p, const hr_frame_inputs* in, cons
     return HR_OK;
 }
 
-hr_status hr_shadows_upsample(hr_shadows* p, const hr_frame_inputs* in, const hr_shadows_params* prm, void* stream_)
+hr_status hr_shadows_upsample(hr_shadows* p, const hr_frame_inputs* in, const hr_shadows_params* prm, void* stream)
 {
     HR_CHECK_ARG(p && in && prm);
-    if (p->scale == 0) return HR_OK; // ray_traced_shadows.cpp:113
-    HR_CHECK_ARG(in->cur_full.gb2 && in->cur_full.gb3 && in->cur_full.width == p->full_w && in->cur_full.height == p->full_h);
-    hipStream_t st = (hipStream_t)stream_;
-    p->last_stream = st;
-    UpsampleArgs a;
-    a.W = p->full_w; a.H = p->full_h; a.w = p->w; a.h = p->h;
-    a.G2 = (const uint2*)in->cur_full.gb2; a.G3 = (const uint2*)in->cur_full.gb3;
-    a.g2 = (const uint2*)in->cur.gb2; a.g3 = (const uint2*)in->cur.gb3;
-    a.in = p->atrous[p->read_idx].p; a.in_channels = 2; a.channels = 1;
-    a.out = p->upsample.p; a.sky_value = 0.0f; a.power = 0.0f;
     const uint64_t PX = (uint64_t)p->full_w * p->full_h, px = (uint64_t)p->w * p->h;
-    int ev = p->prof.begin("upsample", st, PX * 18 + px * 20);
-    if (prm->exact) launch_upsample(a, st);
-    else launch_upsample_fast(a, st);
-    p->prof.end(ev, st);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return pass_upsample(p, in, prm->exact != 0, p->atrous[p->read_idx].p, 2, 1, 0.0f, 0.0f, PX * 18 + px * 20, stream);
 }
 
 // Everything of RayTracedShadows::render after the ray trace (ray_traced_shadows.cpp:104-113): temporal accumulation, the a-trous
@@ -1090,11 +956,6 @@ hr_status hr_shadows_render(hr_shadows* p, const hr_scene* scene, const hr_frame
     hr_status s = hr_shadows_ray_trace(p, scene, in, prm, stream);
     if (s != HR_OK) return s;
     return hr_shadows_denoise(p, in, prm, stream);
-}
-
-static void fill_view(hr_image_view* v, void* data, int w, int h, int bpp, hr_format f)
-{
-    v->data = data; v->width = w; v->height = h; v->row_pitch_bytes = w * bpp; v->format = f;
 }
 
 hr_status hr_shadows_image(hr_shadows* p, int32_t which, hr_image_view* v)
