@@ -38,6 +38,8 @@
 
 using namespace hr;
 
+#include "atrous_filters.h"   // the a-trous / blur filter bodies; under the contract(fast) above, like the kernels that call them
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -466,19 +468,9 @@ __global__ __launch_bounds__(64 * FT_WAVES, FT_SHADOWS_EU) void kf_shadows_tempo
 
 // ------------------------------------------------------------------------------------------------------------------------
 // shadows_denoise_atrous.comp:94-174 + copy_shadow_tiles (tile class), tolerance mode.  STEP > 0: compile-time tap distance and
-// radius 1 (the reference default, fully unrolled: atrous_gather_pixel); STEP == 0: run-time step and radius.
-struct EdgeK { float kz, phi_n, inv_phi_l; bool n32; };
-HR_DEV float edge_weight_fast(const EdgeK& k, float cd, float sd, f3 cn, f3 sn, float cl, float sl)
-{
-    // edge_stopping.glsl:31-62 (NORMAL + LUMA): exp(-max(wL, 0) - max(wZ, 0)) * wN with wZ = exp(-|dz| / sigma) — sic, the depth
-    // WEIGHT is used as an exponent term upstream; kept
-    const float wZ = fm::exp2f_(-__builtin_fabsf(cd - sd) * k.kz);
-    const float dn = fm::sat(fm::dot(cn, sn));
-    const float wN = k.n32 ? fm::pow32(dn) : fm::powf_(dn, k.phi_n);
-    const float wL = __builtin_fabsf(cl - sl) * k.inv_phi_l;
-    return fm::exp2f_((wL + wZ) * -1.44269504088896341f) * wN;
-}
-
+// radius 1 (the reference default, fully unrolled: atrous_gather_pixel); STEP == 0: run-time step and radius.  The filter itself is
+// atrous_filters.h.
+//
 // One pixel of a live tile for kf_shadows_atrous<STEP > 0>: every load first, in one batch, then the arithmetic.  INTERIOR: the
 // workgroup's whole footprint is resident, no bounds test; else a texel that is not resident is fetched at the centre's address
 // and counts as 0 (variance) / gets weight 0 (tap).  Two whole copies of the pixel on purpose: with only the loads in the two
@@ -507,8 +499,7 @@ HR_DEV void atrous_gather_pixel(const AtrousArgs& a, int x, int y, uint32_t o)
 #pragma unroll
     for (int t = 0; t < 8; t++)
     {
-        const int k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-        const int px = x + xx * STEP, py = y + yy * STEP;
+        const int px = x + tap_xy(t).xx * STEP, py = y + tap_xy(t).yy * STEP;
         // a tap outside the image is skipped; one outside the resident rows of a band reads zeros, whose weight is 0 (halo
         // rows only): both get weight 0 below
         const bool     res = INTERIOR || (px >= 0 && py >= 0 && px < a.w && py < a.h && py >= a.y0 && py < a.y1);
@@ -518,41 +509,21 @@ HR_DEV void atrous_gather_pixel(const AtrousArgs& a, int x, int y, uint32_t o)
         t_nd[t] = fm::ld<uint2>(a.nd, so * 8u);
     }
     __builtin_amdgcn_sched_barrier(0);   // nothing of the arithmetic (and none of its waits) in front of a load
-    // compute_variance_center (:65-88): 3x3 gaussian of the variance channel, unit taps
-    float var = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 9; k++)
+    // the texel source: those register arrays, decoded at use
+    struct Loaded
     {
-        const int   xx = k % 3 - 1, yy = k / 3 - 1;
-        const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
-        var += fm::hi(v_in[k]) * kw;
-    }
-    const float cz = fm::hi(cnd.y);
-    const f3    cn = fm::oct_unit(cnd.x);
-    const float cv = fm::lo(c);
-    EdgeK ek;
-    ek.kz        = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-    ek.phi_n     = a.phi_normal;
-    ek.n32       = N32;
-    ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
-    float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-    {
-        const int   k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-        const float kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
-        const float sv = fm::lo(t_in[t]);
-        float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(t_nd[t].y), cn, fm::oct_unit(t_nd[t].x), cv, sv), kk);
-        if (!t_ok[t]) wv = 0.0f;
-        sum_w += wv;
-        sum_v += wv * sv;
-        sum_var += (wv * wv) * fm::hi(t_in[t]);
-    }
-    const float iw = fm::rcp(sum_w);
-    float ov = sum_v * iw;
-    const float ovar = sum_var * (iw * iw);
-    if (a.power != 0.0f) ov = fm::powf_(fm::fmax_(ov, 0.0f), a.power);
-    const uint32_t result = cz < 0.0f ? c : fm::pack2(ov, ovar);   // a sky centre passes through: its taps were fetched for nothing
+        const uint32_t (&v_in)[9], (&t_in)[8];
+        const uint2    (&t_nd)[8], cnd;
+        const bool     (&t_ok)[8];
+        static HR_DEV constexpr int k(int xx, int yy) { return (yy + 1) * 3 + (xx + 1); }
+        static HR_DEV constexpr int t(int xx, int yy) { return k(xx, yy) < 4 ? k(xx, yy) : k(xx, yy) - 1; }
+        HR_DEV uint32_t unit(int xx, int yy) const { return v_in[k(xx, yy)]; }
+        HR_DEV uint32_t tap(int xx, int yy) const { return t_in[t(xx, yy)]; }
+        HR_DEV NZ       nz(int xx, int yy) const { return (xx == 0 && yy == 0) ? nz_of(cnd.x, cnd.y) : nz_of(t_nd[t(xx, yy)].x, t_nd[t(xx, yy)].y); }
+        HR_DEV bool     ok(int xx, int yy) const { return t_ok[t(xx, yy)]; }
+    };
+    // a sky centre passes through by select: its taps were fetched for nothing
+    const uint32_t result = shadows_filter<false>(Loaded { v_in, t_in, t_nd, cnd, t_ok }, [&] { return edge_setup(a.sigma_depth, a.phi_normal, N32); }, a.phi_visibility, a.power);
     *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out) + o * 4u) = result;
     if (a.out2) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) = result;
 }
@@ -611,62 +582,30 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
     const uint32_t c   = fm::ld<uint32_t>(a.in.p, o * 4u);
     const uint2    cnd = fm::ld<uint2>(a.nd, o * 8u);   // oct normal (fp16 x 2), mesh id | linear z (fp16 x 2)
     const float    cz  = fm::hi(cnd.y);
-    float var = 0.0f;
     // compute_variance_center (:65-88): 3x3 gaussian of the variance channel, unit taps
-    if (interior)
-    {
-#pragma unroll
-        for (int k = 0; k < 9; k++)
-        {
-            const int   xx = k % 3 - 1, yy = k / 3 - 1;
-            const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
-            var += fm::hi(fm::ld<uint32_t>(a.in.p, (uint32_t)((y + yy) * a.w + (x + xx)) * 4u)) * kw;
-        }
-    }
-    else
-    {
-#pragma unroll
-        for (int k = 0; k < 9; k++)
-        {
-            const int   xx = k % 3 - 1, yy = k / 3 - 1;
-            const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
-            var += fm::hi(a.in.raw(x + xx, y + yy)) * kw;
-        }
-    }
+    const float var = interior ? prefilter_variance([=](int xx, int yy) { return fm::hi(fm::ld<uint32_t>(a.in.p, (uint32_t)((y + yy) * a.w + (x + xx)) * 4u)); })
+                               : prefilter_variance([=](int xx, int yy) { return fm::hi(a.in.raw(x + xx, y + yy)); });
     uint32_t result = c;
     if (!(cz < 0.0f))
     {
-        const f3    cn = fm::oct_unit(cnd.x);
-        const float cv = fm::lo(c);
-        EdgeK ek;
-        ek.kz        = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-        ek.phi_n     = a.phi_normal;
-        ek.n32       = N32;
-        ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
-        float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
+        const NZ    cnz = nz_of(cnd.x, cnd.y);
+        const float cv  = fm::lo(c);
+        EdgeK ek = edge_setup(a.sigma_depth, a.phi_normal, N32);
+        ek.inv_phi_l = edge_luma(a.phi_visibility, var);
+        ShadowSums sum { 1.0f, cv, fm::hi(c) };
         for (int yy = -R; yy <= R; yy++)
             for (int xx = -R; xx <= R; xx++)
             {
                 const int px = x + xx * step, py = y + yy * step;
                 if (px < 0 || py < 0 || px >= a.w || py >= a.h || (xx == 0 && yy == 0)) continue;
-                const int   axx = xx < 0 ? -xx : xx, ayy = yy < 0 ? -yy : yy;
-                const float kx = axx == 0 ? 1.0f : (axx == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
-                const float ky = ayy == 0 ? 1.0f : (ayy == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
+                const float kk = tap_weight(xx, yy);
                 if (py < a.y0 || py >= a.y1) continue;   // outside the resident rows of a band: zeros, weight 0
                 const uint32_t so = (uint32_t)(py * a.w + px);
                 const uint32_t s  = fm::ld<uint32_t>(a.in.p, so * 4u);
                 const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
-                const float sv = fm::lo(s);
-                const float wv = fm::mul_rn(edge_weight_fast(ek, cz, fm::hi(nd.y), cn, fm::oct_unit(nd.x), cv, sv), kx * ky);
-                sum_w += wv;
-                sum_v += wv * sv;
-                sum_var += (wv * wv) * fm::hi(s);
+                sum.add(ek, cnz, cv, nz_of(nd.x, nd.y), s, kk, true);
             }
-        const float iw = fm::rcp(sum_w);
-        float ov = sum_v * iw;
-        const float ovar = sum_var * (iw * iw);
-        if (a.power != 0.0f) ov = fm::powf_(fm::fmax_(ov, 0.0f), a.power);
-        result = fm::pack2(ov, ovar);
+        result = sum.finish(a.power);
     }
     *outp = result;
     if (out2p) *out2p = result;
@@ -705,14 +644,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
         for (int i = threadIdx.x; i < TH * TW; i += 256)
         {
             const int  cy = i / TW, cx = i - cy * TW;
-            const int  gx = bx0 - STEP + cx, gy = by0 - STEP + cy;
-            const bool res = gx >= 0 && gx < a.w && gy >= ry0 && gy < ry1;
-            const uint32_t so = res ? (uint32_t)(gy * a.w + gx) : (uint32_t)(ry0 * a.w);
-            const uint32_t v  = fm::ld<uint32_t>(a.in.p, so * 4u);
-            const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
-            const f3       n  = fm::oct_unit(nd.x);
-            s_in[i] = res ? v : 0u;
-            s_nz[i] = res ? make_float4(n.x, n.y, n.z, fm::hi(nd.y)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            shadows_stage_texel(a, bx0 - STEP + cx, by0 - STEP + cy, ry0, ry1, s_in[i], s_nz[i]);
         }
         __syncthreads();
     }
@@ -726,49 +658,8 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
         if (out2p) *out2p = 0u;
         return;
     }
-    const int      ci  = (ly + STEP) * TW + (lx + STEP);
-    const uint32_t c   = s_in[ci];
-    const float4   cnz = s_nz[ci];
-    // compute_variance_center (:65-88): 3x3 gaussian of the variance channel, unit taps
-    float var = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 9; k++)
-    {
-        const int   xx = k % 3 - 1, yy = k / 3 - 1;
-        const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
-        var += fm::hi(s_in[ci + yy * TW + xx]) * kw;
-    }
-    uint32_t result = c;
-    if (!(cnz.w < 0.0f))
-    {
-        const f3    cn = mk3(cnz.x, cnz.y, cnz.z);
-        const float cv = fm::lo(c);
-        EdgeK ek;
-        ek.kz        = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-        ek.phi_n     = a.phi_normal;
-        ek.n32       = N32;
-        ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
-        float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
-#pragma unroll
-        for (int t = 0; t < 8; t++)
-        {
-            const int      k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-            const float    kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
-            const int      ti = ci + yy * STEP * TW + xx * STEP;
-            const uint32_t tv = s_in[ti];
-            const float4   tn = s_nz[ti];
-            const float    sv = fm::lo(tv);
-            const float    wv = fm::mul_rn(edge_weight_fast(ek, cnz.w, tn.w, cn, mk3(tn.x, tn.y, tn.z), cv, sv), kk);
-            sum_w += wv;
-            sum_v += wv * sv;
-            sum_var += (wv * wv) * fm::hi(tv);
-        }
-        const float iw = fm::rcp(sum_w);
-        float ov = sum_v * iw;
-        const float ovar = sum_var * (iw * iw);
-        if (a.power != 0.0f) ov = fm::powf_(fm::fmax_(ov, 0.0f), a.power);
-        result = fm::pack2(ov, ovar);
-    }
+    const int      ci     = (ly + STEP) * TW + (lx + STEP);
+    const uint32_t result = shadows_filter<true>(StagedTaps { s_in, s_nz, TW, ci, TW, ci, STEP }, [&] { return edge_setup(a.sigma_depth, a.phi_normal, N32); }, a.phi_visibility, a.power);
     *outp = result;
     if (out2p) *out2p = result;
 }
@@ -816,55 +707,13 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
     for (int i = threadIdx.x; i < AH * AW; i += 256)
     {
         const int  cy = i / AW, cx = i - cy * AW;
-        const int  gx = bx0 - 3 + cx, gy = by0 - 3 + cy;
-        const bool res = gx >= 0 && gx < a.w && gy >= ry0 && gy < ry1;
-        const uint32_t so = res ? (uint32_t)(gy * a.w + gx) : (uint32_t)(ry0 * a.w);
-        const uint32_t v  = fm::ld<uint32_t>(a.in.p, so * 4u);
-        const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
-        const f3       n  = fm::oct_unit(nd.x);
-        s_in[i] = res ? v : 0u;
-        s_nz[i] = res ? make_float4(n.x, n.y, n.z, fm::hi(nd.y)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        shadows_stage_texel(a, bx0 - 3 + cx, by0 - 3 + cy, ry0, ry1, s_in[i], s_nz[i]);
     }
     __syncthreads();
-    EdgeK ek;
-    ek.kz    = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-    ek.phi_n = a.phi_normal;
-    ek.n32   = N32;
+    const EdgeK ek = edge_setup(a.sigma_depth, a.phi_normal, N32);
     // one filter evaluation: centre index ci in the A grid, values from `img` (stride IW, centre index vi), taps at distance D
     auto filter = [&](const uint32_t* img, int IW, int vi, int ci, int D, float power) -> uint32_t {
-        const uint32_t c   = img[vi];
-        const float4   cnz = s_nz[ci];
-        float var = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 9; k++)
-        {
-            const int   xx = k % 3 - 1, yy = k / 3 - 1;
-            const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
-            var += fm::hi(img[vi + yy * IW + xx]) * kw;
-        }
-        if (cnz.w < 0.0f) return c;
-        const f3    cn = mk3(cnz.x, cnz.y, cnz.z);
-        const float cv = fm::lo(c);
-        ek.inv_phi_l = fm::rcp(a.phi_visibility * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
-        float sum_w = 1.0f, sum_v = cv, sum_var = fm::hi(c);
-#pragma unroll
-        for (int t = 0; t < 8; t++)
-        {
-            const int      k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-            const float    kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
-            const uint32_t tv = img[vi + yy * D * IW + xx * D];
-            const float4   tn = s_nz[ci + yy * D * AW + xx * D];
-            const float    sv = fm::lo(tv);
-            const float    wv = fm::mul_rn(edge_weight_fast(ek, cnz.w, tn.w, cn, mk3(tn.x, tn.y, tn.z), cv, sv), kk);
-            sum_w += wv;
-            sum_v += wv * sv;
-            sum_var += (wv * wv) * fm::hi(tv);
-        }
-        const float iw = fm::rcp(sum_w);
-        float ov = sum_v * iw;
-        const float ovar = sum_var * (iw * iw);
-        if (power != 0.0f) ov = fm::powf_(fm::fmax_(ov, 0.0f), power);
-        return fm::pack2(ov, ovar);
+        return shadows_filter<true>(StagedTaps { img, s_nz, IW, vi, AW, ci, D }, [&] { return ek; }, a.phi_visibility, power);
     };
     // iteration 0 on region B
     for (int j = threadIdx.x; j < BH * BW; j += 256)
@@ -1000,13 +849,7 @@ __global__ __launch_bounds__(64 * FT_WAVES, FT_AO_EU) void kf_ao_temporal(AOTemp
 // ------------------------------------------------------------------------------------------------------------------------
 // ao_denoise_bilateral_blur.comp:75-139, tolerance mode.  LDS-tiled: the tile + its apron along the blur direction is decoded
 // ONCE (linear eye depth, unit normal, AO value: 20 B per texel in LDS) instead of per tap — 8 taps of a radius-4 blur re-derived
-// an octahedral decode + a normalisation + a reciprocal each.
-HR_DEV float gaussian_weight_fast(float offset, float deviation)
-{
-    const float d2 = deviation * deviation;
-    return fm::rsq(2.0f * HR_M_PI * d2) * fm::expf_(-(offset * offset) * fm::rcp(2.0f * d2));
-}
-
+// an octahedral decode + a normalisation + a reciprocal each.  The staging step and the 1-D tap loop are atrous_filters.h.
 template <int RADIUS>
 __global__ __launch_bounds__(256) void kf_ao_blur(AOBlurArgs a)
 {
@@ -1028,16 +871,7 @@ __global__ __launch_bounds__(256) void kf_ao_blur(AOBlurArgs a)
     for (int i = threadIdx.x; i < SW * SH; i += 256)
     {
         const int  sy = i / SW, sx = i - sy * SW;
-        const int  px = ox + sx, py = oy + sy;
-        const bool ok = !(px < 0 || py < a.y0 || px >= a.w || py >= a.y1);
-        const uint32_t off = ok ? (uint32_t)(py * a.w + px) : (uint32_t)(a.y0 * a.w);
-        float    z  = fm::ld<float>(a.depth.p, off * 4u);
-        uint32_t g2 = fm::ld<uint32_t>(a.gb2.p, off * 8u);
-        uint16_t v  = fm::ld<uint16_t>(a.in.p, off * 2u);
-        if (!ok) { z = 0.0f; g2 = 0u; v = 0; }          // texel fetches outside the image read 0 (pinned rule), then decode as usual
-        const f3 n = fm::oct_unit(g2);
-        s_nz[i] = make_float4(n.x, n.y, n.z, fm::rcp_nr(fm::mad_rn(a.zbp[2], z, a.zbp[3])));
-        s_ao[i] = (float)__builtin_bit_cast(_Float16, v);
+        ao_stage_texel(a, ox + sx, oy + sy, s_nz[i], s_ao[i], [](bool, int, int, float) {});
     }
     __syncthreads();
     if (!have) return;
@@ -1045,7 +879,7 @@ __global__ __launch_bounds__(256) void kf_ao_blur(AOBlurArgs a)
     const uint16_t one = 0x3c00u;
     if (!tclass) { *outp = one; return; }   // cleared image (ray_traced_ao.cpp:1048-1055)
     if (cdepth == 1.0f) { *outp = one; return; }
-    const int    ci = (ly + RADIUS * a.dy) * SW + lx + RADIUS * a.dx, stride = a.dy * SW + a.dx;
+    const int ci = (ly + RADIUS * a.dy) * SW + lx + RADIUS * a.dx, stride = a.dy * SW + a.dx;
     const float4 c  = s_nz[ci];
     float total_ao = s_ao[ci], total_w = 1.0f;
 #pragma unroll
@@ -1053,13 +887,11 @@ __global__ __launch_bounds__(256) void kf_ao_blur(AOBlurArgs a)
     {
         if (i == 0) continue;
         const float4 t  = s_nz[ci + i * stride];
-        const float  wZ = fm::exp2f_(-__builtin_fabsf(c.w - t.w) * 1.44269504088896341f);
-        const float  wN = fm::pow32(fm::sat(c.x * t.x + c.y * t.y + c.z * t.z));
-        const float  w  = s_gauss[i + RADIUS] * (fm::exp2f_((1.0f + wZ) * -1.44269504088896341f) * wN);
+        const float  w  = ao_tap_weight(&s_gauss[i + RADIUS], c.w, t.w, c.x * t.x + c.y * t.y + c.z * t.z);
         total_ao += w * s_ao[ci + i * stride];
         total_w += w;
     }
-    *outp = fm::half_bits(total_ao * fm::rcp(fm::fmax_(total_w, 0.0001f)));
+    *outp = fm::half_bits(ao_normalise(total_ao, total_w));
 }
 
 // Both passes of the separable blur in ONE launch: the X result of the tile's rows + a RADIUS-row apron above
@@ -1085,18 +917,10 @@ __global__ __launch_bounds__(256) void kf_ao_blur_xy(AOBlurArgs a)
     for (int i = threadIdx.x; i < SW * SH; i += 256)
     {
         const int  sy = i / SW, sx = i - sy * SW;
-        const int  px = ox + sx, py = oy + sy;
-        const bool ok = !(px < 0 || py < a.y0 || px >= a.w || py >= a.y1);
-        const uint32_t off = ok ? (uint32_t)(py * a.w + px) : (uint32_t)(a.y0 * a.w);
-        float    z  = fm::ld<float>(a.depth.p, off * 4u);
-        uint32_t g2 = fm::ld<uint32_t>(a.gb2.p, off * 8u);
-        uint16_t v  = fm::ld<uint16_t>(a.in.p, off * 2u);
-        const uint8_t tc = a.tile_class[ok ? (size_t)(py >> 3) * a.tiles_x + (px >> 3) : 0];
-        s_kind[i] = !ok ? 0 : ((!tc || z == 1.0f) ? 1 : 2);
-        if (!ok) { z = 0.0f; g2 = 0u; v = 0; }          // texel fetches outside the image read 0 (pinned rule), then decode as usual
-        const f3 n = fm::oct_unit(g2);
-        s_nz[i] = make_float4(n.x, n.y, n.z, fm::rcp_nr(fm::mad_rn(a.zbp[2], z, a.zbp[3])));
-        s_ao[i] = (float)__builtin_bit_cast(_Float16, v);
+        ao_stage_texel(a, ox + sx, oy + sy, s_nz[i], s_ao[i], [&](bool ok, int px, int py, float z) {
+            const uint8_t tc = a.tile_class[ok ? (size_t)(py >> 3) * a.tiles_x + (px >> 3) : 0];
+            s_kind[i] = !ok ? 0 : ((!tc || z == 1.0f) ? 1 : 2);
+        });
     }
     __syncthreads();
     // X pass over the tile's columns and SH rows
@@ -1105,23 +929,7 @@ __global__ __launch_bounds__(256) void kf_ao_blur_xy(AOBlurArgs a)
         const int sy = j >> 5, sx = j & 31, ci = sy * SW + sx + RADIUS;
         const uint8_t kind = s_kind[ci];
         float r = kind == 1 ? 1.0f : 0.0f;
-        if (kind == 2)
-        {
-            const float4 c = s_nz[ci];
-            float total_ao = s_ao[ci], total_w = 1.0f;
-#pragma unroll
-            for (int i = -RADIUS; i <= RADIUS; i++)
-            {
-                if (i == 0) continue;
-                const float4 t  = s_nz[ci + i];
-                const float  wZ = fm::exp2f_(-__builtin_fabsf(c.w - t.w) * 1.44269504088896341f);
-                const float  wN = fm::pow32(fm::sat(c.x * t.x + c.y * t.y + c.z * t.z));
-                const float  w  = s_gauss[i + RADIUS] * (fm::exp2f_((1.0f + wZ) * -1.44269504088896341f) * wN);
-                total_ao += w * s_ao[ci + i];
-                total_w += w;
-            }
-            r = (float)__builtin_bit_cast(_Float16, fm::half_bits(total_ao * fm::rcp(fm::fmax_(total_w, 0.0001f))));
-        }
+        if (kind == 2) r = (float)__builtin_bit_cast(_Float16, fm::half_bits(ao_blur_1d<RADIUS>(s_nz, ci, 1, s_ao, ci, 1, s_gauss)));
         s_x[j] = r;
     }
     __syncthreads();
@@ -1133,20 +941,7 @@ __global__ __launch_bounds__(256) void kf_ao_blur_xy(AOBlurArgs a)
         uint16_t* outp = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(a.out) + (uint32_t)(y * a.w + x) * 2u);
         const int ci = (ly + RADIUS) * SW + lx + RADIUS, xi = (ly + RADIUS) * 32 + lx;
         if (s_kind[ci] != 2) { *outp = 0x3c00u; continue; }   // cleared image (ray_traced_ao.cpp:1048-1055) / sky
-        const float4 c = s_nz[ci];
-        float total_ao = s_x[xi], total_w = 1.0f;
-#pragma unroll
-        for (int i = -RADIUS; i <= RADIUS; i++)
-        {
-            if (i == 0) continue;
-            const float4 t  = s_nz[ci + i * SW];
-            const float  wZ = fm::exp2f_(-__builtin_fabsf(c.w - t.w) * 1.44269504088896341f);
-            const float  wN = fm::pow32(fm::sat(c.x * t.x + c.y * t.y + c.z * t.z));
-            const float  w  = s_gauss[i + RADIUS] * (fm::exp2f_((1.0f + wZ) * -1.44269504088896341f) * wN);
-            total_ao += w * s_x[xi + i * 32];
-            total_w += w;
-        }
-        *outp = fm::half_bits(total_ao * fm::rcp(fm::fmax_(total_w, 0.0001f)));
+        *outp = fm::half_bits(ao_blur_1d<RADIUS>(s_nz, ci, SW, s_x, xi, 32, s_gauss));
     }
 }
 
@@ -1179,13 +974,11 @@ __global__ __launch_bounds__(256) void kf_ao_blur_generic(AOBlurArgs a)
         uint16_t v  = fm::ld<uint16_t>(a.in.p, off * 2u);
         if (!ok) { z = 0.0f; g2 = 0u; v = 0; }
         const float sd = fm::rcp_nr(fm::mad_rn(a.zbp[2], z, a.zbp[3]));
-        const float wZ = fm::exp2f_(-__builtin_fabsf(cd - sd) * 1.44269504088896341f);
-        const float wN = fm::pow32(fm::sat(fm::dot(cn, fm::oct_unit(g2))));
-        const float w  = s_gauss[i + a.radius] * (fm::exp2f_((1.0f + wZ) * -1.44269504088896341f) * wN);
+        const float w  = ao_tap_weight(&s_gauss[i + a.radius], cd, sd, fm::dot(cn, fm::oct_unit(g2)));
         total_ao += w * (float)__builtin_bit_cast(_Float16, v);
         total_w += w;
     }
-    *outp = fm::half_bits(total_ao * fm::rcp(fm::fmax_(total_w, 0.0001f)));
+    *outp = fm::half_bits(ao_normalise(total_ao, total_w));
 }
 
 
@@ -1414,14 +1207,14 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
         const int  step = STEP > 0 ? STEP : a.step, R = STEP > 0 ? 1 : a.radius;
         const int  fx0 = (int)BLK.x * 32, fy0 = a.y0 + (int)BLK.y * 8, reach = step * R > 1 ? step * R : 1;
         const bool interior = fx0 - reach >= 0 && fx0 + 31 + reach < a.w && fy0 - reach >= a.in.y0 && fy0 + 7 + reach < a.in.y1;
-        const f3    cc = mk3(fm::lo(c.x), fm::hi(c.x), fm::lo(c.y));
-        const float center_luma = fm::fmax_(0.299f * cc.x + 0.587f * cc.y + 0.114f * cc.z, 0.0001f);
+        const f3    cc = refl_colour(c);
+        const float center_luma = refl_luma(cc);
         float var = 0.0f;
 #pragma unroll
         for (int k = 0; k < 9; k++)
         {
             const int   xx = k % 3 - 1, yy = k / 3 - 1;
-            const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
+            const float kw = prefilter_weight(xx, yy);
             const uint32_t v = interior ? fm::ld<uint32_t>(a.in.p, (uint32_t)((y + yy) * a.w + (x + xx)) * 8u + 4u) : a.in.raw(x + xx, y + yy).y;
             var += fm::hi(v) * kw;
         }
@@ -1433,15 +1226,12 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
         {
             const f3    cn = fm::oct_unit(g2x);
             const float center_depth = fm::hi(g3.y);
-            EdgeK ek;
-            ek.kz        = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-            ek.phi_n     = a.phi_normal;
-            ek.n32       = N32;
-            ek.inv_phi_l = fm::rcp(a.phi_color * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
+            EdgeK ek = edge_setup(a.sigma_depth, a.phi_normal, N32);
+            ek.inv_phi_l = edge_luma(a.phi_color, var);
             float sum_w = 1.0f, s0 = cc.x, s1 = cc.y, s2 = cc.z, s3 = fm::hi(c.y);
             auto tap = [&](uint2 q, uint32_t q2x, uint32_t q3y, float kk, bool ok) {
-                const f3    sc = mk3(fm::lo(q.x), fm::hi(q.x), fm::lo(q.y));
-                const float sl = fm::fmax_(0.299f * sc.x + 0.587f * sc.y + 0.114f * sc.z, 0.0001f);
+                const f3    sc = refl_colour(q);
+                const float sl = refl_luma(sc);
                 float wc = fm::mul_rn(edge_weight_fast(ek, center_depth, fm::hi(q3y), cn, fm::oct_unit(q2x), center_luma, sl), kk);
                 if (!ok) wc = 0.0f;
                 sum_w += wc;
@@ -1458,7 +1248,7 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
 #pragma unroll
                     for (int t = 0; t < 8; t++)
                     {
-                        const int      k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
+                        const int      xx = tap_xy(t).xx, yy = tap_xy(t).yy;
                         const uint32_t so = (uint32_t)((y + yy * STEP) * a.w + (x + xx * STEP));
                         t_ok[t] = true;
                         t_in[t] = fm::ld<uint2>(a.in.p, so * 8u);
@@ -1471,7 +1261,7 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
 #pragma unroll
                     for (int t = 0; t < 8; t++)
                     {
-                        const int k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
+                        const int xx = tap_xy(t).xx, yy = tap_xy(t).yy;
                         const int px = x + xx * STEP, py = y + yy * STEP;
                         t_ok[t] = px >= 0 && py >= 0 && px < a.w && py < a.h;
                         t_in[t] = a.in.raw(px, py); t_g2[t] = a.gb2.raw(px, py).x; t_g3[t] = a.gb3.raw(px, py).y;
@@ -1480,8 +1270,8 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
 #pragma unroll
                 for (int t = 0; t < 8; t++)
                 {
-                    const int k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-                    tap(t_in[t], t_g2[t], t_g3[t], (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f), t_ok[t]);
+                    const int xx = tap_xy(t).xx, yy = tap_xy(t).yy;
+                    tap(t_in[t], t_g2[t], t_g3[t], tap_weight(xx, yy), t_ok[t]);
                 }
             }
             else
@@ -1491,10 +1281,7 @@ __global__ __launch_bounds__(256) void kf_refl_atrous(ReflAtrousArgs a)
                     {
                         const int px = x + xx * step, py = y + yy * step;
                         if (px < 0 || py < 0 || px >= a.w || py >= a.h || (xx == 0 && yy == 0)) continue;
-                        const int   axx = xx < 0 ? -xx : xx, ayy = yy < 0 ? -yy : yy;
-                        const float kx = axx == 0 ? 1.0f : (axx == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
-                        const float ky = ayy == 0 ? 1.0f : (ayy == 1 ? 2.0f / 3.0f : 1.0f / 6.0f);
-                        tap(a.in.raw(px, py), a.gb2.raw(px, py).x, a.gb3.raw(px, py).y, kx * ky, true);
+                        tap(a.in.raw(px, py), a.gb2.raw(px, py).x, a.gb3.raw(px, py).y, tap_weight(xx, yy), true);
                     }
             }
             const float iw = fm::rcp(sum_w);
@@ -1540,10 +1327,7 @@ __global__ __launch_bounds__(256) void kf_refl_atrous01(ReflAtrousArgs a, uint2*
         s_r[i]  = d == 1.0f ? -1.0f : fm::lo(g3.x);
     }
     __syncthreads();
-    EdgeK ek;
-    ek.kz    = 1.44269504088896341f * fm::rcp(a.sigma_depth);
-    ek.phi_n = a.phi_normal;
-    ek.n32   = N32;
+    EdgeK ek = edge_setup(a.sigma_depth, a.phi_normal, N32);
     auto filter = [&](const uint2* img, int IW, int vi, int ci, int D) -> uint2 {
         const uint2 c = img[vi];
         const float roughness = s_r[ci];
@@ -1554,24 +1338,24 @@ __global__ __launch_bounds__(256) void kf_refl_atrous01(ReflAtrousArgs a, uint2*
         for (int k = 0; k < 9; k++)
         {
             const int   xx = k % 3 - 1, yy = k / 3 - 1;
-            const float kw = (xx == 0 ? (yy == 0 ? 0.25f : 0.125f) : (yy == 0 ? 0.125f : 0.0625f));
+            const float kw = prefilter_weight(xx, yy);
             var += fm::hi(img[vi + yy * IW + xx].y) * kw;
         }
         const float4 cnz = s_nz[ci];
         const f3     cn  = mk3(cnz.x, cnz.y, cnz.z);
-        const f3     cc  = mk3(fm::lo(c.x), fm::hi(c.x), fm::lo(c.y));
-        const float  center_luma = fm::fmax_(0.299f * cc.x + 0.587f * cc.y + 0.114f * cc.z, 0.0001f);
-        ek.inv_phi_l = fm::rcp(a.phi_color * fm::sqrt1(fm::fmax_(0.0f, 1e-10f + var)));
+        const f3     cc  = refl_colour(c);
+        const float  center_luma = refl_luma(cc);
+        ek.inv_phi_l = edge_luma(a.phi_color, var);
         float sum_w = 1.0f, s0 = cc.x, s1 = cc.y, s2 = cc.z, s3 = fm::hi(c.y);
 #pragma unroll
         for (int t = 0; t < 8; t++)
         {
-            const int    k = t < 4 ? t : t + 1, xx = k % 3 - 1, yy = k / 3 - 1;
-            const float  kk = (xx == 0 ? 1.0f : 2.0f / 3.0f) * (yy == 0 ? 1.0f : 2.0f / 3.0f);
+            const int    xx = tap_xy(t).xx, yy = tap_xy(t).yy;
+            const float  kk = tap_weight(xx, yy);
             const uint2  q  = img[vi + yy * D * IW + xx * D];
             const float4 tn = s_nz[ci + yy * D * AW + xx * D];
-            const f3     sc = mk3(fm::lo(q.x), fm::hi(q.x), fm::lo(q.y));
-            const float  sl = fm::fmax_(0.299f * sc.x + 0.587f * sc.y + 0.114f * sc.z, 0.0001f);
+            const f3     sc = refl_colour(q);
+            const float  sl = refl_luma(sc);
             const float  wc = fm::mul_rn(edge_weight_fast(ek, cnz.w, tn.w, cn, mk3(tn.x, tn.y, tn.z), center_luma, sl), kk);
             sum_w += wc;
             s0 += wc * sc.x; s1 += wc * sc.y; s2 += wc * sc.z;
