@@ -60,9 +60,14 @@ struct ReprojOut { float col[3]; float mom[2]; float length; };
 // loads.  Same values (the record holds copies of the G-buffer words), so the results are bit-identical.  GEO = 1: as described
 // (shadows, reflections).  GEO = 2 (AO, whose history value is a single fp16): the record is {oct normal, mesh id | AO history}, i.e. the
 // colour history rides in the record too — 2 images + the history length, 9 loads against 17.
-template <int HIST_BPP, bool MOMENTS, bool REFL, int GEO = 0>
+// PATHS (TemporalPaths bits; shadows on the record path, GEO = 1): TP_PAIRS — the taps (bx, py) and (bx + 1, py) of a footprint row are
+// neighbours in memory, so one load per image and row fetches both: 8 loads for 16, the same bytes; see issue().
+template <int HIST_BPP, bool MOMENTS, bool REFL, int GEO = 0, int PATHS = 0>
 struct Reproj
 {
+    static constexpr bool PAIRS   = (PATHS & TP_PAIRS) != 0 && GEO == 1 && MOMENTS && HIST_BPP == 4;
+    struct alignas(8) Pair8 { uint32_t x0, y0, x1, y1; };   // two 8-byte texels
+    struct alignas(4) Pair4 { uint32_t v0, v1; };           // two 4-byte texels
     static constexpr int NC = HIST_BPP == 8 ? 3 : 1;
     const float* __restrict__ M;
     const void* __restrict__  pgb2;
@@ -175,30 +180,59 @@ struct Reproj
 #pragma unroll
         for (int s = 0; s < 4; s++) off[s] = tap_offset(bx + (s & 1), by + (s >> 1), tok[s]);
         const uint32_t loff = tap_offset(hcx, hcy, lok);
-#pragma unroll
-        for (int s = 0; s < 4; s++)
+        if constexpr (PAIRS)
         {
-            if constexpr (GEO != 0)
+            // Both taps of a row from the texel pair at column bxc = bx clamped into [0, w - 2] (the launcher grants w >= 2), so the pair never
+            // leaves its row; a row that is not resident reads row y0, as a lone tap does.  bx == bxc: the taps are the pair.  bx < bxc (bx < 0):
+            // tap 0 is outside the image (tok: its value is discarded) and tap 1, if inside, is the pair's first texel.  bx > bxc: tap 0, if
+            // inside, is the pair's second texel and tap 1 is outside.
+            const int  bxc = bx < 0 ? 0 : (bx > g.w - 2 ? g.w - 2 : bx);
+            const bool up = bx > bxc, down = bx < bxc;
+            lraw = 0u;
+#pragma unroll
+            for (int r = 0; r < 2; r++)
             {
-                const uint2 q = fm::ld<uint2>(geo, off[s] * 8u);
-                g2x[s] = q.x; g3y[s] = q.y;
+                const int      py = by + r;
+                const uint32_t o  = (uint32_t)(((py >= g.y0 && py < g.y1) ? py : g.y0) * g.w + bxc);
+                const Pair8 q = fm::ld<Pair8>(geo, o * 8u), m = fm::ld<Pair8>(hist_moments, o * 8u);
+                const Pair4 d = fm::ld<Pair4>(pdepth, o * 4u), c = fm::ld<Pair4>(hist, o * 4u);
+                const int   s0 = 2 * r, s1 = 2 * r + 1;
+                g2x[s0] = up ? q.x1 : q.x0;  g3y[s0] = up ? q.y1 : q.y0;  td[s0] = __builtin_bit_cast(float, up ? d.v1 : d.v0);  hx[s0] = up ? c.v1 : c.v0;
+                mm[s0]  = up ? m.x1 : m.x0;  hy[s0] = 0u;
+                g2x[s1] = down ? q.x0 : q.x1; g3y[s1] = down ? q.y0 : q.y1; td[s1] = __builtin_bit_cast(float, down ? d.v0 : d.v1); hx[s1] = down ? c.v0 : c.v1;
+                mm[s1]  = down ? m.x0 : m.x1; hy[s1] = 0u;
+                // the nearest history texel (hcx, hcy) is one of the four taps (below): its length word, picked here so that four of them need not live on
+                if (hcy - by == r) lraw = (hcx - bx) != 0 ? (down ? m.y0 : m.y1) : (up ? m.y1 : m.y0);
             }
-            else
-            {
-                g2x[s] = fm::ld<uint32_t>(pgb2, off[s] * 8u);
-                g3y[s] = fm::ld<uint32_t>(pgb3, off[s] * 8u + 4u);
-            }
-            td[s]  = fm::ld<float>(pdepth, off[s] * 4u);
-            if constexpr (GEO == 2) { hx[s] = g3y[s] >> 16; hy[s] = 0u; }
-            else hist_load(off[s], hx[s], hy[s]);
-            if constexpr (MOMENTS && GEO != 0)
-            {
-                const uint2 m = fm::ld<uint2>(hist_moments, off[s] * 8u);
-                mm[s] = m.x; mlen[s] = m.y;
-            }
-            else mm[s] = MOMENTS ? fm::ld<uint32_t>(hist_moments, off[s] * 8u) : 0u;
         }
-        if constexpr (MOMENTS && GEO != 0)
+        else
+        {
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+            {
+                if constexpr (GEO != 0)
+                {
+                    const uint2 q = fm::ld<uint2>(geo, off[s] * 8u);
+                    g2x[s] = q.x; g3y[s] = q.y;
+                }
+                else
+                {
+                    g2x[s] = fm::ld<uint32_t>(pgb2, off[s] * 8u);
+                    g3y[s] = fm::ld<uint32_t>(pgb3, off[s] * 8u + 4u);
+                }
+                td[s]  = fm::ld<float>(pdepth, off[s] * 4u);
+                if constexpr (GEO == 2) { hx[s] = g3y[s] >> 16; hy[s] = 0u; }
+                else hist_load(off[s], hx[s], hy[s]);
+                if constexpr (MOMENTS && GEO != 0)
+                {
+                    const uint2 m = fm::ld<uint2>(hist_moments, off[s] * 8u);
+                    mm[s] = m.x; mlen[s] = m.y;
+                }
+                else mm[s] = MOMENTS ? fm::ld<uint32_t>(hist_moments, off[s] * 8u) : 0u;
+            }
+        }
+        if constexpr (PAIRS) {}
+        else if constexpr (MOMENTS && GEO != 0)
         {
             // the nearest history texel (hcx, hcy) is one of the four taps: bx <= hcx <= bx + 1 (truncation on both sides)
             const int sel = (hcx - bx) + 2 * (hcy - by);
@@ -354,7 +388,10 @@ HR_DEV bool geo_apron_rides(const GeoApronArgs& g)
                           // spill: 48-50 us at 1080p, 208 at 4K; 7 (72 VGPRs + 24 B of scratch) 58.7 / 252.8; 8 (64 VGPRs, more scratch) 81.4 / 362 — spills
                           // cost far more than waves buy
 #endif
-template <int GEO>
+// PATHS: TemporalPaths bits (pass_args.h) — forms of the first run's history loads; the cold copy keeps the form it had (its code and its
+// registers stay what they were), and the outputs are the same bits
+template <bool B> struct BoolC { static constexpr bool value = B; };
+template <int GEO, int PATHS>
 __global__ __launch_bounds__(64 * FT_WAVES, FT_SHADOWS_EU) void kf_shadows_temporal(TemporalArgs a)
 {
     if (geo_apron_rides<64 * FT_WAVES>(a.apron)) return;   // row bands: the records of the history apron, as extra grid rows behind the sort's
@@ -382,12 +419,13 @@ __global__ __launch_bounds__(64 * FT_WAVES, FT_SHADOWS_EU) void kf_shadows_tempo
     // nothing of the first run live — in which the noted pixels take the parity kernels' verdicts on their taps (Reproj::exact_bits), and
     // stores again.  Returns near13 (0: no tap of this pixel was in doubt); flag = the pixel's vote in the tile classification.
     bool flag = false;
-    auto pixel = [&](const float d_in, const uint2 cg2_in, const uint2 cg3_in, const bool redo) -> uint32_t {
+    auto pixel = [&](const float d_in, const uint2 cg2_in, const uint2 cg3_in, auto redo_c) -> uint32_t {
+        constexpr bool redo = decltype(redo_c)::value;
         const float d   = edge ? 0.0f : d_in;
         const uint2 cg2 = edge ? make_uint2(0u, 0u) : cg2_in, cg3 = edge ? make_uint2(0u, 0u) : cg3_in;
         const f3    cn  = fm::oct_unit(cg2.x);
         const bool  live = (in_image || edge) && d != 1.0f;
-        Reproj<4, true, false, GEO> rp;
+        Reproj<4, true, false, GEO, redo ? 0 : PATHS> rp;
         rp.M = a.vpi; rp.pgb2 = a.pgb2.p; rp.pgb3 = a.pgb3.p; rp.pdepth = a.pdepth.p; rp.hist = a.hist.p; rp.hist_moments = a.hist_moments.p; rp.hist_len = nullptr;
         rp.geo = a.geo_hist;
         rp.g = HistGeom { a.w, a.h, a.pgb2.y0, a.pgb2.y1 };
@@ -457,10 +495,10 @@ __global__ __launch_bounds__(64 * FT_WAVES, FT_SHADOWS_EU) void kf_shadows_tempo
         }
         return reproj ? rp.near13 : 0u;
     };
-    const uint32_t doubt = pixel(d_raw, cg2_raw, cg3_raw, false);
+    const uint32_t doubt = pixel(d_raw, cg2_raw, cg3_raw, BoolC<false>());
 #if HR_TAP_REDO
     if (__any(doubt != 0u))   // rare: the cold copy (re-reads the centre texels: nothing of the first run is kept)
-        pixel(fm::ld<float>(a.depth.p, pix * 4u), fm::ld<uint2>(a.gb2.p, pix * 8u), fm::ld<uint2>(a.gb3.p, pix * 8u), true);
+        pixel(fm::ld<float>(a.depth.p, pix * 4u), fm::ld<uint2>(a.gb2.p, pix * 8u), fm::ld<uint2>(a.gb3.p, pix * 8u), BoolC<true>());
 #endif
     const unsigned long long any = __ballot(flag);
     if (lane == 0) a.tile_class[(size_t)ty * a.tiles_x + tx] = any ? 1 : 0;
@@ -1504,8 +1542,10 @@ void launch_shadows_temporal_fast(const TemporalArgs& a_, int n_tiles, hipStream
 {
     TemporalArgs a = a_;
     const dim3 grid = grid_with_apron(grid_with_sort(a.sort, grid_cols(cdiv(a.tiles_x, FT_WAVES), 4), a.tiles_y), a.apron, 64 * FT_WAVES);
-    if (a.geo_hist) hipLaunchKernelGGL(kf_shadows_temporal<1>, grid, dim3(64 * FT_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(kf_shadows_temporal<0>, grid, dim3(64 * FT_WAVES), 0, st, a);
+    // the paired history loads (TemporalPaths) apply on the record path; a pair of texels needs two columns
+    if (!a.geo_hist) hipLaunchKernelGGL((kf_shadows_temporal<0, 0>), grid, dim3(64 * FT_WAVES), 0, st, a);
+    else if ((a.paths & TP_PAIRS) && a.w >= 2) hipLaunchKernelGGL((kf_shadows_temporal<1, TP_PAIRS>), grid, dim3(64 * FT_WAVES), 0, st, a);
+    else hipLaunchKernelGGL((kf_shadows_temporal<1, 0>), grid, dim3(64 * FT_WAVES), 0, st, a);
 }
 
 void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st)

@@ -56,6 +56,15 @@ struct TemporalArgs
     int             band_y0, band_y1;
     TileSortArgs    sort;           // rides along as extra grid rows (tolerance-mode kernel only)
     GeoApronArgs    apron;          // rides along behind the sort (tolerance-mode kernel, row bands only)
+    int             paths;          // tolerance-mode kernel: TemporalPaths bits, which form of its history loads runs (same bits out either way)
+};
+
+// Forms of kf_shadows_temporal's hot path that keep the older form beside them (developer A/B switches of hr_shadows_create, read once; a
+// bit selects an instantiation of the kernel, and both write the same bits).  One is left of the five that were measured (docs/EXPERIMENTS.md, "Shadow temporal kernel"):
+enum TemporalPaths : int
+{
+    TP_PAIRS = 1,   // HR_TEMPORAL_PAIRS: on the record path the two taps of a footprint row come in one load per image (8 history loads for 16)
+    TP_ALL   = 1
 };
 
 struct AtrousArgs

@@ -558,6 +558,7 @@ __global__ __launch_bounds__(256) void k_shadows_atrous(AtrousArgs a)
 struct hr_shadows : PassCore
 {
     DevBuf  mask, temporal_out, moments[2], prev_image, atrous[2], nd, occluder;
+    int     temporal_paths = TP_ALL;  // developer A/B switch HR_TEMPORAL_PAIRS=0 (pass_args.h TemporalPaths; read once at create)
     bool    occluder_cache = true;    // developer A/B switch HR_SHADOW_CACHE=0 (read once at create)
     int     read_idx = 0;             // ATrous::read_idx
     int     last_ping_pong = 0;
@@ -594,6 +595,7 @@ hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height
 #endif
     if (const char* e = getenv("HR_DEBUG_ONLY_TILE")) sscanf(e, "%d,%d", &p->dbg_only_tx, &p->dbg_only_ty);
     if (const char* e = getenv("HR_SHADOW_CACHE")) p->occluder_cache = atoi(e) != 0;
+    if (const char* e = getenv("HR_TEMPORAL_PAIRS")) p->temporal_paths = atoi(e) != 0 ? (p->temporal_paths | TP_PAIRS) : (p->temporal_paths & ~TP_PAIRS);
     p->tile_order.min_spread = HR_ORDER_COHERENT_SPREAD;   // rays towards one light: coherent
     p->dbg_skip_traversal = getenv("HR_DEBUG_SKIP_TRAVERSAL") != nullptr;
     p->dbg_skip_reproject = getenv("HR_DEBUG_SKIP_REPROJECT") != nullptr;
@@ -822,6 +824,7 @@ hr_status hr_shadows_temporal(hr_shadows* p, const hr_frame_inputs* in, const hr
     a.debug_skip_reproject = p->dbg_skip_reproject ? 1 : 0;
     a.apron_flag = p->apron_flag();
     a.band_y0 = p->band_y0; a.band_y1 = p->band_y1;
+    a.paths = p->temporal_paths;
     p->last_ping_pong = in->ping_pong ? 1 : 0;
     const uint64_t px = (uint64_t)w * (y1 - y0);
     int ev = p->prof.begin("temporal_accumulation", st, px * 64 + px / 8);
