@@ -96,7 +96,7 @@ ABI_SYMBOLS = [
     "hr_shadows_render", "hr_shadows_output", "hr_shadows_reset_history", "hr_shadows_destroy", "hr_shadows_ray_trace", "hr_shadows_denoise", "hr_shadows_temporal",
     "hr_shadows_atrous_iteration", "hr_shadows_upsample", "hr_shadows_image", "hr_shadows_history_apron_exceeded", "hr_shadows_set_profiling", "hr_shadows_get_stage_times",
     "hr_gbuffer_mip_nearest", "hr_bvh_build_info", "hr_bvh_selfcheck", "hr_bvh_child_boxes", "hr_shadows_ray_count", "hr_shadows_tile_ray_counts", "hr_shadows_trace_stats", "hr_shadows_trace_stats_timed", "hr_shadows_launch_order", "hr_shadows_trace_divergence", "hr_selftest_math",
-    "hr_selftest_math_sweep", "hr_selftest_fast_math",
+    "hr_selftest_math_sweep", "hr_selftest_fast_math", "hr_selftest_shading",
     "hr_scene_create_instanced_shared", "hr_scene_is_shared", "hr_instanced_scene_footprint", "hr_scene_enable_two_level_passes", "hr_scene_two_level_passes",
     "hr_scene_create_deformable", "hr_scene_update_vertices", "hr_scene_refit_cost", "hr_scene_rebuild", "hr_bvh_build_info_deformable",
     "hr_scene_create_instanced_shared_deformable", "hr_scene_update_meshes", "hr_scene_mesh_refit_cost", "hr_scene_update_meshes_stats", "hr_scene_read_instance_records",

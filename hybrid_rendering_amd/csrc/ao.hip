@@ -8,6 +8,7 @@
 #include "hr_internal.h"
 #include "reproject.h"
 #include "traverse2.h"
+#include "sampling.h"
 #include "cutout_host.h"
 #include "mask_window.h"
 #include "upsample.h"
@@ -17,21 +18,7 @@
 
 using namespace hr;
 
-// brdf.glsl:8-32 sample_cosine_lobe + make_rotation_matrix
-HR_DEV f3 sample_cosine_lobe(f3 n, float rx, float ry)
-{
-    rx = max2(0.00001f, rx);
-    ry = max2(0.00001f, ry);
-    const float phi = 2.0f * HR_M_PI * ry;
-    const float ct = hr_sqrt(rx), st = hr_sqrt(1.0f - rx);
-    float s, c;
-    det_sincos(phi, s, c);
-    const f3 t   = mk3(st * c, st * s, ct);
-    const f3 ref = fabsf(dot3(n, mk3(0.0f, 1.0f, 0.0f))) > 0.99f ? mk3(0.0f, 0.0f, 1.0f) : mk3(0.0f, 1.0f, 0.0f);
-    const f3 x   = normalize3(cross3(ref, n));
-    const f3 y   = cross3(n, x);
-    return normalize3(mk3((x.x * t.x + y.x * t.y) + n.x * t.z, (x.y * t.x + y.y * t.y) + n.y * t.z, (x.z * t.x + y.z * t.y) + n.z * t.z));
-}
+// sample_cosine_lobe (brdf.glsl:8-32): sampling.h
 
 struct AOTraceArgs
 {

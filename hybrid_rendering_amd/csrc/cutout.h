@@ -31,8 +31,11 @@ HR_DEV void sample_texture_channels(const uint4* __restrict__ tex_table, const u
     const float px = u * (float)w - 0.5f, py = v * (float)h - 0.5f;
     const float fx0 = floorf(px), fy0 = floorf(py);
     const float fx = px - fx0, fy = py - fy0;
-    int x0 = (int)fx0 % w, x1 = ((int)fx0 + 1) % w, y0 = (int)fy0 % h, y1 = ((int)fy0 + 1) % h;
-    x0 = x0 < 0 ? x0 + w : x0; x1 = x1 < 0 ? x1 + w : x1; y0 = y0 < 0 ? y0 + h : y0; y1 = y1 < 0 ? y1 + h : y1;
+    // (int) of a float outside the int range saturates (v_cvt_i32_f32; NaN: 0), so the texel's neighbour is taken AFTER the wrap: `(int)fx0 + 1`
+    // would overflow there.  For every index in range ((i mod w) + 1) mod w is (i + 1) mod w.
+    int x0 = (int)fx0 % w, y0 = (int)fy0 % h;
+    x0 = x0 < 0 ? x0 + w : x0; y0 = y0 < 0 ? y0 + h : y0;
+    const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
     const uint32_t* base = tex_data + t.x;
     const uint32_t t00 = base[(size_t)y0 * w + x0], t10 = base[(size_t)y0 * w + x1], t01 = base[(size_t)y1 * w + x0], t11 = base[(size_t)y1 * w + x1];
 #pragma unroll

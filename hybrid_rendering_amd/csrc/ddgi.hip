@@ -13,18 +13,7 @@
 
 using namespace hr;
 
-// gi_ray_trace.rgen:61-72.  PHI = sqrt(5)*0.5+0.5 evaluated in fp32; PHI - 1 is exact.
-HR_DEV f3 spherical_fibonacci(float i, float n)
-{
-    const float PHI_M1 = 0.61803400516510009765625f;
-    const float a   = i * PHI_M1;
-    const float phi = 2.0f * HR_M_PI * (a - floorf(a));
-    const float ct  = 1.0f - (2.0f * i + 1.0f) * __fdiv_rn(1.0f, n);
-    const float st  = hr_sqrt(glsl_clamp(1.0f - ct * ct, 0.0f, 1.0f));
-    float s, c;
-    det_sincos(phi, s, c);
-    return mk3(c * st, s * st, ct);
-}
+// spherical_fibonacci (gi_ray_trace.rgen:61-72): sampling.h
 
 struct DDGITraceArgs
 {

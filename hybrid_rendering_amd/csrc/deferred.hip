@@ -175,7 +175,7 @@ hr_status hr_deferred_render(hr_deferred* p, const hr_frame_inputs* in, const hr
     if (a.flags & 1) HR_CHECK_ARG(view_ok(shadow, p->w, p->h));
     if (a.flags & 2) HR_CHECK_ARG(view_ok(ao, p->w, p->h));
     if (a.flags & 4) HR_CHECK_ARG(view_ok(reflections, p->w, p->h) && reflections->format == HR_FORMAT_RGBA16F);
-    else HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0);
+    else HR_CHECK_ARG(env->prefiltered && prefiltered_chain_ok(env->prefiltered_size, env->prefiltered_levels));
     if (a.flags & 8) HR_CHECK_ARG(view_ok(gi, p->w, p->h) && gi->format == HR_FORMAT_RGBA16F);
     for (int i = 0; i < 16; i++) a.vpi[i] = in->ubo.view_proj_inverse[i];
     for (int i = 0; i < 3; i++) a.cam[i] = in->ubo.cam_pos[i];

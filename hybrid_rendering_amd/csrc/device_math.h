@@ -54,6 +54,8 @@ HR_DEV float smoothstep1(float e0, float e1, float x)
     return t * t * (3.0f - 2.0f * t);
 }
 HR_DEV float hr_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// i + 1 that stays at INT_MAX: the neighbour texel of an index that came out of a saturated float -> int conversion
+HR_DEV int inc_sat(int i) { return i < 0x7fffffff ? i + 1 : i; }
 
 // column-major mat4 * vec4, rows summed left to right
 struct f4 { float x, y, z, w; };

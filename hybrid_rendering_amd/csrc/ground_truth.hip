@@ -30,20 +30,7 @@ struct GTArgs
 };
 
 #define GT_MAX_DEPTH 32
-// brdf.glsl:96-112
-HR_DEV f3 sample_specular_ggx_lobe(f3 n, float alpha, float xi_x, float xi_y)
-{
-    const float phi = 2.0f * HR_M_PI * xi_x;
-    const float ct  = hr_sqrt(__fdiv_rn(1.0f - xi_y, 1.0f + (alpha * alpha - 1.0f) * xi_y));
-    const float st  = hr_sqrt(1.0f - ct * ct);
-    float s, c;
-    det_sincos(phi, s, c);
-    const f3 t   = mk3(st * c, st * s, ct);
-    const f3 ref = fabsf(dot3(n, mk3(0.0f, 1.0f, 0.0f))) > 0.99f ? mk3(0.0f, 0.0f, 1.0f) : mk3(0.0f, 1.0f, 0.0f);
-    const f3 x   = normalize3(cross3(ref, n));
-    const f3 y   = cross3(n, x);
-    return normalize3(mk3((x.x * t.x + y.x * t.y) + n.x * t.z, (x.y * t.x + y.y * t.y) + n.y * t.z, (x.z * t.x + y.z * t.y) + n.z * t.z));
-}
+// sample_specular_ggx_lobe (brdf.glsl:96-112): sampling.h
 
 // INDIRECT = false is the reference as shipped (one invocation per pixel: no payload chain to keep)
 // SHARED: every bounce and every visibility ray over a shared instanced scene (a.sh.inst_shared set) — the two-level walk of traverse2.h

@@ -35,6 +35,9 @@ void set_last_error(const std::string& s);
     } while (0)
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// hr_environment's prefiltered chain: level l has size prefiltered_size >> l, and the last level still has a texel (CubeMap::fetch with S = 0 would
+// clamp its texel to -1 and read in front of the level)
+inline bool prefiltered_chain_ok(int size, int levels) { return size > 0 && levels > 0 && levels < 32 && (size >> (levels - 1)) > 0; }
 
 // Profiler ranges under the REFERENCE's sample names (DW_SCOPED_SAMPLE: ray_traced_shadows.cpp:102,974,1043,1096,1147,1221, ray_traced_ao.cpp:100,
 // 865,985,1034,1042,1091, ray_traced_reflections.cpp:109,999,1089,1145,1188,1262, ddgi.cpp:91,769,831,864,906,945, ...), so that a

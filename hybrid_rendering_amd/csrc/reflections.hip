@@ -17,49 +17,7 @@
 
 using namespace hr;
 
-HR_DEV f3 reflect3(f3 I, f3 N) { return sub3(I, scale3(N, 2.0f * dot3(N, I))); }
-
-// reflections_ray_trace.rgen:78-105
-HR_DEV f3 importance_sample_ggx(float Ex, float Ey, f3 N, float roughness)
-{
-    const float a = roughness * roughness, m2 = a * a;
-    const float phi = 2.0f * HR_M_PI * Ex;
-    const float ct  = hr_sqrt(__fdiv_rn(1.0f - Ey, 1.0f + (m2 - 1.0f) * Ey));
-    const float st  = hr_sqrt(1.0f - ct * ct);
-    float s, c;
-    det_sincos(phi, s, c);
-    const f3 H  = mk3(c * st, s * st, ct);
-    const f3 up = fabsf(N.z) < 0.999f ? mk3(0.0f, 0.0f, 1.0f) : mk3(1.0f, 0.0f, 0.0f);
-    const f3 tangent   = normalize3(cross3(up, N));
-    const f3 bitangent = cross3(N, tangent);
-    return normalize3(add3(add3(scale3(tangent, H.x), scale3(bitangent, H.y)), scale3(N, H.z)));
-}
-
-struct EnvDev
-{
-    CubeMap         sky;
-    const uint2*    prefiltered;
-    int             pre_size, pre_levels;
-    const uint32_t* lut;
-    int             lut_size;
-    HR_DEV f3 prefiltered_fetch(f3 dir, float lod) const
-    {
-        int level = (int)floorf(lod + 0.5f);
-        level     = level < 0 ? 0 : (level > pre_levels - 1 ? pre_levels - 1 : level);
-        size_t off = 0;
-        for (int l = 0; l < level; l++) off += (size_t)6 * (pre_size >> l) * (pre_size >> l);
-        CubeMap c { prefiltered + off, pre_size >> level };
-        return c.fetch(dir);
-    }
-    HR_DEV void lut_fetch(float u, float v, float& a, float& b) const
-    {
-        int ix = (int)floorf(u * (float)lut_size), iy = (int)floorf(v * (float)lut_size);
-        ix = ix < 0 ? 0 : (ix > lut_size - 1 ? lut_size - 1 : ix);
-        iy = iy < 0 ? 0 : (iy > lut_size - 1 ? lut_size - 1 : iy);
-        const uint32_t q = lut[(size_t)iy * lut_size + ix];
-        a = h2f_lo(q); b = h2f_hi(q);
-    }
-};
+// reflect3, importance_sample_ggx: sampling.h; EnvDev: shading.h
 
 struct ReflTraceArgs
 {
@@ -531,7 +489,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     hr_status s = check_inputs(p, in, false);
     if (s != HR_OK) return s;
     HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
-    if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && env->prefiltered_levels > 0 && env->brdf_lut && env->brdf_lut_size > 0);
+    if (prm->sample_gi) HR_CHECK_ARG(env->prefiltered && prefiltered_chain_ok(env->prefiltered_size, env->prefiltered_levels) && env->brdf_lut && env->brdf_lut_size > 0);
     HR_REJECT_SHARED_DEV(scene, "hr_reflections_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_REFLECTION, "hr_reflections_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_reflections_ray_trace", p->want_stats);

@@ -10,6 +10,7 @@
 #pragma once
 #include "../../include/hr_api.h"
 #include "traverse2.h"
+#include "sampling.h"
 #include <type_traits>
 
 #ifdef HR_PROBE_FAST_HIT
@@ -75,6 +76,33 @@ struct CubeMap
         iy = iy < 0 ? 0 : (iy > S - 1 ? S - 1 : iy);
         const uint2 q = p[((size_t)face * S + iy) * S + ix];
         return mk3(h2f_lo(q.x), h2f_hi(q.x), h2f_lo(q.y));
+    }
+};
+// the reflections pass's environment: the sky, the specular-prefiltered chain (level l has size pre_size >> l and starts right after level
+// l - 1; hr_environment) and the BRDF LUT, all NEAREST
+struct EnvDev
+{
+    CubeMap         sky;
+    const uint2*    prefiltered;
+    int             pre_size, pre_levels;
+    const uint32_t* lut;
+    int             lut_size;
+    HR_DEV f3 prefiltered_fetch(f3 dir, float lod) const
+    {
+        int level = (int)floorf(lod + 0.5f);
+        level     = level < 0 ? 0 : (level > pre_levels - 1 ? pre_levels - 1 : level);
+        size_t off = 0;
+        for (int l = 0; l < level; l++) off += (size_t)6 * (pre_size >> l) * (pre_size >> l);
+        CubeMap c { prefiltered + off, pre_size >> level };
+        return c.fetch(dir);
+    }
+    HR_DEV void lut_fetch(float u, float v, float& a, float& b) const
+    {
+        int ix = (int)floorf(u * (float)lut_size), iy = (int)floorf(v * (float)lut_size);
+        ix = ix < 0 ? 0 : (ix > lut_size - 1 ? lut_size - 1 : ix);
+        iy = iy < 0 ? 0 : (iy > lut_size - 1 ? lut_size - 1 : iy);
+        const uint32_t q = lut[(size_t)iy * lut_size + ix];
+        a = h2f_lo(q); b = h2f_hi(q);
     }
 };
 
@@ -230,7 +258,8 @@ HR_DEV void bilinear_setup(float u, float v, int w, int h, int& x0, int& x1, int
     const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
     const float fx0 = floorf(x), fy0 = floorf(y);
     fx = x - fx0; fy = y - fy0;
-    x0 = (int)fx0; y0 = (int)fy0; x1 = x0 + 1; y1 = y0 + 1;
+    // (int) of a float outside the int range saturates (v_cvt_i32_f32; NaN: 0): the neighbour is inc_sat, not `+ 1`, which would overflow at INT_MAX
+    x0 = (int)fx0; y0 = (int)fy0; x1 = inc_sat(x0); y1 = inc_sat(y0);
     x0 = clampi(x0, 0, w - 1); x1 = clampi(x1, 0, w - 1); y0 = clampi(y0, 0, h - 1); y1 = clampi(y1, 0, h - 1);
 }
 HR_DEV f3 atlas_bilinear_rgb(const AtlasRGBA& a, float u, float v)

@@ -37,7 +37,8 @@ HR_DEV f4 bilinear(const TexRGBA& t, float u, float v)
     const float x0 = floorf(fx), y0 = floorf(fy);
     const float ax = fx - x0, ay = fy - y0;
     const int   ix = (int)x0, iy = (int)y0;
-    const f4 t00 = t.texel(ix, iy), t10 = t.texel(ix + 1, iy), t01 = t.texel(ix, iy + 1), t11 = t.texel(ix + 1, iy + 1);
+    const int   jx = inc_sat(ix), jy = inc_sat(iy);   // ix, iy saturate outside the int range: `+ 1` would overflow
+    const f4 t00 = t.texel(ix, iy), t10 = t.texel(jx, iy), t01 = t.texel(ix, jy), t11 = t.texel(jx, jy);
     return mix4(mix4(t00, t10, ax), mix4(t01, t11, ax), ay);
 }
 

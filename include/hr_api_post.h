@@ -119,8 +119,7 @@ hr_status hr_scene_get_cull_mask(const hr_scene* scene, int32_t ray_class, uint3
 hr_status hr_scene_set_alpha_cutoffs(hr_scene* scene, const float* cutoffs /* HOST [n_materials], copied before return; <= 0 = opaque (the default) */, void* stream); hr_status hr_scene_get_alpha_cutoffs(const hr_scene* scene, float* cutoffs_out /* HOST [n_materials] */);
 hr_status hr_scene_set_ray_class_opaque(hr_scene* scene, int32_t ray_class, int32_t force_opaque /* 1: the class skips the test (gl_RayFlagsOpaqueEXT); 0: default; read at enqueue */); hr_status hr_scene_get_ray_class_opaque(const hr_scene* scene, int32_t ray_class, int32_t* force_opaque);
 
-/* ---- self test ------------------------------------------------------------------------------------ */
-/* Evaluates the device-side arithmetic of the numerical contract on arrays so tests can
+/* ---- self test: evaluates the device-side arithmetic of the numerical contract on arrays so tests can
  * compare it bit for bit with a CPU replay.  which: 0 sincos(x)->(s,c)  1 exp(x)  2 log(x)  3 pow(x,y)
  * 4 fp32->fp16 bits (as float of the uint16)  5 oct_decode(x,y)->(nx,ny,nz)  6 oct_encode(x,y,z)->(ex,ey).
  * in: device [n][3] floats, out: device [n][3] floats. */
@@ -129,10 +128,11 @@ hr_status hr_selftest_math(int32_t which, int64_t n, const float* in, float* out
  * 13 powi, pow  14 world_pos_from_depth  15 (int)x), with inputs from `in` ([n][8], gen 0) or from the index first + i (gen 1: fp32 bits, 2: fp16
  * pair, 3: denominator x numerator grid); params: host, 80 floats (matrices, constants); out: device [nout][n] floats.  hr_selftest_fast_math
  * evaluates the tolerance-mode helpers (fast_math.h, exact_predicates.h) in their own translation unit.  Test infrastructure. */
-hr_status hr_selftest_math_sweep(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out,
-                                 void* stream);
-hr_status hr_selftest_fast_math(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out,
-                                void* stream);
+hr_status hr_selftest_math_sweep(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out, void* stream);
+hr_status hr_selftest_fast_math(int32_t which, int32_t gen, int64_t first, int64_t n, const float* in, const float* params, int32_t nout, float* out, void* stream);
+/* The shading layer (shading.h, cutout.h, sampling.h) function by function; modes, element layout ([n][24] in, [nout <= 12][n] out, n <= 2^17) and
+ * the host-side table block `tables`: csrc/selftest_shading.h.  Test infrastructure. */
+hr_status hr_selftest_shading(int32_t mode, int64_t n, const float* in, const void* tables, int32_t nout, float* out, void* stream);
 
 #ifdef __cplusplus
 }

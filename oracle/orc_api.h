@@ -117,4 +117,6 @@ void     orc_world_position_from_depth(float u, float v, float depth, const floa
 int     orc_selftest_math(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, float* out);
 int64_t orc_selftest_compare(int tu, int which, int gen, int64_t first, int64_t n, const float* in, const float* params, int nout, const float* gpu_out,
                              int64_t max_report, int64_t* report_out);
+// ---- mirror of hr_selftest_shading (orc_selftest_shading.cpp): the shading layer function by function; tables: the block of csrc/selftest_shading.h ----
+int     orc_selftest_shading(int mode, int64_t n, const float* in, const void* tables, int nout, float* out);
 }

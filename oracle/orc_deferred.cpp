@@ -107,14 +107,14 @@ void orc_deferred_shade(const void* ubo_, int w, int h, const uint8_t* gb1, cons
                 if (flags & 4) pre = v3(f16_to_f32(reflections[i * 4]), f16_to_f32(reflections[i * 4 + 1]), f16_to_f32(reflections[i * 4 + 2]));
                 else
                 {
-                    int level = (int)std::floor(roughness * 4.0f + 0.5f);
+                    int level = f2i_sat(std::floor(roughness * 4.0f + 0.5f));
                     level     = level < 0 ? 0 : (level > pre_levels - 1 ? pre_levels - 1 : level);
                     size_t off = 0;
                     for (int l = 0; l < level; l++) off += (size_t)6 * (pre_size >> l) * (pre_size >> l) * 4;
                     CubeH cm { prefiltered + off, pre_size >> level };
                     pre = cm.fetch(Rr);
                 }
-                int ix = (int)std::floor(ndv * (float)lut_size), iy = (int)std::floor(roughness * (float)lut_size);
+                int ix = f2i_sat(std::floor(ndv * (float)lut_size)), iy = f2i_sat(std::floor(roughness * (float)lut_size));
                 ix = ix < 0 ? 0 : (ix > lut_size - 1 ? lut_size - 1 : ix);
                 iy = iy < 0 ? 0 : (iy > lut_size - 1 ? lut_size - 1 : iy);
                 const float bx = f16_to_f32(lut[((size_t)iy * lut_size + ix) * 2]), by = f16_to_f32(lut[((size_t)iy * lut_size + ix) * 2 + 1]);

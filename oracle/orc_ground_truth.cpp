@@ -19,19 +19,7 @@ void fetch_light_properties_shadow(const Light& light, vec3 P, vec3 N, float rx,
 
 extern "C" {
 
-// brdf.glsl:96-112 sample_specular_ggx_lobe
-static inline vec3 sample_specular_ggx_lobe(vec3 n, float alpha, float xi_x, float xi_y)
-{
-    const float phi       = 2.0f * ORC_M_PI * xi_x;
-    const float cos_theta = std::sqrt((1.0f - xi_y) / (1.0f + (alpha * alpha - 1.0f) * xi_y));
-    const float sin_theta = std::sqrt(1.0f - cos_theta * cos_theta);
-    float s, c;
-    det_sincos(phi, &s, &c);
-    const vec3 d = v3(sin_theta * c, sin_theta * s, cos_theta);
-    vec3 x, y;
-    make_rotation_matrix(n, &x, &y);
-    return normalize(v3((x.x * d.x + y.x * d.y) + n.x * d.z, (x.y * d.x + y.y * d.y) + n.y * d.z, (x.z * d.x + y.z * d.y) + n.z * d.z));
-}
+// sample_specular_ggx_lobe (brdf.glsl:96-112): orc_shading.h
 
 // prev / cur: [h][w][4] fp16 bit patterns.  rows [y0, y1) are rendered.
 // trace_indirect = 0 is the reference as shipped (the recursive traceRayEXT of rchit:95-105 is commented out, so

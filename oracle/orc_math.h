@@ -116,6 +116,17 @@ static inline float clampf(float x, float lo, float hi) { return fmin2(fmax2(x, 
 static inline float glsl_min(float x, float y) { return y < x ? y : x; }
 static inline float glsl_max(float x, float y) { return x < y ? y : x; }
 static inline float glsl_clamp(float x, float lo, float hi) { return glsl_min(glsl_max(x, lo), hi); }
+// float -> int as the samplers mean it: truncation toward zero, SATURATING outside the int range, NaN -> 0.  That is gfx950's v_cvt_i32_f32
+// (tests/test_gpu_trace.py test_det_sincos_beyond_int_range recorded it) and what a clamp-to-edge or repeat sampler means by a coordinate that
+// far out; a plain (int) is undefined there and returns INT_MIN on x86 for all three cases.  inc_sat: the neighbour texel of such an index.
+static inline int f2i_sat(float x)
+{
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return 2147483647;
+    if (x <= -2147483648.0f) return -2147483647 - 1;
+    return (int)x;
+}
+static inline int inc_sat(int i) { return i < 2147483647 ? i + 1 : i; }
 static inline float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 static inline vec3  mix3(vec3 a, vec3 b, float t) { return a * (1.0f - t) + b * t; }
 static inline float fractf(float x) { return x - std::floor(x); }

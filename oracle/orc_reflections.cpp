@@ -19,50 +19,7 @@ using namespace orc;
 
 namespace orc {
 
-static inline vec3 reflect3(vec3 I, vec3 N) { return I - N * (2.0f * dot(N, I)); }
-
-// reflections_ray_trace.rgen:78-105 (the PDF it also computes is unused by the caller)
-static inline vec3 importance_sample_ggx(float Ex, float Ey, vec3 N, float roughness)
-{
-    float a = roughness * roughness, m2 = a * a;
-    float phi = 2.0f * ORC_M_PI * Ex;
-    float cos_theta = std::sqrt((1.0f - Ey) / (1.0f + (m2 - 1.0f) * Ey));
-    float sin_theta = std::sqrt(1.0f - cos_theta * cos_theta);
-    float s, c;
-    det_sincos(phi, &s, &c);
-    vec3 H  = v3(c * sin_theta, s * sin_theta, cos_theta);
-    vec3 up = std::fabs(N.z) < 0.999f ? v3(0, 0, 1) : v3(1, 0, 0);
-    vec3 tangent   = normalize(cross(up, N));
-    vec3 bitangent = cross(N, tangent);
-    vec3 sv        = (tangent * H.x + bitangent * H.y) + N * H.z;
-    return normalize(sv);
-}
-
-struct EnvMaps
-{
-    CubeH           sky;
-    const uint16_t* prefiltered; // levels of [6][s][s][4], s = size >> level
-    int             pre_size, pre_levels;
-    const uint16_t* lut;         // [n][n][2]
-    int             lut_size;
-    inline vec3 prefiltered_fetch(vec3 dir, float lod) const
-    {
-        int level = (int)std::floor(lod + 0.5f);
-        level     = level < 0 ? 0 : (level > pre_levels - 1 ? pre_levels - 1 : level);
-        size_t off = 0;
-        for (int l = 0; l < level; l++) off += (size_t)6 * (pre_size >> l) * (pre_size >> l) * 4;
-        CubeH c { prefiltered + off, pre_size >> level };
-        return c.fetch(dir);
-    }
-    inline vec2 lut_fetch(float u, float v) const
-    {
-        int ix = (int)std::floor(u * (float)lut_size), iy = (int)std::floor(v * (float)lut_size);
-        ix = ix < 0 ? 0 : (ix > lut_size - 1 ? lut_size - 1 : ix);
-        iy = iy < 0 ? 0 : (iy > lut_size - 1 ? lut_size - 1 : iy);
-        const uint16_t* q = lut + ((size_t)iy * lut_size + ix) * 2;
-        return vec2 { f16_to_f32(q[0]), f16_to_f32(q[1]) };
-    }
-};
+// reflect3, importance_sample_ggx, EnvMaps: orc_shading.h
 
 } // namespace orc
 

@@ -63,7 +63,7 @@ struct CubeH // [6][S][S][4] fp16, faces +X -X +Y -Y +Z -Z
         else if (ay >= az) { ma = ay; if (d.y >= 0.0f) { face = 2; sc = d.x; tc = d.z; } else { face = 3; sc = d.x; tc = -d.z; } }
         else { ma = az; if (d.z >= 0.0f) { face = 4; sc = d.x; tc = -d.y; } else { face = 5; sc = -d.x; tc = -d.y; } }
         float s = 0.5f * (sc / ma + 1.0f), t = 0.5f * (tc / ma + 1.0f);
-        int   ix = (int)std::floor(s * (float)S), iy = (int)std::floor(t * (float)S);
+        int   ix = f2i_sat(std::floor(s * (float)S)), iy = f2i_sat(std::floor(t * (float)S));
         ix = ix < 0 ? 0 : (ix > S - 1 ? S - 1 : ix);
         iy = iy < 0 ? 0 : (iy > S - 1 ? S - 1 : iy);
         const uint16_t* q = p + (((size_t)face * S + iy) * S + ix) * 4;
@@ -112,6 +112,81 @@ static inline vec3 fresnel_schlick_roughness(float cos_theta, vec3 F0, float rou
 }
 vec3 sample_cosine_lobe(vec3 n, float rx, float ry); // orc_ao.cpp (brdf.glsl:20-32)
 void make_rotation_matrix(vec3 z, vec3* x, vec3* y);   // orc_ao.cpp (brdf.glsl:8-16)
+// brdf.glsl:96-112 sample_specular_ggx_lobe (the ground-truth path tracer's specular bounce)
+static inline vec3 sample_specular_ggx_lobe(vec3 n, float alpha, float xi_x, float xi_y)
+{
+    const float phi       = 2.0f * ORC_M_PI * xi_x;
+    const float cos_theta = std::sqrt((1.0f - xi_y) / (1.0f + (alpha * alpha - 1.0f) * xi_y));
+    const float sin_theta = std::sqrt(1.0f - cos_theta * cos_theta);
+    float s, c;
+    det_sincos(phi, &s, &c);
+    const vec3 d = v3(sin_theta * c, sin_theta * s, cos_theta);
+    vec3 x, y;
+    make_rotation_matrix(n, &x, &y);
+    return normalize(v3((x.x * d.x + y.x * d.y) + n.x * d.z, (x.y * d.x + y.y * d.y) + n.y * d.z, (x.z * d.x + y.z * d.y) + n.z * d.z));
+}
+
+// gi_ray_trace.rgen:61-72
+static inline vec3 spherical_fibonacci(float i, float n)
+{
+    // PHI = sqrt(5)*0.5 + 0.5 evaluated in fp32 (= 1.61803400516510009765625); PHI - 1 is exact
+    const float PHI_M1 = 0.61803400516510009765625f;
+    float a   = i * PHI_M1;
+    float phi = 2.0f * ORC_M_PI * (a - std::floor(a));
+    float cos_theta = 1.0f - (2.0f * i + 1.0f) * (1.0f / n);
+    float sin_theta = std::sqrt(glsl_clamp(1.0f - cos_theta * cos_theta, 0.0f, 1.0f));
+    float s, c;
+    det_sincos(phi, &s, &c);
+    return v3(c * sin_theta, s * sin_theta, cos_theta);
+}
+// lighting.glsl:6-111 with SOFT_SHADOWS | SHADOW_RAY_ONLY | RAY_TRACING (orc_shadows.cpp)
+void fetch_light_properties_shadow(const Light& light, vec3 P, vec3 N, float rx, float ry, vec3* Wi, float* t_max, float* attenuation);
+
+static inline vec3 reflect3(vec3 I, vec3 N) { return I - N * (2.0f * dot(N, I)); }
+
+// reflections_ray_trace.rgen:78-105 (the PDF it also computes is unused by the caller)
+static inline vec3 importance_sample_ggx(float Ex, float Ey, vec3 N, float roughness)
+{
+    float a = roughness * roughness, m2 = a * a;
+    float phi = 2.0f * ORC_M_PI * Ex;
+    float cos_theta = std::sqrt((1.0f - Ey) / (1.0f + (m2 - 1.0f) * Ey));
+    float sin_theta = std::sqrt(1.0f - cos_theta * cos_theta);
+    float s, c;
+    det_sincos(phi, &s, &c);
+    vec3 H  = v3(c * sin_theta, s * sin_theta, cos_theta);
+    vec3 up = std::fabs(N.z) < 0.999f ? v3(0, 0, 1) : v3(1, 0, 0);
+    vec3 tangent   = normalize(cross(up, N));
+    vec3 bitangent = cross(N, tangent);
+    vec3 sv        = (tangent * H.x + bitangent * H.y) + N * H.z;
+    return normalize(sv);
+}
+
+// the reflections pass's environment: sky, specular-prefiltered chain, BRDF LUT, all NEAREST
+struct EnvMaps
+{
+    CubeH           sky;
+    const uint16_t* prefiltered; // levels of [6][s][s][4], s = size >> level
+    int             pre_size, pre_levels;
+    const uint16_t* lut;         // [n][n][2]
+    int             lut_size;
+    inline vec3 prefiltered_fetch(vec3 dir, float lod) const
+    {
+        int level = f2i_sat(std::floor(lod + 0.5f));
+        level     = level < 0 ? 0 : (level > pre_levels - 1 ? pre_levels - 1 : level);
+        size_t off = 0;
+        for (int l = 0; l < level; l++) off += (size_t)6 * (pre_size >> l) * (pre_size >> l) * 4;
+        CubeH c { prefiltered + off, pre_size >> level };
+        return c.fetch(dir);
+    }
+    inline vec2 lut_fetch(float u, float v) const
+    {
+        int ix = f2i_sat(std::floor(u * (float)lut_size)), iy = f2i_sat(std::floor(v * (float)lut_size));
+        ix = ix < 0 ? 0 : (ix > lut_size - 1 ? lut_size - 1 : ix);
+        iy = iy < 0 ? 0 : (iy > lut_size - 1 ? lut_size - 1 : iy);
+        const uint16_t* q = lut + ((size_t)iy * lut_size + ix) * 2;
+        return vec2 { f16_to_f32(q[0]), f16_to_f32(q[1]) };
+    }
+};
 
 // ------------------------------------------------------------------------------------------- DDGI
 struct DDGIUniforms // ddgi.cpp:14-32 == gi_common.glsl:10-28, scalar layout, 88 bytes
@@ -182,7 +257,7 @@ static inline vec3 atlas_bilinear(const uint16_t* p, int w, int h, float u, floa
     float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
     float fx0 = std::floor(x), fy0 = std::floor(y);
     float fx = x - fx0, fy = y - fy0;
-    int   x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+    int   x0 = f2i_sat(fx0), y0 = f2i_sat(fy0), x1 = inc_sat(x0), y1 = inc_sat(y0);
     auto  cl = [](int a, int n) { return a < 0 ? 0 : (a > n - 1 ? n - 1 : a); };
     x0 = cl(x0, w); x1 = cl(x1, w); y0 = cl(y0, h); y1 = cl(y1, h);
     float r[3] = { 0, 0, 0 };
@@ -195,16 +270,18 @@ static inline vec3 atlas_bilinear(const uint16_t* p, int w, int h, float u, floa
     return v3(r[0], r[1], r[2]);
 }
 
-// gi_common.glsl:188-320
-static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3 Wo, const uint16_t* irradiance, const uint16_t* depth)
+// what the gather decided for one of its eight probes: recorded (never read) so that a test can assert which branch a constructed case took
+struct IrrProbeTrace { int cx, cy, cz; float tri[3], dist, mean, m2, variance, weight_before_crush, net_before_nan[3]; };
+// gi_common.glsl:188-316: the weighted sqrt-space mean (NaN components replaced by 0.5), before the squaring and scaling of :317-320
+static inline vec3 sample_irradiance_net(const DDGIUniforms& d, vec3 P, vec3 N, vec3 Wo, const uint16_t* irradiance, const uint16_t* depth, IrrProbeTrace* trace = nullptr)
 {
     const vec3 gs = v3(d.grid_step[0], d.grid_step[1], d.grid_step[2]);
     const vec3 g0 = v3(d.grid_start_position[0], d.grid_start_position[1], d.grid_start_position[2]);
     auto clampi = [](int a, int lo, int hi) { return a < lo ? lo : (a > hi ? hi : a); };
     // base_grid_coord: clamp(ivec3((X - start) / step), 0, counts - 1)
-    int bx = clampi((int)((P.x - g0.x) / gs.x), 0, d.probe_counts[0] - 1);
-    int by = clampi((int)((P.y - g0.y) / gs.y), 0, d.probe_counts[1] - 1);
-    int bz = clampi((int)((P.z - g0.z) / gs.z), 0, d.probe_counts[2] - 1);
+    int bx = clampi(f2i_sat((P.x - g0.x) / gs.x), 0, d.probe_counts[0] - 1);
+    int by = clampi(f2i_sat((P.y - g0.y) / gs.y), 0, d.probe_counts[1] - 1);
+    int bz = clampi(f2i_sat((P.z - g0.z) / gs.z), 0, d.probe_counts[2] - 1);
     vec3 base_pos = grid_coord_to_position(d, bx, by, bz);
     vec3 sum_irr = v3(0, 0, 0);
     float sum_w = 0.0f;
@@ -218,6 +295,7 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
         vec3 probe_to_point = (P - probe_pos) + (N + 3.0f * Wo) * d.normal_bias;
         vec3 dir = normalize(-probe_to_point);
         vec3 tri = v3(mixf(1.0f - alpha.x, alpha.x, (float)ox), mixf(1.0f - alpha.y, alpha.y, (float)oy), mixf(1.0f - alpha.z, alpha.z, (float)oz));
+        if (trace) { trace[i] = IrrProbeTrace {}; trace[i].cx = cx; trace[i].cy = cy; trace[i].cz = cz; trace[i].tri[0] = tri.x; trace[i].tri[1] = tri.y; trace[i].tri[2] = tri.z; }
         float weight = 1.0f;
         {
             vec3  tdp = normalize(probe_pos - P);
@@ -235,8 +313,10 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
             float che = variance / (variance + dm * dm);
             che       = glsl_max(che * che * che, 0.0f);
             weight    = weight * ((dist <= mean) ? 1.0f : che);
+            if (trace) { trace[i].dist = dist; trace[i].mean = mean; trace[i].m2 = temp.y; trace[i].variance = variance; }
         }
         weight = glsl_max(0.000001f, weight);
+        if (trace) trace[i].weight_before_crush = weight;
         vec2 tc = texture_coord_from_direction(normalize(N), p, d.irradiance_texture_width, d.irradiance_texture_height, d.irradiance_probe_side_length);
         vec3 probe_irr = atlas_bilinear<4>(irradiance, d.irradiance_texture_width, d.irradiance_texture_height, tc.x, tc.y);
         const float crush = 0.2f;
@@ -247,9 +327,16 @@ static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3
         sum_w += weight;
     }
     vec3 net = sum_irr / sum_w;
+    if (trace) { trace[0].net_before_nan[0] = net.x; trace[0].net_before_nan[1] = net.y; trace[0].net_before_nan[2] = net.z; }
     net.x = (net.x != net.x) ? 0.5f : net.x;
     net.y = (net.y != net.y) ? 0.5f : net.y;
     net.z = (net.z != net.z) ? 0.5f : net.z;
+    return net;
+}
+// gi_common.glsl:188-320
+static inline vec3 sample_irradiance(const DDGIUniforms& d, vec3 P, vec3 N, vec3 Wo, const uint16_t* irradiance, const uint16_t* depth)
+{
+    vec3 net = sample_irradiance_net(d, P, N, Wo, irradiance, depth);
     net = net * net;
     net = net * d.energy_preservation;
     return (0.5f * ORC_M_PI) * net;
@@ -271,7 +358,8 @@ static inline vec4 sample_texture(const Scene::Texture& t, float u, float v)
     const float fx0 = std::floor(px), fy0 = std::floor(py);
     const float fx = px - fx0, fy = py - fy0;
     auto wrap = [](int c, int n) { c %= n; return c < 0 ? c + n : c; };
-    const int x0 = wrap((int)fx0, t.w), x1 = wrap((int)fx0 + 1, t.w), y0 = wrap((int)fy0, t.h), y1 = wrap((int)fy0 + 1, t.h);
+    // the neighbour texel is taken after the wrap: f2i_sat(fx0) + 1 would overflow at a saturated index (((i mod n) + 1) mod n is (i + 1) mod n in range)
+    const int x0 = wrap(f2i_sat(fx0), t.w), y0 = wrap(f2i_sat(fy0), t.h), x1 = x0 + 1 == t.w ? 0 : x0 + 1, y1 = y0 + 1 == t.h ? 0 : y0 + 1;
     auto texel = [&](int x, int y, int c) { return (float)t.rgba[((size_t)y * t.w + x) * 4 + c] / 255.0f; };
     float r[4];
     for (int c = 0; c < 4; c++)

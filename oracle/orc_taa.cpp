@@ -36,12 +36,12 @@ struct Tex4 // RGBA16F
         const float fx = u * (float)w - 0.5f, fy = v * (float)h - 0.5f;
         const float x0 = std::floor(fx), y0 = std::floor(fy);
         const float ax = fx - x0, ay = fy - y0;
-        const int   ix = (int)x0, iy = (int)y0;
-        const V4 t00 = texel(ix, iy), t10 = texel(ix + 1, iy), t01 = texel(ix, iy + 1), t11 = texel(ix + 1, iy + 1);
+        const int   ix = f2i_sat(x0), iy = f2i_sat(y0), jx = inc_sat(ix), jy = inc_sat(iy);   // saturating, like the device (orc_math.h)
+        const V4 t00 = texel(ix, iy), t10 = texel(jx, iy), t01 = texel(ix, jy), t11 = texel(jx, jy);
         auto mix4 = [](V4 a, V4 b, float t) { return add(scale(a, 1.0f - t), scale(b, t)); };
         return mix4(mix4(t00, t10, ax), mix4(t01, t11, ax), ay);
     }
-    V4 nearest(float u, float v) const { return texel((int)std::floor(u * (float)w), (int)std::floor(v * (float)h)); }
+    V4 nearest(float u, float v) const { return texel(f2i_sat(std::floor(u * (float)w)), f2i_sat(std::floor(v * (float)h))); }
 };
 
 struct Tex1 // R32F
@@ -49,7 +49,7 @@ struct Tex1 // R32F
     const float* p; int w, h;
     float nearest(float u, float v) const
     {
-        int x = (int)std::floor(u * (float)w), y = (int)std::floor(v * (float)h);
+        int x = f2i_sat(std::floor(u * (float)w)), y = f2i_sat(std::floor(v * (float)h));
         x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
         y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
         return p[(size_t)y * w + x];

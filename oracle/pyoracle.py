@@ -146,6 +146,58 @@ def selftest_compare(tu, which, gen, first, n, gpu_out, params=None, inp=None, m
     return int(bad), np.sort(rep[:min(bad, max_report)])
 
 
+# ---- mirror of hr_selftest_shading (orc_selftest_shading.cpp; layout: hybrid_rendering_amd/csrc/selftest_shading.h) ----
+(SHADING_RNG, SHADING_CUBE, SHADING_TEXTURE, SHADING_BRDF_TERMS, SHADING_BRDF_UBER, SHADING_LOBES, SHADING_LIGHT_HARD, SHADING_LIGHT_SHADOW,
+ SHADING_GI_OCT, SHADING_GI_COORDS, SHADING_GATHER, SHADING_SURFACE, SHADING_GATHER_TRACE) = range(13)   # GATHER_TRACE: the oracle only
+SHADING_IN, SHADING_MAX_OUT, SHADING_MAX_N = 24, 12, 1 << 17
+SHADING_POINTERS = ("cube", "prefiltered", "lut", "tex_table", "tex_data", "cutout_tab", "uvs", "irradiance", "depth", "positions", "normals", "tangents", "tri_uvs",
+                    "tri_material", "materials", "mat_tex", "inst_m")
+SHADING_INTS = ("cube_size", "pre_size", "pre_levels", "lut_size", "n_tex", "n_attr", "n_tris", "n_mats")
+
+
+class ShadingTables(C.Structure):
+    """The table block both self tests take by pointer: addresses (host memory for the oracle, device memory for the device), extents, one
+    hr_ddgi_uniforms (88 bytes) and one hr_light (16 floats)."""
+    _fields_ = [(n, C.c_void_p) for n in SHADING_POINTERS] + [(n, C.c_int32) for n in SHADING_INTS] + [("ddgi", C.c_uint8 * 88), ("light", C.c_float * 16)]
+
+
+assert C.sizeof(ShadingTables) == 17 * 8 + 8 * 4 + 88 + 64
+
+
+def shading_tables(arrays, address=None):
+    """arrays: dict with numpy arrays under SHADING_POINTERS' names (missing: null), ints under SHADING_INTS', `ddgi` (88 bytes) and `light` (16 floats);
+    address: name -> the address to store instead of the host array's own (the GPU tests pass the device copies')."""
+    t = ShadingTables()
+    for n in SHADING_POINTERS:
+        if arrays.get(n) is not None:
+            assert arrays[n].flags["C_CONTIGUOUS"], n
+            setattr(t, n, arrays[n].ctypes.data if address is None else address[n])
+    for n in SHADING_INTS:
+        setattr(t, n, int(arrays.get(n, 0)))
+    if arrays.get("ddgi") is not None:
+        raw = np.ascontiguousarray(arrays["ddgi"]).view(np.uint8).reshape(-1)
+        assert raw.size == 88
+        C.memmove(t.ddgi, raw.ctypes.data, 88)
+    if arrays.get("light") is not None:
+        t.light[:] = [float(x) for x in np.asarray(arrays["light"], np.float32).reshape(16)]
+    return t
+
+
+def selftest_shading(mode, inp, arrays, nout):
+    """[nout][n] float32 outputs of the mirror; inp: [n][24] float32"""
+    inp = np.ascontiguousarray(inp, np.float32)
+    n = inp.shape[0]
+    assert inp.shape == (n, SHADING_IN) and n <= SHADING_MAX_N
+    t = shading_tables(arrays)
+    out = np.empty((nout, n), np.float32)
+    L = lib()
+    L.orc_selftest_shading.restype = C.c_int
+    L.orc_selftest_shading.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    st = L.orc_selftest_shading(mode, n, inp.ctypes.data, C.addressof(t), nout, out.ctypes.data)
+    assert st == 0, ("orc_selftest_shading", mode)
+    return out
+
+
 def _p(a, t):
     if a is None:
         return None
