@@ -82,6 +82,7 @@ const char* sample_name_of_stage(const char* stage)
         { "probe_update", "Irradiance + Depth + Border Update" },   // one launch for the three (ddgi.hip k_ddgi_probe_update)
         { "sample_probe_grid", "Sample Probe Grid" },
         { "path_trace", "Ground Truth Path Trace" }, { "taa", "TAA" },
+        { "env_sh9", "Cubemap SH Projection" }, { "env_prefilter", "Cubemap Prefilter" }, { "env_brdf_lut", "BRDF Integrate LUT" },   // the framework's passes behind hr_env (env.hip)
     };
     for (const auto& t : table)
         if (std::strcmp(t.stage, stage) == 0) return t.label;

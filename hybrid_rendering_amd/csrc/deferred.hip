@@ -3,6 +3,7 @@
 // indirect_lighting :151-173, lighting.glsl direct_lighting without RAY_TRACING).  SURVEY.md §8f row 1.
 #include "hr_internal.h"
 #include "shading.h"
+#include "../../include/hr_env.h"
 
 using namespace hr;
 
@@ -22,6 +23,7 @@ struct DeferredArgs
     const uint2*    prefiltered; int pre_size, pre_levels;
     const uint32_t* lut;    int lut_size;
     float           sh9[9][4];
+    const float*    sh9_dev;                // hr_deferred_bind_sh9: device [9][4], read by the SH9_DEV instantiation in the place of sh9
     uint2*          out;
     int             w, h, flags;
     // render_skybox (deferred_shading.cpp:734-789, skybox.vert/.frag): sky texels (depth == 1) take the cubemap colour
@@ -29,6 +31,8 @@ struct DeferredArgs
     float           view_inverse[16], proj_inverse[16];
 };
 
+// SH9_DEV: the nine coefficients come from device memory (wave-uniform loads) and not from the arguments; everything else is one body
+template <bool SH9_DEV>
 __global__ __launch_bounds__(256) void k_deferred(DeferredArgs a)
 {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
@@ -79,7 +83,11 @@ __global__ __launch_bounds__(256) void k_deferred(DeferredArgs a)
             c[0] *= A0; c[1] *= A1; c[2] *= A1; c[3] *= A1; c[4] *= A2; c[5] *= A2; c[6] *= A2; c[7] *= A2; c[8] *= A2;
             f3 col = mk3(0.0f, 0.0f, 0.0f);
 #pragma unroll
-            for (int k = 0; k < 9; k++) col = add3(col, scale3(mk3(a.sh9[k][0], a.sh9[k][1], a.sh9[k][2]), c[k]));
+            for (int k = 0; k < 9; k++)
+            {
+                const f3 sh = SH9_DEV ? mk3(a.sh9_dev[k * 4 + 0], a.sh9_dev[k * 4 + 1], a.sh9_dev[k * 4 + 2]) : mk3(a.sh9[k][0], a.sh9[k][1], a.sh9[k][2]);
+                col = add3(col, scale3(sh, c[k]));
+            }
             col = mk3(glsl_max(0.0f, col.x), glsl_max(0.0f, col.y), glsl_max(0.0f, col.z));
             irradiance = div3s(col, Pi);
         }
@@ -125,6 +133,7 @@ struct hr_deferred
     hr_ctx* ctx = nullptr;
     int     w = 0, h = 0;
     DevBuf  out;
+    const float* sh9_dev = nullptr;   // hr_deferred_bind_sh9
 };
 
 extern "C" {
@@ -192,8 +201,17 @@ hr_status hr_deferred_render(hr_deferred* p, const hr_frame_inputs* in, const hr
     a.out = (uint2*)p->out.p; a.w = p->w; a.h = p->h;
     a.sky = (prm->draw_skybox && env->sky) ? (const uint2*)env->sky : nullptr; a.sky_size = env->sky_size;
     for (int i = 0; i < 16; i++) { a.view_inverse[i] = in->ubo.view_inverse[i]; a.proj_inverse[i] = in->ubo.proj_inverse[i]; }
-    hipLaunchKernelGGL(k_deferred, dim3(cdiv(p->w, 32), cdiv(p->h, 8)), dim3(256), 0, (hipStream_t)stream, a);
+    a.sh9_dev = p->sh9_dev;
+    if (p->sh9_dev) hipLaunchKernelGGL(k_deferred<true>, dim3(cdiv(p->w, 32), cdiv(p->h, 8)), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_deferred<false>, dim3(cdiv(p->w, 32), cdiv(p->h, 8)), dim3(256), 0, (hipStream_t)stream, a);
     HR_HIP(hipGetLastError());
+    return HR_OK;
+}
+
+hr_status hr_deferred_bind_sh9(hr_deferred* p, const float* device_sh9)
+{
+    HR_CHECK_ARG(p);
+    p->sh9_dev = device_sh9;
     return HR_OK;
 }
 

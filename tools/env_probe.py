@@ -1,0 +1,71 @@
+"""What the environment pipeline costs (developer tool, GPU): the stage times of hr_env_update (env_sh9, env_prefilter) and of the one-off BRDF
+LUT (env_brdf_lut, integrated by hr_env_create) at hr_env_default_desc's sizes, next to the wall time of the host path they replace —
+synth_env.sh9_from_cubemap + prefiltered_chain + brdf_lut in numpy, plus the upload of their results.  The two paths do not compute the same
+thing (the host stand-ins are a box-filter chain and an analytic LUT fit): the comparison is of what a frame with a moving sun pays either way.
+
+    python tools/env_probe.py [--sky 128 --prefiltered 128 --levels 5 --lut 128 --samples 1024] [--updates 50] [--host-rounds 3]
+
+One JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    import torch
+    from hybrid_rendering_amd import api as hr, env, synth_env
+    d = env.default_desc()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sky", type=int, default=d.sky_size)
+    ap.add_argument("--prefiltered", type=int, default=d.prefiltered_size)
+    ap.add_argument("--levels", type=int, default=d.prefiltered_levels)
+    ap.add_argument("--lut", type=int, default=d.brdf_lut_size)
+    ap.add_argument("--samples", type=int, default=d.n_samples)
+    ap.add_argument("--updates", type=int, default=50)
+    ap.add_argument("--host-rounds", type=int, default=3)
+    args = ap.parse_args()
+    ctx = hr.Context(0)
+    sky = synth_env.sky_cubemap(size=args.sky)
+    sky_d = torch.from_numpy(sky).cuda().view(torch.float16)
+    t0 = time.perf_counter()
+    E = env.Environment(ctx, args.sky, args.prefiltered, args.levels, args.lut, args.samples)
+    create_ms = (time.perf_counter() - t0) * 1e3
+    stages = {name: ms for name, ms, _ in E.stage_times()}          # the first read: the LUT's launch at creation
+    for _ in range(3):
+        E.update(sky_d)
+    torch.cuda.synchronize()
+    E.set_profiling(True)
+    t0 = time.perf_counter()
+    for _ in range(args.updates):
+        E.update(sky_d)
+    torch.cuda.synchronize()
+    wall_ms = (time.perf_counter() - t0) * 1e3 / args.updates       # with the profiler's events in the stream: an upper bound
+    stages.update({name: ms for name, ms, _ in E.stage_times()})
+    E.set_profiling(False)
+    host = []
+    for _ in range(args.host_rounds):
+        t0 = time.perf_counter()
+        sh9 = synth_env.sh9_from_cubemap(sky)
+        pre = synth_env.prefiltered_chain(sky, args.levels)
+        t1 = time.perf_counter()
+        up = [torch.from_numpy(a).cuda() for a in (sh9, pre)]
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        host.append(((t1 - t0) * 1e3, (t2 - t1) * 1e3))
+    t0 = time.perf_counter()
+    synth_env.brdf_lut(args.lut)
+    host_lut_ms = (time.perf_counter() - t0) * 1e3
+    best = min(host, key=lambda p: p[0] + p[1])
+    print(json.dumps(dict(sky=args.sky, prefiltered=args.prefiltered, levels=args.levels, lut=args.lut, samples=args.samples, updates=args.updates,
+                          device_us={k: round(v * 1e3, 2) for k, v in sorted(stages.items())}, update_wall_us=round(wall_ms * 1e3, 1), create_ms=round(create_ms, 2),
+                          host_update_ms=dict(compute=round(best[0], 2), upload=round(best[1], 3)), host_lut_ms=round(host_lut_ms, 2))))
+    E.close()
+
+
+if __name__ == "__main__":
+    main()
