@@ -46,7 +46,7 @@ vec3 sample_cosine_lobe(vec3 n, float rx, float ry)
 
 extern "C" {
 
-// A1.  mask: [spp][ceil(h/4)][ceil(w/8)]; pixels outside the image contribute 0.
+// A1.  mask: [spp][ceil(h/4)][ceil(w/8)]; edge threads of a ragged image trace and contribute their bit (below).
 void orc_ao_ray_trace(const void* scene_, const void* ubo_, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol,
                       const uint8_t* scrambling_ranking, float bias, float ray_length, uint32_t num_frames, int spp, uint32_t* mask, uint64_t* rays_out)
 {
@@ -86,6 +86,36 @@ void orc_ao_ray_trace(const void* scene_, const void* ubo_, int w, int h, const 
                 mask[((size_t)s * mh + my) * mw + mx] = bits;
             }
     if (rays_out) *rays_out = rays;
+}
+
+// The rays of EVERY thread of the dispatch orc_ao_ray_trace restates (edge threads of a ragged image included), all spp samples, the same
+// sample index.  rays: [spp][ceil(h/4)*4][ceil(w/8)*8][8] = origin xyz, ray_length, dir xyz, fired (1/0); sky: all zeros.
+void orc_ao_gen_rays(const void* ubo_, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol, const uint8_t* scrambling_ranking,
+                     float bias, float ray_length, uint32_t num_frames, int spp, float* rays)
+{
+    const UBO& ubo = *(const UBO*)ubo_;
+    BlueNoise  bn { sobol, scrambling_ranking };
+    ImgH<4>    g2 { gb2, w, h };
+    const int  pw = ceil_div(w, 8) * 8, ph = ceil_div(h, 4) * 4;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < ph; y++)
+        for (int x = 0; x < pw; x++)
+            for (int s = 0; s < spp; s++)
+            {
+                float* r = rays + (((size_t)s * ph + y) * pw + x) * 8;
+                for (int i = 0; i < 8; i++) r[i] = 0.0f;
+                float d = (x < w && y < h) ? depth[(size_t)y * w + x] : 0.0f;
+                if (d == 1.0f) continue;
+                float tu = ((float)x + 0.5f) / (float)w, tv = ((float)y + 0.5f) / (float)h;
+                vec3  world_pos  = world_position_from_depth(tu, tv, d, ubo.view_proj_inverse);
+                vec3  normal     = octohedral_to_direction(g2.fetch(x, y, 0), g2.fetch(x, y, 1));
+                vec3  ray_origin = world_pos + normal * bias;
+                int   idx        = (int)num_frames * spp + s;
+                float r0 = sample_blue_noise(x, y, idx, 0, bn), r1 = sample_blue_noise(x, y, idx, 1, bn);
+                vec3  dir = sample_cosine_lobe(normal, r0, r1);
+                r[0] = ray_origin.x; r[1] = ray_origin.y; r[2] = ray_origin.z; r[3] = ray_length;
+                r[4] = dir.x; r[5] = dir.y; r[6] = dir.z; r[7] = 1.0f;
+            }
 }
 
 static inline float unpack_bit(const ImgU& m, int x, int y, uint32_t oob)

@@ -43,6 +43,8 @@ void orc_shadows_ray_trace(const void* scene, const void* ubo, int w, int h, con
                            uint32_t* mask, uint64_t* rays_out);
 void orc_shadows_gen_rays(const void* ubo, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol,
                           const uint8_t* scrambling_ranking, float bias, uint32_t num_frames, float* rays);
+void orc_shadows_gen_rays_padded(const void* ubo, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol,
+                                 const uint8_t* scrambling_ranking, float bias, uint32_t num_frames, float* rays);
 void orc_shadows_temporal(const void* ubo, int w, int h, const uint32_t* mask, const float* depth, const uint16_t* gb2,
                           const uint16_t* gb3, const float* prev_depth, const uint16_t* prev_gb2, const uint16_t* prev_gb3,
                           const uint16_t* hist_vis_var, const uint16_t* hist_moments, float alpha, float moments_alpha,
@@ -57,6 +59,8 @@ void orc_upsample(int W, int H, int w, int h, const uint16_t* gb2_full, const ui
 // ---- ambient occlusion ---------------------------------------------------------------------
 void orc_ao_ray_trace(const void* scene, const void* ubo, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol,
                       const uint8_t* scrambling_ranking, float bias, float ray_length, uint32_t num_frames, int spp, uint32_t* mask, uint64_t* rays_out);
+void orc_ao_gen_rays(const void* ubo, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol, const uint8_t* scrambling_ranking,
+                     float bias, float ray_length, uint32_t num_frames, int spp, float* rays);
 void orc_ao_temporal(const void* ubo, int w, int h, int spp, const uint32_t* mask, const float* depth, const uint16_t* gb2, const uint16_t* gb3,
                      const float* prev_depth, const uint16_t* prev_gb2, const uint16_t* prev_gb3, const uint16_t* hist_ao,
                      const uint16_t* hist_len, float alpha, uint16_t* out_ao, uint16_t* out_len, uint8_t* tile_class);

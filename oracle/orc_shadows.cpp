@@ -140,6 +140,39 @@ void orc_shadows_gen_rays(const void* ubo_, int w, int h, const float* depth, co
         }
 }
 
+// The ray of EVERY thread of the dispatch orc_shadows_ray_trace restates: the padded ceil(h/4)*4 x ceil(w/8)*8 thread grid, edge threads of a
+// ragged image included (depth 0, normal code (0,0): the pinned out-of-image rule above).
+// rays: [ceil(h/4)*4][ceil(w/8)*8][8] = origin xyz, t_max, dir xyz, fired (1/0); a thread that sees sky keeps all zeros.
+// (tests/trace_cases.py builds its occluders from these rays; tests/test_trace_cases.py pins orc_shadows_ray_trace to brute force over them.)
+void orc_shadows_gen_rays_padded(const void* ubo_, int w, int h, const float* depth, const uint16_t* gb2, const uint8_t* sobol,
+                                 const uint8_t* scrambling_ranking, float bias, uint32_t num_frames, float* rays)
+{
+    const UBO& ubo = *(const UBO*)ubo_;
+    BlueNoise  bn { sobol, scrambling_ranking };
+    ImgH<4>    g2 { gb2, w, h };
+    const int  pw = ceil_div(w, 8) * 8, ph = ceil_div(h, 4) * 4;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < ph; y++)
+        for (int x = 0; x < pw; x++)
+        {
+            float* r = rays + ((size_t)y * pw + x) * 8;
+            for (int i = 0; i < 8; i++) r[i] = 0.0f;
+            float d = (x < w && y < h) ? depth[(size_t)y * w + x] : 0.0f;
+            if (d == 1.0f) continue;
+            float tu = ((float)x + 0.5f) / (float)w, tv = ((float)y + 0.5f) / (float)h;
+            vec3  world_pos  = world_position_from_depth(tu, tv, d, ubo.view_proj_inverse);
+            vec3  normal     = octohedral_to_direction(g2.fetch(x, y, 0), g2.fetch(x, y, 1));
+            vec3  ray_origin = world_pos + normal * bias;
+            float r0 = sample_blue_noise(x, y, (int)num_frames, 0, bn);
+            float r1 = sample_blue_noise(x, y, (int)num_frames, 1, bn);
+            vec3  Wi;
+            float t_max, attenuation;
+            fetch_light_properties_shadow(ubo.light, world_pos, normal, r0, r1, &Wi, &t_max, &attenuation);
+            r[0] = ray_origin.x; r[1] = ray_origin.y; r[2] = ray_origin.z; r[3] = t_max;
+            r[4] = Wi.x; r[5] = Wi.y; r[6] = Wi.z; r[7] = attenuation > 0.0f ? 1.0f : 0.0f;
+        }
+}
+
 static inline float unpack_hit(const ImgU& m, int x, int y, uint32_t oob)
 {
     // populate_cache + unpack_shadow_hit_value (shadows_denoise_reprojection.comp:114-153):

@@ -365,6 +365,16 @@ def shadows_gen_rays(ubo, depth, gb2, sobol, sr, bias=0.5, num_frames=0):
     return rays
 
 
+def shadows_gen_rays_padded(ubo, depth, gb2, sobol, sr, bias=0.5, num_frames=0):
+    """[ceil(h/4)*4][ceil(w/8)*8][8]: the ray of every thread of the trace dispatch, edge threads of a ragged image included
+    (origin, t_max, direction, fired flag)"""
+    h, w = depth.shape
+    rays = np.zeros((((h + 3) // 4) * 4, ((w + 7) // 8) * 8, 8), np.float32)
+    lib().orc_shadows_gen_rays_padded(_ubo_ptr(ubo), C.c_int(w), C.c_int(h), _p(depth, c_f32p), _p(gb2, c_u16p), _p(sobol, c_u8p), _p(sr, c_u8p),
+                                      C.c_float(bias), C.c_uint32(num_frames), _p(rays, c_f32p))
+    return rays
+
+
 def shadows_temporal(ubo, mask, cur, prev, hist_vis_var, hist_moments, alpha=0.01, moments_alpha=0.2):
     h, w = cur["depth"].shape
     out = np.zeros((h, w, 2), np.uint16)
@@ -437,6 +447,15 @@ def ao_ray_trace(scene, ubo, depth, gb2, sobol, sr, bias=0.3, ray_length=7.0, nu
     lib().orc_ao_ray_trace(scene.h, _ubo_ptr(ubo), C.c_int(w), C.c_int(h), _p(depth, c_f32p), _p(gb2, c_u16p), _p(sobol, c_u8p), _p(sr, c_u8p),
                            C.c_float(bias), C.c_float(ray_length), C.c_uint32(num_frames), C.c_int(spp), _p(mask, c_u32p), C.byref(rays))
     return mask, rays.value
+
+
+def ao_gen_rays(ubo, depth, gb2, sobol, sr, bias=0.3, ray_length=7.0, num_frames=0, spp=1):
+    """[spp][ceil(h/4)*4][ceil(w/8)*8][8]: the sample rays of every thread of the trace dispatch (origin, ray_length, direction, fired flag)"""
+    h, w = depth.shape
+    rays = np.zeros((spp, ((h + 3) // 4) * 4, ((w + 7) // 8) * 8, 8), np.float32)
+    lib().orc_ao_gen_rays(_ubo_ptr(ubo), C.c_int(w), C.c_int(h), _p(depth, c_f32p), _p(gb2, c_u16p), _p(sobol, c_u8p), _p(sr, c_u8p),
+                          C.c_float(bias), C.c_float(ray_length), C.c_uint32(num_frames), C.c_int(spp), _p(rays, c_f32p))
+    return rays
 
 
 def ao_temporal(ubo, mask, cur, prev, hist_ao, hist_len, alpha=0.01):

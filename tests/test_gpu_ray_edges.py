@@ -6,9 +6,9 @@ Reference everywhere: the oracle's brute-force queries (no box test of any kind)
 t, u, v as bit patterns.  Mismatches allowed: 0.  The box test of the walk (traverse.h test_node) only has to be conservative; its error
 budget is DESIGN.md section 3.3 — these tests are what holds a change of ray_prepare / test_node / the box pad to it.
 
-Not covered here: the shadow pass's own trace kernel (occluder cache, G-buffer driven rays) on synthesised G-buffers whose pixel rays run
-through box edges — its walk and its wave-uniform triangle test are the ones hr_trace_any_hit runs (trace_any, ray_tri_raw_uniform), which
-the sorted / interleaved submissions below exercise; the pass itself stays pinned by tests/test_gpu_shadows.py."""
+Not covered here, but in tests/test_gpu_trace_gbuffer_edges.py: the shadow and AO passes' own trace kernels (ray set-up from the G-buffer,
+fire / no-fire decisions, edge threads, the occluder cache's per-lane triangle test, the AO entry-node table) on synthesised G-buffers
+whose pixel rays run through triangle edges, vertices and box planes — pinned to the same brute force."""
 import numpy as np
 import pytest
 
