@@ -138,17 +138,70 @@ HR_DEV uint32_t shadows_filter(const Src& s, Edge edge, float phi_visibility, fl
     return BRANCH ? r : (cnz.z < 0.0f ? c : r);
 }
 
-// "fetch, decode, zero if not resident" of one texel of a staged tile (resident: inside the image and rows ry0 .. ry1)
-HR_DEV void shadows_stage_texel(const AtrousArgs& a, int gx, int gy, int ry0, int ry1, uint32_t& s_in, float4& s_nz)
+// "fetch, decode, zero if not resident" of one texel of a staged tile (resident: inside the image and rows ry0 .. ry1), in its three steps:
+// where (a texel that is not resident is fetched at the first resident texel), fetch, decode and select
+HR_DEV bool shadows_stage_where(const AtrousArgs& a, int gx, int gy, int ry0, int ry1, uint32_t& so)
 {
     const bool res = gx >= 0 && gx < a.w && gy >= ry0 && gy < ry1;
-    const uint32_t so = res ? (uint32_t)(gy * a.w + gx) : (uint32_t)(ry0 * a.w);
-    const uint32_t v  = fm::ld<uint32_t>(a.in.p, so * 4u);
-    const uint2    nd = fm::ld<uint2>(a.nd, so * 8u);
-    const f3       n  = fm::oct_unit(nd.x);
+    // select the coordinates, then one 24-bit multiply-add (rows and widths are far below 2^24).  `res ? gy * a.w + gx : ry0 * a.w` compiles
+    // to a branch around a 64-bit v_mad whose unused high addend is whatever register comes to hand — the destination of the load
+    // issued just before, which makes every load of a batch wait for the one in front of it.
+    const uint32_t sx = res ? (uint32_t)gx : 0u, sy = res ? (uint32_t)gy : (uint32_t)ry0;
+    so = __umul24(sy, (uint32_t)a.w) + sx;
+    return res;
+}
+HR_DEV void shadows_stage_decode(bool res, uint32_t v, uint2 nd, uint32_t& s_in, float4& s_nz)
+{
+    const f3 n = fm::oct_unit(nd.x);
     s_in = res ? v : 0u;
     s_nz = res ? make_float4(n.x, n.y, n.z, fm::hi(nd.y)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
+HR_DEV void shadows_stage_texel(const AtrousArgs& a, int gx, int gy, int ry0, int ry1, uint32_t& s_in, float4& s_nz)
+{
+    uint32_t       so;
+    const bool     res = shadows_stage_where(a, gx, gy, ry0, ry1, so);
+    const uint32_t v   = fm::ld<uint32_t>(a.in.p, so * 4u);
+    const uint2    nd  = fm::ld<uint2>(a.nd, so * 8u);
+    shadows_stage_decode(res, v, nd, s_in, s_nz);
+}
+
+// A staged tile of N texels, row length TW, fetched by 256 threads in ONE batch: load() requests every texel of this thread — ROUNDS of
+// them, texel i = thread + 256 * round — before anything waits; a round past the tile's end requests the first resident texel, so that no
+// load sits behind a branch.  store() decodes and writes the LDS tile.  The kernel puts whatever else belongs to the batch, and then
+// __builtin_amdgcn_sched_barrier(0), between the two: one global round trip for the whole tile.
+template <int ROUNDS, int TW, int N>
+struct ShadowsStageBatch
+{
+    static_assert(ROUNDS * 256 >= N && (ROUNDS - 1) * 256 < N, "ROUNDS = ceil(N / 256)");
+    uint32_t v[ROUNDS];
+    uint2    nd[ROUNDS];
+    bool     res[ROUNDS];
+    // (gx0, gy0): the image position of the tile's texel 0
+    HR_DEV void load(const AtrousArgs& a, int gx0, int gy0, int ry0, int ry1)
+    {
+#pragma unroll
+        for (int r = 0; r < ROUNDS; r++)
+        {
+            const int i = (int)threadIdx.x + r * 256, cy = i / TW, cx = i - cy * TW;
+            uint32_t  so;   // past the tile's end (the last round only): row ry1, which is not resident
+            res[r] = shadows_stage_where(a, gx0 + cx, (r * 256 + 255 < N || i < N) ? gy0 + cy : ry1, ry0, ry1, so);
+            v[r]   = fm::ld<uint32_t>(a.in.p, so * 4u);
+            nd[r]  = fm::ld<uint2>(a.nd, so * 8u);
+        }
+    }
+    HR_DEV void store(uint32_t* s_in, float4* s_nz) const
+    {
+#pragma unroll
+        for (int r = 0; r < ROUNDS; r++)
+        {
+            const int i = (int)threadIdx.x + r * 256;
+            uint32_t  sv;
+            float4    sn;
+            shadows_stage_decode(res[r], v[r], nd[r], sv, sn);
+            if (r * 256 + 255 < N || i < N) { s_in[i] = sv; s_nz[i] = sn; }
+        }
+    }
+};
 
 // ---- reflections: reflections_denoise_atrous.comp:94-181 -------------------------------------------------------------------------------
 HR_DEV f3    refl_colour(uint2 q) { return mk3(fm::lo(q.x), fm::hi(q.x), fm::lo(q.y)); }

@@ -661,6 +661,16 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
 #ifndef FT_ATROUS_VOTE
 #define FT_ATROUS_VOTE 1   // 0: stage unconditionally — 14.4 -> 17.8 µs (step 1): the shadow-tile workgroups are a large share of the launch
 #endif
+// How the staged kernels (kf_shadows_atrous_lds, kf_shadows_atrous01) read global memory.  1: a workgroup's whole staged tile in one batch
+// of loads (atrous_filters.h ShadowsStageBatch), and kf_shadows_atrous01's vote from wave-uniform dwords; 0: the loops and the vote they
+// replaced — a round trip per value, per geometry record and per round, and one plus a barrier for the vote.  FT_ATROUS01_SVOTE selects
+// the vote alone (docs/EXPERIMENTS.md, "Shadow a-trous 0+1: the staging in one round trip", has each part's time).
+#ifndef FT_ATROUS01_BATCH
+#define FT_ATROUS01_BATCH 1
+#endif
+#ifndef FT_ATROUS01_SVOTE
+#define FT_ATROUS01_SVOTE FT_ATROUS01_BATCH
+#endif
 template <int STEP, bool N32>
 __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
 {
@@ -679,11 +689,18 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
 #endif
     {
         const int ry0 = a.y0 > 0 ? a.y0 : 0, ry1 = a.y1 < a.h ? a.y1 : a.h;
+#if FT_ATROUS01_BATCH
+        ShadowsStageBatch<(TH * TW + 255) / 256, TW, TH * TW> batch;   // the tile in one round trip
+        batch.load(a, bx0 - STEP, by0 - STEP, ry0, ry1);
+        __builtin_amdgcn_sched_barrier(0);
+        batch.store(s_in, s_nz);
+#else
         for (int i = threadIdx.x; i < TH * TW; i += 256)
         {
             const int  cy = i / TW, cx = i - cy * TW;
             shadows_stage_texel(a, bx0 - STEP + cx, by0 - STEP + cy, ry0, ry1, s_in[i], s_nz[i]);
         }
+#endif
         __syncthreads();
     }
     if (!inside) return;
@@ -711,6 +728,11 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
 // Texel rules are those of kf_shadows_atrous_lds: a texel outside the image / the band's resident rows is (0, normal 0) in BOTH
 // images (weight exactly 0), a texel of a shadow tile is 0 after iteration 0 (copy_shadow_tiles.comp), so the result is
 // bit-identical to the two launches (tests/test_gpu_fused.py).  a.out2 = feedback copy of iteration 1, a.out_first2 = of iteration 0.
+// Global reads of a workgroup: the classes of its own 4 x (TH / 8) tiles as wave-uniform dwords (a workgroup of shadow tiles writes its
+// zeros and leaves after that, with no vector load and no barrier), then region A in ONE batch — four texels per thread, value and
+// geometry record, eight loads with nothing waiting between them (the parent: eight dependent round trips) — then one class byte per
+// round of the two filter loops (five rounds; keeping the classes of the 6 x (TH / 8 + 2) reachable tiles in LDS instead was measured
+// twice and is worth 0.2 µs: docs/EXPERIMENTS.md, "Shadow a-trous 0+1: the staging in one round trip").  tests/test_gpu_atrous01_staging.py.
 template <int TH, bool N32>
 __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_t* out_first2, float power1)
 {
@@ -723,6 +745,26 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
     if (bx0 >= a.w) return;   // a padding column of the launch (block_map.h grid_cols)
     const int ry0 = a.y0 > 0 ? a.y0 : 0, ry1 = a.y1 < a.h ? a.y1 : a.h;
     // tile classes of this workgroup's own tiles: all shadow => every output is 0 and nothing is staged
+#if FT_ATROUS01_SVOTE
+    // wave-uniform, as in kf_shadows_atrous<STEP > 0>: per tile row the two aligned dwords that hold its four bytes, shifted.  No vector
+    // round trip and no barrier in front of the decision.  A tile row is read only if its first pixel row lies above ry1 <= h, that is if
+    // it exists, so the reads end at most 8 bytes past the last tile (hr_shadows_create allocates those) for the second tile row as for
+    // the first; the columns past tiles_x are masked off.
+    uint32_t any_cls = 0u;
+    {
+        const uint32_t cols = a.tiles_x - (bx0 >> 3) >= 4 ? 0xffffffffu : (1u << ((a.tiles_x - (bx0 >> 3)) * 8)) - 1u;
+#pragma unroll
+        for (int r = 0; r < TH / 8; r++)
+        {
+            const bool      row  = by0 + 8 * r < ry1;
+            const uint32_t  tb   = (uint32_t)((by0 >> 3) + (row ? r : 0)) * (uint32_t)a.tiles_x + (uint32_t)(bx0 >> 3);
+            const uint32_t* tc   = reinterpret_cast<const uint32_t*>(a.tile_class) + (tb >> 2);
+            const uint32_t  cls4 = (uint32_t)(((uint64_t)tc[0] | ((uint64_t)tc[1] << 32)) >> ((tb & 3u) * 8u));
+            any_cls |= row ? (cls4 & cols) : 0u;
+        }
+    }
+    if (!any_cls)
+#else
     int any_cls = 0;
     if ((int)threadIdx.x < 4 * (TH / 8))
     {
@@ -730,6 +772,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
         if (tx < a.tiles_x && ty * 8 < a.y1) any_cls = a.tile_class[(size_t)ty * a.tiles_x + tx];
     }
     if (!__syncthreads_or(any_cls))
+#endif
     {
         for (int j = threadIdx.x; j < TH * 32; j += 256)
         {
@@ -742,11 +785,19 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
         }
         return;
     }
+#if FT_ATROUS01_BATCH
+    // region A, requested at once: four texels per thread, value + geometry record
+    ShadowsStageBatch<(AH * AW + 255) / 256, AW, AH * AW> batch;
+    batch.load(a, bx0 - 3, by0 - 3, ry0, ry1);
+    __builtin_amdgcn_sched_barrier(0);   // nothing of the decode (and none of its waits) in front of a load
+    batch.store(s_in, s_nz);
+#else
     for (int i = threadIdx.x; i < AH * AW; i += 256)
     {
         const int  cy = i / AW, cx = i - cy * AW;
         shadows_stage_texel(a, bx0 - 3 + cx, by0 - 3 + cy, ry0, ry1, s_in[i], s_nz[i]);
     }
+#endif
     __syncthreads();
     const EdgeK ek = edge_setup(a.sigma_depth, a.phi_normal, N32);
     // one filter evaluation: centre index ci in the A grid, values from `img` (stride IW, centre index vi), taps at distance D
