@@ -566,8 +566,31 @@ HR_DEV void atrous_gather_pixel(const AtrousArgs& a, int x, int y, uint32_t o)
     if (a.out2) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) = result;
 }
 
+// Per-wave record of the instrumented kernels kf_shadows_atrous_timeline / kf_shadows_atrous01_timeline (developer switch
+// HR_DEBUG_ATROUS_TIMELINE, tools/atrous_balance.py), the way k_shadows_trace fills TraceArgs::timeline: register reads only.  They run the
+// bodies of kf_shadows_atrous<4 | 8> / kf_shadows_atrous01, which return whether the workgroup was live (had a tile that is no shadow tile);
+// the default kernels drop that value and hold none of this.
+struct AtrousTimeline
+{
+    unsigned long long t_begin;
+    HR_DEV AtrousTimeline() : t_begin(wall_clock64()) {}
+    HR_DEV void exit(unsigned long long* timeline, int live) const
+    {
+        if (!timeline || (threadIdx.x & 63u)) return;
+        const unsigned long long t_end = wall_clock64();
+        uint32_t hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4u + (threadIdx.x >> 6);   // four waves per workgroup
+        timeline[slot * 4 + 0] = t_begin;
+        timeline[slot * 4 + 1] = t_end;
+        timeline[slot * 4 + 2] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
+        timeline[slot * 4 + 3] = (unsigned long long)live;
+    }
+};
+
 template <int STEP, bool N32>
-__global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
+HR_DEV int shadows_atrous_body(const AtrousArgs& a)
 {
     const uint2 BLK = block_xy<0>();
     if constexpr (STEP > 0)
@@ -580,29 +603,30 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
         // tile) throws its taps away afterwards.
         const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
         const int fx0 = (int)BLK.x * 32, fy0 = a.y0 + (int)BLK.y * 8;
-        if (fx0 >= a.w) return;   // a padding column of the launch (block_map.h grid_cols)
+        if (fx0 >= a.w) return 0;   // a padding column of the launch (block_map.h grid_cols)
         const uint32_t  tb   = (uint32_t)(fy0 >> 3) * (uint32_t)a.tiles_x + (uint32_t)(fx0 >> 3);
         const uint32_t* tc   = reinterpret_cast<const uint32_t*>(a.tile_class) + (tb >> 2);
         const uint32_t  cls4 = (uint32_t)(((uint64_t)tc[0] | ((uint64_t)tc[1] << 32)) >> ((tb & 3u) * 8u));
+        const int live = (cls4 & (a.tiles_x - (fx0 >> 3) >= 4 ? 0xffffffffu : (1u << ((a.tiles_x - (fx0 >> 3)) * 8)) - 1u)) ? 1 : 0;   // for the timeline only
         const int x = fx0 + lx, y = fy0 + ly;
-        if (x >= a.w || y >= a.y1) return;
+        if (x >= a.w || y >= a.y1) return live;
         const uint32_t o = (uint32_t)(y * a.w + x);
         if (!((cls4 >> ((lx >> 3) * 8)) & 0xffu))
         {
             *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out) + o * 4u) = 0u; // shadows_denoise_copy_shadow_tiles.comp:35
             if (a.out2) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) = 0u;
-            return;
+            return live;
         }
         // a workgroup whose whole footprint lies inside the resident rows needs no bounds test at all (uniform branch)
         const bool interior = fx0 - STEP >= 0 && fx0 + 31 + STEP < a.w && fy0 - STEP >= (a.y0 > 0 ? a.y0 : 0) && fy0 + 7 + STEP < (a.y1 < a.h ? a.y1 : a.h);
         if (interior) atrous_gather_pixel<STEP, N32, true>(a, x, y, o);
         else atrous_gather_pixel<STEP, N32, false>(a, x, y, o);
-        return;
+        return live;
     }
     // STEP == 0: run-time tap distance and radius
     const int x = BLK.x * 32 + (threadIdx.x & 31);
     const int y = a.y0 + BLK.y * 8 + (threadIdx.x >> 5);
-    if (x >= a.w || y >= a.y1) return;
+    if (x >= a.w || y >= a.y1) return 1;
     const uint32_t o = (uint32_t)(y * a.w + x);
     uint32_t* outp  = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out) + o * 4u);
     uint32_t* out2p = a.out2 ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out2) + o * 4u) : nullptr;
@@ -610,7 +634,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
     {
         *outp = 0u; // shadows_denoise_copy_shadow_tiles.comp:35
         if (out2p) *out2p = 0u;
-        return;
+        return 1;
     }
     const int step = a.step, R = a.radius;
     // a workgroup whose whole footprint lies inside the resident rows needs no bounds test at all (uniform branch)
@@ -647,6 +671,21 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
     }
     *outp = result;
     if (out2p) *out2p = result;
+    return 1;
+}
+
+template <int STEP, bool N32>
+__global__ __launch_bounds__(256) void kf_shadows_atrous(AtrousArgs a)
+{
+    (void)shadows_atrous_body<STEP, N32>(a);
+}
+
+template <int STEP>
+__global__ __launch_bounds__(256) void kf_shadows_atrous_timeline(AtrousArgs a, unsigned long long* timeline)
+{
+    const AtrousTimeline tl;
+    const int live = shadows_atrous_body<STEP, true>(a);
+    tl.exit(timeline, live);
 }
 
 
@@ -734,7 +773,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous_lds(AtrousArgs a)
 // round of the two filter loops (five rounds; keeping the classes of the 6 x (TH / 8 + 2) reachable tiles in LDS instead was measured
 // twice and is worth 0.2 µs: docs/EXPERIMENTS.md, "Shadow a-trous 0+1: the staging in one round trip").  tests/test_gpu_atrous01_staging.py.
 template <int TH, bool N32>
-__global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_t* out_first2, float power1)
+HR_DEV int shadows_atrous01_body(const AtrousArgs& a, uint32_t* out_first2, float power1)
 {
     const uint2 BLK = block_xy<0>();
     constexpr int AW = 38, AH = TH + 6, BW = 36, BH = TH + 4;   // A = tile + 3 all round, B = tile + 2 (round-3 advisor: one ring too many each)
@@ -742,7 +781,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
     __shared__ float4   s_nz[AH * AW];   // unit normal, linear z
     __shared__ uint32_t s_mid[BH * BW];  // iteration 0, as the RG16F image would hold it
     const int bx0 = (int)BLK.x * 32, by0 = a.y0 + (int)BLK.y * TH;
-    if (bx0 >= a.w) return;   // a padding column of the launch (block_map.h grid_cols)
+    if (bx0 >= a.w) return 0;   // a padding column of the launch (block_map.h grid_cols)
     const int ry0 = a.y0 > 0 ? a.y0 : 0, ry1 = a.y1 < a.h ? a.y1 : a.h;
     // tile classes of this workgroup's own tiles: all shadow => every output is 0 and nothing is staged
 #if FT_ATROUS01_SVOTE
@@ -783,7 +822,7 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
             if (a.out2) a.out2[o] = 0u;
             if (out_first2) out_first2[o] = 0u;
         }
-        return;
+        return 0;
     }
 #if FT_ATROUS01_BATCH
     // region A, requested at once: four texels per thread, value + geometry record
@@ -831,6 +870,21 @@ __global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_
         a.out[o] = r;
         if (a.out2) a.out2[o] = r;
     }
+    return 1;
+}
+
+template <int TH, bool N32>
+__global__ __launch_bounds__(256) void kf_shadows_atrous01(AtrousArgs a, uint32_t* out_first2, float power1)
+{
+    (void)shadows_atrous01_body<TH, N32>(a, out_first2, power1);
+}
+
+template <int TH>
+__global__ __launch_bounds__(256) void kf_shadows_atrous01_timeline(AtrousArgs a, uint32_t* out_first2, float power1, unsigned long long* timeline)
+{
+    const AtrousTimeline tl;
+    const int live = shadows_atrous01_body<TH, true>(a, out_first2, power1);
+    tl.exit(timeline, live);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1599,10 +1653,16 @@ void launch_shadows_temporal_fast(const TemporalArgs& a_, int n_tiles, hipStream
     else hipLaunchKernelGGL((kf_shadows_temporal<1, 0>), grid, dim3(64 * FT_WAVES), 0, st, a);
 }
 
-void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st)
+void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st, unsigned long long* timeline)
 {
     const dim3 grid(grid_cols(cdiv(a.w, 32), (a.step >= 4 || !FT_ATROUS_LDS) ? 0 : 7), cdiv(a.y1 - a.y0, 8));
     const bool n32 = a.phi_normal == 32.0f;
+    if (timeline && n32 && a.radius == 1 && (a.step == 4 || a.step == 8))   // developer switch HR_DEBUG_ATROUS_TIMELINE: the instrumented kernel
+    {
+        if (a.step == 4) hipLaunchKernelGGL((kf_shadows_atrous_timeline<4>), grid, dim3(256), 0, st, a, timeline);
+        else hipLaunchKernelGGL((kf_shadows_atrous_timeline<8>), grid, dim3(256), 0, st, a, timeline);
+        return;
+    }
 #define HR_LAUNCH_ATROUS(K, S) \
     do { if (n32) hipLaunchKernelGGL((K<S, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((K<S, false>), grid, dim3(256), 0, st, a); } while (0)
     // tap distances 1 and 2 through LDS (apron 1-2 texels: 14.4 / 14.6 µs against 15.8 / 15.9 for per-pixel gathers at 1080p, event
@@ -1622,13 +1682,30 @@ void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st)
 #endif
 // iterations 0 + 1 in one launch; `a` describes iteration 0 (a.in = temporal output, a.step == 1), a.out = the image iteration 1
 // writes, a.out2 / out_first2 = the feedback copy of iteration 1 / 0, power1 = iteration 1's power.  false: not available
-bool launch_shadows_atrous01_fast(const AtrousArgs& a, uint32_t* out_first2, float power1, hipStream_t st)
+// lds_pad: bytes of unused dynamic LDS on top of the kernel's own, which bound how many of its workgroups a CU holds (pass_core.h
+// atrous_resident_pad); timeline: nullptr, or the records of the instrumented kernel (developer switch HR_DEBUG_ATROUS_TIMELINE)
+bool launch_shadows_atrous01_fast(const AtrousArgs& a, uint32_t* out_first2, float power1, hipStream_t st, int lds_pad, unsigned long long* timeline)
 {
     if (a.radius != 1 || a.step != 1) return false;
-    const dim3 grid(grid_cols(cdiv(a.w, 32), 7), cdiv(a.y1 - a.y0, FT_ATROUS01_TH));
-    if (a.phi_normal == 32.0f) hipLaunchKernelGGL((kf_shadows_atrous01<FT_ATROUS01_TH, true>), grid, dim3(256), 0, st, a, out_first2, power1);
-    else hipLaunchKernelGGL((kf_shadows_atrous01<FT_ATROUS01_TH, false>), grid, dim3(256), 0, st, a, out_first2, power1);
+    const dim3   grid(grid_cols(cdiv(a.w, 32), 7), cdiv(a.y1 - a.y0, FT_ATROUS01_TH));
+    const size_t pad = lds_pad > 0 ? (size_t)lds_pad : 0;
+    if (a.phi_normal != 32.0f) hipLaunchKernelGGL((kf_shadows_atrous01<FT_ATROUS01_TH, false>), grid, dim3(256), pad, st, a, out_first2, power1);
+    else if (timeline) hipLaunchKernelGGL((kf_shadows_atrous01_timeline<FT_ATROUS01_TH>), grid, dim3(256), pad, st, a, out_first2, power1, timeline);
+    else hipLaunchKernelGGL((kf_shadows_atrous01<FT_ATROUS01_TH, true>), grid, dim3(256), pad, st, a, out_first2, power1);
     return true;
+}
+
+// static LDS of kf_shadows_atrous01, for the pad (once, at create); < 0: unknown
+int shadows_atrous01_static_lds()
+{
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&kf_shadows_atrous01<FT_ATROUS01_TH, true>)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (int)fa.sharedSizeBytes;
+}
+// workgroups of the largest grid either launcher makes for these arguments (the timeline buffer's size)
+int shadows_atrous_max_workgroups(const AtrousArgs& a)
+{
+    return (cdiv(a.w, 32) + 8) * cdiv(a.y1 - a.y0, 8);
 }
 
 void launch_ao_temporal_fast(const AOTemporalArgs& a_, int n_tiles, hipStream_t st)

@@ -167,8 +167,10 @@ struct DDGISampleArgs
 // hardware's v_rcp / v_rsq / v_sqrt / v_exp / v_log, contracted FMAs and re-associated sums.  The visibility
 // masks never pass through them (the trace kernels have one mode).
 void launch_shadows_temporal_fast(const TemporalArgs& a, int n_tiles, hipStream_t st);
-void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st);
-bool launch_shadows_atrous01_fast(const AtrousArgs& a, uint32_t* out_first2, float power1, hipStream_t st);   // iterations 0 + 1 in one launch
+void launch_shadows_atrous_fast(const AtrousArgs& a, hipStream_t st, unsigned long long* timeline = nullptr);
+bool launch_shadows_atrous01_fast(const AtrousArgs& a, uint32_t* out_first2, float power1, hipStream_t st, int lds_pad = 0, unsigned long long* timeline = nullptr);   // iterations 0 + 1 in one launch
+int  shadows_atrous01_static_lds();                        // of that kernel, bytes; < 0: unknown
+int  shadows_atrous_max_workgroups(const AtrousArgs& a);   // upper bound of either launcher's grid
 void launch_ao_temporal_fast(const AOTemporalArgs& a, int n_tiles, hipStream_t st);
 void launch_ao_blur_fast(const AOBlurArgs& a, hipStream_t st);
 bool launch_ao_blur_xy_fast(const AOBlurArgs& a, hipStream_t st);   // X + Y in one launch (radius 4); false: not available for these arguments

@@ -107,6 +107,24 @@ struct GeoRecords
     static std::string require_message(const char* stage) { return std::string(stage) + ": HR_DEBUG_REQUIRE_GEO is set and the record path was not taken"; }
 };
 
+// ------------------------------------------------------------------------------------------------ residency cap
+// kf_shadows_atrous01 (denoise_fast.hip): how many bytes of unused dynamic LDS a launch asks for so that a CU holds at most R of its
+// workgroups.  The live workgroups of a launch (30 % at the 1080p bench frame; the others leave after a scalar vote) have all started
+// within its first 5 us, 2 to 8 of them to a CU, and the launch lasts as long as the CU that was dealt the most (measured: tools/
+// atrous_balance.py, docs/EXPERIMENTS.md "live workgroups per CU"): the pad bounds how many a CU runs at a time.  static + pad = the largest size, a multiple of the allocation granule, of which R fit into a CU's LDS (if the
+// granule is too coarse for any multiple to give exactly R: the largest size as such).  0 when the kernel's own LDS already allows R or
+// fewer (a pad can only lower the residency), or R <= 0.  R >= 3: static + pad <= lds_per_cu / 3, within the 64 KiB a workgroup may ask for.
+inline int atrous_resident_pad(int lds_per_cu, int static_bytes, int R, int granule)
+{
+    if (R < 3 || lds_per_cu <= 0 || static_bytes < 0 || granule <= 0) return 0;
+    const int own = (static_bytes + granule - 1) / granule * granule;      // what the kernel's own LDS occupies
+    if (own > 0 && lds_per_cu / own <= R) return 0;
+    const int most = lds_per_cu / R;                                       // R of these fit, R + 1 of anything at most (R / (R + 1)) of it do
+    int total = most / granule * granule;
+    if (total <= 0 || lds_per_cu / total != R) total = most;
+    return total > static_bytes ? total - static_bytes : 0;
+}
+
 } // namespace hr
 
 #ifdef __HIPCC__

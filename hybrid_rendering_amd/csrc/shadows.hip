@@ -572,6 +572,42 @@ struct hr_shadows : PassCore
     uint64_t      last_wave_max_steps = 0; // sum over waves of the slowest lane's (node + triangle) steps
     // tolerance mode: the geometry records (pass_core.h GeoRecords) alternate between the two halves of `nd`; the parity mode's float4 layout covers both
     void*         nd_cur = nullptr;         // the side image of the frame in flight (a-trous stages)
+    // tolerance mode, fused chain: the residency cap of kf_shadows_atrous01, as bytes of unused dynamic LDS (pass_core.h atrous_resident_pad; fixed at create)
+    int           atrous01_pad = 0;
+    std::string   dbg_atrous_timeline;      // HR_DEBUG_ATROUS_TIMELINE=<prefix> (tools/atrous_balance.py)
+};
+
+// How many workgroups of kf_shadows_atrous01 a CU may hold (docs/EXPERIMENTS.md, "Shadow a-trous chain: live workgroups per CU", has the
+// sweep: 1080p 21.9 us without, 19.8 / 19.6 / 19.3 / 20.6 at 4 / 5 / 6 / 7); 0: as many as fit (8).  HR_ATROUS01_RESIDENT, read once in
+// hr_shadows_create, overrides it (A/B runs, tests).  Applied to images of at most HR_ATROUS01_REGIONS_PER_SLOT regions per slot.
+#ifndef FT_ATROUS01_RESIDENT
+#define FT_ATROUS01_RESIDENT 6
+#endif
+#ifndef HR_ATROUS01_REGIONS_PER_SLOT
+#define HR_ATROUS01_REGIONS_PER_SLOT 4
+#endif
+#define HR_LDS_GRANULE 1280        // gfx950 allocates LDS in blocks of 320 dwords
+
+// developer switch HR_DEBUG_ATROUS_TIMELINE=<prefix>: the per-wave records of ONE launch go to <prefix>.<tag>, rewritten by every frame
+// (synchronises and allocates: never in a timed run)
+struct AtrousTimelineDump
+{
+    DevBuf buf;
+    unsigned long long* ptr() const { return (unsigned long long*)buf.p; }
+    hr_status begin(const std::string& prefix, const AtrousArgs& a)
+    {
+        if (prefix.empty()) return HR_OK;
+        return buf.alloc((size_t)shadows_atrous_max_workgroups(a) * 4 * 32);   // zeroed: a wave that wrote nothing has entry time 0
+    }
+    hr_status end(const std::string& prefix, const char* tag, hipStream_t st)
+    {
+        if (!buf.p) return HR_OK;
+        HR_HIP(hipStreamSynchronize(st));
+        std::vector<unsigned long long> host(buf.bytes / 8);
+        HR_HIP(hipMemcpy(host.data(), buf.p, buf.bytes, hipMemcpyDeviceToHost));
+        if (FILE* f = fopen((prefix + "." + tag).c_str(), "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
+        return HR_OK;
+    }
 };
 
 bool hr::profiling_enabled(const hr_shadows* p) { return p && p->prof.enabled; }
@@ -601,6 +637,22 @@ hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height
     p->dbg_skip_reproject = getenv("HR_DEBUG_SKIP_REPROJECT") != nullptr;
     p->dbg_timeline_stats = getenv("HR_DEBUG_TIMELINE_STATS") != nullptr;
     if (const char* e = getenv("HR_DEBUG_TIMELINE")) p->dbg_timeline = e;
+    if (const char* e = getenv("HR_DEBUG_ATROUS_TIMELINE")) p->dbg_atrous_timeline = e;
+    {
+        int resident = FT_ATROUS01_RESIDENT;
+        if (const char* e = getenv("HR_ATROUS01_RESIDENT")) resident = atoi(e);
+        hipDeviceProp_t prop;
+        if (resident >= 3 && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess)
+        {
+            // The cap pays while the live workgroups of a launch (about 30 % of the regions on the bench scenes) all fit into the
+            // resident * CUs slots at once; past that the live ones that wait for a slot start late and the launch is slower than without
+            // (3840 x 2160: 45.5 -> 47.7 us at 6, -> 49.9 at 5).  The host knows the regions, not the live ones: a quarter of them per slot.
+            const int own = shadows_atrous01_static_lds(), regions = cdiv(p->w, 32) * cdiv(p->y1 - p->y0, 16);
+            if (regions > HR_ATROUS01_REGIONS_PER_SLOT * resident * prop.multiProcessorCount) resident = 0;
+            if (own >= 0) p->atrous01_pad = atrous_resident_pad((int)prop.maxSharedMemoryPerMultiProcessor, own, resident, HR_LDS_GRANULE);
+            if (own + p->atrous01_pad > (int)prop.sharedMemPerBlock) p->atrous01_pad = 0;   // more than a workgroup may ask for: no cap
+        }
+    }
     const size_t px = (size_t)p->w * p->h; // full-frame sized (bands index with absolute rows)
     HR_PASS_ALLOC(mask, (size_t)p->mw * p->mh * 4)
     HR_PASS_ALLOC(temporal_out, px * 4)
@@ -869,12 +921,15 @@ hr_status hr_shadows_atrous_iteration(hr_shadows* p, const hr_frame_inputs* in, 
     int ev = p->prof.begin(names[i], st, px * 24 + (a.out2 ? px * 4 : 0));
     const dim3 grid(cdiv(w, 32), cdiv(y1 - y0, 8));
     const bool fast = (prm->phi_normal == 32.0f && prm->sigma_depth == 1.0f);
-    if (!prm->exact) launch_shadows_atrous_fast(a, st);
+    AtrousTimelineDump tl;   // developer switch HR_DEBUG_ATROUS_TIMELINE: iterations 2 and 3 of the fused chain
+    if (!prm->exact && p->fuse && prm->radius == 1 && (i == 2 || i == 3) && (s = tl.begin(p->dbg_atrous_timeline, a)) != HR_OK) return s;
+    if (!prm->exact) launch_shadows_atrous_fast(a, st, tl.ptr());
     else if (prm->radius == 1 && fast) hipLaunchKernelGGL((k_shadows_atrous<1, true>), grid, dim3(256), 0, st, a);
     else if (prm->radius == 1) hipLaunchKernelGGL((k_shadows_atrous<1, false>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_shadows_atrous<-1, false>), grid, dim3(256), 0, st, a);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
+    if ((s = tl.end(p->dbg_atrous_timeline, i == 2 ? "atrous4" : "atrous8", st)) != HR_OK) return s;
     return HR_OK;
 }
 
@@ -912,9 +967,12 @@ static hr_status shadows_atrous01(hr_shadows* p, const hr_frame_inputs* in, cons
     a.power = 0.0f;
     const uint64_t px = (uint64_t)w * (y1 - y0);
     // algorithmic bytes: in 4 + normal/depth 8 + out 4 (+ 4 feedback); the G-buffer side image counts once
+    AtrousTimelineDump tl;
+    if ((s = tl.begin(p->dbg_atrous_timeline, a)) != HR_OK) return s;
     int ev = p->prof.begin("atrous_01", st, px * 16 + ((a.out2 || first2) ? px * 4 : 0));
-    *done = launch_shadows_atrous01_fast(a, first2, prm->filter_iterations == 2 ? prm->power : 0.0f, st);
+    *done = launch_shadows_atrous01_fast(a, first2, prm->filter_iterations == 2 ? prm->power : 0.0f, st, p->atrous01_pad, tl.ptr());
     p->prof.end(ev, st);
+    if ((s = tl.end(p->dbg_atrous_timeline, "atrous01", st)) != HR_OK) return s;
     if (*done) p->read_idx = 0;
     HR_HIP(hipGetLastError());
     return HR_OK;
