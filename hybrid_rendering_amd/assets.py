@@ -5,7 +5,8 @@
 The reference loads meshes through assimp and images through stb_image (external/dwSampleFramework, absent here); these
 are self-contained readers for the subset those assets use: triangulated or polygonal ``f`` records with v / v/vt / v//vn /
 v/vt/vn indices (negative indices allowed), ``usemtl`` + ``mtllib`` (Kd, Pr / Ns, Pm, Ke), ``o`` / ``g`` groups -> mesh ids;
-8-bit non-interlaced PNG of colour type 0, 2, 4 or 6 with all five scanline filters.
+8-bit non-interlaced PNG of colour type 0, 2, 4 or 6 with all five scanline filters; Radiance ``.hdr`` (RGBE, flat or new-style run-length
+scanlines, top-down) -> the fp32 equirectangular image env.Environment.update_equirect takes (common.cpp:597-612 loads its four through stbi_loadf).
 """
 from __future__ import annotations
 
@@ -196,6 +197,134 @@ def load_blue_noise(sobol_png: str, scrambling_ranking_png: str):
     if s.shape[1] < 256 or r.shape[0] < 128 or r.shape[1] < 128:
         raise ValueError("blue-noise tables must be at least 256 wide (sobol) and 128x128 (scrambling/ranking)")
     return np.ascontiguousarray(s[0, :256]), np.ascontiguousarray(r[:128, :128])
+
+
+# ------------------------------------------------------------------------------------------------ Radiance .hdr (RGBE)
+_HDR_MAX = float(255.0 * 2.0 ** 119)      # the largest RGBE value: mantissa 255 at exponent byte 255
+
+
+def decode_hdr(data: bytes, path: str = "<memory>") -> np.ndarray:
+    """float32 [h, w, 4], alpha 1.  Header ``#?RADIANCE`` or ``#?RGBE``, ``FORMAT=32-bit_rle_rgbe``, a blank line, ``-Y h +X w``; every scanline is flat
+    (w RGBE quadruples) or new-style run-length (2, 2, w >> 8, w & 255, then four channel planes of runs; widths 8..32767).  A texel decodes as
+    stbi_loadf does: mantissa * 2^(exponent - 136), exponent byte 0 gives 0.  Anything else raises ValueError naming the file and the offset."""
+    def fail(what, o):
+        raise ValueError(f"{path}: {what} at offset {o}")
+
+    o, lines = 0, []
+    while True:                                          # header lines up to the resolution line, which follows the blank line
+        nl = data.find(b"\n", o)
+        if nl < 0:
+            fail("truncated header", o)
+        line = data[o:nl]
+        lines.append((o, line))
+        o = nl + 1
+        if len(lines) >= 2 and lines[-2][1] == b"":
+            break
+    if lines[0][1] not in (b"#?RADIANCE", b"#?RGBE"):
+        fail("not a Radiance file (no #?RADIANCE / #?RGBE)", 0)
+    formats = [(lo, ln) for lo, ln in lines[1:-2] if ln.startswith(b"FORMAT=")]
+    if not formats or formats[0][1] != b"FORMAT=32-bit_rle_rgbe":
+        fail("unsupported format (FORMAT=32-bit_rle_rgbe only)", formats[0][0] if formats else lines[0][0])
+    ro, res = lines[-1]
+    t = res.split()
+    if len(t) != 4 or t[0] != b"-Y" or t[2] != b"+X" or not t[1].isdigit() or not t[3].isdigit() or int(t[1]) < 1 or int(t[3]) < 1:
+        fail(f"unsupported resolution line {res!r} (-Y h +X w only)", ro)
+    h, w = int(t[1]), int(t[3])
+    buf = np.frombuffer(data, np.uint8)
+    rgbe = np.zeros((h, w, 4), np.uint8)
+    for y in range(h):
+        rle = 8 <= w <= 32767 and o + 4 <= len(data) and data[o] == 2 and data[o + 1] == 2 and not data[o + 2] & 0x80
+        if not rle:
+            if o + 4 * w > len(data):
+                fail(f"truncated flat scanline {y}", len(data))
+            rgbe[y] = buf[o:o + 4 * w].reshape(w, 4)
+            o += 4 * w
+            continue
+        if (data[o + 2] << 8 | data[o + 3]) != w:
+            fail(f"scanline {y} is {data[o + 2] << 8 | data[o + 3]} wide, the image {w}", o)
+        o += 4
+        for c in range(4):
+            x = 0
+            while x < w:
+                if o >= len(data):
+                    fail(f"truncated run-length scanline {y}", o)
+                n = data[o]
+                run = n > 128
+                n = n - 128 if run else n
+                if n == 0 or n > w - x:
+                    fail(f"malformed run of {n} at column {x} of scanline {y}", o)
+                if o + 1 + (1 if run else n) > len(data):
+                    fail(f"truncated run-length scanline {y}", len(data))
+                rgbe[y, x:x + n, c] = data[o + 1] if run else buf[o + 1:o + 1 + n]
+                o += 2 if run else 1 + n
+                x += n
+    e = rgbe[..., 3].astype(np.int32)
+    out = np.ones((h, w, 4), np.float32)
+    out[..., :3] = rgbe[..., :3].astype(np.float32) * np.where(e > 0, np.ldexp(np.float32(1.0), e - 136), np.float32(0.0)).astype(np.float32)[..., None]
+    return out
+
+
+def load_hdr(path: str) -> np.ndarray:
+    """Radiance .hdr -> float32 [h, w, 4] with alpha 1 (decode_hdr)"""
+    return decode_hdr(open(path, "rb").read(), path)
+
+
+def _rle_plane(row: np.ndarray) -> bytes:
+    """one channel of a scanline as runs: 128 + n, value for n = 4..127 equal bytes; n, bytes for up to 128 literals"""
+    out, w, x, lit = bytearray(), len(row), 0, 0           # lit: start of the pending literals
+    b = row.tobytes()
+    while x < w:
+        n = 1
+        while x + n < w and n < 127 and b[x + n] == b[x]:
+            n += 1
+        if n >= 4:
+            while lit < x:
+                k = min(128, x - lit)
+                out.append(k); out += b[lit:lit + k]
+                lit += k
+            out.append(128 + n); out.append(b[x])
+            x += n
+            lit = x
+        else:
+            x += n
+    while lit < w:
+        k = min(128, w - lit)
+        out.append(k); out += b[lit:lit + k]
+        lit += k
+    return bytes(out)
+
+
+def encode_hdr(rgb: np.ndarray, rle: bool = True) -> bytes:
+    """[h, w, >= 3] -> the bytes of a Radiance file.  Per texel the shared exponent is that of the largest channel (mantissas truncate, as Ward's
+    float2rgbe does), so a value that RGBE can represent is written exactly; below 1e-32 a texel is stored as zeros; negative and NaN channels become 0,
+    larger ones the largest RGBE value.  rle: new-style run-length scanlines where the width allows (8..32767), flat otherwise."""
+    a = np.asarray(rgb, np.float32)
+    if a.ndim != 3 or a.shape[2] < 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("save_hdr: rgb must be [h, w, >= 3]")
+    h, w = a.shape[:2]
+    c = np.clip(np.nan_to_num(a[..., :3].astype(np.float64), nan=0.0, posinf=_HDR_MAX), 0.0, _HDR_MAX)
+    v = c.max(-1)
+    _, e = np.frexp(v)
+    on = v >= 1e-32
+    rgbe = np.zeros((h, w, 4), np.uint8)
+    mant = np.floor(c * np.ldexp(1.0, 8 - e)[..., None])
+    rgbe[..., :3] = np.where(on[..., None], np.clip(mant, 0, 255), 0).astype(np.uint8)
+    rgbe[..., 3] = np.where(on, e + 128, 0).astype(np.uint8)
+    out = bytearray(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n" % (h, w))
+    for y in range(h):
+        if rle and 8 <= w <= 32767:
+            out += bytes([2, 2, w >> 8, w & 255])
+            for ch in range(4):
+                out += _rle_plane(np.ascontiguousarray(rgbe[y, :, ch]))
+        else:
+            out += rgbe[y].tobytes()
+    return bytes(out)
+
+
+def save_hdr(path: str, rgb: np.ndarray, rle: bool = True) -> None:
+    """write [h, w, >= 3] as a Radiance .hdr (encode_hdr)"""
+    with open(path, "wb") as f:
+        f.write(encode_hdr(rgb, rle))
 
 
 # ------------------------------------------------------------------------------------------------ glTF 2.0

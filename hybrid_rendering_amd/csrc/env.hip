@@ -2,9 +2,7 @@
 // dw::CubemapSHProjection, dw::CubemapPrefiler (re-run whenever the sun moves, main.cpp:975-990) and dw::BRDFIntegrateLUT (once,
 // common.cpp:307).  The framework's shaders are not part of the reference tree, so the arithmetic is specified in include/hr_env.h
 //  and restated in float32 numpy by tests/env_reference.py; every kernel below follows that text operation by operation.
-#include "hr_internal.h"
-#include "shading.h"
-#include "../../include/hr_env.h"
+#include "env_internal.h"
 #include <cmath>
 #include <new>
 
@@ -13,22 +11,6 @@ using namespace hr;
 namespace {
 
 constexpr int kMaxSkySize = 2048, kMaxLut = 512, kMaxSamples = 4096;
-
-// hr_env.h "Texel direction": the inverse of CubeMap::fetch, unnormalised
-HR_DEV f3 texel_dir(int face, int x, int y, int s)
-{
-    const float u = 2.0f * __fdiv_rn((float)x + 0.5f, (float)s) - 1.0f;
-    const float v = 2.0f * __fdiv_rn((float)y + 0.5f, (float)s) - 1.0f;
-    switch (face)
-    {
-    case 0: return mk3(1.0f, -v, -u);
-    case 1: return mk3(-1.0f, -v, u);
-    case 2: return mk3(u, 1.0f, v);
-    case 3: return mk3(u, -1.0f, -v);
-    case 4: return mk3(u, -v, 1.0f);
-    default: return mk3(-u, -v, -1.0f);
-    }
-}
 
 // hr_env.h "GGX half vector", in the tangent frame of the normal
 HR_DEV f3 ggx_half(float r, float4 row)
@@ -246,14 +228,23 @@ void sample_table(int n, float* out)
 
 } // namespace
 
-struct hr_env
+// what every update enqueues behind its write of the sky (hr_env_update's copy, env_sources.hip's two kernels)
+hr_status hr::env_enqueue_derived(hr_env* e, hipStream_t st)
 {
-    hr_ctx*     ctx = nullptr;
-    hr_env_desc d;
-    size_t      chain_texels = 0;
-    DevBuf      sky, chain, lut, sh9, sh_rows, table, ht;
-    StageProfiler prof;
-};
+    const int S = e->d.sky_size, P = e->d.prefiltered_size, levels = e->d.prefiltered_levels, n = e->d.n_samples;
+    const CubeMap sky { (const uint2*)e->sky.p, S };
+    int ev = e->prof.begin("env_sh9", st, e->sky.bytes);
+    hipLaunchKernelGGL(k_env_sh_rows, dim3(cdiv(6 * S, 4)), dim3(256), 0, st, sky, (float*)e->sh_rows.p);
+    hipLaunchKernelGGL(k_env_sh_final, dim3(1), dim3(64), 0, st, (const float*)e->sh_rows.p, 6 * S, (float*)e->sh9.p);
+    e->prof.end(ev, st);
+    ev = e->prof.begin("env_prefilter", st, e->sky.bytes + e->chain.bytes);
+    hipLaunchKernelGGL(k_env_level0, dim3((unsigned)(((size_t)6 * P * P + 255) / 256)), dim3(256), 0, st, sky, P, (uint2*)e->chain.p);
+    const size_t waves = e->chain_texels - (size_t)6 * P * P;
+    if (waves) hipLaunchKernelGGL(k_env_prefilter, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, sky, P, levels, n, (const float4*)e->ht.p, (uint2*)e->chain.p);
+    e->prof.end(ev, st);
+    HR_HIP(hipGetLastError());
+    return HR_OK;
+}
 
 extern "C" {
 
@@ -327,21 +318,9 @@ hr_status hr_env_update(hr_env* e, const void* sky_device, void* stream)
     HR_CHECK_ARG(e && sky_device);
     HR_HIP(hipSetDevice(e->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const int S = e->d.sky_size, P = e->d.prefiltered_size, levels = e->d.prefiltered_levels, n = e->d.n_samples;
     e->prof.begin_frame();
     HR_HIP(hipMemcpyAsync(e->sky.p, sky_device, e->sky.bytes, hipMemcpyDeviceToDevice, st));
-    const CubeMap sky { (const uint2*)e->sky.p, S };
-    int ev = e->prof.begin("env_sh9", st, e->sky.bytes);
-    hipLaunchKernelGGL(k_env_sh_rows, dim3(cdiv(6 * S, 4)), dim3(256), 0, st, sky, (float*)e->sh_rows.p);
-    hipLaunchKernelGGL(k_env_sh_final, dim3(1), dim3(64), 0, st, (const float*)e->sh_rows.p, 6 * S, (float*)e->sh9.p);
-    e->prof.end(ev, st);
-    ev = e->prof.begin("env_prefilter", st, e->sky.bytes + e->chain.bytes);
-    hipLaunchKernelGGL(k_env_level0, dim3((unsigned)(((size_t)6 * P * P + 255) / 256)), dim3(256), 0, st, sky, P, (uint2*)e->chain.p);
-    const size_t waves = e->chain_texels - (size_t)6 * P * P;
-    if (waves) hipLaunchKernelGGL(k_env_prefilter, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, sky, P, levels, n, (const float4*)e->ht.p, (uint2*)e->chain.p);
-    e->prof.end(ev, st);
-    HR_HIP(hipGetLastError());
-    return HR_OK;
+    return env_enqueue_derived(e, st);
 }
 
 hr_status hr_env_get(const hr_env* e, hr_environment* out)

@@ -69,6 +69,16 @@ class Environment(api._Pass):
         assert tuple(sky.shape) == (6, S, S, 4) and sky.element_size() == 2 and sky.is_contiguous() and sky.is_cuda, "sky: cuda fp16 [6,S,S,4]"
         _check(lib().hr_env_update(self.h, C.c_void_p(sky.data_ptr()), _stream_ptr(stream)), "hr_env_update")
 
+    def update_equirect(self, image, stream=None):
+        """hr_env_update_equirect (include/hr_env_sources.h): the sky from an equirectangular cuda float32 tensor [h,w,4], e.g. assets.load_hdr's"""
+        from . import env_sources
+        env_sources.update_equirect(self.h, image, stream)
+
+    def update_sky(self, stream=None, **params):
+        """hr_env_update_sky: the analytic sky; sun_dir, turbidity, scale, ground_albedo, each defaulting to hr_sky_default_params'"""
+        from . import env_sources
+        env_sources.update_sky(self.h, stream, **params)
+
     def get(self) -> hr_environment:
         e = hr_environment()
         _check(lib().hr_env_get(self.h, C.byref(e)), "hr_env_get")

@@ -4,13 +4,14 @@
 //   reference (main.cpp:975-990, a frame in which the sun moved)     this header
 //   ---------------------------------------------------------------  ---------------------------------------------------------------
 //   hosek_wilkie_sky_model->update(cmd_buf, sun_dir)                 the application renders its sky into a device buffer
+//                                                                    ... or env.update_sky(cmd_buf, params) / env.update_equirect(cmd_buf, ...)
 //   cubemap_sh_projection->update(cmd_buf)                           env.update(cmd_buf, sky)      (both, and the copy of the sky)
 //   cubemap_prefilter->update(cmd_buf)
 //   write_descriptor_sets(...)                                       nothing: the pointers env.get() hands out never change
 //
 // common.environment = &env.get() once; deferred.bind(env) once (or env.bind_sh9(deferred.handle())).
 #pragma once
-#include "../hr_env.h"
+#include "../hr_env_sources.h"
 #include "passes.hpp"
 
 namespace hr {
@@ -37,6 +38,10 @@ public:
 
     // sky: device [6][sky_size][sky_size] RGBA16F.  Enqueues the copy and the SH9 / prefilter launches on cmd_buf; no host work
     void update(Stream cmd_buf, const void* sky) { check(hr_env_update(m_env, sky, cmd_buf), "Environment::update"); }
+    // hr_env_sources.h: the sky from an equirectangular map, device [h][w][4] fp32 (the first call on an env allocates and must not be captured),
+    // or from the analytic model; then the same launches as update.  The parameters are read by the call: a captured update_sky replays them
+    void update_equirect(Stream cmd_buf, const float* equirect, int32_t w, int32_t h) { check(hr_env_update_equirect(m_env, equirect, w, h, cmd_buf), "Environment::update_equirect"); }
+    void update_sky(Stream cmd_buf, const hr_sky_params& params) { check(hr_env_update_sky(m_env, &params, cmd_buf), "Environment::update_sky"); }
     // what Frame::environment / CommonResources::environment point to; valid for the life of this object
     const hr_environment& get() const { return m_environment; }
     const float*          sh9_device() const { return m_sh9; }

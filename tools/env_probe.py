@@ -3,7 +3,10 @@ LUT (env_brdf_lut, integrated by hr_env_create) at hr_env_default_desc's sizes, 
 synth_env.sh9_from_cubemap + prefiltered_chain + brdf_lut in numpy, plus the upload of their results.  The two paths do not compute the same
 thing (the host stand-ins are a box-filter chain and an analytic LUT fit): the comparison is of what a frame with a moving sun pays either way.
 
-    python tools/env_probe.py [--sky 128 --prefiltered 128 --levels 5 --lut 128 --samples 1024] [--updates 50] [--host-rounds 3]
+The two sources of the sky (include/hr_env_sources.h) are timed the same way: hr_env_update_equirect over a --map W H fp32 map (stage env_equirect)
+and hr_env_update_sky (stage env_sky), each in front of the same env_sh9 / env_prefilter; --no-sources leaves them out (a library from before them).
+
+    python tools/env_probe.py [--sky 128 --prefiltered 128 --levels 5 --lut 128 --samples 1024] [--updates 50] [--host-rounds 3] [--map 2048 1024]
 
 One JSON line."""
 import argparse
@@ -28,6 +31,8 @@ def main():
     ap.add_argument("--samples", type=int, default=d.n_samples)
     ap.add_argument("--updates", type=int, default=50)
     ap.add_argument("--host-rounds", type=int, default=3)
+    ap.add_argument("--map", type=int, nargs=2, default=(2048, 1024), metavar=("W", "H"), help="size of the equirectangular map of the env_equirect stage")
+    ap.add_argument("--no-sources", action="store_true", help="time hr_env_update alone")
     args = ap.parse_args()
     ctx = hr.Context(0)
     sky = synth_env.sky_cubemap(size=args.sky)
@@ -47,6 +52,26 @@ def main():
     wall_ms = (time.perf_counter() - t0) * 1e3 / args.updates       # with the profiler's events in the stream: an upper bound
     stages.update({name: ms for name, ms, _ in E.stage_times()})
     E.set_profiling(False)
+    sources = {}
+    if not args.no_sources:
+        import numpy as np
+        w, h = args.map
+        rng = np.random.RandomState(1)
+        image = torch.from_numpy(np.concatenate([rng.uniform(0.0, 4.0, (h, w, 3)).astype(np.float32), np.ones((h, w, 1), np.float32)], -1)).cuda()
+        for name, call in (("equirect", lambda: E.update_equirect(image)), ("sky", lambda: E.update_sky())):
+            for _ in range(3):      # the first equirect call builds and uploads the table
+                call()
+            torch.cuda.synchronize()
+            E.set_profiling(True)
+            t0 = time.perf_counter()
+            for _ in range(args.updates):
+                call()
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e6 / args.updates
+            st = {k: round(ms * 1e3, 2) for k, ms, _ in E.stage_times()}
+            E.set_profiling(False)
+            sources[name] = dict(device_us=st, update_wall_us=round(wall, 1))
+        sources["map"] = [w, h]
     host = []
     for _ in range(args.host_rounds):
         t0 = time.perf_counter()
@@ -63,7 +88,7 @@ def main():
     best = min(host, key=lambda p: p[0] + p[1])
     print(json.dumps(dict(sky=args.sky, prefiltered=args.prefiltered, levels=args.levels, lut=args.lut, samples=args.samples, updates=args.updates,
                           device_us={k: round(v * 1e3, 2) for k, v in sorted(stages.items())}, update_wall_us=round(wall_ms * 1e3, 1), create_ms=round(create_ms, 2),
-                          host_update_ms=dict(compute=round(best[0], 2), upload=round(best[1], 3)), host_lut_ms=round(host_lut_ms, 2))))
+                          host_update_ms=dict(compute=round(best[0], 2), upload=round(best[1], 3)), host_lut_ms=round(host_lut_ms, 2), sources=sources)))
     E.close()
 
 

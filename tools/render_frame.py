@@ -1,6 +1,8 @@
 """Renders N frames of the whole pass chain (shadows, AO half-res, DDGI, reflections half-res, deferred composite, TAA, tone
 map) of the procedural Sponza-like bench scene on one GPU and writes the last one as a PNG — a look at what the numbers in
 bench.py are numbers of.   python tools/render_frame.py [--width 960 --height 540 --frames 24 --out gpurun_out/frame.png]"""
+# --hdr FILE lights the frame with a Radiance .hdr map, --sky with the analytic sky under the scene's sun: either goes through hr_env on the GPU
+# (the sky, SH9, the prefiltered chain and the BRDF LUT); without them the environment is synth_env's host-made gradient.
 import argparse, os, struct, sys, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +23,9 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--textured", action="store_true")
+    src = ap.add_mutually_exclusive_group()
+    src.add_argument("--hdr", metavar="FILE", help="a Radiance .hdr equirectangular map as the environment (hr_env_update_equirect)")
+    src.add_argument("--sky", action="store_true", help="the analytic sky, its sun along the scene's light (hr_env_update_sky)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame.png"))
     a = ap.parse_args()
     import torch
@@ -38,12 +43,25 @@ def main():
     ddgi_u = synth_env.ddgi_uniforms(lo, hi, probe_counts=(16, 8, 16), rays_per_probe=256, normal_bias=0.1)
     sky = synth_env.sky_cubemap(32)
     f16 = lambda x: torch.from_numpy(x).cuda().view(torch.float16)
-    env = api_gi.environment(f16(sky), f16(synth_env.prefiltered_chain(sky, 5)), 32, 5, f16(synth_env.brdf_lut(32)))
+    E = None
+    if a.hdr or a.sky:
+        from hybrid_rendering_amd import assets, env as envmod
+        E = envmod.Environment(ctx)
+        if a.hdr:
+            E.update_equirect(torch.from_numpy(assets.load_hdr(a.hdr)).cuda())
+        else:
+            E.update_sky(sun_dir=[float(v) for v in light[0:3]])      # data0.xyz: the direction TO the light
+        env = E.get()
+    else:
+        env = api_gi.environment(f16(sky), f16(synth_env.prefiltered_chain(sky, 5)), 32, 5, f16(synth_env.brdf_lut(32)))
     zbp = synth.z_buffer_params()
     sh, ao = hr.RayTracedShadows(ctx, W, H), hr.RayTracedAO(ctx, W, H, hr.SCALE_HALF_RES)
     gi, rf = api_gi.DDGI(ctx, W, H, ddgi_u), api_reflections.RayTracedReflections(ctx, W, H, hr.SCALE_HALF_RES)
     df, taa = api_deferred.DeferredShading(ctx, W, H), api_post.TemporalAA(ctx, W, H)
-    df.set_sh9(synth_env.sh9_from_cubemap(sky))
+    if E is not None:
+        envmod.bind_sh9(df, E.sh9_device())
+    else:
+        df.set_sh9(synth_env.sh9_from_cubemap(sky))
     df.params.use_ray_traced_shadows = df.params.use_ray_traced_ao = df.params.use_ray_traced_reflections = df.params.use_ddgi = 1
     taa.params.reset = 0
     rng = np.random.RandomState(1)
