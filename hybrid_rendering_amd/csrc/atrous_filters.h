@@ -1,6 +1,6 @@
 // The edge-stopping filters of the tolerance-mode denoisers: the shadows' SVGF a-trous body, the AO blur's 1-D pass and staging step, and
 // the tables, EdgeK set-up and colour helpers that the reflections' a-trous kernels share with them.
-// Included by denoise_fast.hip AFTER its `#pragma clang fp contract(fast)` and after exact_predicates.h (the pragma is part of what
+// Included by denoise_fast_common.h AFTER its `#pragma clang fp contract(fast)` and after exact_predicates.h (the pragma is part of what
 // these bodies compute; the parity helpers fm::*_rn keep their own roundings).
 //
 // A filter body is written over a TEXEL SOURCE: an object that yields, for an offset from the centre in units of the tap distance,
@@ -138,8 +138,9 @@ HR_DEV uint32_t shadows_filter(const Src& s, Edge edge, float phi_visibility, fl
     return BRANCH ? r : (cnz.z < 0.0f ? c : r);
 }
 
-// "fetch, decode, zero if not resident" of one texel of a staged tile (resident: inside the image and rows ry0 .. ry1), in its three steps:
-// where (a texel that is not resident is fetched at the first resident texel), fetch, decode and select
+// "fetch, decode, zero if not resident" of one texel of a staged tile (resident: inside the image and rows ry0 .. ry1), in its steps:
+// where (a texel that is not resident is fetched at the first resident texel), then — after the fetch, which ShadowsStageBatch issues for a
+// whole batch — decode and select
 HR_DEV bool shadows_stage_where(const AtrousArgs& a, int gx, int gy, int ry0, int ry1, uint32_t& so)
 {
     const bool res = gx >= 0 && gx < a.w && gy >= ry0 && gy < ry1;
@@ -155,14 +156,6 @@ HR_DEV void shadows_stage_decode(bool res, uint32_t v, uint2 nd, uint32_t& s_in,
     const f3 n = fm::oct_unit(nd.x);
     s_in = res ? v : 0u;
     s_nz = res ? make_float4(n.x, n.y, n.z, fm::hi(nd.y)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-HR_DEV void shadows_stage_texel(const AtrousArgs& a, int gx, int gy, int ry0, int ry1, uint32_t& s_in, float4& s_nz)
-{
-    uint32_t       so;
-    const bool     res = shadows_stage_where(a, gx, gy, ry0, ry1, so);
-    const uint32_t v   = fm::ld<uint32_t>(a.in.p, so * 4u);
-    const uint2    nd  = fm::ld<uint2>(a.nd, so * 8u);
-    shadows_stage_decode(res, v, nd, s_in, s_nz);
 }
 
 // A staged tile of N texels, row length TW, fetched by 256 threads in ONE batch: load() requests every texel of this thread — ROUNDS of

@@ -23,7 +23,7 @@ namespace exact {
 // (n . n')^2 > 0.1 — a history tap is in or out, an fp32 ulp decides on the knife edge (one pixel in ~50 M in the shadow pass; the history
 // is then re-weighted over other texels).  The tolerance-mode temporal kernels of the shadow and AO passes keep their fast test, note taps
 // inside a guard band around either threshold and, for the (rare) wave that has one, ask THIS function and run the pixel again with its
-// verdicts (denoise_fast.hip Reproj::exact_bits).  (x, y): the pixel; depth / c2x / c2y: its depth and the two words of its GB2 texel as the
+// verdicts (denoise_fast_common.h Reproj::exact_bits).  (x, y): the pixel; depth / c2x / c2y: its depth and the two words of its GB2 texel as the
 // kernel uses them (edge threads: zeros); q2x / q3y / d: the tap's normal word, mesh-id word and depth (out-of-image taps: zeros).
 HR_DEV bool tap_valid(const float* __restrict__ M, int x, int y, int w, int h, float depth, uint32_t c2x, uint32_t c2y, float cur_id, int hcx, int hcy,
                       uint32_t q2x, uint32_t q3y, float d)

@@ -1,4 +1,4 @@
-// Tolerance-mode arithmetic (hr_*_params.exact == 0) — include ONLY from denoise_fast.hip.
+// Tolerance-mode arithmetic (hr_*_params.exact == 0) — include ONLY from denoise_fast_common.h (the denoise_fast_*.hip units).
 //
 // The exact kernels pin every GLSL built-in to one correctly rounded fp32 definition so that all stage images can be compared
 // bit for bit with the oracle.  That contract costs 10-20 VALU instructions per division / square root / exp

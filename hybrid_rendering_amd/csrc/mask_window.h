@@ -1,5 +1,5 @@
 // 17x17 box sums over the packed 8x4 visibility masks of the trace kernels — integer work shared by both arithmetic modes
-// (k_ao_temporal in ao.hip, kf_shadows_temporal / kf_ao_temporal in denoise_fast.hip): the counts are exact either way.
+// (k_ao_temporal in ao.hip, kf_shadows_temporal in denoise_fast_shadows.hip, kf_ao_temporal in denoise_fast_ao.hip): the counts are exact either way.
 #pragma once
 #include "device_math.h"
 

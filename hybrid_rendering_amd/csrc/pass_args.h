@@ -1,5 +1,5 @@
 // Kernel argument blocks of the denoise / resolve stages, shared by the exact kernels (shadows.hip, ao.hip, reflections.hip,
-// ddgi.hip) and their tolerance-mode counterparts (denoise_fast.hip): both read the same images and write the same outputs.
+// ddgi.hip) and their tolerance-mode counterparts (denoise_fast_*.hip): both read the same images and write the same outputs.
 #pragma once
 #include "reproject.h"
 #include "shading.h"
@@ -162,7 +162,7 @@ struct DDGISampleArgs
     float        gi_intensity;
 };
 
-// ---- tolerance-mode ("fast") launchers, denoise_fast.hip ----------------------------------------------------------------
+// ---- tolerance-mode ("fast") launchers, denoise_fast_{shadows,ao,reflections,resolve}.hip ---------------------------------
 // hr_*_params.exact == 0 selects them: same inputs, same outputs, same tile classification rule; fp32 arithmetic through the
 // hardware's v_rcp / v_rsq / v_sqrt / v_exp / v_log, contracted FMAs and re-associated sums.  The visibility
 // masks never pass through them (the trace kernels have one mode).

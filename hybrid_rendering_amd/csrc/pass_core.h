@@ -108,7 +108,7 @@ struct GeoRecords
 };
 
 // ------------------------------------------------------------------------------------------------ residency cap
-// kf_shadows_atrous01 (denoise_fast.hip): how many bytes of unused dynamic LDS a launch asks for so that a CU holds at most R of its
+// kf_shadows_atrous01 (denoise_fast_shadows.hip): how many bytes of unused dynamic LDS a launch asks for so that a CU holds at most R of its
 // workgroups.  The live workgroups of a launch (30 % at the 1080p bench frame; the others leave after a scalar vote) have all started
 // within its first 5 us, 2 to 8 of them to a CU, and the launch lasts as long as the CU that was dealt the most (measured: tools/
 // atrous_balance.py, docs/EXPERIMENTS.md "live workgroups per CU"): the pad bounds how many a CU runs at a time.  static + pad = the largest size, a multiple of the allocation granule, of which R fit into a CU's LDS (if the

@@ -1,4 +1,4 @@
-// Self-test sweeps of the device arithmetic (hr_selftest_math_sweep in api.hip, hr_selftest_fast_math in denoise_fast.hip).
+// Self-test sweeps of the device arithmetic (hr_selftest_math_sweep in api.hip, hr_selftest_fast_math in denoise_fast_resolve.hip).
 //
 // An element's inputs v[0..7] come either from an array ([n][8] floats, gen 0) or from its index j = first + i, so that sweeps over all
 // 2^32 fp32 patterns never move inputs across the bus; the CPU mirror of the tests regenerates the same inputs on the host.  Outputs are planar:

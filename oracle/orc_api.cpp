@@ -326,7 +326,7 @@ mat4 to_mat4(const float* m)
     return r;
 }
 
-// tu 0: device_math.h (api.hip), every mode has a definition here.  tu 1: denoise_fast.hip; modes 0-2 and 4 are the hardware's
+// tu 0: device_math.h (api.hip), every mode has a definition here.  tu 1: denoise_fast_resolve.hip; modes 0-2 and 4 are the hardware's
 // approximations (rcp, rsq, exp, log, oct_unit): their accuracy is measured against float64 by the tests, they have no oracle here.
 bool eval(int tu, int which, const float v[8], const SelftestParams& P, float r[MAX_OUT])
 {

@@ -1,5 +1,5 @@
 """Adversarial G-buffers for the history reprojection (numpy only: no GPU, no oracle) — the counterpart of ray_cases.py for
-reprojection.glsl:115-328 (csrc/reproject.h, Reproj<> in csrc/denoise_fast.hip, oracle/orc_reproject.h).
+reprojection.glsl:115-328 (csrc/reproject.h, Reproj<> in csrc/denoise_fast_common.h, oracle/orc_reproject.h).
 
 craft(gb_h, gb_c, ubo_c) takes two consecutive rendered G-buffers (dicts gb1 / gb2 / gb3 / depth as oracle.Scene.gbuffer returns them) and the
 current frame's UBO and returns rewritten copies (H, C) and an `info` dict.  Frame H is the history side — the caller passes it UNCHANGED as frame

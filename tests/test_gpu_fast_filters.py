@@ -1,7 +1,7 @@
 """The bits of the tolerance-mode (exact = 0) denoise chains, pinned: SHA-256 digests of every stage image in tests/golden/fast_filters.json.
 
 tests/test_gpu_golden.py pins the parity mode only; this module pins what bench.py times.  The digests were recorded from the library
-as it stood BEFORE the filters of csrc/denoise_fast.hip were moved into shared bodies (csrc/atrous_filters.h), so the module is the proof
+as it stood BEFORE the filters of csrc/denoise_fast_*.hip (then one file) were moved into shared bodies (csrc/atrous_filters.h), so the module is the proof
 that the move changed no bit.  Tolerance-mode arithmetic is ALLOWED to change later: a pull request that changes it on purpose re-records the
 fixture (`python tests/test_gpu_fast_filters.py --record`, on the GPU) and says so in its description.  HR_LIBRARY selects the library.
 
@@ -22,7 +22,6 @@ Kernel instantiations of the product library's launch_*_fast, and the case that 
   kf_shadows_atrous<4 | 8, false>       shadows/fused_phi12_iter5, unfused_phi12
   kf_shadows_atrous<0, true>            shadows/iter5 (tap distance 16, radius 1), radius2 (every iteration)
   kf_shadows_atrous<0, false>           shadows/fused_phi12_iter5 (tap distance 16), radius2_phi12
-  (kf_shadows_atrous<1 | 2, *> exist only in a -DFT_ATROUS_LDS=0 build)
   kf_ao_temporal<false, 0 | 2>          ao/fused, unfused: frame 0 | frames 1, 2
   kf_ao_temporal<true, 0 | 2>           ao/radius6_spp2, half_radius2_spp2
   kf_ao_temporal<false | true, 1>       ao/band | ao/unfused_band_spp2 (frames 1, 2)

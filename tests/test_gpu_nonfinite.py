@@ -150,7 +150,7 @@ def _check(got, ref, what, exact, **rule):
 
 @pytest.mark.parametrize("exact,stages", [(1, "all"), (0, "trace_temporal"),
                                           pytest.param(0, "atrous", marks=pytest.mark.xfail(strict=True, reason=
-                                              "known: the tolerance-mode a-trous kernels (denoise_fast.hip) take max(variance, 0) with the IEEE "
+                                              "known: the tolerance-mode a-trous kernels (denoise_fast_reflections.hip) take max(variance, 0) with the IEEE "
                                               "v_max, which drops a NaN variance that the reference keeps (841 texels of channel 3); open"))])
 def test_reflections_tolerance_mode_on_nan_hits(oracle, hr, ctx, exact, stages):
     """the reflections pass in both modes on the NaN hit colours of test_reflections_on_inf_irradiance_and_metallic_hits: the trace image

@@ -1,5 +1,5 @@
 """Tolerance mode (hr_*_params.exact = 0: hardware rcp / rsq / sqrt / exp / log, fused multiply-adds, re-associated sums —
-csrc/denoise_fast.hip) against the CPU oracle.  THE CONTRACT these runners enforce is stated once, clause by clause, in docs/TOLERANCE.md
+csrc/denoise_fast_*.hip) against the CPU oracle.  THE CONTRACT these runners enforce is stated once, clause by clause, in docs/TOLERANCE.md
 (north_star "AO / reflections / GI within a stated fp32 tolerance"): masks, ray counts, DDGI atlases and the reflections'
 trace image bit-exact; every other fp16 image <= 2 fp16 ulp (or 2^-20 absolute) on >= 99.9 % of the texels, relative L2 <= 1e-3 (<= 1e-2 over all texels), a hard
 cap of 32 ulp / 2^-10 per texel outside flipped-tile neighbourhoods, one bounded allowance for the reflections' denoised images, tile classes

@@ -141,7 +141,7 @@ def test_det_sincos_quadrant_beyond_int_range(po):
 
 
 def test_fast_parity_modes_exist_and_approximations_do_not(po):
-    """tu 1 (denoise_fast.hip): the parity helpers have a definition in the mirror; the hardware approximations (rcp, rsq, exp, log, pow,
+    """tu 1 (denoise_fast_resolve.hip): the parity helpers have a definition in the mirror; the hardware approximations (rcp, rsq, exp, log, pow,
     oct_unit) deliberately have none (their accuracy is measured against float64)"""
     inp = _inputs(np.ones(4, F32), np.ones(4, F32), np.ones(4, F32), np.ones(4, F32), np.ones(4, F32), np.ones(4, F32), np.ones(4, F32))
     p = po.selftest_params(m=np.eye(4), m2=np.eye(4), w=64, h=64)

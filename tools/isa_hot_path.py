@@ -6,7 +6,7 @@ leaves out the cold copy's entry block: the fall-through block behind the condit
 (where the centre texels are loaded again).  What it reaches is the first run — every block a wave can execute without running twice,
 both sides of divergent branches included — plus the riders in front of it, which are the same in every instantiation.
 
-    python tools/isa_hot_path.py [hybrid_rendering_amd/csrc/denoise_fast.hip] [kernel-name-filter]
+    python tools/isa_hot_path.py [hybrid_rendering_amd/csrc/denoise_fast_shadows.hip] [kernel-name-filter]
 """
 import os, re, subprocess, sys, tempfile
 
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from hybrid_rendering_amd import build as hb
 
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "hybrid_rendering_amd", "csrc", "denoise_fast.hip")
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "hybrid_rendering_amd", "csrc", "denoise_fast_shadows.hip")
 flt = sys.argv[2] if len(sys.argv) > 2 else "kf_shadows_temporal"
 
 if src.endswith(".s"):

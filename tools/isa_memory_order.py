@@ -1,8 +1,8 @@
 """The order of a kernel's global reads (no GPU needed): every global_load, every s_waitcnt that waits on vmcnt, every s_barrier and every
 loop (as the compiler marks its basic blocks) of the gfx950 assembly hipcc emits, in program order.
 Dependent round trips show as load(s) -> wait -> load(s); a load inside `loop { ... }` is paid once per trip of that loop.
-    python tools/isa_memory_order.py hybrid_rendering_amd/csrc/denoise_fast.hip 'kf_shadows_atrous01<16, true>'
-HR_CFLAGS adds compiler flags, as in the build (e.g. HR_CFLAGS=-DFT_ATROUS01_BATCH=0 for the form a switch keeps)."""
+    python tools/isa_memory_order.py hybrid_rendering_amd/csrc/denoise_fast_shadows.hip 'kf_shadows_atrous01<16, true>'
+HR_CFLAGS adds compiler flags, as in the build (e.g. HR_CFLAGS=-DFT_ATROUS01_TH=8 for another value of a knob)."""
 import os, re, subprocess, sys, tempfile
 
 src = sys.argv[1]

@@ -1,7 +1,8 @@
 """Static per-kernel ISA statistics of one HIP source (no GPU needed): registers, LDS, scratch and instruction mix from the
 gfx950 assembly hipcc emits.  The denoise kernels are VALU-bound, so the static VALU count along the hot path is the offline
-proxy for their run time.   python tools/isa_stats.py hybrid_rendering_amd/csrc/denoise_fast.hip [kernel-name-filter]"""
-import os, re, subprocess, sys, tempfile
+proxy for their run time; `isa` is a short hash of the kernel's instruction text (comments and the function's number in local labels
+removed), so two builds of a kernel can be compared.   python tools/isa_stats.py hybrid_rendering_amd/csrc/denoise_fast_shadows.hip [kernel-name-filter]"""
+import hashlib, os, re, subprocess, sys, tempfile
 
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
@@ -30,5 +31,8 @@ for blk in kernels:
     trans = cnt(r"v_(rcp|rsq|sqrt|exp|log|sin|cos)_")
     short = re.sub(r"\(anonymous namespace\)::", "", name)
     short = re.sub(r"^void ", "", short).split("(")[0]
-    print(f"{short[-48:]:48s} vgpr {g('amdhsa_next_free_vgpr'):>3} sgpr {g('amdhsa_next_free_sgpr'):>3} lds {g('amdhsa_group_segment_fixed_size'):>6} "
+    # the instruction text without comments and without the function's number in local labels (.LBB<fn>_<block>): equal hashes = same assembly
+    code = [re.sub(r"\.L([A-Za-z_]+)\d+_", r".L\1_", l.split(";")[0].strip()) for l in body.splitlines()]
+    isa = hashlib.sha1("\n".join(l for l in code if l and (not l.startswith(".") or l.startswith(".L") and l.endswith(":"))).encode()).hexdigest()[:10]
+    print(f"{short[-48:]:48s} isa {isa} vgpr {g('amdhsa_next_free_vgpr'):>3} sgpr {g('amdhsa_next_free_sgpr'):>3} lds {g('amdhsa_group_segment_fixed_size'):>6} "
           f"scratch {g('amdhsa_private_segment_fixed_size'):>4} | valu {cnt(r'v_'):5d} (trans {trans:3d}) salu {cnt(r's_'):5d} vmem {cnt(r'(global|buffer|flat|scratch)_'):4d} lds {cnt(r'ds_'):4d}")
