@@ -13,6 +13,7 @@
 // get tighter.  Deterministic: no RNG, and the subtrees that are built on several threads (step 1) are merged in left-right order, so
 // the tree does not depend on the number of threads (HR_BVH_THREADS) or on scheduling.
 #include "bvh.h"
+#include "instance_math.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -686,8 +687,7 @@ void build_bvh8(const float* positions, int n_tris, BuiltBVH& out, bool spatial)
         diag = std::sqrt(dx * dx + dy * dy + dz * dz);
         // Boxes are padded well above the fp32 error of the triangle test so that box culling can
         // never reject a triangle the test would accept.
-        out.pad = (float)(3e-5 * diag);
-        if (!(out.pad > 0.0f)) out.pad = 1e-6f;
+        out.pad = imath::leaf_pad(out.lo, out.hi);   // 3e-5 x diag, at least a few float steps of the largest coordinate
     }
     if (n_tris == 0)
     {

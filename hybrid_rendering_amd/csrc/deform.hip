@@ -8,8 +8,15 @@
 // (the launch shape of instances.hip), no bounds given and the root box it publishes ignored.  hr_scene_refit_cost is that mesh's cost.
 // A refit never changes which triangles share a leaf, so a query's ANSWER is the one a fresh build over the same vertices gives (any-hit is a
 // function of the triangle set, closest hit is the smallest t with ties to the smallest triangle index); only the boxes' quality decays.
+// That holds for hostile vertices too (tests/test_gpu_deform_edges.py): a triangle with a NaN or infinite coordinate gets no box, as the builder
+// gives it no reference — it is never hit, its leaf keeps the other triangles' bounds, a leaf or node with nothing finite in it is stored inverted
+// and stays out of its parent's box (refit.h) — and comes back with its next finite vertices; and the leaf pad is the builder's rule applied to the
+// CURRENT exact bounds of the finite triangles (instance_math.h leaf_pad, from k_deform_bounds on the same stream: no host synchronisation), so a
+// scene created from a placeholder, inflated, collapsed or drifted away is padded for the size and place it has now.
+// A triangle that was not finite when the scene was BUILT (created or rebuilt) has no reference to update: it stays out until the next rebuild.
 // hr_scene_rebuild is the slow way back: vertices read back, host build, upload.  Nothing calls it automatically.
 #include "deform_refit.h"
+#include "instance_math.h"
 #include "scene_create.h"
 #include <algorithm>
 #include <cmath>
@@ -142,6 +149,8 @@ hr_status hr::deformable_scene_refresh_bounds(const hr_scene* scene)
         s->info.bounds_lo[k] = any ? ordered_float(bits[k]) : 0.0f;
         s->info.bounds_hi[k] = any ? ordered_float(bits[3 + k]) : 0.0f;
     }
+    // the pad the last refit used: the builder's for these bounds (refit.h refit_pad)
+    s->info.box_pad = imath::leaf_pad(s->info.bounds_lo, s->info.bounds_hi);
     s->bounds_stale = false;
     return HR_OK;
 }

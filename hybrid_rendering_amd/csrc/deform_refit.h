@@ -15,7 +15,7 @@ struct DeformMesh
     uint32_t        ref_base;       // its first reference in the scene's `tris`
     uint32_t        tri_base;       // its first triangle in the attribute arrays the scatter writes
     int32_t         n_tris;
-    float           pad;            // the leaf pad its builder used
+    float           pad;            // the leaf pad its builder used (not read: a refit derives the pad from the mesh's current bounds)
     bool            flag;           // may be updated
     int             narrow;         // levels of at most this many nodes, from the root down to the first wider one, stay in the mesh's own workgroup
 };

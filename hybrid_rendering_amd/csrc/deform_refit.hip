@@ -1,11 +1,15 @@
 // The refit of split-free trees under new vertices: the engine of hr_scene_update_vertices (deform.hip: a flat scene is ONE flagged mesh with root 0)
 // and hr_scene_update_meshes (instances_shared_deform.hip: the flagged meshes of a shared instanced scene).  A flagged mesh is built without
-// spatial splits, so every finite triangle has ONE reference and a leaf's box is the bounds of its triangles plus the pad of that mesh's builder:
+// spatial splits, so every finite triangle has ONE reference and a leaf's box is the bounds of its finite triangles plus the builder's pad for the mesh's current bounds:
 // a refit needs no cells (instances.hip needs them because its trees are split).
 //
 // An update, all on the caller's stream, in this order (entries are taken kMaxUpdatesPerLaunch at a time):
 //   k_deform_scatter     one launch for all entries: one thread per updated triangle writes the 36 vertex bytes of its reference (through the
 //                        triangle -> reference map; prim and the padding words stand), its positions row and, when given, its normals row
+//   k_deform_bounds      one launch for all updated meshes: the exact bounds of every mesh's finite references, by one atomic pair per axis per
+//                        workgroup (of up to 64 a mesh) into the mesh's six words of bounds_bits — what the builder computes before it pads (bvh_build.cpp), so that the
+//                        refit pads for the size the mesh has NOW (refit.h refit_pad).  The words stand at 0xffffffff / 0 between updates: the
+//                        mesh's workgroup of k_deform_refit_top, their last reader, puts them back.
 //   k_deform_refit       refit.h refit_node<false>, level d of ALL updated meshes in one launch, deepest level first: the launch count follows the
 //                        deepest updated mesh, not the number of meshes.  Only levels wider than the mesh's narrow width come here.
 //   k_deform_refit_top   one launch, one workgroup per updated mesh: the narrow levels near its root, a barrier between levels, then the refitted
@@ -71,10 +75,60 @@ __global__ __launch_bounds__(256) void k_deform_scatter(ScatterArgs a)
     }
 }
 
-struct LevelEntry { int32_t first, end, slot, block_first; float pad; };   // the level's range in `lists`, its first partial slot, the mesh's pad
+struct BoundsEntry { uint32_t first, mesh; int32_t count, block_first, blocks; };   // the mesh's references in `tris`, its workgroups in this launch
+struct BoundsArgs
+{
+    const TriGPU* tris;
+    uint32_t*     bits;
+    int           n;
+    BoundsEntry   e[kMaxUpdatesPerLaunch];
+};
+constexpr int kBoundsPerBlock = 1024, kBoundsMaxBlocks = 64;   // references a workgroup takes before a mesh gets another one; workgroups per mesh at most
+
+// Atomics of all workgroups on the same six words serialise across the XCDs (one per wave cost a 20 k-triangle mesh more than its whole refit): a
+// workgroup strides over its share, reduces in registers, then through LDS, and issues ONE pair per axis.
+__global__ __launch_bounds__(256) void k_deform_bounds(BoundsArgs a)
+{
+    __shared__ float s_lo[4][3], s_hi[4][3];
+    int j = 0;
+    for (int i = 1; i < a.n; i++) if ((int)blockIdx.x >= a.e[i].block_first) j = i;
+    const BoundsEntry& e = a.e[j];
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (int t = ((int)blockIdx.x - e.block_first) * 256 + (int)threadIdx.x; t < e.count; t += e.blocks * 256)
+    {
+        const uint4* p = reinterpret_cast<const uint4*>(a.tris + (size_t)e.first + t);   // three 16-byte loads (traverse.h load_tri)
+        const uint4  q0 = p[0], q1 = p[1], q2 = p[2];
+        const float  v[3][3] = { { __uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z) }, { __uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z) },
+                                 { __uint_as_float(q2.x), __uint_as_float(q2.y), __uint_as_float(q2.z) } };
+        bool fin = true;
+        for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) fin = fin && fabsf(v[i][k]) < INFINITY;
+        for (int k = 0; k < 3; k++)
+        {
+            lo[k] = fminf(lo[k], fin ? fminf(v[0][k], fminf(v[1][k], v[2][k])) : INFINITY);
+            hi[k] = fmaxf(hi[k], fin ? fmaxf(v[0][k], fmaxf(v[1][k], v[2][k])) : -INFINITY);
+        }
+    }
+    for (int k = 0; k < 3; k++)
+    {
+        float l = lo[k], h = hi[k];
+        for (int o = 32; o > 0; o >>= 1) { l = fminf(l, __shfl_xor(l, o)); h = fmaxf(h, __shfl_xor(h, o)); }
+        if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6][k] = l; s_hi[threadIdx.x >> 6][k] = h; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+    {
+        const int   k = (int)threadIdx.x;
+        const float l = fminf(fminf(s_lo[0][k], s_lo[1][k]), fminf(s_lo[2][k], s_lo[3][k])), h = fmaxf(fmaxf(s_hi[0][k], s_hi[1][k]), fmaxf(s_hi[2][k], s_hi[3][k]));
+        uint32_t*   bits = a.bits + (size_t)e.mesh * 6;
+        if (l <= h) { atomicMin(bits + k, ordered_bits(l)); atomicMax(bits + 3 + k, ordered_bits(h)); }
+    }
+}
+
+struct LevelEntry { int32_t first, end, slot, block_first; uint32_t mesh; };   // the level's range in `lists`, its first partial slot, the mesh
 struct LevelArgs
 {
     RefitArgs       r;          // list / count / pad unused: they differ per mesh
+    const uint32_t* bits;       // bounds_bits of all meshes
     const uint32_t* lists;
     double*         partials;
     int             n;
@@ -92,7 +146,7 @@ __global__ __launch_bounds__(64) void k_deform_refit(LevelArgs a)
     if (i < e.end)
     {
         RefitArgs r = a.r;
-        r.pad = e.pad;
+        r.pad = refit_pad(a.bits + (size_t)e.mesh * 6);
         area = refit_node<false>(r, a.lists[i]);
     }
     for (int o = 32; o > 0; o >>= 1) area += __shfl_xor(area, o);
@@ -106,12 +160,12 @@ struct TopEntry
     int16_t  d_top;
     uint16_t offs_at;                // offs[offs_at + d] .. offs[offs_at + d + 1]: level d in `lists`
     uint32_t has_bounds;
-    float    pad;
     float    bounds[6];
 };
 struct TopArgs
 {
     RefitArgs       r;
+    uint32_t*       bits;       // bounds_bits of all meshes
     const uint32_t* lists;
     double*         partials;
     float*          root_box;
@@ -129,7 +183,8 @@ __global__ __launch_bounds__(256) void k_deform_refit_top(TopArgs t)
     const TopEntry& e   = t.e[blockIdx.x];
     const int32_t*  row = t.offs + e.offs_at;
     RefitArgs r = t.r;
-    r.pad = e.pad;
+    uint32_t* bits = t.bits + (size_t)e.mesh * 6;
+    r.pad = refit_pad(bits);
     double area = 0.0;
     for (int d = e.d_top; d >= 0; d--)
     {
@@ -151,10 +206,13 @@ __global__ __launch_bounds__(256) void k_deform_refit_top(TopArgs t)
         {
             // the root box is the union of leaf boxes, each its triangles' bounds -/+ the pad in fp32: bounds that hold every vertex pass the
             // same subtraction / addition, which is monotonic, so exact bounds are never reported
+            // (an empty root box, +inf / -inf, lies inside any bounds)
+            const float pad = r.pad;
             for (int k = 0; k < 3; k++)
-                if (!(b[k] >= e.bounds[k] - e.pad) || !(b[4 + k] <= e.bounds[3 + k] + e.pad)) out = 1u;
+                if (b[k] <= b[4 + k] && (!(b[k] >= e.bounds[k] - pad) || !(b[4 + k] <= e.bounds[3 + k] + pad))) out = 1u;
         }
         t.outside[e.mesh] = out;
+        for (int k = 0; k < 3; k++) { bits[k] = 0xffffffffu; bits[3 + k] = 0u; }   // every reader of this update is done (the barrier above)
     }
 }
 
@@ -173,13 +231,26 @@ hr_status enqueue(hr_scene* s, DeformRefit& sd, Node8* nodes, float* node_box, c
 {
     RefitArgs r;
     r.nodes = nodes; r.tris = (const TriGPU*)s->tris.p; r.node_box = node_box; r.pad = 0.0f;
+    {
+        BoundsArgs b;
+        b.tris = r.tris; b.bits = (uint32_t*)sd.bounds_bits.p; b.n = 0;
+        int blocks = 0;
+        for (int j = 0; j < n; j++)
+        {
+            if (sd.n_refs[ms[j]] == 0) continue;
+            const int mine = std::min(kBoundsMaxBlocks, cdiv(sd.n_refs[ms[j]], kBoundsPerBlock));
+            b.e[b.n++] = { sd.ref_base[ms[j]], ms[j], sd.n_refs[ms[j]], blocks, mine };
+            blocks += mine;
+        }
+        if (b.n > 0) hipLaunchKernelGGL(k_deform_bounds, dim3(blocks), dim3(256), 0, st, b);
+    }
     r.cells = nullptr; r.node_inst = nullptr; r.inst = nullptr; r.dirty = nullptr; r.list = nullptr; r.count = 0;
     int deepest = 0;
     for (int j = 0; j < n; j++) deepest = std::max(deepest, sd.n_levels[ms[j]]);
     for (int d = deepest - 1; d >= 0; d--)
     {
         LevelArgs a;
-        a.r = r; a.lists = (const uint32_t*)sd.level_nodes.p; a.partials = (double*)sd.partials.p; a.n = 0;
+        a.r = r; a.bits = (const uint32_t*)sd.bounds_bits.p; a.lists = (const uint32_t*)sd.level_nodes.p; a.partials = (double*)sd.partials.p; a.n = 0;
         int blocks = 0;
         for (int j = 0; j < n; j++)
         {
@@ -187,7 +258,7 @@ hr_status enqueue(hr_scene* s, DeformRefit& sd, Node8* nodes, float* node_box, c
             if (d >= sd.n_levels[m] || d <= sd.d_top[m]) continue;
             const int32_t* row = &sd.levels_host[(size_t)m * 2 * kLevelStride];
             if (row[d + 1] <= row[d]) continue;
-            a.e[a.n++] = { row[d], row[d + 1], sd.partial_base[m] + row[kLevelStride + d], blocks, sd.pad[m] };
+            a.e[a.n++] = { row[d], row[d + 1], sd.partial_base[m] + row[kLevelStride + d], blocks, m };
             blocks += cdiv(row[d + 1] - row[d], 64);
         }
         if (a.n == 0) continue;
@@ -195,7 +266,7 @@ hr_status enqueue(hr_scene* s, DeformRefit& sd, Node8* nodes, float* node_box, c
         sd.level_launches++;
     }
     TopArgs t;
-    t.r = r; t.lists = (const uint32_t*)sd.level_nodes.p; t.partials = (double*)sd.partials.p; t.root_box = (float*)sd.root_box.p; t.outside = (uint32_t*)sd.outside.p;
+    t.r = r; t.bits = (uint32_t*)sd.bounds_bits.p; t.lists = (const uint32_t*)sd.level_nodes.p; t.partials = (double*)sd.partials.p; t.root_box = (float*)sd.root_box.p; t.outside = (uint32_t*)sd.outside.p;
     t.n = t.n_offs = 0;
     for (int j = 0; j <= n; j++)
     {
@@ -209,7 +280,7 @@ hr_status enqueue(hr_scene* s, DeformRefit& sd, Node8* nodes, float* node_box, c
         if (j == n) break;
         const uint32_t m = ms[j];
         TopEntry& e = t.e[t.n++];
-        e.mesh = m; e.root = sd.root[m]; e.slot = sd.partial_base[m]; e.d_top = (int16_t)sd.d_top[m]; e.offs_at = (uint16_t)t.n_offs; e.pad = sd.pad[m];
+        e.mesh = m; e.root = sd.root[m]; e.slot = sd.partial_base[m]; e.d_top = (int16_t)sd.d_top[m]; e.offs_at = (uint16_t)t.n_offs;
         e.has_bounds = bounds && bounds[j] ? 1u : 0u;
         if (e.has_bounds) std::memcpy(e.bounds, bounds[j], 24); else std::memset(e.bounds, 0, 24);
         std::memcpy(t.offs + t.n_offs, &sd.levels_host[(size_t)m * 2 * kLevelStride], (size_t)need * 4);
@@ -260,7 +331,7 @@ hr_status hr::deform_refit_adopt(hr_scene* s, const std::vector<DeformMesh>& mes
     const size_t M = meshes.size();
     std::unique_ptr<DeformRefit> fresh(new DeformRefit());   // the scene takes it only when it stands complete: a failure leaves an earlier one in place
     DeformRefit& sd = *fresh;
-    sd.flag.assign(M, 0); sd.root.assign(M, 0); sd.ref_base.assign(M, 0); sd.tri_base.assign(M, 0); sd.n_tris.assign(M, 0); sd.pad.assign(M, 0.0f);
+    sd.flag.assign(M, 0); sd.root.assign(M, 0); sd.ref_base.assign(M, 0); sd.tri_base.assign(M, 0); sd.n_tris.assign(M, 0); sd.n_refs.assign(M, 0);
     sd.n_levels.assign(M, 0); sd.d_top.assign(M, -1); sd.partial_base.assign(M, 0); sd.n_partials.assign(M, 0);
     sd.cost_at_build.assign(M, 0.0); sd.cost_known.assign(M, 1); sd.cost_ratio.assign(M, 1.0);
     sd.levels_host.assign(M * 2 * kLevelStride, 0);
@@ -269,7 +340,7 @@ hr_status hr::deform_refit_adopt(hr_scene* s, const std::vector<DeformMesh>& mes
     for (size_t k = 0; k < M; k++)
     {
         sd.flag[k] = meshes[k].flag ? 1 : 0; sd.root[k] = meshes[k].root; sd.ref_base[k] = meshes[k].ref_base; sd.tri_base[k] = meshes[k].tri_base;
-        sd.n_tris[k] = meshes[k].n_tris; sd.pad[k] = meshes[k].pad;
+        sd.n_tris[k] = meshes[k].n_tris; sd.n_refs[k] = meshes[k].flag ? (int32_t)meshes[k].bvh->tris.size() : 0;
         any = any || sd.flag[k];
         n_tris_all = std::max(n_tris_all, (size_t)meshes[k].tri_base + (size_t)meshes[k].n_tris);
     }
@@ -323,6 +394,12 @@ hr_status hr::deform_refit_adopt(hr_scene* s, const std::vector<DeformMesh>& mes
     if ((e = sd.partials.alloc((size_t)partials * 8)) != HR_OK) return e;
     if ((e = sd.root_box.alloc(M * 32)) != HR_OK) return e;
     if ((e = sd.outside.alloc(M * 4)) != HR_OK) return e;
+    if ((e = sd.bounds_bits.alloc(M * 24)) != HR_OK) return e;
+    {
+        std::vector<uint32_t> idle(M * 6);
+        for (size_t k = 0; k < M * 6; k++) idle[k] = k % 6 < 3 ? 0xffffffffu : 0u;
+        HR_HIP(hipMemcpy(sd.bounds_bits.p, idle.data(), M * 24, hipMemcpyHostToDevice));
+    }
     DevBuf node_box;
     if ((e = node_box.alloc(n_nodes_all * 32)) != HR_OK) return e;
     HR_HIP(hipHostMalloc((void**)&sd.root_box_host, M * 32, hipHostMallocDefault));

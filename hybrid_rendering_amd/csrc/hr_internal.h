@@ -171,8 +171,7 @@ struct DeformRefit
 {
     std::vector<uint8_t>  flag;                   // per mesh: may be updated
     std::vector<uint32_t> root, ref_base, tri_base;   // per mesh: its root in `nodes` / first reference in `tris` / first triangle in the attribute arrays
-    std::vector<float>    pad;                    // per mesh: the leaf pad its builder used
-    std::vector<int32_t>  n_tris;
+    std::vector<int32_t>  n_tris, n_refs;         // per mesh: triangles / references (a flagged mesh: one per triangle that was finite when built)
     std::vector<int32_t>  n_levels, d_top;        // per mesh: levels of its tree / deepest level the one-workgroup launch takes (-1: unflagged)
     std::vector<int32_t>  partial_base, n_partials;
     std::vector<double>   cost_at_build;
@@ -184,6 +183,8 @@ struct DeformRefit
     DevBuf   tri_ref;                             // per mesh triangle (concatenated): global index of its one reference, -1: none (not finite when built)
     DevBuf   partials;                            // per refit workgroup: sum of its nodes' half areas (double)
     DevBuf   root_box;                            // per mesh 8 floats: the refitted root box (lo xyz, 0, hi xyz, 0)
+    DevBuf   bounds_bits;                         // per mesh 6 words: ordered bits of the exact bounds of its finite references during an update,
+                                                  // 0xffffffff x 3, 0 x 3 between updates (deform_refit.hip k_deform_bounds)
     DevBuf   outside;                             // per mesh one word: the bounds given with the last update do not contain the refitted root box
     float*   root_box_host = nullptr;             // pinned, per mesh 8 floats
     int64_t  level_launches = 0, top_launches = 0, stream_waits = 0;   // what the updates so far enqueued (hr_scene_update_meshes_stats)

@@ -122,6 +122,17 @@ HR_HD float pad_of_bounds(const float* lo, const float* hi)
     return pad > 0.0f ? pad : 1e-6f;
 }
 
+// The pad of every leaf box of a triangle tree (bvh_build.cpp, refit.h): 3e-5 x the diagonal of the bounds, and never less
+// than 2^-21 of the largest coordinate — 4 to 8 float steps there.  A scene that is small against its distance from the origin (a placeholder, a
+// collapsed mesh, a mesh that drifted away: diagonal under 1/60 of that distance) has coordinates too coarse to hold 3e-5 diagonals: lo - pad
+// would round back to lo, and a ray that runs IN the plane of such a box face meets a slab of no thickness, which the box test rejects.
+HR_HD float leaf_pad(const float* lo, const float* hi)
+{
+    float m = 0.0f;
+    for (int k = 0; k < 3; k++) m = fmax_(m, fmax_(__builtin_fabsf(lo[k]), __builtin_fabsf(hi[k])));
+    return fmax_(pad_of_bounds(lo, hi), m * 4.76837158203125e-7f);
+}
+
 // smallest e in [1, 254] with extent <= 255 * 2^(e - 127) (bvh_build.cpp exponent_for)
 HR_HD uint8_t exponent_for(float extent)
 {

@@ -103,7 +103,10 @@ def check_boxes(g, sd, what):
       * every internal slot's de-quantised box contains the child node's true box (so everything beneath it, at every level);
       * a child's de-quantised child boxes lie inside the parent's slot grown by ONE grid step of the child per axis on the upper side and not at
         all on the lower (the format's precision: floor / ceil on a grid whose origin is the child's exact lower corner);
-      * hr_scene_get_info reports the numpy min / max of the vertices."""
+      * hr_scene_get_info reports the numpy min / max of the vertices.
+    Triangles with a NaN or infinite coordinate count for nothing, as in the builder: a leaf without a finite triangle and a node without a
+    non-empty child are EMPTY — stored inverted (lo > hi on every axis) in their parent, outside every true box; a node that holds nothing has
+    origin 0 — and the bounds reported are those of the finite triangles, 0 when there are none."""
     boxes, leaf, nodes, tris = own_boxes(g)
     info = g.refresh_info()
     pad = F32(info.box_pad)
@@ -119,27 +122,35 @@ def check_boxes(g, sd, what):
         count_of_node[int(b["node"])] = count_of_node.get(int(b["node"]), 0) + 1
     true_lo, true_hi = np.zeros((n, 3), F32), np.zeros((n, 3), F32)
     slot_lo, slot_hi = np.zeros((len(boxes), 3), F32), np.zeros((len(boxes), 3), F32)   # true box of what every slot holds
+    empty = np.zeros(len(boxes), bool)
+    fin = np.isfinite(tv.reshape(len(tv), 9)).all(1)
     for j in sorted(first_of_node, reverse=True):   # children sit behind their parent
         k, c = first_of_node[j], count_of_node[j]
         for i in range(k, k + c):
             if boxes[i]["is_leaf"]:
-                v = tv[leaf[i, 0]:leaf[i, 0] + leaf[i, 1]].reshape(-1, 3)
-                assert len(v) > 0, f"{what}: an empty leaf (node {j})"
-                slot_lo[i], slot_hi[i] = (v.min(0) - pad).astype(F32), (v.max(0) + pad).astype(F32)
+                assert leaf[i, 1] > 0, f"{what}: an empty leaf (node {j})"
+                v = tv[leaf[i, 0]:leaf[i, 0] + leaf[i, 1]][fin[leaf[i, 0]:leaf[i, 0] + leaf[i, 1]]].reshape(-1, 3)
+                empty[i] = len(v) == 0
+                if len(v):
+                    slot_lo[i], slot_hi[i] = (v.min(0) - pad).astype(F32), (v.max(0) + pad).astype(F32)
             else:
                 slot_lo[i], slot_hi[i] = true_lo[leaf[i, 0]], true_hi[leaf[i, 0]]
-        true_lo[j], true_hi[j] = slot_lo[k:k + c].min(0), slot_hi[k:k + c].max(0)
-        assert np.array_equal(nodes[j, 0:12].copy().view(F32), true_lo[j]), f"{what}: node {j}'s origin is not the lower corner of its true box"
-    holds = (boxes["lo"] <= slot_lo).all(1) & (boxes["hi"] >= slot_hi).all(1)
+                empty[i] = not (true_lo[leaf[i, 0]] <= true_hi[leaf[i, 0]]).all()
+        full = np.flatnonzero(~empty[k:k + c]) + k
+        true_lo[j], true_hi[j] = (slot_lo[full].min(0), slot_hi[full].max(0)) if len(full) else (np.full(3, np.inf, F32), np.full(3, -np.inf, F32))
+        assert np.array_equal(nodes[j, 0:12].copy().view(F32), true_lo[j] if len(full) else np.zeros(3, F32)), f"{what}: node {j}'s origin is not the lower corner of its true box"
+    assert (boxes["lo"][empty] > boxes["hi"][empty]).all(), f"{what}: an empty slot is not stored inverted on every axis"
+    holds = empty | ((boxes["lo"] <= slot_lo).all(1) & (boxes["hi"] >= slot_hi).all(1))
     assert holds.all(), f"{what}: {int((~holds).sum())} de-quantised slot boxes do not contain what they hold, first (node, slot) {boxes['node'][~holds][:4]}, {boxes['slot'][~holds][:4]}"
     for i, b in enumerate(boxes):
-        if not b["is_leaf"] and int(leaf[i, 0]) in first_of_node:
+        if not b["is_leaf"] and not empty[i] and int(leaf[i, 0]) in first_of_node:
             k = first_of_node[int(leaf[i, 0])]
-            kids = boxes[k:k + count_of_node[int(leaf[i, 0])]]
+            kids = boxes[k:k + count_of_node[int(leaf[i, 0])]][~empty[k:k + count_of_node[int(leaf[i, 0])]]]
             assert (kids["lo"] >= b["lo"]).all() and (kids["hi"] <= (b["hi"] + kids["step"]).astype(F32)).all(), \
                 f"{what}: a child box more than one grid step outside its parent's (node {b['node']} slot {b['slot']})"
-    v = sd.verts.reshape(-1, 3)
-    assert list(info.bounds_lo) == list(v.min(0)) and list(info.bounds_hi) == list(v.max(0)), f"{what}: exact bounds after the update"
+    v = sd.verts[np.isfinite(sd.verts.reshape(sd.n_tris, 9)).all(1)].reshape(-1, 3)
+    lo, hi = (v.min(0), v.max(0)) if len(v) else (np.zeros(3, F32), np.zeros(3, F32))
+    assert list(info.bounds_lo) == list(lo) and list(info.bounds_hi) == list(hi), f"{what}: exact bounds after the update"
 
 
 def test_refit_with_the_creation_vertices_reproduces_the_builders_nodes(hr, ctx):
