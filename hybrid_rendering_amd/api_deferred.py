@@ -41,6 +41,12 @@ class DeferredShading:
         _check(lib().hr_deferred_render(self.h, C.byref(inputs), C.byref(env), ptr(vs[0]), ptr(vs[1]), ptr(vs[2]), ptr(vs[3]), C.byref(self.params),
                                         _stream_ptr(stream)), "hr_deferred_render")
 
+    def render_probes(self, inputs, ddgi, radius=0.5, what=0, depth_out=None, probe_id_out=None, stream=None):
+        """DeferredShading::render_probes (include/hr_probe_vis.h): the DDGI probe grid drawn onto this pass's output, after ``render`` on the same
+        stream.  depth_out (cuda float32 [h, w]) and probe_id_out (cuda int32 [h, w]) are optional."""
+        from . import probe_vis
+        probe_vis.render_probes(self.h, inputs, ddgi.h, radius, what, depth_out, probe_id_out, stream)
+
     def output(self):
         v = hr_image_view()
         _check(lib().hr_deferred_output(self.h, C.byref(v)), "hr_deferred_output")

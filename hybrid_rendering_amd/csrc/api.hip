@@ -8,6 +8,7 @@
 #include "traverse.h"
 #include "traverse2.h"
 #include "shading.h"
+#include "pixel_dir.h"
 #include "cutout_host.h"
 #include "selftest.h"
 #include <cstring>
@@ -231,11 +232,7 @@ struct GBufArgs
     const uint32_t* tri_mesh_id;   // [n] or null; not read for a shared scene (its mesh id is the record's)
 };
 
-HR_DEV f3 gb_pixel_dir(const GBufArgs& a, float px, float py)
-{
-    f3 far_p = world_pos_from_depth(__fdiv_rn(px, (float)a.w), __fdiv_rn(py, (float)a.h), 1.0f, a.vpi);
-    return normalize3(sub3(far_p, mk3(a.cam[0], a.cam[1], a.cam[2])));
-}
+// gb_pixel_dir: pixel_dir.h (k_probe_vis forms its rays with the same function)
 
 // n, v: the hit triangle's nine world vertex-normal floats (read only where has_normals) and nine world vertex floats
 HR_DEV f3 gb_normal_at(const float* n, const float* v, bool has_normals, float b0, float b1, float b2)

@@ -136,6 +136,8 @@ struct hr_deferred
     const float* sh9_dev = nullptr;   // hr_deferred_bind_sh9
 };
 
+namespace hr { hr_ctx* deferred_ctx(const ::hr_deferred* p) { return p->ctx; } }
+
 extern "C" {
 
 void hr_deferred_default_params(hr_deferred_params* p)

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+struct hr_deferred;   // hr_api_post.h
+
 namespace hr {
 
 void set_last_error(const std::string& s);
@@ -62,6 +64,8 @@ bool profiling_enabled(const hr_shadows* p);
 bool profiling_enabled(const hr_ao* p);
 bool profiling_enabled(const hr_ddgi* p);
 bool profiling_enabled(const hr_reflections* p);
+// deferred.hip: the context a composite pass was created on (probe_vis.hip draws onto the pass's output)
+hr_ctx* deferred_ctx(const ::hr_deferred* p);
 // instances.hip: brings info.bounds_* of an instanced scene up to date with its last update (synchronises the device when they lag)
 hr_status instanced_scene_refresh_bounds(const hr_scene* scene);
 

@@ -19,6 +19,7 @@
 // explicitly (tests, tools).  render() returns void like the reference; failures throw hr::Error on THIS side of the ABI only.
 #pragma once
 #include "../hr_api.h"
+#include "../hr_probe_vis.h"
 #include <stdexcept>
 #include <string>
 
@@ -537,13 +538,29 @@ public:
     {
         if (!m_common_resources || !m_g_buffer) throw Error(HR_ERR_INVALID_ARG, "DeferredShading::render(cmd_buf, ...): constructed without CommonResources / GBuffer");
         const ImageView a = ao->output_ds(), s = shadows->output_ds(), r = reflections->output_ds(), g = ddgi->output_ds();
-        render(cmd_buf, make_frame(*m_common_resources, *m_g_buffer, 0), &a, &s, &r, &g);
+        render(cmd_buf, make_frame(*m_common_resources, *m_g_buffer, 0), &a, &s, &r, &g, ddgi);
     }
-    // explicit-inputs form: the pass outputs are the views returned by their output_ds()
-    void render(Stream cmd_buf, const Frame& frame, const ImageView* ao, const ImageView* shadows, const ImageView* reflections, const ImageView* gi)
+    // explicit-inputs form: the pass outputs are the views returned by their output_ds().  ddgi: whose probe grid render_probes draws when
+    // visualize_probe_grid() is on (deferred_shading.cpp:58-70: render_shading, render_probes, render_skybox); NULL: never drawn
+    void render(Stream cmd_buf, const Frame& frame, const ImageView* ao, const ImageView* shadows, const ImageView* reflections, const ImageView* gi, DDGI* ddgi = nullptr)
     {
         check(hr_deferred_render(m_pass, &frame.inputs, frame.environment, shadows, ao, reflections, gi, &params, cmd_buf), "DeferredShading::render");
+        if (m_visualize_probe_grid && ddgi) render_probes(cmd_buf, frame, ddgi);
     }
+    // DeferredShading::render_probes (deferred_shading.cpp:797-866; hr_probe_vis.h): one sphere of radius probe_visualization_scale() per probe, over
+    // the composite.  depth_out ([h][w] floats, device): the depth buffer with the spheres written into it, for what follows (TAA)
+    void render_probes(Stream cmd_buf, const Frame& frame, DDGI* ddgi, float* depth_out = nullptr, int32_t* probe_id_out = nullptr)
+    {
+        hr_probe_vis_params p;
+        hr_probe_vis_default_params(&p);
+        p.radius = m_probe_visualization_scale;
+        check(hr_deferred_render_probes(m_pass, &frame.inputs, ddgi->handle(), &p, depth_out, probe_id_out, cmd_buf), "DeferredShading::render_probes");
+    }
+    // deferred_shading.h:35-42; off and 1.0 by default, as there
+    bool  visualize_probe_grid() const { return m_visualize_probe_grid; }
+    float probe_visualization_scale() const { return m_probe_visualization_scale; }
+    void  set_visualize_probe_grid(bool v) { m_visualize_probe_grid = v; }
+    void  set_probe_visualization_scale(float v) { m_probe_visualization_scale = v; }
     ImageView output_ds()
     {
         ImageView v;
@@ -558,6 +575,8 @@ private:
     CommonResources* m_common_resources = nullptr;
     GBuffer*         m_g_buffer = nullptr;
     hr_deferred* m_pass = nullptr;
+    bool         m_visualize_probe_grid = false;
+    float        m_probe_visualization_scale = 1.0f;
 };
 
 // src/ground_truth_path_tracer.h:7-44

@@ -3,6 +3,8 @@ map) of the procedural Sponza-like bench scene on one GPU and writes the last on
 bench.py are numbers of.   python tools/render_frame.py [--width 960 --height 540 --frames 24 --out gpurun_out/frame.png]"""
 # --hdr FILE lights the frame with a Radiance .hdr map, --sky with the analytic sky under the scene's sun: either goes through hr_env on the GPU
 # (the sky, SH9, the prefiltered chain and the BRDF LUT); without them the environment is synth_env's host-made gradient.
+# --probes [SCALE] draws the DDGI probe grid over the composite (DeferredShading::render_probes): one sphere of radius SCALE per probe, an eighth
+# of the smallest grid step by default, coloured with the probe's irradiance; the depth it writes is the depth TAA sees.
 import argparse, os, struct, sys, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +28,7 @@ def main():
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--hdr", metavar="FILE", help="a Radiance .hdr equirectangular map as the environment (hr_env_update_equirect)")
     src.add_argument("--sky", action="store_true", help="the analytic sky, its sun along the scene's light (hr_env_update_sky)")
+    ap.add_argument("--probes", nargs="?", type=float, const=0.0, default=None, metavar="SCALE", help="visualise the DDGI probe grid; SCALE: the spheres' radius (default: min grid step / 8)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame.png"))
     a = ap.parse_args()
     import torch
@@ -76,8 +79,13 @@ def main():
         fh = hr.frame_inputs(half, ph, ubo, f, f & 1, sob_d, sr_d, cur_full=cur, z_buffer_params=zbp)
         sh.render(scene, fi); ao.render(scene, fh); gi.render(scene, fi, env, synth_env.random_orientation(rng)); rf.render(scene, fh, env, gi)
         df.render(fi, env, shadow=sh.output(hr.OUTPUT_UPSAMPLE), ao=ao.output(hr.OUTPUT_UPSAMPLE), reflections=rf.output(hr.OUTPUT_UPSAMPLE), gi=gi.output())
+        seen = cur
+        if a.probes is not None:
+            depth_out = torch.empty_like(cur["depth"])
+            df.render_probes(fi, gi, radius=a.probes if a.probes > 0 else float(ddgi_u["grid_step"].min()) / 8.0, depth_out=depth_out)
+            seen = dict(cur, depth=depth_out)
         taa.update(f)
-        taa.render(df.output(), cur, f & 1)
+        taa.render(df.output(), seen, f & 1)
         prev = (cur, half)
     _, ldr = api_post.tone_map(ctx, taa.output((a.frames - 1) & 1), False, a.exposure)
     torch.cuda.synchronize()
