@@ -7,6 +7,8 @@ are self-contained readers for the subset those assets use: triangulated or poly
 v/vt/vn indices (negative indices allowed), ``usemtl`` + ``mtllib`` (Kd, Pr / Ns, Pm, Ke), ``o`` / ``g`` groups -> mesh ids;
 8-bit non-interlaced PNG of colour type 0, 2, 4 or 6 with all five scanline filters; Radiance ``.hdr`` (RGBE, flat or new-style run-length
 scanlines, top-down) -> the fp32 equirectangular image env.Environment.update_equirect takes (common.cpp:597-612 loads its four through stbi_loadf).
+``load_gltf_skinned`` reads what the static loaders drop — skins, JOINTS_0 / WEIGHTS_0, morph targets and animations — into a SkinnedMesh for
+skinning.Skin (include/hr_skin.h).
 """
 from __future__ import annotations
 
@@ -553,3 +555,285 @@ def load_gltf_instanced(path: str, scale: float = 1.0):
     by several nodes is stored once.  hr.InstancedScene(ctx, it) builds it; its flatten() gives the world-space triangles load_gltf() returns
     (up to the rounding of the pinned fp32 transform; normals through mat3(model), as transform_vertex does, not the inverse transpose)."""
     return load_gltf(path, scale, instanced=True)
+
+
+# ------------------------------------------------------------------------------------------------ glTF 2.0: skins, morph targets, animations
+def _gltf_document(path: str):
+    """(doc, buffers) of a .gltf (external / base64 buffers) or .glb"""
+    import base64
+    import json
+    raw = open(path, "rb").read()
+    base = os.path.dirname(os.path.abspath(path))
+    glb_bin, doc = None, None
+    if raw[:4] == b"glTF":
+        _, _, total = struct.unpack("<4sII", raw[:12])
+        o = 12
+        while o < total:
+            n, typ = struct.unpack("<II", raw[o:o + 8])
+            body = raw[o + 8:o + 8 + n]
+            if typ == 0x4E4F534A:
+                doc = json.loads(body.decode("utf-8"))
+            elif typ == 0x004E4942 and glb_bin is None:
+                glb_bin = bytes(body)
+            o += 8 + n
+    else:
+        doc = json.loads(raw.decode("utf-8"))
+    buffers = []
+    for b in doc.get("buffers", []):
+        uri = b.get("uri")
+        if uri is None:
+            buffers.append(glb_bin)
+        elif uri.startswith("data:"):
+            buffers.append(base64.b64decode(uri.split(",", 1)[1]))
+        else:
+            buffers.append(open(os.path.join(base, uri), "rb").read())
+    return doc, buffers
+
+
+_GLTF_COMP = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
+_GLTF_NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
+
+
+def _gltf_accessor(doc, buffers, i, path, as_float: bool = False):
+    """accessor i as [count, components]; as_float: float64, integer components de-normalised as glTF specifies (c / max, signed clamped at -1)"""
+    a = doc["accessors"][i]
+    if "sparse" in a:
+        raise ValueError(f"{path}: accessor {i} is sparse: sparse accessors are not supported by load_gltf_skinned")
+    dt, nc, cnt = np.dtype(_GLTF_COMP[a["componentType"]]), _GLTF_NCOMP[a["type"]], a["count"]
+    if "bufferView" not in a:
+        v = np.zeros((cnt, nc), dt)
+    else:
+        bv = doc["bufferViews"][a["bufferView"]]
+        off = bv.get("byteOffset", 0) + a.get("byteOffset", 0)
+        stride = bv.get("byteStride", 0) or dt.itemsize * nc
+        buf = np.frombuffer(buffers[bv["buffer"]], np.uint8)
+        rows = np.lib.stride_tricks.as_strided(buf[off:], shape=(cnt, dt.itemsize * nc), strides=(stride, 1))
+        v = np.ascontiguousarray(rows).view(dt).reshape(cnt, nc)
+    if not as_float:
+        return v
+    if dt.kind == "f":
+        return v.astype(np.float64)
+    top = float(np.iinfo(dt).max)
+    return np.maximum(v.astype(np.float64) / top, -1.0) if dt.kind == "i" else v.astype(np.float64) / top
+
+
+def _slerp(a, b, u):
+    """glTF's spherical linear interpolation of unit quaternions (x, y, z, w), along the shorter arc"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    d = float(np.dot(a, b))
+    if d < 0.0:
+        b, d = -b, -d
+    if d > 0.9995:
+        q = a + u * (b - a)
+        return q / np.linalg.norm(q)
+    th = np.arccos(min(d, 1.0))
+    return (np.sin((1.0 - u) * th) * a + np.sin(u * th) * b) / np.sin(th)
+
+
+class SkinnedMesh:
+    """What load_gltf_skinned returns.  ``rest``: SceneData of the skinned mesh in the SKIN's space (positions and normals as stored: the skinned
+    node's own transform is ignored, as glTF specifies); ``joints`` [n,3,4] uint16 / ``weights`` [n,3,4] float32 per corner; ``target_positions`` /
+    ``target_normals`` [n_targets,n,3,3] (None without targets / when a target lacks NORMAL); ``default_morph_weights``; the skeleton — ``joint_nodes``
+    (glTF node per joint), ``parents`` (joint index of the nearest ancestor that is a joint, -1: none), ``node_parent`` / ``node_trs`` (every node's
+    parent and rest translation, rotation xyzw, scale; a node given by `matrix` keeps it in ``node_matrix``), ``inverse_bind`` [n_joints,4,4] float64 —
+    and ``animations``: name -> list of (node, path, times, values, interpolation).  skinning.Skin(ctx, mesh) takes it as it is."""
+
+    def __init__(self):
+        self.rest = None
+        self.joints = self.weights = None
+        self.n_joints = 0
+        self.target_positions = self.target_normals = self.default_morph_weights = None
+        self.joint_nodes, self.parents, self.node_parent, self.node_trs, self.node_matrix = [], [], [], [], {}
+        self.inverse_bind = None
+        self.animations = {}
+        self.scale = 1.0
+        self.name = "skinned"
+
+    @property
+    def n_targets(self) -> int:
+        return 0 if self.target_positions is None else int(self.target_positions.shape[0])
+
+    def duration(self, animation) -> float:
+        return max([float(ch[2][-1]) for ch in self._channels(animation)] or [0.0])
+
+    def _channels(self, animation):
+        if animation is None:
+            return []
+        if isinstance(animation, int):
+            animation = list(self.animations)[animation]
+        return self.animations[animation]
+
+    @staticmethod
+    def _sample(times, values, interpolation, t, rotation):
+        t = min(max(float(t), float(times[0])), float(times[-1]))      # clamped to the track
+        if len(times) == 1:
+            return values[0]
+        k = int(np.clip(np.searchsorted(times, t, side="right") - 1, 0, len(times) - 2))
+        if interpolation == "STEP":
+            return values[k + 1] if t >= times[k + 1] else values[k]
+        u = (t - float(times[k])) / (float(times[k + 1]) - float(times[k]))
+        if rotation:
+            return _slerp(values[k], values[k + 1], u)
+        return values[k] + u * (values[k + 1] - values[k])
+
+    def pose(self, animation=None, t: float = 0.0):
+        """(matrices [n_joints,16] float32 column-major, morph weights [n_targets] float32 or None) at time ``t`` of ``animation`` (a name, an index,
+        or None: the rest pose): world joint matrix times inverse bind matrix, rows scaled by the loader's ``scale``; the hierarchy in float64;
+        LINEAR (slerp for rotations) and STEP samplers; ``t`` clamped to each track."""
+        trs = [[np.array(v, np.float64) for v in n] for n in self.node_trs]
+        mw = None if self.default_morph_weights is None else np.array(self.default_morph_weights, np.float64)
+        animated = set()
+        for node, path, times, values, interp in self._channels(animation):
+            v = self._sample(times, values, interp, t, path == "rotation")
+            if path == "weights":
+                mw = np.array(v, np.float64)
+            else:
+                trs[node][("translation", "rotation", "scale").index(path)] = np.array(v, np.float64)
+                animated.add(node)
+        world = {}
+
+        def world_of(n):
+            if n not in world:
+                if n in self.node_matrix and n not in animated:
+                    local = self.node_matrix[n]
+                else:
+                    tr, ro, sc = trs[n]
+                    local = np.eye(4)
+                    local[:3, :3] = _quat_to_mat(ro) @ np.diag(sc)
+                    local[:3, 3] = tr
+                p = self.node_parent[n]
+                world[n] = local if p < 0 else world_of(p) @ local
+            return world[n]
+
+        out = np.zeros((self.n_joints, 16), np.float32)
+        for j, n in enumerate(self.joint_nodes):
+            M = world_of(n) @ self.inverse_bind[j]
+            M = M.copy()
+            M[:3, :] *= self.scale
+            out[j] = M.T.reshape(16)
+        return out, (None if mw is None or self.n_targets == 0 else mw.astype(np.float32))
+
+
+def load_gltf_skinned(path: str, scale: float = 1.0) -> SkinnedMesh:
+    """The first skinned mesh of a glTF 2.0 file (a node with `mesh` and `skin`) as a SkinnedMesh: every TRIANGLES primitive's (indexed) triangles
+    expanded to the [n][3][3] corner stream with JOINTS_0 (uint8 / uint16) and WEIGHTS_0 (float or normalised integers; each vertex's four weights
+    are normalised to sum 1 in float64 before they are rounded to float32), the morph `targets` (POSITION and NORMAL deltas; mesh.weights as the
+    default weights), the skeleton and the animations (LINEAR and STEP).  Raises ValueError, naming the cause, for CUBICSPLINE samplers, JOINTS_1
+    (more than four influences) and sparse accessors.  Materials as load_gltf gives them, without textures."""
+    doc, buffers = _gltf_document(path)
+    acc = lambda i, as_float=False: _gltf_accessor(doc, buffers, i, path, as_float)
+    nodes = doc.get("nodes", [])
+    skinned = [i for i, n in enumerate(nodes) if "mesh" in n and "skin" in n]
+    if not skinned:
+        raise ValueError(f"{path}: no node carries both a mesh and a skin")
+    node = nodes[skinned[0]]
+    skin, mesh = doc["skins"][node["skin"]], doc["meshes"][node["mesh"]]
+    out = SkinnedMesh()
+    out.scale, out.name = float(scale), mesh.get("name", os.path.basename(path))
+    out.joint_nodes = [int(j) for j in skin["joints"]]
+    out.n_joints = len(out.joint_nodes)
+
+    mats = []
+    for m in doc.get("materials", []):
+        pbr = m.get("pbrMetallicRoughness", {})
+        bc, em = pbr.get("baseColorFactor", [1, 1, 1, 1]), m.get("emissiveFactor", [0, 0, 0])
+        mats.append([bc[0], bc[1], bc[2], pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), em[0], em[1], em[2]])
+    default_mat = len(mats)
+    mats.append([0.8, 0.8, 0.8, 0.0, 0.5, 0.0, 0.0, 0.0])
+
+    V, N, J, W, TM, TP, TN = [], [], [], [], [], [], []
+    normal_deltas = True
+    for prim in mesh["primitives"]:
+        if prim.get("mode", 4) != 4:
+            continue
+        at = prim["attributes"]
+        if "JOINTS_1" in at or "WEIGHTS_1" in at:
+            raise ValueError(f"{path}: JOINTS_1 / WEIGHTS_1: more than four influences per vertex are not supported")
+        if "JOINTS_0" not in at or "WEIGHTS_0" not in at:
+            raise ValueError(f"{path}: a primitive of the skinned mesh has no JOINTS_0 / WEIGHTS_0")
+        pos = acc(at["POSITION"]).astype(np.float32)
+        idx = acc(prim["indices"]).reshape(-1).astype(np.int64) if "indices" in prim else np.arange(len(pos))
+        idx = idx[: len(idx) // 3 * 3].reshape(-1, 3)
+        tri = pos[idx]
+        if "NORMAL" in at:
+            tn = acc(at["NORMAL"]).astype(np.float32)[idx]
+        else:
+            fn = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).astype(np.float64)
+            fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-20)
+            tn = np.repeat(fn[:, None, :], 3, axis=1).astype(np.float32)
+        jn = acc(at["JOINTS_0"])
+        if jn.dtype not in (np.uint8, np.uint16):
+            raise ValueError(f"{path}: JOINTS_0 must be unsigned byte or unsigned short")
+        w = acc(at["WEIGHTS_0"], as_float=True)
+        s = w.sum(1, keepdims=True)
+        w = np.where(s > 0.0, w / np.where(s > 0.0, s, 1.0), w)
+        V.append(tri); N.append(tn); J.append(jn.astype(np.uint16)[idx]); W.append(w.astype(np.float32)[idx])
+        TM.append(np.full(len(tri), prim.get("material", default_mat), np.uint32))
+        tp, tnd = [], []
+        for tg in prim.get("targets", []):
+            tp.append(acc(tg["POSITION"], as_float=True).astype(np.float32)[idx] if "POSITION" in tg else np.zeros_like(tri))
+            if "NORMAL" in tg:
+                tnd.append(acc(tg["NORMAL"], as_float=True).astype(np.float32)[idx])
+            else:
+                normal_deltas = False
+                tnd.append(np.zeros_like(tri))
+        TP.append(tp); TN.append(tnd)
+    if not V:
+        raise ValueError(f"{path}: the skinned mesh has no triangle primitives")
+    n_targets = len(TP[0])
+    if any(len(tp) != n_targets for tp in TP):
+        raise ValueError(f"{path}: the primitives of the skinned mesh differ in their number of morph targets")
+    verts = np.ascontiguousarray(np.concatenate(V), np.float32)
+    out.rest = SceneData(verts=verts, normals=np.ascontiguousarray(np.concatenate(N), np.float32), tri_material=np.concatenate(TM),
+                         tri_mesh_id=np.ones(len(verts), np.uint32), materials=np.asarray(mats, np.float32), name=out.name)
+    out.joints = np.ascontiguousarray(np.concatenate(J), np.uint16)
+    out.weights = np.ascontiguousarray(np.concatenate(W), np.float32)
+    if n_targets:
+        out.target_positions = np.ascontiguousarray(np.stack([np.concatenate([tp[t] for tp in TP]) for t in range(n_targets)]), np.float32)
+        if normal_deltas:
+            out.target_normals = np.ascontiguousarray(np.stack([np.concatenate([tn[t] for tn in TN]) for t in range(n_targets)]), np.float32)
+        out.default_morph_weights = np.asarray(mesh.get("weights", [0.0] * n_targets), np.float32)
+
+    out.node_parent = [-1] * len(nodes)
+    for i, n in enumerate(nodes):
+        for c in n.get("children", []):
+            out.node_parent[c] = i
+    for i, n in enumerate(nodes):
+        out.node_trs.append([np.asarray(n.get("translation", [0, 0, 0]), np.float64), np.asarray(n.get("rotation", [0, 0, 0, 1]), np.float64),
+                             np.asarray(n.get("scale", [1, 1, 1]), np.float64)])
+        if "matrix" in n:
+            out.node_matrix[i] = np.asarray(n["matrix"], np.float64).reshape(4, 4).T
+    joint_of = {n: j for j, n in enumerate(out.joint_nodes)}
+    for n in out.joint_nodes:
+        p = out.node_parent[n]
+        while p >= 0 and p not in joint_of:
+            p = out.node_parent[p]
+        out.parents.append(joint_of.get(p, -1))
+    if "inverseBindMatrices" in skin:
+        ibm = acc(skin["inverseBindMatrices"], as_float=True)
+        out.inverse_bind = np.ascontiguousarray(ibm.reshape(-1, 4, 4).transpose(0, 2, 1))
+    else:
+        out.inverse_bind = np.tile(np.eye(4), (out.n_joints, 1, 1))
+    if len(out.inverse_bind) != out.n_joints:
+        raise ValueError(f"{path}: {len(out.inverse_bind)} inverse bind matrices for {out.n_joints} joints")
+
+    for k, an in enumerate(doc.get("animations", [])):
+        channels = []
+        for ch in an.get("channels", []):
+            sm, target = an["samplers"][ch["sampler"]], ch["target"]
+            interp = sm.get("interpolation", "LINEAR")
+            if interp == "CUBICSPLINE":
+                raise ValueError(f"{path}: animation {an.get('name', k)!r} uses a CUBICSPLINE sampler: only LINEAR and STEP are supported")
+            if interp not in ("LINEAR", "STEP"):
+                raise ValueError(f"{path}: unknown sampler interpolation {interp!r}")
+            if "node" not in target or target["path"] not in ("translation", "rotation", "scale", "weights"):
+                continue
+            times = acc(sm["input"], as_float=True).reshape(-1)
+            values = acc(sm["output"], as_float=True)
+            if target["path"] == "weights":
+                if target["node"] != skinned[0]:
+                    continue
+                values = values.reshape(len(times), -1)
+            channels.append((int(target["node"]), target["path"], times, values, interp))
+        out.animations[an.get("name", f"animation{k}")] = channels
+    return out

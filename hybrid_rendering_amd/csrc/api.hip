@@ -85,6 +85,7 @@ const char* sample_name_of_stage(const char* stage)
         { "path_trace", "Ground Truth Path Trace" }, { "taa", "TAA" },
         { "env_sh9", "Cubemap SH Projection" }, { "env_prefilter", "Cubemap Prefilter" }, { "env_brdf_lut", "BRDF Integrate LUT" },   // the framework's passes behind hr_env (env.hip)
         { "env_equirect", "Equirectangular To Cubemap" }, { "env_sky", "Sky Model" },   // what fills the env's sky (env_sources.hip)
+        { "skin_pose", "Skinning" },   // hr_skin.h (skinning.hip); the reference has static meshes only
     };
     for (const auto& t : table)
         if (std::strcmp(t.stage, stage) == 0) return t.label;
