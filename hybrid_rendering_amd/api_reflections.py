@@ -41,6 +41,17 @@ class RayTracedReflections(_Pass):
         _check(lib().hr_reflections_render(self.h, scene.h, C.byref(inputs), C.byref(env), ddgi.h, C.byref(self.params), _stream_ptr(stream)),
                "hr_reflections_render")
 
+    # stage-level entry points after the trace (hr_api_stages.h), as RayTracedShadows / RayTracedAO have them
+    def denoise(self, inputs, stream=None):
+        """everything of render() after the trace (the fused launches in tolerance mode)"""
+        _check(lib().hr_reflections_denoise(self.h, C.byref(inputs), C.byref(self.params), _stream_ptr(stream)), "hr_reflections_denoise")
+
+    def temporal(self, inputs, stream=None):
+        _check(lib().hr_reflections_temporal(self.h, C.byref(inputs), C.byref(self.params), _stream_ptr(stream)), "hr_reflections_temporal")
+
+    def upsample(self, inputs, stream=None):
+        _check(lib().hr_reflections_upsample(self.h, C.byref(inputs), C.byref(self.params), _stream_ptr(stream)), "hr_reflections_upsample")
+
     def atrous_iteration(self, inputs, i, stream=None):
         """one iteration of a_trous_filter (ray_traced_reflections.cpp:1143-1256) on the pass's current images: iteration 0 reads the temporal colour image,
         iteration i > 0 the a-trous image iteration i - 1 wrote (IMG_ATROUS1 for even i - 1, IMG_ATROUS0 for odd); writes the other one"""
