@@ -9,6 +9,7 @@
 #include "reproject.h"
 #include "traverse2.h"
 #include "sampling.h"
+#include "shading.h"   // CoopWaveOf
 #include "cutout_host.h"
 #include "mask_window.h"
 #include "upsample.h"
@@ -85,17 +86,8 @@ extern "C" int hr_debug_divergence_ao(uint64_t* out, int reset)
 #ifndef AO_TRACE_WAVES
 #define AO_TRACE_WAVES 1   // waves (8x8 tiles) per workgroup, see k_shadows_trace: finished waves' slots back-fill at once
 #endif
-#ifndef AO_SEQ
-#define AO_SEQ 0    // N: the sample rays of a pixel, N at a time, walked back to back per lane inside ONE wave loop (traverse.h trace_any_seq);
-                    // 0: one wave-level traversal per sample.  Measured (round 3, 4 spp, bit-identical masks): 1080p 395 us (0) / 468 (2) / 498 (4),
-                    // 4K 1303 / 1540 / 1563 — every iteration of the wave pays for the ray switch of whichever lane just finished, and the
-                    // triangle tests lose the wave-cooperative path; kept as a measured A/B path only
-#endif
 #ifndef AO_ORDER
 #define AO_ORDER HR_ORDER_SLOTS   // the short AO rays (97 % of them miss) gain nothing from a visiting order (tools/bvh_eval.cpp): plain slot order, no rev logic
-#endif
-#ifndef AO_COOP
-#define AO_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop) for the AO rays: 0.418 -> 0.399 ms at 1080p, 4 spp
 #endif
 #ifndef AO_COOP2
 #define AO_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane (trace2): 0.557 -> 0.546 ms at
@@ -121,21 +113,17 @@ HR_DEV void ao_store_mask_rows(const AOTraceArgs& a, uint32_t* m, int tx, int ty
 // two-level walk of traverse2.h.  The entry node is a TOP-LEVEL node there: entry_node_for_box stops at the first node with a leaf — an
 // instance — among the children that overlap the ball, and k_ao_entry_grid builds the pass's table with it, so both stay above the mesh trees.
 // <STATS, false> is the kernel as it was.
+// The flat product kernels test triangles wave-cooperatively (traverse.h trace_coop: 0.418 -> 0.399 ms at 1080p, 4 spp, against one ray per lane);
+// STATS: the per-lane walk, which counts node steps and triangle tests.
 // CUTOUT: the walks run the alpha test (cutout.h) through `cv`; the host picks it iff cutout_on(scene, HR_RAY_AO).  Its register bound is its own
 // (AO_TRACE_CUTOUT_EU): the uv and texel addressing do not fit under the opaque kernel's.
 template <bool STATS, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64 * AO_TRACE_WAVES, CUTOUT ? AO_TRACE_CUTOUT_EU : SHARED ? AO_TRACE_SHARED_EU : AO_TRACE_EU) void k_ao_trace(AOTraceArgs a, CutoutView cv)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
-    static_assert(!(STATS && CUTOUT) && !(CUTOUT && AO_SEQ), "no statistics or -DAO_SEQ build of the cutout walks");
-    static_assert(!(SHARED && AO_SEQ), "-DAO_SEQ walks one level: it cannot trace a shared instanced scene");
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     __shared__ uint32_t s_stack[AO_TRACE_WAVES][HR_STACK_ENTRIES * 64];
-#if AO_COOP && !AO_SEQ
-    __shared__ CoopWave s_coop[AO_TRACE_WAVES];
-#endif
-#if AO_COOP2
-    __shared__ CoopWave2 s_coop2[AO_TRACE_WAVES];   // SHARED only: the other instantiation never names it
-#endif
+    __shared__ CoopWaveOf<SHARED> s_coop[AO_TRACE_WAVES];   // the cooperative walks' scratch: an instantiation that walks per lane never names it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * AO_TRACE_WAVES + wave;
     if (launch_slot >= a.tiles_x * a.tiles_y) return;
@@ -181,82 +169,28 @@ __global__ __launch_bounds__(64 * AO_TRACE_WAVES, CUTOUT ? AO_TRACE_CUTOUT_EU : 
         }
         if (!looked_up) entry = entry_node_for_box(a.nodes, mk3(ro.x - r, ro.y - r, ro.z - r), mk3(ro.x + r, ro.y + r, ro.z + r));
     }
-#if AO_SEQ && !defined(HR_DEV_PATHS)
-#error "-DAO_SEQ=N is an A/B path: build with -DHR_DEV_PATHS"
-#endif
-#if AO_SEQ
-    if (!STATS)
-    {
-        // the sample rays of a pixel, AO_SEQ at a time, back to back inside one wave loop (traverse.h trace_any_seq)
-        for (int s0 = 0; s0 < a.spp; s0 += AO_SEQ)
-        {
-            f3 dir[AO_SEQ];
-            const int n = a.spp - s0 < AO_SEQ ? a.spp - s0 : AO_SEQ;
-#pragma unroll
-            for (int k = 0; k < AO_SEQ; k++)
-            {
-                dir[k] = mk3(0.0f, 0.0f, 1.0f);
-                if (active && k < n)
-                {
-                    const int   idx = (int)a.num_frames * a.spp + s0 + k;
-                    const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
-                    dir[k] = sample_cosine_lobe(N, r0, r1);
-                }
-            }
-            float tm[AO_SEQ];
-#pragma unroll
-            for (int k = 0; k < AO_SEQ; k++) tm[k] = a.ray_length;
-            const uint32_t occ = trace_any_seq<AO_SEQ, AO_ORDER>(active, n, a.nodes, a.tris, ro, dir, 0.01f, tm, s_stack[wave], lane, entry HR_DIV(, &dv));
-            for (int k = 0; k < n; k++)
-            {
-                const unsigned long long bits = __ballot(active && !((occ >> k) & 1u));
-                if (lane == 0) ao_store_mask_rows(a, a.mask + (size_t)(s0 + k) * a.mh * a.mw, tx, ty, bits);
-            }
-        }
-    }
-    else
-#endif
     for (int s = 0; s < a.spp; s++)
     {
         bool visible = false;
-        if constexpr (SHARED)
-        {
-            f3 dir = mk3(0.0f, 0.0f, 1.0f);
-            if (active)
-            {
-                const int   idx = (int)a.num_frames * a.spp + s;
-                const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
-                dir = sample_cosine_lobe(N, r0, r1);
-            }
-#if AO_COOP2
-            visible = trace_coop2<true, CUTOUT>(active, { a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop2[wave], lane, entry, cv).prim != 0 && active;
-#else
-            if (active) visible = !trace_any2<CUTOUT>({ a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry, cv);
-#endif
-        }
-        else
-#if AO_COOP && !AO_SEQ
-        if (!STATS)
-        {
-            f3 dir = mk3(0.0f, 0.0f, 1.0f);
-            if (active)
-            {
-                const int   idx = (int)a.num_frames * a.spp + s;
-                const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
-                dir = sample_cosine_lobe(N, r0, r1);
-            }
-            visible = trace_coop<true, AO_ORDER, CUTOUT>(active, a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry, nullptr, cv).prim != 0 && active;
-        }
-        else
-#endif
+        f3   dir = mk3(0.0f, 0.0f, 1.0f);
         if (active)
         {
             const int   idx = (int)a.num_frames * a.spp + s;
             const float r0  = sample_blue_noise(x, y, idx, 0, a.sobol, a.sr), r1 = sample_blue_noise(x, y, idx, 1, a.sobol, a.sr);
-            const f3    dir = sample_cosine_lobe(N, r0, r1);
+            dir = sample_cosine_lobe(N, r0, r1);
+        }
+        // the cooperative walks take the whole wave (lanes without a ray serve as job lanes), the per-lane ones only the lanes with a ray
+        if constexpr (SHARED)
+        {
+            if constexpr (AO_COOP2 != 0) visible = trace_coop2<true, CUTOUT>(active, { a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry, cv).prim != 0 && active;
+            else if (active) visible = !trace_any2<CUTOUT>({ a.nodes, a.tris, a.inst, a.cull }, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, entry, cv);
+        }
+        else if constexpr (!STATS) visible = trace_coop<true, AO_ORDER, CUTOUT>(active, a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], s_coop[wave], lane, entry, nullptr, cv).prim != 0 && active;
+        else if (active)
+        {
             DivCounters* dvp = nullptr;
             HR_DIV(dvp = &dv;)
-            visible         = !trace_any<STATS, AO_ORDER, CUTOUT>(a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, nn, nt, entry, dvp, nullptr, cv);
+            visible = !trace_any<STATS, AO_ORDER, CUTOUT>(a.nodes, a.tris, ro, dir, 0.01f, a.ray_length, s_stack[wave], lane, nn, nt, entry, dvp, nullptr, cv);
         }
         const unsigned long long bits = __ballot(visible);
         if (lane == 0) ao_store_mask_rows(a, a.mask + (size_t)s * a.mh * a.mw, tx, ty, bits);

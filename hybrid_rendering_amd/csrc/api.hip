@@ -309,9 +309,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_raycast(GBufArgs a, MotionArgs 
     const size_t i   = (size_t)y * a.w + x;
     const f3     cam = mk3(a.cam[0], a.cam[1], a.cam[2]);
     const f3     d   = gb_pixel_dir(a, (float)x + 0.5f, (float)y + 0.5f);
-    HitOf<TWO_LEVEL> hit;
-    if constexpr (TWO_LEVEL) hit = trace_closest2<CUTOUT>(Scene2 { a.nodes, a.tris, a.inst, a.cull }, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane, cv);
-    else hit = trace_closest<false, CUTOUT>(a.nodes, a.tris, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane, nullptr, nullptr, nullptr, cv);
+    const HitOf<TWO_LEVEL> hit = trace_closest_of<TWO_LEVEL, CUTOUT>(a.nodes, a.tris, a.inst, a.cull, cam, d, 0.0f, 1.0e30f, s_stack[wave], lane, cv);
     if (hit.prim < 0)
     {
         a.gb1[i]   = 0u;

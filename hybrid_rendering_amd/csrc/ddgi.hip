@@ -51,14 +51,6 @@ extern "C" int hr_debug_divergence_ddgi(uint64_t* out, int reset)
 #ifndef DDGI_TRACE_WAVES
 #define DDGI_TRACE_WAVES 1
 #endif
-#ifndef DDGI_SEQ
-#define DDGI_SEQ 0   // 1: the two visibility rays of a hit point as ONE lane-sequential wave loop (traverse.h trace_any_seq) instead of two wave-level
-                     // traversals.  Measured (round 3, 16x8x16x256, bit-identical atlases): 322.4 us vs 324.3 — the ray LENGTHS are heavy-tailed, one
-                     // straggler ray per wave sets the wave's time whether the other lanes' rays are summed or not; kept as a measured A/B path
-#endif
-#ifndef DDGI_COOP
-#define DDGI_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop); 0 = the per-lane loops
-#endif
 #ifndef DDGI_COOP2
 #define DDGI_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane: 0.400 -> 0.351 ms
 #endif                 // (16x8x16 probes, 256 rays, 201 instances; docs/EXPERIMENTS.md), images bit-identical
@@ -82,15 +74,9 @@ template <bool STATS, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_EU : SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow)
 {
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
-    static_assert(!(STATS && CUTOUT) && !(CUTOUT && DDGI_SEQ), "no statistics or -DDDGI_SEQ build of the cutout walks");
-    static_assert(!(SHARED && DDGI_SEQ), "-DDDGI_SEQ walks one level: it cannot trace a shared instanced scene");
+    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     __shared__ uint32_t s_stack[DDGI_TRACE_WAVES][HR_STACK_ENTRIES * 64];
-#if DDGI_COOP
-    __shared__ CoopWave s_coop[DDGI_TRACE_WAVES];
-#endif
-#if DDGI_COOP2
-    __shared__ CoopWave2 s_coop2[DDGI_TRACE_WAVES];   // SHARED only: the other instantiation never names it
-#endif
+    __shared__ CoopWaveOf<SHARED> s_coop[DDGI_TRACE_WAVES];   // the cooperative walks' scratch: an instantiation that walks per lane never names it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int R = a.d.rays_per_probe;
     const long long gid = (long long)blockIdx.x * (64 * DDGI_TRACE_WAVES) + threadIdx.x;
@@ -109,34 +95,20 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_E
     }
     uint32_t st_n = 0, st_t = 0;
     HitOf<SHARED> h;
-    if constexpr (SHARED)
+    // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
+    // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
+    if constexpr (STATS || (SHARED && !DDGI_COOP2))
     {
-        // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
-        // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
-#if DDGI_COOP2
-        h = trace_coop2<false, CUTOUT>(valid, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane, 0u, cv_gi);
-#else
+        // the per-lane walks (the statistics kernel, the perlane2 variant) take only the lanes with a ray.  This guard stays in the kernel:
+        // behind a function that every lane enters, these kernels' code moves (docs/EXPERIMENTS.md, "One walk call per ray")
         h.prim = -1;
-        if (valid) h = trace_closest2<CUTOUT>({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI] }, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_gi);
-#endif
-    }
-    else
-    {
-#if DDGI_COOP
-        if constexpr (CUTOUT) h = trace_coop<false, HR_ORDER_NEAR, true>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv_gi);
-        else if (!STATS) h = trace_coop<false>(valid, a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
-        else
+        if (valid)
         {
-            h.prim = -1;
-            if (valid) h = trace_closest<STATS>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+            if constexpr (STATS) h = trace_closest<true>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+            else h = trace_closest_of<SHARED, CUTOUT>(a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI], origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_gi);
         }
-#else
-        h.prim = -1;
-        DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
-        HR_DIV(dvp_ptr = &dvp;)
-        if (valid) h = trace_closest<STATS, CUTOUT>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t, cv_gi);
-#endif
     }
+    else h = trace_closest_wave<SHARED, CUTOUT>(valid, a.nodes, a.tris, a.sh, HR_RAY_GI, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, cv_gi HR_DIV(, &dvp));
     if (valid)
     {
         Rng   rng = rng_init((uint32_t)ray, (uint32_t)probe, a.num_frames);
@@ -157,25 +129,8 @@ __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_E
             TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
             if constexpr (CUTOUT) tc.cv = cv_shadow;
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
-#if DDGI_SEQ && !defined(HR_DEV_PATHS)
-#error "-DDDGI_SEQ=1 is an A/B path: build with -DHR_DEV_PATHS"
-#endif
-#if DDGI_SEQ
-            // the light ray and the sky ray of the hit point back to back per lane inside ONE wave loop (traverse.h trace_any_seq) instead of
-            // two wave-level traversals; the visibilities enter direct_lighting's result exactly as in shading.h DirectSplit
-            const DirectSplit ds = direct_lighting_split(a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky);
-            const f3    sdir[2] = { ds.ray1 ? ds.Wi1 : ds.Wi2, ds.Wi2 };
-            const float stm[2]  = { ds.ray1 ? ds.t_max1 : 10000.0f, 10000.0f };
-            const int   nsec    = ds.ray1 ? 2 : 1;
-            rays += (uint32_t)nsec;
-            const uint32_t occ = trace_any_seq<2>(true, nsec, a.nodes, a.tris, ds.origin, sdir, 0.01f, stm, s_stack[wave], lane, 0u HR_DIV(, &dvs));
-            const bool o1 = ds.ray1 && (occ & 1u), o2 = ds.ray1 ? ((occ >> 1) & 1u) != 0u : (occ & 1u) != 0u;
-            f3 Lo = o1 ? mk3(0.0f, 0.0f, 0.0f) : ds.P1;
-            if (!o2) Lo = add3(Lo, ds.P2);
-#else
             f3 Lo = direct_lighting<STATS, CUTOUT>(tc, a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
-#endif
 #ifndef HR_ABL_DDGI_NO_IRRADIANCE
             if (a.infinite_bounces == 1)
 #else

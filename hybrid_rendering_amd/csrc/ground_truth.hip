@@ -70,17 +70,12 @@ __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a, CutoutView cv_pri
         {
             adds[depth] = mk3(0.0f, 0.0f, 0.0f);
             rays++;
+            // the camera ray, then the bounces: their own ray classes (tc's is the visibility rays').  The view and the cull mask are picked only
+            // where they are read: picking them in every instantiation changes the code of the INDIRECT kernels (docs/EXPERIMENTS.md, "One walk call per ray")
+            CutoutView cv;
+            if constexpr (CUTOUT) cv = depth == 0 ? cv_primary : cv_gi;
             HitOf<SHARED> h;
-            if constexpr (CUTOUT)
-            {
-                const CutoutView cv = depth == 0 ? cv_primary : cv_gi;
-                if constexpr (SHARED)
-                    h = trace_closest2<true>(Scene2 { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] }, o, d, t_min, 10000.0f, s_stack, lane, cv);
-                else h = trace_closest<false, true>(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane, nullptr, nullptr, nullptr, cv);
-            }
-            else if constexpr (SHARED)   // the camera ray, then the bounces: their own ray classes (tc's is the visibility rays')
-                h = trace_closest2(Scene2 { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] }, o, d, t_min, 10000.0f, s_stack, lane);
-            else h = trace_closest(a.nodes, a.tris, o, d, t_min, 10000.0f, s_stack, lane);
+            h = trace_closest_of<SHARED, CUTOUT>(a.nodes, a.tris, a.sh.inst_shared, SHARED ? a.sh.cull[depth == 0 ? HR_RAY_PRIMARY : HR_RAY_GI] : 0u, o, d, t_min, 10000.0f, s_stack, lane, cv);
             if (h.prim < 0)
             {
                 const f3 env = a.sky.fetch(d);

@@ -60,9 +60,6 @@ extern "C" int hr_debug_divergence_refl(uint64_t* out, int reset)
 #ifndef REFL_TRACE_WAVES
 #define REFL_TRACE_WAVES 1
 #endif
-#ifndef REFL_COOP
-#define REFL_COOP 1   // wave-cooperative triangle tests (traverse.h trace_coop); 0 = the per-lane loops
-#endif
 #ifndef REFL_COOP2
 #define REFL_COOP2 1   // SHARED: wave-cooperative triangle tests on two levels (traverse2.h trace_coop2); 0 = one ray per lane: 0.239 -> 0.188 ms
 #endif                 // (half of 1080p, 201 instances; docs/EXPERIMENTS.md), trace image bit-identical
@@ -89,12 +86,7 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
     static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
     static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
     __shared__ uint32_t s_stack[REFL_TRACE_WAVES][HR_STACK_ENTRIES * 64];
-#if REFL_COOP
-    __shared__ CoopWave s_coop[REFL_TRACE_WAVES];
-#endif
-#if REFL_COOP2
-    __shared__ CoopWave2 s_coop2[REFL_TRACE_WAVES];   // SHARED only: the other instantiation never names it
-#endif
+    __shared__ CoopWaveOf<SHARED> s_coop[REFL_TRACE_WAVES];   // the cooperative walks' scratch: an instantiation that walks per lane never names it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int launch_slot = blockIdx.x * REFL_TRACE_WAVES + wave;
     if (launch_slot >= a.tiles_x * a.tiles_y) return;   // wave-uniform
@@ -144,34 +136,19 @@ __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_t
     if (trace) rays++;
     uint32_t st_n = 0, st_t = 0;
     HitOf<SHARED> hit;
-    if constexpr (SHARED)
+    // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
+    // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
+    if constexpr (STATS || (SHARED && !REFL_COOP2))
     {
-        // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
-        // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
-#if REFL_COOP2
-        hit = trace_coop2<false, CUTOUT>(trace, { a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop2[wave], lane, 0u, cv_refl);
-#else
+        // the per-lane walks take only the lanes with a ray; the guard stays in the kernel (see k_ddgi_trace)
         hit.prim = -1;
-        if (trace) hit = trace_closest2<CUTOUT>({ a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION] }, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_refl);
-#endif
-    }
-    else
-    {
-#if REFL_COOP
-        if constexpr (CUTOUT) hit = trace_coop<false, HR_ORDER_NEAR, true>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u, nullptr, cv_refl);
-        else if (!STATS) hit = trace_coop<false>(trace, a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, 0u HR_DIV(, &dvp));
-        else
+        if (trace)
         {
-            hit.prim = -1;
-            if (trace) hit = trace_closest<STATS>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+            if constexpr (STATS) hit = trace_closest<true>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
+            else hit = trace_closest_of<SHARED, CUTOUT>(a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_REFLECTION], ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_refl);
         }
-#else
-        hit.prim = -1;
-        DivCounters* dvp_ptr = nullptr;   // (without HR_TRACE_DIVERGENCE the HR_DIV() argument vanished and &st_n slid into the `dv` slot)
-        HR_DIV(dvp_ptr = &dvp;)
-        if (trace) hit = trace_closest<STATS, CUTOUT>(a.nodes, a.tris, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, dvp_ptr, &st_n, &st_t, cv_refl);
-#endif
     }
+    else hit = trace_closest_wave<SHARED, CUTOUT>(trace, a.nodes, a.tris, a.sh, HR_RAY_REFLECTION, ray_origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, cv_refl HR_DIV(, &dvp));
     if (trace)
     {
         if (hit.prim < 0) { color = a.env.sky.fetch(dir); ray_length = -1.0f; }

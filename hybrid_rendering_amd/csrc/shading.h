@@ -701,11 +701,33 @@ HR_DEV bool visibility_ray_occluded(TraceCtx2& tc, f3 o, f3 d, float t_min, floa
 // what a kernel templated on TWO_LEVEL (a shared instanced scene) walks with and gets back
 template <bool TWO_LEVEL> using TraceCtxOf = typename std::conditional<TWO_LEVEL, TraceCtx2, TraceCtx>::type;
 template <bool TWO_LEVEL> using HitOf      = typename std::conditional<TWO_LEVEL, Hit2, HitRec>::type;
+template <bool TWO_LEVEL> using CoopWaveOf = typename std::conditional<TWO_LEVEL, CoopWave2, CoopWave>::type;
 template <bool TWO_LEVEL>
 HR_DEV TraceCtxOf<TWO_LEVEL> make_trace_ctx(const Node8* nodes, const TriGPU* tris, const SceneShading& sh, uint32_t* wave_stack, int lane)
 {
     if constexpr (TWO_LEVEL) return TraceCtx2 { Scene2 { nodes, tris, sh.inst_shared, sh.cull[HR_RAY_SHADOW] }, wave_stack, lane };
     else return TraceCtx { nodes, tris, wave_stack, lane };
+}
+
+// Closest hit of the lane's own ray, walked per lane (the wave may be diverged).  `inst` and `cull` (the ray class's cull mask) are read iff
+// TWO_LEVEL, `cv` iff CUTOUT.
+template <bool TWO_LEVEL, bool CUTOUT>
+HR_DEV HitOf<TWO_LEVEL> trace_closest_of(const Node8* nodes, const TriGPU* tris, const InstanceShared* inst, uint32_t cull, f3 o, f3 d, float t_min, float t_max,
+                                         uint32_t* wave_stack, int lane, const CutoutView& cv)
+{
+    if constexpr (TWO_LEVEL) return trace_closest2<CUTOUT>(Scene2 { nodes, tris, inst, cull }, o, d, t_min, t_max, wave_stack, lane, cv);
+    else return trace_closest<false, CUTOUT>(nodes, tris, o, d, t_min, t_max, wave_stack, lane, nullptr, nullptr, nullptr, cv);
+}
+
+// Closest hit of the wave's primary rays, one per lane that has one (`want`), walked by the whole wave: the lanes without a ray serve the
+// cooperative triangle tests, so the caller keeps the wave converged around the call.  `ray_class` picks the cull mask of a two-level scene.
+// The cutout and the two-level walks count nothing into `dv`.
+template <bool TWO_LEVEL, bool CUTOUT>
+HR_DEV HitOf<TWO_LEVEL> trace_closest_wave(bool want, const Node8* nodes, const TriGPU* tris, const SceneShading& sh, int ray_class, f3 o, f3 d, float t_min, float t_max,
+                                           uint32_t* wave_stack, CoopWaveOf<TWO_LEVEL>& cw, int lane, const CutoutView& cv, DivCounters* dv = nullptr)
+{
+    if constexpr (TWO_LEVEL) return trace_coop2<false, CUTOUT>(want, { nodes, tris, sh.inst_shared, sh.cull[ray_class] }, o, d, t_min, t_max, wave_stack, cw, lane, 0u, cv);
+    else return trace_coop<false, HR_ORDER_NEAR, CUTOUT>(want, nodes, tris, o, d, t_min, t_max, wave_stack, cw, lane, 0u, CUTOUT ? nullptr : dv, cv);
 }
 
 // direct_lighting (lighting.glsl:117-196); Ctx: TraceCtx or TraceCtx2
@@ -746,7 +768,7 @@ HR_DEV f3 direct_lighting(Ctx& tc, const hr_light& light, f3 Wo, f3 N, f3 P, f3 
     return Lo;
 }
 
-#ifdef HR_DEV_PATHS   // only the A/B paths that lost use it (ddgi.hip wavefront kernels, -DDDGI_SEQ)
+#ifdef HR_DEV_PATHS   // only the A/B paths that lost use it (ddgi.hip wavefront kernels)
 // direct_lighting split for the wavefront path (trace_queue.h): everything but the two visibility rays.  With occlusion o1 / o2 of
 // the light ray and the sky ray known, direct_lighting's result is, operation for operation,
 //     Lo = (ray1 && o1) ? 0 : P1;   if (sky && !o2) Lo = Lo + P2;
