@@ -41,7 +41,12 @@ class RayTracedReflections(_Pass):
         _check(lib().hr_reflections_render(self.h, scene.h, C.byref(inputs), C.byref(env), ddgi.h, C.byref(self.params), _stream_ptr(stream)),
                "hr_reflections_render")
 
-    # stage-level entry points after the trace (hr_api_stages.h), as RayTracedShadows / RayTracedAO have them
+    # stage-level entry points (hr_api_stages.h), as RayTracedShadows / RayTracedAO have them
+    def ray_trace(self, scene, inputs, env, ddgi, stream=None):
+        """the trace stage alone: writes IMG_TRACE and the ray counters"""
+        _check(lib().hr_reflections_ray_trace(self.h, scene.h, C.byref(inputs), C.byref(env), ddgi.h, C.byref(self.params), _stream_ptr(stream)),
+               "hr_reflections_ray_trace")
+
     def denoise(self, inputs, stream=None):
         """everything of render() after the trace (the fused launches in tolerance mode)"""
         _check(lib().hr_reflections_denoise(self.h, C.byref(inputs), C.byref(self.params), _stream_ptr(stream)), "hr_reflections_denoise")

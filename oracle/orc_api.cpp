@@ -79,6 +79,8 @@ void orc_scene_set_instances(void* scene, int n_instances, const float* matrices
 }
 void orc_scene_destroy(void* scene) { delete (Scene*)scene; }
 int  orc_scene_num_nodes(const void* scene) { return (int)((const Scene*)scene)->nodes.size(); }
+// on != 0: every query of this scene, those of the passes' hit shaders included, tests every triangle (tests/closest_cases.py)
+void orc_scene_set_brute_force(void* scene, int on) { ((Scene*)scene)->brute_force = on != 0; }
 
 // single-ray entry points: the ray-query / traceRay mock of oracle/refshim calls these through a function pointer
 int orc_any_hit_one(void* scene, const float* o, const float* d, float t_min, float t_max)

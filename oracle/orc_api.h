@@ -27,6 +27,9 @@ void     orc_scene_set_instances(void* scene, int n_instances, const float* matr
                                  const float* mesh_uvs, const float* mesh_tangents);
 void     orc_scene_destroy(void* scene);
 int      orc_scene_num_nodes(const void* scene);
+// Test switch, off by default: Scene::any_hit / closest_hit dispatch to their brute-force versions (no box test at all), for every caller —
+// the batch queries and the whole of orc_reflections_ray_trace / orc_ddgi_ray_trace (primary rays, the hit shader's light and sky rays).
+void     orc_scene_set_brute_force(void* scene, int on);
 // rays: [n][8] = origin xyz, t_max, dir xyz, t_min.  out: [n] uint8 (1 = occluded).
 int      orc_any_hit_one(void* scene, const float* o, const float* d, float t_min, float t_max);
 int      orc_closest_hit_one(void* scene, const float* o, const float* d, float t_min, float t_max, float* tuv /*[3]*/);
@@ -73,6 +76,12 @@ void orc_ao_blur(int w, int h, const uint16_t* in_ao, const float* depth, const 
 void orc_ddgi_ray_trace(const void* scene, const void* ubo, const void* ddgi, const float* orientation, uint32_t num_frames,
                         int infinite_bounces, float gi_intensity, const uint16_t* sky, int sky_size, const uint16_t* prev_irradiance,
                         const uint16_t* prev_depth, uint16_t* radiance, uint16_t* direction_distance, uint64_t* rays_out);
+// the same for the probes probe_begin .. probe_end - 1 only (a z-slab shard); the other probes' texels are left untouched
+void orc_ddgi_ray_trace_range(const void* scene, const void* ubo, const void* ddgi, const float* orientation, uint32_t num_frames,
+                              int infinite_bounces, float gi_intensity, const uint16_t* sky, int sky_size, const uint16_t* prev_irradiance,
+                              const uint16_t* prev_depth, int probe_begin, int probe_end, uint16_t* radiance, uint16_t* direction_distance, uint64_t* rays_out);
+// rays: [n_probes][rays_per_probe][8] = origin, t_max (10000), direction, t_min (0.001): the layout of orc_closest_hit_batch
+void orc_ddgi_gen_rays(const void* ddgi, const float* orientation, float* rays);
 void orc_ddgi_probe_update(const void* ddgi, int depth_probe, int first_frame, const uint16_t* radiance, const uint16_t* direction_distance,
                            const uint16_t* prev_atlas, uint16_t* out_atlas);
 void orc_ddgi_border_update(const void* ddgi, int depth_probe, uint16_t* atlas);
@@ -91,6 +100,9 @@ void orc_reflections_ray_trace(const void* scene, const void* ubo, const void* d
                                const uint16_t* gb3, const uint8_t* sobol, const uint8_t* scrambling_ranking, const orc_refl_trace_params* prm,
                                const uint16_t* sky, int sky_size, const uint16_t* prefiltered, int pre_size, int pre_levels, const uint16_t* lut,
                                int lut_size, const uint16_t* irradiance, const uint16_t* depth_atlas, uint16_t* out, uint64_t* rays_out);
+// rays: [ceil(h/8)*8][ceil(w/8)*8][8] = origin, regime (0 sky, 1 mirror, 2 GGX, 3 DDGI-rough, -1 no thread), direction, traced (1 / 0)
+void orc_reflections_gen_rays(const void* ubo, int w, int h, const float* depth, const uint16_t* gb2, const uint16_t* gb3, const uint8_t* sobol,
+                              const uint8_t* scrambling_ranking, const orc_refl_trace_params* prm, float* rays);
 void orc_reflections_temporal(const void* ubo, int w, int h, const uint16_t* input, const float* depth, const uint16_t* gb2, const uint16_t* gb3,
                               const float* prev_depth, const uint16_t* prev_gb2, const uint16_t* prev_gb3, const uint16_t* hist_color,
                               const uint16_t* hist_moments, const float* camera_delta, float alpha, float moments_alpha, int approximate_with_ddgi,

@@ -101,6 +101,8 @@ void Scene::build(const float* verts, int n_tris)
         {
             float ext = cb.hi[a] - cb.lo[a];
             if (!(ext > 0.0f)) continue;
+            // a denormal extent (centroids a few ulps of 0 apart) makes NB / ext infinite and 0 * inf a NaN bin index: no split on this axis
+            if (!std::isfinite((float)NB / ext)) continue;
             AABB bb[NB];
             int  bc[NB];
             for (int b = 0; b < NB; b++) { bb[b].reset(); bc[b] = 0; }
@@ -178,6 +180,7 @@ static inline bool slab(const BVH2Node& n, vec3 o, vec3 id, float t_min, float t
 
 bool Scene::any_hit(vec3 o, vec3 d, float t_min, float t_max) const
 {
+    if (brute_force) return any_hit_brute(o, d, t_min, t_max);
     if (nodes.empty()) return false;
     RayPre r  = ray_prepare(o, d);
     vec3   id = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
@@ -218,6 +221,7 @@ bool Scene::any_hit_brute(vec3 o, vec3 d, float t_min, float t_max) const
 // closest hit: smallest t; ties broken by the smallest original triangle index.
 Hit Scene::closest_hit(vec3 o, vec3 d, float t_min, float t_max) const
 {
+    if (brute_force) return closest_hit_brute(o, d, t_min, t_max);
     Hit best { t_max, 0, 0, -1 };
     if (nodes.empty()) return best;
     RayPre r  = ray_prepare(o, d);

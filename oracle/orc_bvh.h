@@ -122,6 +122,10 @@ struct Scene
     std::vector<float>    mesh_positions, mesh_normals, mesh_uvs, mesh_tangents;
     std::vector<uint32_t> mesh_material;
 
+    // test switch (orc_scene_set_brute_force): any_hit / closest_hit dispatch to the _brute versions, so that a whole pass — primary rays, the
+    // hit shader's light and sky rays — runs without a box test of any kind.  Off by default.
+    bool brute_force = false;
+
     void build(const float* verts, int n_tris);
     bool any_hit(vec3 o, vec3 d, float t_min, float t_max) const;
     bool any_hit_brute(vec3 o, vec3 d, float t_min, float t_max) const;

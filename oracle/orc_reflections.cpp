@@ -21,6 +21,45 @@ namespace orc {
 
 // reflect3, importance_sample_ggx, EnvMaps: orc_shading.h
 
+// The ray set-up of one pixel (reflections_ray_trace.rgen:119-160): ONE body for orc_reflections_ray_trace and orc_reflections_gen_rays, so
+// that the rays a test aims its geometry at are the rays the pass traces.  regime: 0 sky (depth == 1), 1 mirror (roughness < 0.05),
+// 2 GGX sample, 3 rough pixel answered by the probe grid (roughness > 0.75 with approximate_with_ddgi; `dir` is then the gather's direction).
+enum { REFL_SKY = 0, REFL_MIRROR = 1, REFL_GGX = 2, REFL_DDGI_ROUGH = 3 };
+struct ReflPixelRay
+{
+    int  regime;
+    bool trace;
+    vec3 P, Wo, origin, dir;
+};
+static inline ReflPixelRay refl_pixel_ray(const UBO& ubo, int w, int h, const float* depth, const ImgH<4>& g2, const ImgH<4>& g3, const BlueNoise& bn,
+                                          const orc_refl_trace_params* prm, int x, int y)
+{
+    ReflPixelRay r;
+    r.regime = REFL_SKY; r.trace = false;
+    r.P = r.Wo = r.origin = r.dir = v3(0, 0, 0);
+    const float dp = depth[(size_t)y * w + x];
+    if (dp == 1.0f) return r;
+    const float roughness = g3.fetch(x, y, 0);
+    const float tu = ((float)x + 0.5f) / (float)w, tv = ((float)y + 0.5f) / (float)h;
+    const vec3  P  = world_position_from_depth(tu, tv, dp, ubo.view_proj_inverse);
+    const vec3  N  = octohedral_to_direction(g2.fetch(x, y, 0), g2.fetch(x, y, 1));
+    const vec3  Wo = normalize(v3(ubo.cam_pos[0], ubo.cam_pos[1], ubo.cam_pos[2]) - P);
+    r.P = P; r.Wo = Wo;
+    r.origin = P + N * prm->bias;
+    if (roughness < 0.05f) { r.dir = reflect3(-Wo, N); r.trace = true; r.regime = REFL_MIRROR; }
+    else if (roughness > 0.75f && prm->approximate_with_ddgi == 1) { r.dir = reflect3(-Wo, N); r.regime = REFL_DDGI_ROUGH; }
+    else
+    {
+        float r0 = sample_blue_noise(x, y, (int)prm->num_frames, 0, bn) * prm->trim;
+        float r1 = sample_blue_noise(x, y, (int)prm->num_frames, 1, bn) * prm->trim;
+        vec3  Wh = importance_sample_ggx(r0, r1, N, roughness);
+        r.dir    = reflect3(-Wo, Wh);
+        r.trace  = true;
+        r.regime = REFL_GGX;
+    }
+    return r;
+}
+
 } // namespace orc
 
 extern "C" {
@@ -43,32 +82,13 @@ void orc_reflections_ray_trace(const void* scene_, const void* ubo_, const void*
         for (int x = 0; x < w; x++)
         {
             uint16_t*   o  = out + ((size_t)y * w + x) * 4;
-            const float dp = depth[(size_t)y * w + x];
-            if (dp == 1.0f) { o[0] = o[1] = o[2] = 0; o[3] = f32_to_f16(-1.0f); continue; }
-            const float roughness = g3.fetch(x, y, 0);
-            const float tu = ((float)x + 0.5f) / (float)w, tv = ((float)y + 0.5f) / (float)h;
-            const vec3  P  = world_position_from_depth(tu, tv, dp, ubo.view_proj_inverse);
-            const vec3  N  = octohedral_to_direction(g2.fetch(x, y, 0), g2.fetch(x, y, 1));
-            const vec3  Wo = normalize(v3(ubo.cam_pos[0], ubo.cam_pos[1], ubo.cam_pos[2]) - P);
-            const vec3  ray_origin = P + N * prm->bias;
+            const ReflPixelRay pr = refl_pixel_ray(ubo, w, h, depth, g2, g3, bn, prm, x, y);
+            if (pr.regime == REFL_SKY) { o[0] = o[1] = o[2] = 0; o[3] = f32_to_f16(-1.0f); continue; }
+            const vec3  ray_origin = pr.origin, dir = pr.dir;
+            const bool  trace = pr.trace;
             vec3  color = v3(0, 0, 0);
             float ray_length = -1.0f;
-            bool  trace = false;
-            vec3  dir = v3(0, 0, 0);
-            if (roughness < 0.05f) { dir = reflect3(-Wo, N); trace = true; }
-            else if (roughness > 0.75f && prm->approximate_with_ddgi == 1)
-            {
-                vec3 R = reflect3(-Wo, N);
-                color  = prm->rough_ddgi_intensity * sample_irradiance(d, P, R, Wo, irradiance, depth_atlas);
-            }
-            else
-            {
-                float r0 = sample_blue_noise(x, y, (int)prm->num_frames, 0, bn) * prm->trim;
-                float r1 = sample_blue_noise(x, y, (int)prm->num_frames, 1, bn) * prm->trim;
-                vec3  Wh = importance_sample_ggx(r0, r1, N, roughness);
-                dir      = reflect3(-Wo, Wh);
-                trace    = true;
-            }
+            if (pr.regime == REFL_DDGI_ROUGH) color = prm->rough_ddgi_intensity * sample_irradiance(d, pr.P, pr.dir, pr.Wo, irradiance, depth_atlas);
             if (trace)
             {
                 rays++;
@@ -101,6 +121,28 @@ void orc_reflections_ray_trace(const void* scene_, const void* ubo_, const void*
             o[3] = f32_to_f16(ray_length);
         }
     if (rays_out) *rays_out = rays;
+}
+
+// The rays of R1, for every thread of the padded 8x8 tile grid: rays [ceil(h/8)*8][ceil(w/8)*8][8] = origin xyz, regime (REFL_SKY .. REFL_DDGI_ROUGH
+// as a float; -1: "no thread", a lane of a ragged tile outside the image — it sets up no ray, whatever the walk borrows it for), direction xyz,
+// traced (1 / 0).  The same per-pixel body as orc_reflections_ray_trace.
+void orc_reflections_gen_rays(const void* ubo_, int w, int h, const float* depth, const uint16_t* gb2, const uint16_t* gb3, const uint8_t* sobol,
+                              const uint8_t* scrambling_ranking, const orc_refl_trace_params* prm, float* rays)
+{
+    const UBO& ubo = *(const UBO*)ubo_;
+    BlueNoise  bn { sobol, scrambling_ranking };
+    ImgH<4>    g2 { gb2, w, h }, g3 { gb3, w, h };
+    const int  ph = ceil_div(h, 8) * 8, pw = ceil_div(w, 8) * 8;
+    for (int y = 0; y < ph; y++)
+        for (int x = 0; x < pw; x++)
+        {
+            float* o = rays + ((size_t)y * pw + x) * 8;
+            for (int k = 0; k < 8; k++) o[k] = 0.0f;
+            if (x >= w || y >= h) { o[3] = -1.0f; continue; }
+            const ReflPixelRay pr = refl_pixel_ray(ubo, w, h, depth, g2, g3, bn, prm, x, y);
+            o[0] = pr.origin.x; o[1] = pr.origin.y; o[2] = pr.origin.z; o[3] = (float)pr.regime;
+            o[4] = pr.dir.x; o[5] = pr.dir.y; o[6] = pr.dir.z; o[7] = pr.trace ? 1.0f : 0.0f;
+        }
 }
 
 // R3.  input RGBA16F (R1 output); history colour RGBA16F, history moments RGBA16F.

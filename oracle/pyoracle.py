@@ -283,6 +283,11 @@ class Scene:
     def num_nodes(self):
         return lib().orc_scene_num_nodes(self.h)
 
+    def set_brute_force(self, on=True):
+        """every query of this scene, the passes' own (primary rays, the hit shaders' light and sky rays) included, tests every triangle"""
+        lib().orc_scene_set_brute_force(self.h, C.c_int(int(bool(on))))
+        return self
+
     def any_hit(self, rays: np.ndarray, brute_force=False, stats=False):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         out = np.zeros(len(rays), np.uint8)

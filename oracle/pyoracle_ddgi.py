@@ -13,17 +13,27 @@ def _ddgi_ptr(u: np.ndarray):
     return C.c_void_p(u.ctypes.data)
 
 
-def ray_trace(scene, ubo, ddgi, orientation, num_frames, infinite_bounces, gi_intensity, sky, prev_irr, prev_depth):
+def ray_trace(scene, ubo, ddgi, orientation, num_frames, infinite_bounces, gi_intensity, sky, prev_irr, prev_depth, probes=None, fill=0):
+    """probes = (begin, end): only those probes are traced (a z-slab shard) and the other probes' texels keep `fill`"""
     n_probes = int(np.prod(ddgi["probe_counts"]))
     R = int(ddgi["rays_per_probe"])
-    rad = np.zeros((n_probes, R, 4), np.uint16)
-    dd = np.zeros((n_probes, R, 4), np.uint16)
+    rad = np.full((n_probes, R, 4), fill, np.uint16)
+    dd = np.full((n_probes, R, 4), fill, np.uint16)
     rays = C.c_uint64(0)
     orientation = np.ascontiguousarray(orientation, np.float32)
-    lib().orc_ddgi_ray_trace(scene.h, _ubo_ptr(ubo), _ddgi_ptr(ddgi), _p(orientation, c_f32p), C.c_uint32(num_frames), C.c_int(int(infinite_bounces)),
-                             C.c_float(gi_intensity), _p(sky, c_u16p), C.c_int(sky.shape[1]), _p(prev_irr, c_u16p), _p(prev_depth, c_u16p),
-                             _p(rad, c_u16p), _p(dd, c_u16p), C.byref(rays))
+    b, e = (0, n_probes) if probes is None else probes
+    lib().orc_ddgi_ray_trace_range(scene.h, _ubo_ptr(ubo), _ddgi_ptr(ddgi), _p(orientation, c_f32p), C.c_uint32(num_frames), C.c_int(int(infinite_bounces)),
+                                   C.c_float(gi_intensity), _p(sky, c_u16p), C.c_int(sky.shape[1]), _p(prev_irr, c_u16p), _p(prev_depth, c_u16p),
+                                   C.c_int(int(b)), C.c_int(int(e)), _p(rad, c_u16p), _p(dd, c_u16p), C.byref(rays))
     return rad, dd, rays.value
+
+
+def gen_rays(ddgi, orientation):
+    """[n_probes][rays_per_probe][8]: origin, t_max, direction, t_min of every probe ray, by the body ray_trace() runs (a closest_hit batch as it is)"""
+    rays = np.zeros((int(np.prod(ddgi["probe_counts"])), int(ddgi["rays_per_probe"]), 8), np.float32)
+    orientation = np.ascontiguousarray(orientation, np.float32)
+    lib().orc_ddgi_gen_rays(_ddgi_ptr(ddgi), _p(orientation, c_f32p), _p(rays, c_f32p))
+    return rays
 
 
 def probe_update(ddgi, depth_probe, first_frame, rad, dd, prev_atlas):

@@ -25,6 +25,19 @@ def ray_trace(scene, ubo, ddgi, cur, sobol, sr, prm: TraceParams, env, irr, dep)
     return out, rays.value
 
 
+SKY, MIRROR, GGX, DDGI_ROUGH, NO_THREAD = 0, 1, 2, 3, -1
+
+
+def gen_rays(ubo, cur, sobol, sr, prm: TraceParams):
+    """[ceil(h/8)*8][ceil(w/8)*8][8]: origin, regime (SKY .. DDGI_ROUGH; NO_THREAD for the lanes of a ragged tile outside the image), direction,
+    traced (1 / 0) of every thread of the trace dispatch, by the per-pixel body ray_trace() runs"""
+    h, w = cur["depth"].shape
+    rays = np.zeros((((h + 7) // 8) * 8, ((w + 7) // 8) * 8, 8), np.float32)
+    lib().orc_reflections_gen_rays(_ubo_ptr(ubo), C.c_int(w), C.c_int(h), _p(cur["depth"], c_f32p), _p(cur["gb2"], c_u16p), _p(cur["gb3"], c_u16p),
+                                   _p(sobol, c_u8p), _p(sr, c_u8p), C.byref(prm), _p(rays, c_f32p))
+    return rays
+
+
 def temporal(ubo, inp, cur, prev, hist_color, hist_moments, camera_delta, alpha, moments_alpha, approx):
     h, w = cur["depth"].shape
     oc, om = np.zeros((h, w, 4), np.uint16), np.zeros((h, w, 4), np.uint16)

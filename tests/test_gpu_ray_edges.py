@@ -8,7 +8,8 @@ budget is DESIGN.md section 3.3 — these tests are what holds a change of ray_p
 
 Not covered here, but in tests/test_gpu_trace_gbuffer_edges.py: the shadow and AO passes' own trace kernels (ray set-up from the G-buffer,
 fire / no-fire decisions, edge threads, the occluder cache's per-lane triangle test, the AO entry-node table) on synthesised G-buffers
-whose pixel rays run through triangle edges, vertices and box planes — pinned to the same brute force."""
+whose pixel rays run through triangle edges, vertices and box planes — pinned to the same brute force.
+The two closest-hit launches (k_ddgi_trace, k_refl_trace) and the probe update: tests/test_gpu_closest_edges.py, tests/test_gpu_probe_update_edges.py."""
 import numpy as np
 import pytest
 

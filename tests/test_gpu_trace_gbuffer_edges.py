@@ -9,6 +9,7 @@ a sample ray along the axis, a flat occluder within ulps of the axial reach).
 Reference: the oracle's any_hit(brute_force=True) — no box test of any kind — over the exact ray of every thread, which the oracle's ray
 generation reproduces bit for bit (tests/test_trace_cases.py pins the reference and keeps these tests from passing vacuously).
 Compared: every mask word (edge-thread bits included), ray_count() and the per-tile ray counts.  Mismatches allowed: 0.  ray_trace() only.
+The closest-hit launches (k_ddgi_trace, k_refl_trace) are pinned the same way by tests/closest_cases.py and tests/test_gpu_closest_edges.py.
 
 That the tests bite (docs/EXPERIMENTS.md, "Adversarial G-buffers"): four throw-away variants of the library, each with ONE answer-changing
 mutation, were run against this file alone — the entry table built without its grow, the cached-triangle test with 10000 for t_max,
