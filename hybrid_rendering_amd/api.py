@@ -103,6 +103,7 @@ ABI_SYMBOLS = [
     "hr_scene_motion_begin_frame", "hr_gbuffer_raycast_motion",
     "hr_scene_update_instances_device", "hr_scene_device_update_status", "hr_scene_device_update_stats",
     "hr_scene_rebuild_top_level_device", "hr_scene_set_device_rebuild_threshold", "hr_scene_device_rebuild_status", "hr_shared_top_fixed_shape", "hr_shared_top_sort_keys",
+    "hr_scene_rebuild_device", "hr_scene_rebuild_meshes_device", "hr_scene_device_rebuild_counts", "hr_deform_leaf_order",
     "hr_scene_set_instance_masks", "hr_scene_set_instance_masks_device", "hr_scene_get_instance_masks", "hr_scene_set_cull_mask", "hr_scene_get_cull_mask",
     "hr_scene_set_alpha_cutoffs", "hr_scene_get_alpha_cutoffs", "hr_scene_set_ray_class_opaque", "hr_scene_get_ray_class_opaque",
 ]
@@ -136,6 +137,14 @@ DEVICE_UPDATE_ARGTYPES = {
     "hr_scene_device_rebuild_status": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
     "hr_shared_top_fixed_shape": [C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "hr_shared_top_sort_keys": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+}
+
+# argtypes of the device re-deal's entry points (include/hr_api_stages.h)
+DEVICE_REDEAL_ARGTYPES = {
+    "hr_scene_rebuild_device": [C.c_void_p, C.c_void_p],
+    "hr_scene_rebuild_meshes_device": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    "hr_scene_device_rebuild_counts": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "hr_deform_leaf_order": [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
 }
 
 _lib = None
@@ -293,6 +302,22 @@ class Scene:
         """hr_scene_rebuild: the slow path — host build over the current vertices; synchronises"""
         _check(lib().hr_scene_rebuild(self.h, _stream_ptr(stream)), "hr_scene_rebuild")
         self.refresh_info()
+
+    def rebuild_device(self, stream=None):
+        """hr_scene_rebuild_device (deformable scenes): the triangles re-dealt among the standing tree's leaves in Morton order by kernels on
+        ``stream`` (default: torch's current stream), then the refit; no host synchronisation, the answers stand.  ``refit_cost`` afterwards is
+        still relative to the host build."""
+        L = lib()
+        L.hr_scene_rebuild_device.argtypes = DEVICE_REDEAL_ARGTYPES["hr_scene_rebuild_device"]
+        _check(L.hr_scene_rebuild_device(self.h, _stream_ptr(stream)), "hr_scene_rebuild_device")
+
+    def device_rebuild_counts(self) -> dict:
+        """hr_scene_device_rebuild_counts (host counters): meshes re-dealt on the device and kernel launches enqueued for that so far"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        L = lib()
+        L.hr_scene_device_rebuild_counts.argtypes = DEVICE_REDEAL_ARGTYPES["hr_scene_device_rebuild_counts"]
+        _check(L.hr_scene_device_rebuild_counts(self.h, C.byref(a), C.byref(b)), "hr_scene_device_rebuild_counts")
+        return dict(rebuilds_enqueued=int(a.value), launches_enqueued=int(b.value))
 
     def any_hit(self, rays, stats=False, stream=None):
         """rays: cuda float32 [n,8] (origin, t_max, dir, t_min) -> uint8 [n] (1 = occluded)."""
@@ -482,6 +507,14 @@ class InstancedScene(Scene):
         _check(L.hr_scene_update_meshes(self.h, C.cast(arr, C.c_void_p), C.c_int32(len(updates)), _stream_ptr(stream)), "hr_scene_update_meshes")
         del keep
 
+    def rebuild_meshes_device(self, mesh_idx, stream=None):
+        """hr_scene_rebuild_meshes_device (shared deformable scenes): the flagged meshes ``mesh_idx`` (distinct) re-dealt by kernels on ``stream``
+        (default: torch's current stream), then refitted; the vertices do not change, so the top level stands untouched"""
+        m = np.ascontiguousarray(np.asarray(mesh_idx, np.int64).reshape(-1).astype(np.uint32))
+        L = lib()
+        L.hr_scene_rebuild_meshes_device.argtypes = DEVICE_REDEAL_ARGTYPES["hr_scene_rebuild_meshes_device"]
+        _check(L.hr_scene_rebuild_meshes_device(self.h, C.c_void_p(m.ctypes.data) if len(m) else None, C.c_int32(len(m)), _stream_ptr(stream)), "hr_scene_rebuild_meshes_device")
+
     def mesh_refit_cost(self, mesh_idx: int) -> float:
         """hr_scene_mesh_refit_cost: sum of mesh ``mesh_idx``'s BVH nodes' half areas after its last update / as built (synchronises); raises HRError
         (HR_ERR_INVALID_ARG) when the bounds given with the last update do not contain the mesh"""
@@ -630,6 +663,19 @@ def bvh_selfcheck(verts, samples_per_triangle: int = 12) -> int:
     L.hr_bvh_selfcheck.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     _check(L.hr_bvh_selfcheck(v.ctypes.data_as(C.POINTER(C.c_float)), C.c_int32(v.shape[0]), C.c_int32(samples_per_triangle), C.byref(bad)), "hr_bvh_selfcheck")
     return int(bad.value)
+
+
+def deform_leaf_order(nodes, root: int = 0, capacity: int = None) -> np.ndarray:
+    """Host-only (hr_deform_leaf_order): the reference slots of the tree under ``root`` in ``nodes`` ([n][80] uint8, csrc/bvh.h) in depth-first
+    order — slots of a node in slot order, a leaf's triangles in offset order — relative to the tree's first reference.  ``capacity``: room
+    for that many (default: 32 per node, more than any tree has); HRError (HR_ERR_INVALID_ARG) when it is too small"""
+    nd = np.ascontiguousarray(np.asarray(nodes, np.uint8).reshape(-1, 80))
+    cap = int(capacity) if capacity is not None else 32 * len(nd)
+    out, n = np.full(max(cap, 1), -1, np.int32), C.c_int32(0)
+    L = lib()
+    L.hr_deform_leaf_order.argtypes = DEVICE_REDEAL_ARGTYPES["hr_deform_leaf_order"]
+    _check(L.hr_deform_leaf_order(C.c_void_p(nd.ctypes.data), C.c_int32(len(nd)), C.c_uint32(root), C.c_void_p(out.ctypes.data), C.c_int32(cap), C.byref(n)), "hr_deform_leaf_order")
+    return out[:int(n.value)].copy()
 
 
 SHARED_TOP_NODE_DTYPE = np.dtype([(k, np.int32) for k in ("n_internal", "n_leaves", "child_base", "leaf_base", "axis", "depth")])

@@ -13,8 +13,11 @@
 // and stays out of its parent's box (refit.h) — and comes back with its next finite vertices; and the leaf pad is the builder's rule applied to the
 // CURRENT exact bounds of the finite triangles (instance_math.h leaf_pad, from k_deform_bounds on the same stream: no host synchronisation), so a
 // scene created from a placeholder, inflated, collapsed or drifted away is padded for the size and place it has now.
-// A triangle that was not finite when the scene was BUILT (created or rebuilt) has no reference to update: it stays out until the next rebuild.
-// hr_scene_rebuild is the slow way back: vertices read back, host build, upload.  Nothing calls it automatically.
+// A triangle that was not finite when the scene was BUILT (created or rebuilt) has no reference to update: it stays out until the next host
+// rebuild, or until a device re-deal hands it a slot that a triangle which is not finite NOW gives up (deform_redeal.hip).
+// Two ways back from a decayed tree, neither called automatically: hr_scene_rebuild, the slow one (vertices read back, host SAH build, upload,
+// new device arrays), and hr_scene_rebuild_device (deform_redeal.hip: kernels only — the tree's shape stands, its triangles are re-dealt among
+// its leaves in Morton order and the refit runs; it does not reach a SAH build's quality).
 #include "deform_refit.h"
 #include "instance_math.h"
 #include "scene_create.h"

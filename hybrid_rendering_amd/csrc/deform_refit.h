@@ -35,6 +35,19 @@ void deform_refit_scatter(hr_scene* s, const DeformScatterEntry* e, int n, float
 // bounds of that mesh (6 floats) or null
 hr_status deform_refit_enqueue(hr_scene* s, Node8* nodes, const uint32_t* ms, int n, const float* const* bounds, hipStream_t st);
 
+// the first launch of deform_refit_enqueue alone: the exact bounds of the finite references of ms[0 .. n) into their words of bounds_bits, which
+// must stand idle.  Whoever calls it puts the words back before the next refit (deform_redeal.hip: its commit launch)
+void deform_refit_bounds_enqueue(hr_scene* s, const uint32_t* ms, int n, hipStream_t st);
+
+// Depth-first list of a tree's reference slots (slots of a node in slot order, a leaf's triangles in offset order), relative to the tree's first
+// reference.  `nodes`: n_nodes nodes whose child_base index that array, `root` among them.  false: a child outside the array, more than
+// `capacity` references, or more node visits than nodes (not a tree); nothing is written then.
+bool deform_leaf_order(const Node8* nodes, int32_t n_nodes, uint32_t root, int32_t* slot_of_rank, int32_t capacity, int32_t* n);
+
+// deform_redeal.hip: the triangles of the flagged meshes ms[0 .. n) (at most kMaxUpdatesPerLaunch, distinct) re-dealt among their standing reference
+// slots in Morton order, then deform_refit_enqueue over all of them (bounds as there).  Kernels only on `st`; allocates at a scene's first call.
+hr_status deform_redeal_enqueue(hr_scene* s, const uint32_t* ms, int n, hipStream_t st);
+
 // sum of mesh m's half areas now / when built; reads the slots back when an update ran since the last call (cost_known[m] == 0): the caller has
 // synchronised the device by then
 hr_status deform_refit_cost(hr_scene* s, uint32_t m, float* ratio);

@@ -226,24 +226,28 @@ hr_status read_partials(const DeformRefit& sd, uint32_t m, double* sum)
     return HR_OK;
 }
 
+// the exact bounds of the finite references of ms[0 .. n) into their words of bounds_bits (idle before)
+void bounds_enqueue(hr_scene* s, const DeformRefit& sd, const uint32_t* ms, int n, hipStream_t st)
+{
+    BoundsArgs b;
+    b.tris = (const TriGPU*)s->tris.p; b.bits = (uint32_t*)sd.bounds_bits.p; b.n = 0;
+    int blocks = 0;
+    for (int j = 0; j < n; j++)
+    {
+        if (sd.n_refs[ms[j]] == 0) continue;
+        const int mine = std::min(kBoundsMaxBlocks, cdiv(sd.n_refs[ms[j]], kBoundsPerBlock));
+        b.e[b.n++] = { sd.ref_base[ms[j]], ms[j], sd.n_refs[ms[j]], blocks, mine };
+        blocks += mine;
+    }
+    if (b.n > 0) hipLaunchKernelGGL(k_deform_bounds, dim3(blocks), dim3(256), 0, st, b);
+}
+
 // the refit of the flagged meshes ms[0 .. n) of `sd` into `nodes` and `node_box`
 hr_status enqueue(hr_scene* s, DeformRefit& sd, Node8* nodes, float* node_box, const uint32_t* ms, int n, const float* const* bounds, hipStream_t st)
 {
     RefitArgs r;
     r.nodes = nodes; r.tris = (const TriGPU*)s->tris.p; r.node_box = node_box; r.pad = 0.0f;
-    {
-        BoundsArgs b;
-        b.tris = r.tris; b.bits = (uint32_t*)sd.bounds_bits.p; b.n = 0;
-        int blocks = 0;
-        for (int j = 0; j < n; j++)
-        {
-            if (sd.n_refs[ms[j]] == 0) continue;
-            const int mine = std::min(kBoundsMaxBlocks, cdiv(sd.n_refs[ms[j]], kBoundsPerBlock));
-            b.e[b.n++] = { sd.ref_base[ms[j]], ms[j], sd.n_refs[ms[j]], blocks, mine };
-            blocks += mine;
-        }
-        if (b.n > 0) hipLaunchKernelGGL(k_deform_bounds, dim3(blocks), dim3(256), 0, st, b);
-    }
+    bounds_enqueue(s, sd, ms, n, st);
     r.cells = nullptr; r.node_inst = nullptr; r.inst = nullptr; r.dirty = nullptr; r.list = nullptr; r.count = 0;
     int deepest = 0;
     for (int j = 0; j < n; j++) deepest = std::max(deepest, sd.n_levels[ms[j]]);
@@ -311,6 +315,8 @@ hr_status hr::deform_refit_enqueue(hr_scene* s, Node8* nodes, const uint32_t* ms
     return enqueue(s, *s->deform, nodes, (float*)s->node_box.p, ms, n, bounds, st);
 }
 
+void hr::deform_refit_bounds_enqueue(hr_scene* s, const uint32_t* ms, int n, hipStream_t st) { bounds_enqueue(s, *s->deform, ms, n, st); }
+
 hr_status hr::deform_refit_cost(hr_scene* s, uint32_t m, float* ratio)
 {
     DeformRefit& sd = *s->deform;
@@ -333,7 +339,7 @@ hr_status hr::deform_refit_adopt(hr_scene* s, const std::vector<DeformMesh>& mes
     DeformRefit& sd = *fresh;
     sd.flag.assign(M, 0); sd.root.assign(M, 0); sd.ref_base.assign(M, 0); sd.tri_base.assign(M, 0); sd.n_tris.assign(M, 0); sd.n_refs.assign(M, 0);
     sd.n_levels.assign(M, 0); sd.d_top.assign(M, -1); sd.partial_base.assign(M, 0); sd.n_partials.assign(M, 0);
-    sd.cost_at_build.assign(M, 0.0); sd.cost_known.assign(M, 1); sd.cost_ratio.assign(M, 1.0);
+    sd.cost_at_build.assign(M, 0.0); sd.cost_known.assign(M, 1); sd.cost_ratio.assign(M, 1.0); sd.redeal_ok.assign(M, 0);
     sd.levels_host.assign(M * 2 * kLevelStride, 0);
     size_t n_tris_all = 0;
     bool any = false;
@@ -376,6 +382,17 @@ hr_status hr::deform_refit_adopt(hr_scene* s, const std::vector<DeformMesh>& mes
         for (int d = n_levels - 1; d > d_top; d--) { row[kLevelStride + d] = slot; slot += cdiv(width[(size_t)d], 64); }
         sd.n_levels[k] = n_levels; sd.d_top[k] = d_top; sd.partial_base[k] = partials; sd.n_partials[k] = slot;
         partials += slot;
+        {
+            // the re-deal's table; a tree whose leaves do not name each reference once (no builder of this library makes one) cannot be re-dealt
+            std::vector<int32_t> order(b.tris.size());
+            int32_t n_order = 0;
+            bool ok = deform_leaf_order(b.nodes.data(), (int32_t)n_nodes, 0u, order.data(), (int32_t)order.size(), &n_order) && (size_t)n_order == b.tris.size();
+            std::vector<uint8_t> seen(b.tris.size(), 0);
+            for (size_t r = 0; ok && r < order.size(); r++) { ok = order[r] >= 0 && (size_t)order[r] < seen.size() && !seen[(size_t)order[r]]; if (ok) seen[(size_t)order[r]] = 1; }
+            sd.redeal_ok[k] = ok ? 1 : 0;
+            if (sd.slot_of_rank_host.size() < (size_t)sd.ref_base[k] + b.tris.size()) sd.slot_of_rank_host.resize((size_t)sd.ref_base[k] + b.tris.size(), -1);
+            for (size_t r = 0; ok && r < order.size(); r++) sd.slot_of_rank_host[(size_t)sd.ref_base[k] + r] = (int32_t)sd.ref_base[k] + order[r];
+        }
         for (size_t r = 0; r < b.tris.size(); r++)
         {
             const uint32_t prim = b.tris[r].prim;

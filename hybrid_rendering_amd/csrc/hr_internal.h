@@ -192,6 +192,15 @@ struct DeformRefit
     DevBuf   outside;                             // per mesh one word: the bounds given with the last update do not contain the refitted root box
     float*   root_box_host = nullptr;             // pinned, per mesh 8 floats
     int64_t  level_launches = 0, top_launches = 0, stream_waits = 0;   // what the updates so far enqueued (hr_scene_update_meshes_stats)
+    // the device re-deal of a mesh's triangles among its standing reference slots (deform_redeal.hip).  The host table is written with the tree
+    // (deform_refit_adopt); the device buffers are allocated by the first re-deal, never after
+    std::vector<int32_t> slot_of_rank_host;       // per flagged mesh, at ref_base[m]: its reference slots (global) in depth-first order of its tree
+    std::vector<uint8_t> redeal_ok;               // per mesh: the table stands (the tree's leaves name each of its references once)
+    bool     redeal_ready = false;
+    DevBuf   rd_slot_of_rank;                     // slot_of_rank_host on the device
+    DevBuf   rd_codes[2], rd_idx[2];              // per triangle of the largest flagged mesh: code / triangle, ping-pong of the radix sort; rd_idx[0]: the order
+    DevBuf   rd_hist;                             // radix sort: per digit and workgroup, a count, then its exclusive prefix
+    DevBuf   rd_tris;                             // per reference of the largest flagged mesh: the records in the new order, before they are copied back
     ~DeformRefit() { if (root_box_host) (void)hipHostFree(root_box_host); }
 };
 
@@ -441,6 +450,8 @@ struct hr_scene
     // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
     std::unique_ptr<hr::DeformRefit> deform;      // set by hr_scene_create_deformable and hr_scene_create_instanced_shared_deformable only
     bool          deformable = false;
+    int64_t       redeals = 0, redeal_launches = 0;   // meshes re-dealt on the device / kernel launches enqueued for that so far (hr_scene_device_rebuild_counts);
+                                                      // here and not in `deform`: a host rebuild replaces that
     mutable bool  bounds_stale = false;           // info.bounds_* lag the last update until hr_scene_get_info reads them back
     // ---- motion vectors (api.hip hr_scene_motion_begin_frame / hr_gbuffer_raycast_motion): the geometry as of the last begin_frame, indexed by
     // instance or by triangle, never by BVH reference — rebuilds, top-level re-builds and refits leave it alone

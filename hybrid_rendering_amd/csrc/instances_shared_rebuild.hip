@@ -15,11 +15,9 @@
 //   (4) the refit               k_shared_top_one or the per-depth launches of instances_shared_update.hip over the fixed table; its last statement
 //                               makes the half-area sum the new baseline of top_cost_ratio, clears the re-build flag and counts the re-build
 //
-// kSortSmall = 4096 keys: 4096 x 8 bytes = 32 KiB of LDS, half of the 64 KiB a workgroup gets without asking for more and a fifth of the 160 KiB
-// a gfx950 workgroup may declare, at 1024 lanes (16 waves of 64) four keys per lane.  The network over n2 = 2^k >= I keys costs k (k + 1) / 2
-// barriers — 78 at 4096 — against the 13 launches of the radix path, which is what a launch-latency-bound job of this size is decided by;
-// doubling the limit would add 13 barriers and halve nothing.  4096 instances is also about where the top level leaves the one-workgroup
-// refit (kOneLaunchNodes = 1024 nodes: 4097 instances make 590), so "small" means the same thing in both files.
+// The two sorts live in device_sort.h (deform_redeal.hip uses them too), with the reasons for kSortSmall = 4096.  4096 instances is also about
+// where the top level leaves the one-workgroup refit (kOneLaunchNodes = 1024 nodes: 4097 instances make 590), so "small" means the same thing in
+// both files.
 //
 // Launches: 4 per re-build up to kSortSmall instances (+1 for (0)), else 1 + 12 + 2 + the refit's.  With a threshold set
 // (hr_scene_set_device_rebuild_threshold) these launches ride behind EVERY device update, each one exiting at once unless the update's refit
@@ -29,6 +27,7 @@
 // call, and the scene is marked order_replayed, on which the AO pass rebuilds its entry table at every render — the table holds top-level node
 // indices, and the fixed shape keeps the slots but not the instances below them.
 #include "instances_shared_device.h"
+#include "device_sort.h"
 #include <cmath>
 #include <cstring>
 
@@ -36,14 +35,8 @@ using namespace hr;
 
 namespace {
 
-constexpr int kSortSmall  = 4096;
-constexpr int kSortLanes  = 1024;
-constexpr int kRadixBits  = 8, kRadixBins = 1 << kRadixBits, kRadixPasses = 4;   // 4 x 8 bits cover the 30-bit code
-constexpr int kRadixTile  = 256;                                                  // one key per lane
 constexpr int kRecordWords = (int)(sizeof(InstanceShared) / 4);
 static_assert(sizeof(InstanceShared) == 160, "InstanceShared layout");
-
-__device__ inline bool skip(const DeviceUpdateStatus* st, int predicated) { return predicated && st->rebuild_flag == 0u; }
 
 __global__ void __launch_bounds__(256) k_boxes_from_records(const InstanceShared* records, const int32_t* leaf_of, const uint32_t* inst_mesh, const MeshTab* mesh,
                                                             float* inst_box, DeviceUpdateStatus* status, int n, const float lo0, const float lo1, const float lo2,
@@ -68,7 +61,7 @@ __global__ void __launch_bounds__(256) k_boxes_from_records(const InstanceShared
 __global__ void __launch_bounds__(kSortLanes) k_sort_small(const float* inst_box, const DeviceUpdateStatus* status, uint32_t* order, int n, int n2, int predicated)
 {
     __shared__ unsigned long long key[kSortSmall];
-    if (skip(status, predicated)) return;
+    if (rebuild_skipped(status, predicated)) return;
     const int t = (int)threadIdx.x;
     float bounds[6];
     for (int k = 0; k < 6; k++) bounds[k] = status->bounds[k];
@@ -84,27 +77,13 @@ __global__ void __launch_bounds__(kSortLanes) k_sort_small(const float* inst_box
         key[e] = v;
     }
     __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1)
-        {
-            for (int e = t; e < n2; e += kSortLanes)
-            {
-                const int p = e ^ j;
-                if (p > e)
-                {
-                    const unsigned long long a = key[e], b = key[p];
-                    const bool up = (e & k) == 0;
-                    if ((a > b) == up) { key[e] = b; key[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_lds(key, n2, t);
     for (int e = t; e < n; e += kSortLanes) order[e] = (uint32_t)(key[e] & 0xffffffffull);
 }
 
 __global__ void __launch_bounds__(256) k_keys(const float* inst_box, const DeviceUpdateStatus* status, uint32_t* codes, uint32_t* idx, int n, int predicated)
 {
-    if (skip(status, predicated)) return;
+    if (rebuild_skipped(status, predicated)) return;
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
     float bounds[6], box[6];
@@ -113,74 +92,10 @@ __global__ void __launch_bounds__(256) k_keys(const float* inst_box, const Devic
     idx[i] = (uint32_t)i;
 }
 
-// hist[digit * n_blocks + block]: keys of this workgroup's tile with that digit
-__global__ void __launch_bounds__(kRadixTile) k_radix_hist(const uint32_t* codes, uint32_t* hist, const DeviceUpdateStatus* status, int n, int shift, int predicated)
-{
-    __shared__ uint32_t cnt[kRadixBins];
-    if (skip(status, predicated)) return;
-    cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    const int i = (int)(blockIdx.x * kRadixTile + threadIdx.x);
-    if (i < n) atomicAdd(&cnt[(codes[i] >> shift) & (kRadixBins - 1)], 1u);
-    __syncthreads();
-    hist[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// exclusive prefix over hist in place (digit-major: all tiles of digit 0, then of digit 1, ...); one workgroup, every lane a contiguous chunk
-__global__ void __launch_bounds__(kSortLanes) k_radix_scan(uint32_t* hist, const DeviceUpdateStatus* status, int total, int predicated)
-{
-    __shared__ uint32_t part[kSortLanes];
-    if (skip(status, predicated)) return;
-    const int t = (int)threadIdx.x, chunk = (total + kSortLanes - 1) / kSortLanes;
-    const int first = t * chunk, end = first + chunk < total ? first + chunk : total;
-    uint32_t sum = 0u;
-    for (int j = first; j < end; j++) sum += hist[j];
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < kSortLanes; off <<= 1)   // inclusive scan of the lanes' sums
-    {
-        const uint32_t add = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (int j = first; j < end; j++) { const uint32_t c = hist[j]; hist[j] = run; run += c; }
-}
-
-// stable: a key's place is its digit's base for this tile + the keys of the same digit before it in the tile
-__global__ void __launch_bounds__(kRadixTile) k_radix_scatter(const uint32_t* codes, const uint32_t* idx, uint32_t* codes_out, uint32_t* idx_out, const uint32_t* hist,
-                                                               const DeviceUpdateStatus* status, int n, int shift, int predicated)
-{
-    __shared__ uint32_t wave_cnt[kRadixTile / 64][kRadixBins];
-    if (skip(status, predicated)) return;
-    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
-    for (int w = 0; w < kRadixTile / 64; w++) wave_cnt[w][t] = 0u;
-    __syncthreads();
-    const int  i = (int)(blockIdx.x * kRadixTile + t);
-    const bool live = i < n;
-    const uint32_t code = live ? codes[i] : 0u, payload = live ? idx[i] : 0u;
-    const uint32_t d = (code >> shift) & (kRadixBins - 1);
-    unsigned long long peers = __ballot(live);   // the lanes of this wave that hold the same digit
-    for (int b = 0; b < kRadixBits; b++)
-    {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long has = __ballot(bit);
-        peers &= bit ? has : ~has;
-    }
-    const uint32_t before = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
-    if (live && before == 0u) wave_cnt[wave][d] = (uint32_t)__popcll(peers);
-    __syncthreads();
-    if (!live) return;
-    uint32_t at = hist[(size_t)d * gridDim.x + blockIdx.x] + before;
-    for (int w = 0; w < wave; w++) at += wave_cnt[w][d];
-    if (at < (uint32_t)n) { codes_out[at] = code; idx_out[at] = payload; }   // always true while hist is this pass's; the guard keeps a stale one in bounds
-}
-
 __global__ void __launch_bounds__(256) k_gather(const uint32_t* records, uint32_t* scratch, const uint32_t* order, const int32_t* leaf_of, const DeviceUpdateStatus* status,
                                                 int n, int predicated)
 {
-    if (skip(status, predicated)) return;
+    if (rebuild_skipped(status, predicated)) return;
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)n * kRecordWords) return;
     const int l = (int)(g / kRecordWords), w = (int)(g % kRecordWords);
@@ -194,7 +109,7 @@ __global__ void __launch_bounds__(256) k_gather(const uint32_t* records, uint32_
 __global__ void __launch_bounds__(256) k_commit(uint32_t* records, const uint32_t* scratch, const uint32_t* order, int32_t* leaf_inst, int32_t* leaf_of,
                                                 const DeviceUpdateStatus* status, int n, int predicated)
 {
-    if (skip(status, predicated)) return;
+    if (rebuild_skipped(status, predicated)) return;
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long long)n * kRecordWords) return;
     records[g] = scratch[g];
@@ -222,7 +137,7 @@ hr_status ensure_buffers(hr_scene* s)
         if ((e = du.rb_codes[k].alloc(I * 4)) != HR_OK) return e;
         if ((e = du.rb_idx[k].alloc(I * 4)) != HR_OK) return e;
     }
-    if ((e = du.rb_hist.alloc((size_t)kRadixBins * (size_t)cdiv((int)I, kRadixTile) * 4)) != HR_OK) return e;
+    if ((e = du.rb_hist.alloc(radix_hist_bytes(I))) != HR_OK) return e;
     if ((e = du.rb_records.alloc(I * sizeof(InstanceShared))) != HR_OK) return e;
     du.rebuild_ready = true;
     return HR_OK;
@@ -299,22 +214,13 @@ hr_status enqueue_launches(hr_scene* s, hipStream_t st, bool counted, bool predi
     }
     else
     {
-        const int blocks = cdiv(I, kRadixTile);
         hipLaunchKernelGGL(k_keys, dim3(cdiv(I, 256)), dim3(256), 0, st, inst_box, status, (uint32_t*)du.rb_codes[0].p, (uint32_t*)du.rb_idx[0].p, I, pred);
         HR_HIP(hipGetLastError());
         launched++;
-        for (int p = 0; p < kRadixPasses; p++)   // an even number of passes: the order ends in rb_idx[0]
-        {
-            const int in = p & 1, out = in ^ 1, shift = p * kRadixBits;
-            hipLaunchKernelGGL(k_radix_hist, dim3(blocks), dim3(kRadixTile), 0, st, (const uint32_t*)du.rb_codes[in].p, (uint32_t*)du.rb_hist.p, status, I, shift, pred);
-            HR_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(kSortLanes), 0, st, (uint32_t*)du.rb_hist.p, status, kRadixBins * blocks, pred);
-            HR_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_radix_scatter, dim3(blocks), dim3(kRadixTile), 0, st, (const uint32_t*)du.rb_codes[in].p, (const uint32_t*)du.rb_idx[in].p,
-                               (uint32_t*)du.rb_codes[out].p, (uint32_t*)du.rb_idx[out].p, (const uint32_t*)du.rb_hist.p, status, I, shift, pred);
-            HR_HIP(hipGetLastError());
-            launched += 3;
-        }
+        uint32_t* const codes[2] = { (uint32_t*)du.rb_codes[0].p, (uint32_t*)du.rb_codes[1].p };
+        uint32_t* const idx[2]   = { (uint32_t*)du.rb_idx[0].p, (uint32_t*)du.rb_idx[1].p };
+        const hr_status rs = radix_sort_enqueue(codes, idx, (uint32_t*)du.rb_hist.p, status, I, pred, st, &launched);   // the order ends in rb_idx[0]
+        if (rs != HR_OK) return rs;
     }
     const int word_blocks = (int)(((long long)I * kRecordWords + 255) / 256);
     hipLaunchKernelGGL(k_gather, dim3(word_blocks), dim3(256), 0, st, (const uint32_t*)s->inst_shared.p, (uint32_t*)du.rb_records.p, (const uint32_t*)order,

@@ -75,11 +75,15 @@ public:
     void     update_vertices(const float* positions, const float* normals, int32_t first_tri, int32_t n_tris, Stream cmd_buf) { check(hr_scene_update_vertices(m_scene, positions, normals, first_tri, n_tris, cmd_buf), "hr_scene_update_vertices"); }
     float    refit_cost() const { float r = 1.0f; check(hr_scene_refit_cost(m_scene, &r), "hr_scene_refit_cost"); return r; }
     void     rebuild(Stream cmd_buf) { check(hr_scene_rebuild(m_scene, cmd_buf), "hr_scene_rebuild"); }
+    // the triangles re-dealt among the standing tree's leaves by kernels on cmd_buf, then the refit: no host synchronisation (hr_api_stages.h)
+    void     rebuild_device(Stream cmd_buf) { check(hr_scene_rebuild_device(m_scene, cmd_buf), "hr_scene_rebuild_device"); }
     // deforming meshes in the shared kind (hr_scene_create_instanced_shared_deformable): Scene(ctx, desc, flags) with one flag per mesh;
     // update_meshes() every frame a flagged mesh moved (bounds given: no wait; null: measured, one stream wait), mesh_refit_cost() per mesh
     Scene(Context& ctx, const hr_instanced_scene_desc& desc, const uint8_t* deformable) { check(hr_scene_create_instanced_shared_deformable(ctx.handle(), &desc, deformable, &m_scene), "hr_scene_create_instanced_shared_deformable"); }
     void     update_meshes(const hr_mesh_update* updates, int32_t n_updates, Stream cmd_buf) { check(hr_scene_update_meshes(m_scene, updates, n_updates, cmd_buf), "hr_scene_update_meshes"); }
     float    mesh_refit_cost(uint32_t mesh_idx) const { float r = 1.0f; check(hr_scene_mesh_refit_cost(m_scene, mesh_idx, &r), "hr_scene_mesh_refit_cost"); return r; }
+    // the flagged meshes mesh_idx[0 .. n) (distinct) re-dealt by kernels on cmd_buf and refitted; the top level stands
+    void     rebuild_meshes_device(const uint32_t* mesh_idx, int32_t n, Stream cmd_buf) { check(hr_scene_rebuild_meshes_device(m_scene, mesh_idx, n, cmd_buf), "hr_scene_rebuild_meshes_device"); }
     bool     is_shared() const { return hr_scene_is_shared(m_scene) != 0; }
     // a shared scene only: AO, DDGI, reflections, the ground truth and HybridFrame walk it on two levels once this is on (off: they refuse it)
     void     enable_two_level_passes(bool enable = true) { check(hr_scene_enable_two_level_passes(m_scene, enable ? 1 : 0), "hr_scene_enable_two_level_passes"); }

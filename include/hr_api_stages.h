@@ -19,7 +19,6 @@ extern "C" {
  * that hr_markers_log() returns as "+name" / "-" lines (tests).  Process-wide. */
 hr_status hr_set_markers(int32_t mode);
 int32_t   hr_markers_log(char* out, int32_t capacity);   /* returns the length of the whole log; out may be NULL */
-
 /* ---- scene introspection ---------------------------------------------------------------------------------------- */
 /* Introspection (tests, tools): copies the device BVH to the host after synchronising the device — hr_scene_info.node_bytes of 80-byte nodes
  * and .tri_bytes of 48-byte triangle references (layouts: csrc/bvh.h).  Either pointer may be NULL. */
@@ -30,8 +29,7 @@ hr_status hr_scene_read_bvh(const hr_scene* scene, void* nodes_out, void* tris_o
  * Launch order: the trace kernels of the shadows, AO and reflections passes record how long each 8x8 tile's wave lived and launch
  * the next frame's tiles heaviest first (the sort runs inside the pass's tolerance-mode temporal launch, else at the start of the next
  * trace call).  Outputs do not depend on it.  Like the visibility mask — which the next trace call overwrites and the temporal stage
- * reads — this state asks for what a frame loop does anyway: a pass's next *_ray_trace call is stream-ordered after its last
- * *_temporal call. */
+ * reads — this state asks for what a frame loop does anyway: a pass's next *_ray_trace call is stream-ordered after its last *_temporal call. */
 hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_shadows_params* params, void* stream);
 /* everything of render() after the trace: temporal + a-trous chain (+ upsample); hr_shadows_ray_trace + hr_shadows_denoise == hr_shadows_render.
  * In tolerance mode this (like render) launches a-trous iterations 0 and 1 as ONE kernel; the per-iteration entry point below stays. */
@@ -91,8 +89,7 @@ hr_status hr_ao_set_profiling(hr_ao* p, int32_t enable);
 hr_status hr_ao_get_stage_times(hr_ao* p, hr_stage_times* out);
 hr_status hr_ao_ray_count(hr_ao* p, uint64_t* rays);
 hr_status hr_ao_trace_stats(hr_ao* p, const hr_scene* scene, const hr_frame_inputs* in, const hr_ao_params* params, uint64_t* out3, void* stream);
-/* as hr_shadows_launch_order */
-hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles);
+hr_status hr_ao_launch_order(hr_ao* p, uint32_t* out, int32_t* n_tiles);   /* as hr_shadows_launch_order */
 /* ---- DDGI: sharding, stages + introspection ------------------------------------------------------------------------ */
 /* Multi-GPU sharding (the reference is single-GPU): this instance traces and updates only the probes
  * of grid z-slabs [probe_z0, probe_z1) — their atlas rows [1 + z0*(side+2), 1 + z1*(side+2)) are contiguous
@@ -144,15 +141,13 @@ hr_status hr_reflections_ray_count(hr_reflections* p, uint64_t* rays);
  * they form (shadows | AO | DDGI probe trace + updates -> reflections | DDGI per-pixel sample), every output bit-identical to the serial
  * order.  The passes are NOT owned; call order at the call site is the reference's, mode picks how the launches reach the GPU. */
 typedef struct hr_hybrid_frame hr_hybrid_frame;
-typedef enum
-{
+typedef enum {
     HR_FRAME_SERIAL  = 0, /* one stream, the reference's order (= calling the four render() yourself) */
     HR_FRAME_STREAMS = 1, /* fork / join over three internal streams + `stream` */
     HR_FRAME_GRAPH   = 2  /* the forked frame captured into one hipGraph per frame; the instantiated graph is updated in place.
                              Stage profiling (hr_*_set_profiling) must be off: timing events cannot be read back from a captured launch */
 } hr_frame_mode;
-typedef struct
-{
+typedef struct {
     const hr_environment*        environment;          /* DDGI + reflections */
     const hr_frame_inputs*       shadows_inputs;       /* each pass reads the G-buffer level of its own RayTraceScale */
     const hr_shadows_params*     shadows_params;
@@ -167,8 +162,7 @@ typedef struct
 hr_status hr_hybrid_frame_create(hr_ctx* ctx, hr_shadows* shadows, hr_ao* ao, hr_ddgi* ddgi, hr_reflections* reflections, hr_hybrid_frame** out);
 hr_status hr_hybrid_frame_render(hr_hybrid_frame* f, const hr_scene* scene, const hr_hybrid_frame_desc* desc, hr_frame_mode mode, void* stream);
 /* Fork / join for a host that enqueues the chains itself (hr::TiledHybridFrame: the row-tiled passes post their neighbour exchanges from
- * inside render()).  fork: side_streams[0..2] (owned by the frame object) wait for everything enqueued on `stream` so far; join: `stream`
- * waits for everything enqueued on them since. */
+ * inside render()).  fork: side_streams[0..2] (owned by the frame object) wait for everything enqueued on `stream` so far; join: `stream` waits for everything enqueued on them since. */
 hr_status hr_hybrid_frame_fork(hr_hybrid_frame* f, void* stream, void** side_streams);
 hr_status hr_hybrid_frame_join(hr_hybrid_frame* f, void* stream);
 /* HR_FRAME_GRAPH bookkeeping: graphs instantiated (1 in steady state) and in-place updates (one per later frame) */
@@ -214,6 +208,12 @@ hr_status hr_scene_rebuild_top_level_device(hr_scene* scene, void* stream);
 hr_status hr_scene_set_device_rebuild_threshold(hr_scene* scene, float ratio, void* stream);
 hr_status hr_scene_device_rebuild_status(const hr_scene* scene, int64_t* rebuilds_done, int64_t* launches_enqueued, int32_t* fixed_shape);
 hr_status hr_shared_top_fixed_shape(int32_t n_instances, void* nodes_out, int64_t capacity, int32_t* n_nodes, int32_t* n_depths); hr_status hr_shared_top_sort_keys(const float* inst_boxes, int32_t n, const float bounds[6], uint64_t* keys_out);   /* host only (tests, tools): the fixed shape's 24-byte records { n_internal, n_leaves, child_base, leaf_base, axis, depth }, breadth-first (nodes_out NULL: the counts only); the 64-bit sort keys (30-bit Morton code << 32 | instance) of n boxes (lo xyz hi xyz) inside bounds */
+/* ---- device re-deal of a deformable mesh's triangles (added within revision 6): the way back for a refitted tree that has decayed, kernels only on `stream`, no host synchronisation, nothing read back, no allocation after a scene's first call (which may not be captured).  The node topology stands as the host built it; the mesh's triangles are sorted by the Morton code of their box (hr_shared_top_sort_keys over the triangle boxes, inside the exact bounds of the mesh's finite references; a triangle with a non-finite coordinate sorts last) and dealt in that order to the tree's reference slots in depth-first order (hr_deform_leaf_order), then the tree is refitted.  Answers of queries and passes do not change.  The cost ratio afterwards is still relative to the host build. rebuild_device: a flat deformable scene; bumps the geometry epoch as hr_scene_update_vertices does.  rebuild_meshes_device: flagged meshes of a shared deformable scene, distinct, more than 64 taken 64 at a time; the vertices do not change, so the top level stands untouched.  HR_ERR_INVALID_ARG, before anything is enqueued: NULL, a scene of another kind, an unflagged or repeated mesh, mesh_idx >= n_meshes, n < 0.  hr_scene_rebuild (host) and these calls may follow each other in any order.  Nothing calls them automatically: decide from hr_scene_refit_cost / hr_scene_mesh_refit_cost.
+ * device_rebuild_counts (host counters): meshes re-dealt and kernel launches enqueued for that so far.  hr_deform_leaf_order (host only; tests, tools): the depth-first list of the reference slots of the tree under `root` in `nodes` (n_nodes x 80 bytes, csrc/bvh.h; child_base indexes that array) — slots of a node in slot order, a leaf's triangles in offset order — relative to the tree's first reference; HR_ERR_INVALID_ARG, nothing written, when capacity is below the count or the nodes are not a tree. */
+hr_status hr_scene_rebuild_device(hr_scene* scene, void* stream);
+hr_status hr_scene_rebuild_meshes_device(hr_scene* scene, const uint32_t* mesh_idx, int32_t n, void* stream);
+hr_status hr_scene_device_rebuild_counts(const hr_scene* scene, int64_t* rebuilds_enqueued, int64_t* launches_enqueued);
+hr_status hr_deform_leaf_order(const void* nodes, int32_t n_nodes, uint32_t root, int32_t* slot_of_rank, int32_t capacity, int32_t* n);
 #ifdef __cplusplus
 }
 #endif

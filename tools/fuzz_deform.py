@@ -1,5 +1,6 @@
 """GPU fuzzer of the deformable scenes (csrc/deform.hip): random scenes (a heightfield, the Cornell box, a triangle soup of tests/ray_cases.py),
-random sequences of synth.deform steps applied over random sub-ranges through hr_scene_update_vertices, a hr_scene_rebuild now and then.  After
+random sequences of synth.deform steps applied over random sub-ranges through hr_scene_update_vertices, a hr_scene_rebuild and a
+hr_scene_rebuild_device (the triangles re-dealt among the standing tree's leaves by kernels, csrc/deform_redeal.hip) now and then.  After
 every step queries (uniform rays, grazers of the scene's own child boxes, rays through edges and vertices) equal those of a fresh
 hr_scene_create over the same vertices and the oracle's brute force, bit for bit.      python tools/fuzz_deform.py [seed] [n]"""
 import os, sys
@@ -44,6 +45,8 @@ def main():
             if rng.randint(5) == 0:
                 g.rebuild()
                 assert g.refit_cost() == 1.0
+            if rng.randint(4) == 0:
+                g.rebuild_device()      # the next step's sub-range update goes through the re-dealt triangle -> reference map
             osc, gf = pyoracle.Scene(cur), hr.Scene(ctx, cur)
             for name, rays in T.ray_sets(g, cur.verts, int(rng.randint(1 << 30)), n_random=4000, n_boxes=40, n_tris=60).items():
                 what = f"seed {seed} trial {trial} step {step} ({sd0.name}, {sd0.n_tris} triangles, range [{first}, {first + count})) {name}"

@@ -8,7 +8,7 @@ image are compared with the oracle's instanced scene.   python tools/fuzz_instan
 (hr_scene_enable_two_level_passes) before AO, DDGI and reflections run on them; the bounds only have to be conservative.
 --deform (implies --shared): hr_scene_create_instanced_shared_deformable with a random subset of the small meshes flagged; between the matrix
 updates and the forced top-level re-builds a random subset of the flagged meshes takes a synth.deform step through hr_scene_update_meshes (whole
-meshes or two sub-ranges, bounds measured or given), and everything is compared with the flattened fresh scene over the deformed meshes.
+meshes or two sub-ranges, bounds measured or given), now and then followed by hr_scene_rebuild_meshes_device over a random subset, and everything is compared with the flattened fresh scene over the deformed meshes.
 --motion (not with --deform): beside the scene under test, a shared scene, a private-copy scene and a deformable scene over the flattened vertices
 take hr_scene_motion_begin_frame and the same updates every step; the four images of hr_gbuffer_raycast_motion must be equal between the shared
 and the private-copy scene, and GB2 (normal + motion vector) and depth equal to the deformable scene's, bit for bit.
@@ -163,6 +163,8 @@ for trial in range(n):
                                 u["bounds"] = m.bounds()
                             ups.append(u)
                     g.update_meshes(ups)
+                    if rng.rand() < 0.3:   # re-deal a random subset of the flagged meshes on the device: the answers and the top level stand
+                        g.rebuild_meshes_device([k for k, f in enumerate(flags) if f and rng.rand() < 0.6])
                     if rng.rand() < 0.5:   # and the matrices once more, behind the mesh update
                         mats[int(rng.randint(0, I)), 12:15] += rng.uniform(-2, 2, 3).astype(np.float32)
                         update(g, isd, mats)

@@ -19,6 +19,8 @@ frames is reported: the host path twice (`host_ms`, `host_ms_again`: their diffe
 given and with the bounds measured; then the same frames back to back without waiting in between (what the calling thread pays per frame).
 Any-hit answers of 20 000 rays must agree after the last frame.  --host-only: the host path's numbers alone (a library built from a revision
 that does not have the device path, selected with HR_LIBRARY).
+--shared --deform --device-rebuild: the --deform probe, then hr_scene_rebuild_meshes_device over every deforming mesh (csrc/deform_redeal.hip): event
+time of the call, the shadow trace on the re-dealt trees beside the refitted and the fresh ones, and per mesh the cost ratio refitted / re-dealt.
 --shared --device-rebuild: what hr_scene_rebuild_top_level_device costs.  Per size of synth.instanced_cornell (70, 600, 3300, 4096 boxes: the
 last one instance above the one-workgroup sort's limit), medians over `--reps` calls timed one by one (call, then wait for the stream) after a
 warm-up: the device re-build; hr_scene_rebuild_top_level on a twin that has just taken a device update (so its wall time includes the read-back
@@ -495,7 +497,7 @@ def deform_probe(a):
     gb = fresh.gbuffer(ubo, W, H)
     fi = hr.frame_inputs(gb, gb, ubo, 0, 0, sob_d, sr_d)
     out = {}
-    for tag, sc in (("refitted", g), ("fresh", fresh)):
+    def trace(sc):
         p = hr.RayTracedShadows(ctx, W, H)
         p.params.exact = 0
         for k in range(6):
@@ -509,8 +511,29 @@ def deform_probe(a):
             for n, t, b in p.stage_times():
                 acc[n] = acc.get(n, 0.0) + t / 20
         torch.cuda.synchronize()
-        out[tag] = (p.image(p.IMG_MASK).cpu().numpy().copy(), acc)
+        r = (p.image(p.IMG_MASK).cpu().numpy().copy(), acc)
         p.close()
+        return r
+    out["refitted"], out["fresh"] = trace(g), trace(fresh)
+    if a.device_rebuild:
+        # hr_scene_rebuild_meshes_device over every deforming mesh: event time of the call (the first call allocates and is not timed), the trace
+        # on the re-dealt trees, and per mesh the cost ratio refitted / re-dealt (a fresh scene's is 1.0: the host build is the baseline)
+        all_meshes = list(range(1, N + 1))
+        refitted = [g.mesh_refit_cost(k) for k in all_meshes]
+        for _ in range(3):
+            g.rebuild_meshes_device(all_meshes)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            g.rebuild_meshes_device(all_meshes)
+        e1.record()
+        torch.cuda.synchronize()
+        res["rebuild_meshes_device_ms"] = round(e0.elapsed_time(e1) / 20, 4)
+        res["rebuild_meshes_device_launches_per_call"] = g.device_rebuild_counts()["launches_enqueued"] // 23
+        out["redealt"] = trace(g)
+        assert np.array_equal(out["redealt"][0], out["fresh"][0]), "masks differ between the re-dealt and the freshly created scene"
+        res["shadow_trace_ms_redealt"] = round(out["redealt"][1]["ray_trace"], 4)
+        res["refit_cost_per_mesh"] = [dict(mesh=k, refitted=round(r, 4), redealt=round(g.mesh_refit_cost(k), 4), host_built=1.0) for k, r in zip(all_meshes, refitted)]
     assert np.array_equal(out["refitted"][0], out["fresh"][0]), "masks differ between the refitted and the freshly created scene"
     res["shadow_trace_ms_refitted"] = round(out["refitted"][1]["ray_trace"], 4)
     res["shadow_trace_ms_fresh"] = round(out["fresh"][1]["ray_trace"], 4)
