@@ -184,149 +184,6 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, SHADOWS_TRACE_EU) void k_shadows_
     }
 }
 
-#ifdef HR_DEV_PATHS   // A/B path that lost (13 % slower, docs/EXPERIMENTS.md 4.2); build with HR_CFLAGS=-DHR_DEV_PATHS, select with HR_TRACE_KERNEL=queue
-// ------------------------------------------------------------------------------------------------
-// Persistent-wave variant (HR_TRACE_KERNEL=queue; NOT the default — measured 13% slower on the bench scene although it
-// raises the SIMD lane utilisation of the traversal loop from 0.50 to 0.83-0.89: mixing rays of several tiles and
-// traversal stages in one wave multiplies the distinct BVH nodes a wave fetches per step, and the loop is bound by
-// those vector-memory requests, not by idle lanes).  A workgroup owns PW_TILES consecutive 8x8 tiles.
-//   phase 1  every wave generates the shadow rays of its tiles and appends the FIRED ones to a ray queue in LDS
-//            (wave ballot + popcount prefix, one LDS atomic per wave);
-//   phase 2  the waves drain the queue: a lane whose ray has terminated fetches the next ray as soon as
-//            PW_REFILL lanes of its wave are idle (ballot / popcount prefix compaction), so the SIMD lanes stay
-//            busy although only ~1/3 of the pixels fire a ray and traversal lengths differ by >10x;
-//   phase 3  visibility bits collected in LDS (atomicOr) are written out as packed 8x4 mask words.
-// The any-hit answer of a ray does not depend on which lane traces it, so the masks are bit-identical.
-#define PW_TILES 4
-#define PW_REFILL 12
-template <bool STATS>
-__global__ __launch_bounds__(256) void k_shadows_trace_pw(TraceArgs a)
-{
-    __shared__ float4   s_qa[PW_TILES * 64];   // origin.xyz, t_max
-    __shared__ float4   s_qb[PW_TILES * 64];   // direction.xyz, pixel code (tile_local << 6 | bit)
-    __shared__ uint32_t s_stack[4][HR_STACK_ENTRIES * 64];
-    __shared__ uint32_t s_bits[PW_TILES][2];
-    __shared__ int      s_head, s_tail;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n_tiles = a.tiles_x * a.tiles_y;
-    if (threadIdx.x < PW_TILES * 2) s_bits[threadIdx.x >> 1][threadIdx.x & 1] = 0u;
-    if (threadIdx.x == 0) { s_head = 0; s_tail = 0; }
-    __syncthreads();
-    // ---- phase 1: ray generation -------------------------------------------------------------------------
-    for (int r = 0; r < PW_TILES / 4; r++)
-    {
-        const int tl   = r * 4 + wave;
-        const int tile = blockIdx.x * PW_TILES + tl;
-        bool      fired = false;
-        f3        ro = mk3(0, 0, 0), Wi = mk3(0, 0, 1);
-        float     t_max = 0.0f;
-        int       tx = 0, ty = 0;
-        if (tile < n_tiles)
-        {
-            tx = tile % a.tiles_x; ty = tile / a.tiles_x + a.tile_y0;
-            const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
-            const int kind = trace_lane_kind(x, y, a.w, a.h, a.y0, a.y1);
-            if (kind)
-            {
-                const float d = kind == 1 ? a.depth[(size_t)y * a.w + x] : 0.0f;
-                if (d != 1.0f)
-                {
-                    const float tu = __fdiv_rn((float)x + 0.5f, (float)a.w), tv = __fdiv_rn((float)y + 0.5f, (float)a.h);
-                    const f3    P  = world_pos_from_depth(tu, tv, d, a.vpi);
-                    const uint2 g2 = kind == 1 ? a.gb2[(size_t)y * a.w + x] : make_uint2(0u, 0u);
-                    const f3    N  = oct_decode(h2f_lo(g2.x), h2f_hi(g2.x));
-                    ro = add3(P, scale3(N, a.bias));
-                    const float r0 = sample_blue_noise(x, y, (int)a.num_frames, 0, a.sobol, a.sr);
-                    const float r1 = sample_blue_noise(x, y, (int)a.num_frames, 1, a.sobol, a.sr);
-                    float att;
-                    fetch_light_shadow(a.light, P, N, r0, r1, Wi, t_max, att);
-                    fired = att > 0.0f;
-                }
-            }
-        }
-        const unsigned long long fb = __ballot(fired);
-        if (fb)
-        {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_tail, __popcll(fb));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (fired)
-            {
-                const int q = base + __popcll(fb & ((1ull << lane) - 1ull));
-                s_qa[q] = make_float4(ro.x, ro.y, ro.z, t_max);
-                s_qb[q] = make_float4(Wi.x, Wi.y, Wi.z, __uint_as_float((uint32_t)(tl << 6 | lane)));
-            }
-        }
-        if (lane == 0 && tile < n_tiles) a.ray_slots[(size_t)ty * a.tiles_x + tx] = (uint16_t)__popcll(fb);
-    }
-    __syncthreads();
-    // ---- phase 2: drain the queue with refilling lanes ----------------------------------------------------------
-    const int  tail = s_tail;
-    uint32_t   spill_array[HR_SPILL_ENTRIES];
-    AnyHitLane st;
-    bool       has = false;
-    uint32_t   code = 0, nn = 0, nt = 0, steps = 0;
-    while (true)
-    {
-        const unsigned long long idle = __ballot(!has);
-        const int n_idle = __popcll(idle);
-        if (n_idle >= PW_REFILL || n_idle == 64)
-        {
-            int head = 0;
-            if (lane == 0) head = (s_head < tail) ? atomicAdd(&s_head, n_idle) : tail;
-            head = __builtin_amdgcn_readfirstlane(head);
-            if (head >= tail && n_idle == 64) break;     // queue empty and nothing in flight
-            if (!has)
-            {
-                const int q = head + __popcll(idle & ((1ull << lane) - 1ull));
-                if (q < tail)
-                {
-                    const float4 qa = s_qa[q], qb = s_qb[q];
-                    code = __float_as_uint(qb.w);
-                    if (a.debug_skip_traversal) atomicOr(&s_bits[code >> 6][(code >> 5) & 1u], 1u << (code & 31u));
-                    else
-                    {
-                        anyhit_begin(st, mk3(qa.x, qa.y, qa.z), mk3(qb.x, qb.y, qb.z), 0.01f, qa.w, s_stack[wave], lane, spill_array);
-                        has = true;
-                    }
-                }
-            }
-            if (!__ballot(has)) { if (head >= tail) break; else continue; }
-        }
-        if (has)
-        {
-            const int res = anyhit_step<STATS>(st, a.nodes, a.tris, nn, nt);
-            if (res == 2) atomicOr(&s_bits[code >> 6][(code >> 5) & 1u], 1u << (code & 31u));
-            if (res != 0) has = false;
-        }
-        if (STATS) steps++;
-    }
-    __syncthreads();
-    // ---- phase 3: packed mask words -----------------------------------------------------------------------------
-    if (threadIdx.x < PW_TILES * 2)
-    {
-        const int tl = threadIdx.x >> 1, half = threadIdx.x & 1, tile = blockIdx.x * PW_TILES + tl;
-        if (tile < n_tiles)
-        {
-            const int tx = tile % a.tiles_x, ty = tile / a.tiles_x + a.tile_y0, my = ty * 2 + half;
-            if (my * 4 >= a.y0 && my * 4 < a.y1 && my * 4 < a.h) a.mask[(size_t)my * a.mw + tx] = s_bits[tl][half];
-        }
-    }
-    if (STATS && a.stats)
-    {
-        uint32_t mx = steps;
-        for (int o = 32; o > 0; o >>= 1) { uint32_t t = __shfl_down(mx, o); mx = t > mx ? t : mx; }
-        for (int o = 32; o > 0; o >>= 1) { nn += __shfl_down(nn, o); nt += __shfl_down(nt, o); }
-        if (lane == 0)
-        {
-            atomicAdd(a.stats + 0, (unsigned long long)nn);
-            atomicAdd(a.stats + 1, (unsigned long long)nt);
-            atomicAdd(a.stats + 2, (unsigned long long)mx);
-        }
-    }
-}
-#endif // HR_DEV_PATHS
-
 // ------------------------------------------------------------------------------------------------
 
 #ifndef TEMPORAL_WAVES
@@ -563,7 +420,6 @@ struct hr_shadows : PassCore
     int     read_idx = 0;             // ATrous::read_idx
     int     last_ping_pong = 0;
     int           latched_exact = -1;       // arithmetic mode of the last temporal stage: the `nd` side image it wrote has a mode-specific layout
-    bool          persistent_waves = false; // HR_TRACE_KERNEL=queue selects the persistent-wave ray-queue kernel (A/B measurements)
     // developer switches (tools/timeline.py, tools/passbench.py), read from the environment ONCE in hr_shadows_create — the
     // render path never calls getenv
     int           dbg_only_tx = -1, dbg_only_ty = -1;
@@ -626,9 +482,6 @@ hr_status hr_shadows_create(hr_ctx* ctx, int32_t full_width, int32_t full_height
     hr_shadows* p = nullptr;
     hr_status   s = pass_new(&p, ctx, full_width, full_height, scale, band, out, BandRule::Shadows, "shadows");
     if (s != HR_OK) return s;
-#ifdef HR_DEV_PATHS
-    { const char* e = getenv("HR_TRACE_KERNEL"); p->persistent_waves = (e && std::string(e) == "queue"); }
-#endif
     if (const char* e = getenv("HR_DEBUG_ONLY_TILE")) sscanf(e, "%d,%d", &p->dbg_only_tx, &p->dbg_only_ty);
     if (const char* e = getenv("HR_SHADOW_CACHE")) p->occluder_cache = atoi(e) != 0;
     if (const char* e = getenv("HR_TEMPORAL_PAIRS")) p->temporal_paths = atoi(e) != 0 ? (p->temporal_paths | TP_PAIRS) : (p->temporal_paths & ~TP_PAIRS);
@@ -703,9 +556,9 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     hr_status s = check_inputs(p, in, false);
     if (s != HR_OK) return s;
     HR_CHECK_ARG(in->sobol && in->scrambling_ranking);
-    // statistics, timelines, the persistent-wave A/B kernel and the debug switches
-    HR_REJECT_SHARED_DEV(scene, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
-    HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->persistent_waves || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
+    // statistics, timelines and the debug switches
+    HR_REJECT_SHARED_DEV(scene, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
+    HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_shadows_ray_trace", p->want_stats || !p->dbg_timeline.empty() || p->dbg_skip_traversal || p->dbg_only_tx >= 0);
     const bool       cutout = cutout_on(scene, HR_RAY_SHADOW);
     const CutoutView cv = cutout ? cutout_view_of(scene) : CutoutView();
     hipStream_t st = (hipStream_t)stream_;
@@ -739,25 +592,12 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
     if ((s = p->tile_order.flush(st)) != HR_OK) return s;   // last launch's costs, if no temporal stage took them along
     a.order = p->tile_order.order_arg(n_tiles); a.cost = p->tile_order.cost_arg(n_tiles);
     const uint64_t px = (uint64_t)p->w * (p->y1 - p->y0);
-    if (scene->shared)
-    {
-        int ev = p->prof.begin("ray_trace", st, px * 12 + px / 8);
-        hipLaunchKernelGGL((cutout ? k_shadows_trace<false, true, true> : k_shadows_trace<false, true>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
-        p->prof.end(ev, st);
-        HR_HIP(hipGetLastError());
-        if (a.cost && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;
-        return HR_OK;
-    }
     if (p->want_stats)
     {
         a.cost = nullptr;
         // instrumented build of the same kernel: counts node visits / triangle tests
         HR_HIP(hipMemsetAsync((char*)p->counters.p + 16, 0, 24, st));
         a.stats = (unsigned long long*)((char*)p->counters.p + 16);
-#ifdef HR_DEV_PATHS
-        if (p->persistent_waves) hipLaunchKernelGGL(k_shadows_trace_pw<true>, dim3(cdiv(n_tiles, PW_TILES)), dim3(256), 0, st, a);
-        else
-#endif
         hipLaunchKernelGGL(k_shadows_trace<true>, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
         HR_HIP(hipGetLastError());
         return HR_OK;
@@ -779,14 +619,13 @@ hr_status hr_shadows_ray_trace(hr_shadows* p, const hr_scene* scene, const hr_fr
         a.timeline = nullptr;
     }
     int ev = p->prof.begin("ray_trace", st, px * 12 + px / 8);
-#ifdef HR_DEV_PATHS
-    if (p->persistent_waves) hipLaunchKernelGGL(k_shadows_trace_pw<false>, dim3(cdiv(n_tiles, PW_TILES)), dim3(256), 0, st, a);
-    else
-#endif
-    hipLaunchKernelGGL((cutout ? k_shadows_trace<false, false, true> : k_shadows_trace<false>), dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
+    // a shared scene arrives here too: HR_REJECT_SHARED_DEV has refused everything above for it
+    const auto kernel = scene->shared ? (cutout ? k_shadows_trace<false, true, true> : k_shadows_trace<false, true>)
+                                      : (cutout ? k_shadows_trace<false, false, true> : k_shadows_trace<false>);
+    hipLaunchKernelGGL(kernel, dim3(cdiv(n_slots, TRACE_WAVES)), dim3(64 * TRACE_WAVES), 0, st, a, cv);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());
-    if (a.cost && !p->persistent_waves && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;
+    if (a.cost && (s = p->tile_order.traced(n_tiles, st)) != HR_OK) return s;
     return HR_OK;
 }
 

@@ -20,6 +20,9 @@
 #if defined(AO_SEQ) || defined(DDGI_SEQ) || defined(AO_COOP) || defined(DDGI_COOP) || defined(REFL_COOP)
 #error "AO_SEQ, DDGI_SEQ, AO_COOP, DDGI_COOP and REFL_COOP are retired (lane-sequential any-hit rays; per-lane flat trace paths): see docs/EXPERIMENTS.md, 'One walk call per ray'"
 #endif
+#ifdef HR_DEV_PATHS
+#error "HR_DEV_PATHS is retired (persistent-wave shadow trace, HR_TRACE_KERNEL=queue; wavefront DDGI probe trace, HR_DDGI_WAVEFRONT=1): see docs/EXPERIMENTS.md, 'The fenced-off A/B kernels retired'"
+#endif
 
 namespace hr {
 
@@ -421,49 +424,6 @@ HR_DEV bool trace_any(const Node8* __restrict__ nodes, const TriGPU* __restrict_
 
 HR_DEV void     wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 HR_DEV uint32_t lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-
-#ifdef HR_DEV_PATHS   // the persistent-wave shadow trace (shadows.hip k_shadows_trace_pw) and the wavefront queue kernels (trace_queue.h)
-// ---- step-wise any-hit traversal (for persistent waves that refill idle lanes from a ray queue) ------------------
-struct AnyHitLane
-{
-    RayPre    r;
-    float     t_min, t_max;
-    uint32_t  cur;
-    LaneStack st;
-};
-
-HR_DEV void anyhit_begin(AnyHitLane& s, f3 o, f3 d, float t_min, float t_max, uint32_t* wave_stack, int lane, uint32_t* spill_array)
-{
-    s.r = ray_prepare(o, d);
-    s.t_min = t_min;
-    s.t_max = t_max;
-    s.st.init(wave_stack, lane, spill_array);
-    s.cur = 1u;
-}
-
-// One node (box tests + the triangles of its hit leaves).  Returns 0 = keep going, 1 = occluded, 2 = done, no hit.
-template <bool STATS>
-HR_DEV int anyhit_step(AnyHitLane& s, const Node8* __restrict__ nodes, const TriGPU* __restrict__ tris, uint32_t& n_nodes, uint32_t& n_tris)
-{
-    uint32_t ni;
-    if (!walk_next<HR_ANY_ORDER != HR_ORDER_SLOTS>(s.cur, s.st, ni)) return 2;
-    const NodeHits h  = test_node<HR_ANY_ORDER>(load_node(nodes, ni), s.r, s.t_min, s.t_max);
-    if (STATS) n_nodes++;
-    uint32_t trimask = walk_expand(h, s.cur, s.st);
-    while (trimask)
-    {
-        const uint32_t i = (uint32_t)__builtin_ctz(trimask);
-        trimask &= trimask - 1u;
-        f3       v0, v1, v2;
-        uint32_t prim;
-        load_tri(tris, h.tri_base + i, v0, v1, v2, prim);
-        if (STATS) n_tris++;
-        float t, u, v;
-        if (ray_tri<false>(s.r, v0, v1, v2, s.t_min, s.t_max, t, u, v)) return 1;
-    }
-    return ((s.cur & 0xffu) != 0u || s.st.sp > 0) ? 0 : 2;
-}
-#endif // HR_DEV_PATHS
 
 struct HitRec
 {

@@ -59,8 +59,7 @@ def test_masks_do_not_depend_on_bvh_shape_or_scheduler(hr, ctx, full, monkeypatc
     ref.ray_trace(full["scene"], _fi(hr, full, 1))
     torch.cuda.synchronize()
     base, rays = ref.image(ref.IMG_MASK).clone(), ref.ray_count()
-    # (a) the persistent-wave ray-queue kernel (another mapping of rays to lanes and waves) is an A/B path of the -DHR_DEV_PATHS build:
-    #     tests/test_gpu_devpaths.py
+    # (a) another mapping of tiles to waves: test_gpu_tile_order.py::test_shadows_and_ao_do_not_depend_on_the_launch_order
     # (b) a BVH over split triangle references: other boxes, duplicated triangles
     monkeypatch.setenv("HR_BVH_SPLIT", "0.02")
     split_scene = hr.Scene(ctx, full["sd"])
