@@ -404,6 +404,42 @@ class Scene:
                "hr_gbuffer_raycast")
         return dict(gb1=gb1, gb2=gb2, gb3=gb3, depth=depth)
 
+    # ---- emissive materials (include/hr_emission.h, emission.py; DESIGN.md §7 "Emissive materials"): opt-in per scene, off by default, every kind of scene
+    def set_emission(self, enable: bool = True, scale: float = 1.0, stream=None):
+        """hr_scene_set_emission: hits on emitting materials add ``scale`` x their emissive colour (or emissive texture) in the DDGI, reflection and
+        ground-truth hit shaders.  Enabling validates the emissive constants (finite, >= 0)."""
+        from . import emission
+        emission.set_emission(self.h, enable, scale, stream)
+        return self
+
+    def emission_state(self):
+        """hr_scene_get_emission -> (enabled, scale)"""
+        from . import emission
+        return emission.get_emission(self.h)
+
+    def set_emissive(self, rgb, stream=None):
+        """hr_scene_set_emissive: per-material emissive rgb [n_materials, 3] (initially materials[:, 5:8]).  A cuda float32 tensor goes through
+        hr_scene_set_emissive_device: one device copy, capturable, unchecked."""
+        from . import emission
+        emission.set_emissive(self.h, self.n_materials, rgb, stream)
+        return self
+
+    def set_emissive_textures(self, tex, stream=None):
+        """hr_scene_set_emissive_textures: per material an index into the scene's textures (-1: none); the texture replaces the constant"""
+        from . import emission
+        emission.set_emissive_textures(self.h, self.n_materials, tex, stream)
+        return self
+
+    def emission(self, prim, tuv, stream=None):
+        """hr_scene_emission: E (cuda float32 [n, 3]) of hits as ``closest_hit`` reports them (``tuv`` [n, 3], ``prim`` [n])"""
+        from . import emission
+        return emission.emission(self.h, prim, tuv, stream)
+
+    def emissive_image(self, np_ubo, w, h, device="cuda", stream=None):
+        """hr_gbuffer_emissive: the E of every pixel's primary hit, cuda float16 [h, w, 4]; zeros where the G-buffer has sky"""
+        from . import emission
+        return emission.emissive_image(self.h, np_ubo, w, h, device, stream)
+
 
 def _instanced_desc(isd):
     """(hr_instanced_scene_desc, the host arrays it points into) of a synth.InstancedSceneData"""

@@ -47,6 +47,12 @@ class DeferredShading:
         from . import probe_vis
         probe_vis.render_probes(self.h, inputs, ddgi.h, radius, what, depth_out, probe_id_out, stream)
 
+    def add_emissive(self, image, stream=None):
+        """hr_deferred_add_emissive (include/hr_emission.h): colour.rgb += image.rgb on this pass's output, after ``render`` on the same stream and
+        before TAA.  ``image``: ``Scene.emissive_image`` or an integrator's own, cuda float16 [h, w, 4]."""
+        from . import emission
+        emission.add_emissive(self.h, image, stream)
+
     def output(self):
         v = hr_image_view()
         _check(lib().hr_deferred_output(self.h, C.byref(v)), "hr_deferred_output")

@@ -346,7 +346,11 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
     metallicRoughnessTexture (roughness = G, metallic = B) become SceneData.uvs / tangents / material_textures / textures
     (the hit shaders' fetch_* inputs); images in other encodings (JPEG) are skipped, the factor then applies.
     alphaMode MASK fills alpha_cutoffs[m] with alphaCutoff (default 0.5) divided by a baseColorFactor alpha other than 1; OPAQUE and BLEND give 0.
-    Nothing applies the array by itself: pass it to Scene.set_alpha_cutoffs."""
+    Nothing applies the array by itself: pass it to Scene.set_alpha_cutoffs.
+    emissiveTexture (PNG) fills emissive_textures[m] with an index into `textures` (-1: none), for Scene.set_emissive_textures.  On the device the
+    emissive texture REPLACES the emissive constant (include/hr_emission.h), so glTF's "emissiveFactor times emissiveTexture" is honoured here: where
+    the factor is not (1, 1, 1) the material gets a COPY of the image whose rgb is round-to-nearest(texel * factor), clipped to 255 (alpha kept); where
+    it is (1, 1, 1) the image itself.  materials[m][5..7] stay emissiveFactor: what the material emits if the texture is not bound."""
     import base64
     import json
     raw = open(path, "rb").read()
@@ -391,28 +395,9 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
 
     textures, image_slot = [], {}
 
-    def texture_slot(tex_info):
-        """glTF textureInfo -> index into `textures` (-1: absent or not a PNG)"""
-        if not tex_info:
-            return -1
-        src = doc["textures"][tex_info["index"]].get("source")
-        if src is None:
-            return -1
-        if src not in image_slot:
-            img, data = doc["images"][src], None
-            if "uri" in img:
-                data = base64.b64decode(img["uri"].split(",", 1)[1]) if img["uri"].startswith("data:") else open(os.path.join(base, img["uri"]), "rb").read()
-            elif "bufferView" in img:
-                bv = doc["bufferViews"][img["bufferView"]]
-                data = bytes(buffers[bv["buffer"]][bv.get("byteOffset", 0):bv.get("byteOffset", 0) + bv["byteLength"]])
-            if data is not None and data[:8] == _PNG_SIG:
-                image_slot[src] = len(textures)
-                textures.append(np.ascontiguousarray(_rgba(decode_png(data))))
-            else:
-                image_slot[src] = -1
-        return image_slot[src]
+    texture_slot = lambda tex_info: _gltf_texture_slot(doc, buffers, base, textures, image_slot, tex_info)
 
-    mats, mat_tex, cutoffs = [], [], []
+    mats, mat_tex, cutoffs, em_tex = [], [], [], []
     for m in doc.get("materials", []):
         pbr = m.get("pbrMetallicRoughness", {})
         bc = pbr.get("baseColorFactor", [1, 1, 1, 1])
@@ -421,6 +406,7 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
         bct, nrm = texture_slot(pbr.get("baseColorTexture")), texture_slot(m.get("normalTexture"))
         mr = texture_slot(pbr.get("metallicRoughnessTexture"))
         mat_tex.append([bct, nrm, mr, mr, 1, 2])
+        em_tex.append(_emissive_slot(textures, texture_slot(m.get("emissiveTexture")), em))
         # alphaMode MASK: texel alpha * baseColorFactor alpha < alphaCutoff is cut away; the back end compares the texel alone, so the factor is folded in
         cut = float(m.get("alphaCutoff", 0.5)) if m.get("alphaMode", "OPAQUE") == "MASK" else 0.0
         if cut > 0.0 and float(bc[3]) != 1.0:
@@ -430,6 +416,7 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
     mats.append([0.8, 0.8, 0.8, 0.0, 0.5, 0.0, 0.0, 0.0])
     mat_tex.append([-1, -1, -1, -1, 1, 2])
     cutoffs.append(0.0)
+    em_tex.append(-1)
 
     verts, norms, tmat, tmesh, uvs, tans = [], [], [], [], [], []
     mesh_id = [0]
@@ -533,7 +520,7 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
             raise ValueError(f"{path}: no triangle primitives")
         return InstancedSceneData(meshes=meshes, instances=inst, materials=np.asarray(mats, np.float32), name=os.path.basename(path),
                                   material_textures=np.asarray(mat_tex, np.int32) if textures else None, textures=textures if textures else None,
-                                  alpha_cutoffs=np.asarray(cutoffs, np.float32))
+                                  alpha_cutoffs=np.asarray(cutoffs, np.float32), emissive_textures=np.asarray(em_tex, np.int32))
     if not verts:
         raise ValueError(f"{path}: no triangle primitives")
     sd = SceneData(verts=np.ascontiguousarray(np.concatenate(verts), np.float32), normals=np.ascontiguousarray(np.concatenate(norms), np.float32),
@@ -545,7 +532,43 @@ def load_gltf(path: str, scale: float = 1.0, instanced: bool = False):
         sd.material_textures = np.asarray(mat_tex, np.int32)
         sd.textures = textures
     sd.alpha_cutoffs = np.asarray(cutoffs, np.float32)
+    sd.emissive_textures = np.asarray(em_tex, np.int32)
     return sd
+
+
+def _gltf_texture_slot(doc, buffers, base, textures, image_slot, tex_info):
+    """glTF textureInfo -> index into `textures`, which grows by the image at its first use (-1: absent or not a PNG)"""
+    import base64
+    if not tex_info:
+        return -1
+    src = doc["textures"][tex_info["index"]].get("source")
+    if src is None:
+        return -1
+    if src not in image_slot:
+        img, data = doc["images"][src], None
+        if "uri" in img:
+            data = base64.b64decode(img["uri"].split(",", 1)[1]) if img["uri"].startswith("data:") else open(os.path.join(base, img["uri"]), "rb").read()
+        elif "bufferView" in img:
+            bv = doc["bufferViews"][img["bufferView"]]
+            data = bytes(buffers[bv["buffer"]][bv.get("byteOffset", 0):bv.get("byteOffset", 0) + bv["byteLength"]])
+        if data is not None and data[:8] == _PNG_SIG:
+            image_slot[src] = len(textures)
+            textures.append(np.ascontiguousarray(_rgba(decode_png(data))))
+        else:
+            image_slot[src] = -1
+    return image_slot[src]
+
+
+def _emissive_slot(textures, slot, factor):
+    """the texture a material's emissiveTexture binds: `slot` itself where emissiveFactor is (1, 1, 1), else a copy of it, appended to `textures`,
+    whose rgb is the image's times the factor, rounded to nearest and clipped to 255 (load_gltf's docstring); -1 stays -1"""
+    f = np.asarray(factor, np.float64)[:3]
+    if slot < 0 or np.all(f == 1.0):
+        return slot
+    t = textures[slot].copy()
+    t[..., :3] = np.clip(np.rint(t[..., :3].astype(np.float64) * f), 0, 255).astype(np.uint8)
+    textures.append(np.ascontiguousarray(t))
+    return len(textures) - 1
 
 
 def load_gltf_instanced(path: str, scale: float = 1.0):
@@ -719,7 +742,8 @@ def load_gltf_skinned(path: str, scale: float = 1.0) -> SkinnedMesh:
     expanded to the [n][3][3] corner stream with JOINTS_0 (uint8 / uint16) and WEIGHTS_0 (float or normalised integers; each vertex's four weights
     are normalised to sum 1 in float64 before they are rounded to float32), the morph `targets` (POSITION and NORMAL deltas; mesh.weights as the
     default weights), the skeleton and the animations (LINEAR and STEP).  Raises ValueError, naming the cause, for CUBICSPLINE samplers, JOINTS_1
-    (more than four influences) and sparse accessors.  Materials as load_gltf gives them, without textures."""
+    (more than four influences) and sparse accessors.  Materials as load_gltf gives them; of their textures only emissiveTexture is read, by load_gltf's
+    rule (rest.emissive_textures, rest.textures, rest.uvs from TEXCOORD_0; rest.material_textures names no other texture)."""
     doc, buffers = _gltf_document(path)
     acc = lambda i, as_float=False: _gltf_accessor(doc, buffers, i, path, as_float)
     nodes = doc.get("nodes", [])
@@ -740,8 +764,12 @@ def load_gltf_skinned(path: str, scale: float = 1.0) -> SkinnedMesh:
         mats.append([bc[0], bc[1], bc[2], pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), em[0], em[1], em[2]])
     default_mat = len(mats)
     mats.append([0.8, 0.8, 0.8, 0.0, 0.5, 0.0, 0.0, 0.0])
+    # the emissive textures alone (load_gltf's rule: a copy times emissiveFactor where that is not (1, 1, 1)), with TEXCOORD_0 when one is bound
+    textures, image_slot, base = [], {}, os.path.dirname(os.path.abspath(path))
+    em_tex = [_emissive_slot(textures, _gltf_texture_slot(doc, buffers, base, textures, image_slot, m.get("emissiveTexture")), m.get("emissiveFactor", [0, 0, 0]))
+              for m in doc.get("materials", [])] + [-1]
 
-    V, N, J, W, TM, TP, TN = [], [], [], [], [], [], []
+    V, N, J, W, TM, TP, TN, UV = [], [], [], [], [], [], [], []
     normal_deltas = True
     for prim in mesh["primitives"]:
         if prim.get("mode", 4) != 4:
@@ -769,6 +797,7 @@ def load_gltf_skinned(path: str, scale: float = 1.0) -> SkinnedMesh:
         w = np.where(s > 0.0, w / np.where(s > 0.0, s, 1.0), w)
         V.append(tri); N.append(tn); J.append(jn.astype(np.uint16)[idx]); W.append(w.astype(np.float32)[idx])
         TM.append(np.full(len(tri), prim.get("material", default_mat), np.uint32))
+        UV.append(acc(at["TEXCOORD_0"], as_float=True).astype(np.float32)[idx] if "TEXCOORD_0" in at else np.zeros((len(tri), 3, 2), np.float32))
         tp, tnd = [], []
         for tg in prim.get("targets", []):
             tp.append(acc(tg["POSITION"], as_float=True).astype(np.float32)[idx] if "POSITION" in tg else np.zeros_like(tri))
@@ -785,7 +814,12 @@ def load_gltf_skinned(path: str, scale: float = 1.0) -> SkinnedMesh:
         raise ValueError(f"{path}: the primitives of the skinned mesh differ in their number of morph targets")
     verts = np.ascontiguousarray(np.concatenate(V), np.float32)
     out.rest = SceneData(verts=verts, normals=np.ascontiguousarray(np.concatenate(N), np.float32), tri_material=np.concatenate(TM),
-                         tri_mesh_id=np.ones(len(verts), np.uint32), materials=np.asarray(mats, np.float32), name=out.name)
+                         tri_mesh_id=np.ones(len(verts), np.uint32), materials=np.asarray(mats, np.float32), name=out.name,
+                         emissive_textures=np.asarray(em_tex, np.int32))
+    if textures:
+        mt = np.full((len(mats), 6), -1, np.int32)
+        mt[:, 4], mt[:, 5] = 1, 2
+        out.rest.uvs, out.rest.material_textures, out.rest.textures = np.ascontiguousarray(np.concatenate(UV), np.float32), mt, textures
     out.joints = np.ascontiguousarray(np.concatenate(J), np.uint16)
     out.weights = np.ascontiguousarray(np.concatenate(W), np.float32)
     if n_targets:

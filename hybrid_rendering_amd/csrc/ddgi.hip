@@ -6,6 +6,7 @@
 #include "hr_internal.h"
 #include "shading.h"
 #include "cutout_host.h"
+#include "emission_host.h"
 #include "pass_args.h"
 
 using namespace hr;
@@ -67,98 +68,23 @@ extern "C" int hr_debug_divergence_ddgi(uint64_t* out, int reset)
 #ifndef DDGI_TRACE_CUTOUT_EU
 #define DDGI_TRACE_CUTOUT_EU 4   // CUTOUT instantiations, flat and SHARED: the uv and texel addressing do not fit under the opaque kernel's bound
 #endif
+// EMISSIVE (emission.h; hr_scene_set_emission): L = Lo + E of the hit, after the infinite-bounce term and before the radiance store.  The kernels
+// that existed before it keep their names, their arguments and their code: the body is ddgi_trace_body.h, included into both.
+#define HR_DDGI_TRACE_BODY   // ddgi_trace_body.h refuses any other includer
 template <bool STATS, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_EU : SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow)
 {
-    static_assert(!(STATS && SHARED), "no statistics build of the two-level walk");
-    static_assert(!(STATS && CUTOUT), "no statistics build of the cutout walks");
-    __shared__ uint32_t s_stack[DDGI_TRACE_WAVES][HR_STACK_ENTRIES * 64];
-    __shared__ CoopWaveOf<SHARED> s_coop[DDGI_TRACE_WAVES];   // the cooperative walks' scratch: an instantiation that walks per lane never names it
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int R = a.d.rays_per_probe;
-    const long long gid = (long long)blockIdx.x * (64 * DDGI_TRACE_WAVES) + threadIdx.x;
-    const int probe = a.probe_begin + (int)(gid / R), ray = (int)(gid % R);
-    uint32_t  rays = 0;
-    HR_DIV(DivCounters dvp = {}, dvs = {};)
-    const bool valid = probe < a.n_probes;
-    f3 origin = mk3(0.0f, 0.0f, 0.0f), dir = mk3(0.0f, 0.0f, 1.0f);
-    if (valid)
-    {
-        origin = probe_location(a.d, probe);
-        const f3 f      = spherical_fibonacci((float)ray, (float)R);
-        const float* M  = a.orientation;
-        dir = normalize3(mk3((M[0] * f.x + M[3] * f.y) + M[6] * f.z, (M[1] * f.x + M[4] * f.y) + M[7] * f.z, (M[2] * f.x + M[5] * f.y) + M[8] * f.z));
-        rays++;
-    }
-    uint32_t st_n = 0, st_t = 0;
-    HitOf<SHARED> h;
-    // the scene triple is spelled here, not taken from a context made before the primary ray: hoisting `tc` above this point changes the
-    // code of the <true, false> statistics kernels (docs/EXPERIMENTS.md, "One trace kernel body"); keep `tc` at the hit
-    if constexpr (STATS || (SHARED && !DDGI_COOP2))
-    {
-        // the per-lane walks (the statistics kernel, the perlane2 variant) take only the lanes with a ray.  This guard stays in the kernel:
-        // behind a function that every lane enters, these kernels' code moves (docs/EXPERIMENTS.md, "One walk call per ray")
-        h.prim = -1;
-        if (valid)
-        {
-            if constexpr (STATS) h = trace_closest<true>(a.nodes, a.tris, origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, nullptr, &st_n, &st_t);
-            else h = trace_closest_of<SHARED, CUTOUT>(a.nodes, a.tris, a.sh.inst_shared, a.sh.cull[HR_RAY_GI], origin, dir, 0.001f, 10000.0f, s_stack[wave], lane, cv_gi);
-        }
-    }
-    else h = trace_closest_wave<SHARED, CUTOUT>(valid, a.nodes, a.tris, a.sh, HR_RAY_GI, origin, dir, 0.001f, 10000.0f, s_stack[wave], s_coop[wave], lane, cv_gi HR_DIV(, &dvp));
-    if (valid)
-    {
-        Rng   rng = rng_init((uint32_t)ray, (uint32_t)probe, a.num_frames);
-        f3    L;
-        float hit_distance = 10000.0f;
-#ifdef HR_ABL_DDGI_PRIMARY_ONLY   // developer ablation (tools/ablate.sh): what does each part of the kernel cost?
-        if (true) { L = mk3(h.t, h.u, h.v); hit_distance = h.t; }
-        else
-#endif
-        if (h.prim < 0) L = a.sky.fetch(dir);
-        else
-        {
-            const SurfaceHit s = surface_at(a.sh, h);
-            const f3 Wo = neg3(dir);
-            const f3 F0 = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
-            const f3 c_diffuse = mix3(mul3(s.albedo, sub3(one3(), F0)), mk3(0.0f, 0.0f, 0.0f), s.metallic);
-            const float r2x = next_float(rng), r2y = next_float(rng);
-            TraceCtxOf<SHARED> tc = make_trace_ctx<SHARED>(a.nodes, a.tris, a.sh, s_stack[wave], lane);
-            if constexpr (CUTOUT) tc.cv = cv_shadow;
-            HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
-            f3 Lo = direct_lighting<STATS, CUTOUT>(tc, a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky, rays);
-            if (STATS) { st_n += tc.nn; st_t += tc.nt; }
-#ifndef HR_ABL_DDGI_NO_IRRADIANCE
-            if (a.infinite_bounces == 1)
-#else
-            if (false)
-#endif
-            {
-                const f3 F   = fresnel_schlick_roughness(glsl_max(dot3(s.N, Wo), 0.0f), F0, s.roughness);
-                const f3 kD  = scale3(sub3(one3(), F), 1.0f - s.metallic);
-                const f3 irr = sample_irradiance(a.d, s.P, s.N, Wo, a.prev_irr, a.prev_depth);
-                Lo = add3(Lo, mul3(mul3(scale3(kD, a.gi_intensity), c_diffuse), irr));
-            }
-            L = Lo;
-            hit_distance = 0.001f + h.t;
-        }
-        const size_t o = (size_t)probe * R + ray;
-#if defined(HR_TRACE_DIVERGENCE) && defined(HR_DDGI_DUMP_STEPS)   // developer study (tools/ddgi_sort_study.py): node steps of the primary ray in the unused .w
-        a.radiance[o] = make_uint2(pack_h2(L.x, L.y), pack_h2(L.z, (float)dvp.lane_nodes));
-#else
-        a.radiance[o] = make_uint2(pack_h2(L.x, L.y), pack_h2(L.z, 0.0f));
-#endif
-        a.dirdist[o]  = make_uint2(pack_h2(dir.x, dir.y), pack_h2(dir.z, hit_distance));
-    }
-    HR_DIV(div_flush(dvp, g_div_ddgi); div_flush(dvs, g_div_ddgi + 8);)
-    for (int o = 32; o > 0; o >>= 1) rays += __shfl_down(rays, o);
-    if (lane == 0) a.ray_slots[blockIdx.x * DDGI_TRACE_WAVES + wave] = rays;
-    if (STATS)
-    {
-        for (int o = 32; o > 0; o >>= 1) { st_n += __shfl_down(st_n, o); st_t += __shfl_down(st_t, o); }
-        if (lane == 0) { atomicAdd(a.stats + 0, (unsigned long long)st_n); atomicAdd(a.stats + 1, (unsigned long long)st_t); atomicAdd(a.stats + 2, (unsigned long long)rays); }
-    }
+    constexpr bool     EMISSIVE = false;
+    [[maybe_unused]] const EmissionView em = EmissionView();   // never read
+#include "ddgi_trace_body.h"
 }
+template <bool SHARED, bool CUTOUT>
+__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_CUTOUT_EU) void k_ddgi_trace_emissive(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow, EmissionView em)
+{
+    constexpr bool STATS = false, EMISSIVE = true;
+#include "ddgi_trace_body.h"
+}
+#undef HR_DDGI_TRACE_BODY
 
 // ------------------------------------------------------------------------------------------------
 struct DDGIUpdateArgs
@@ -446,6 +372,7 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
     HR_REJECT_SHARED_DEV(scene, "hr_ddgi_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_GI, "hr_ddgi_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_ddgi_ray_trace", p->want_stats);
+    HR_REJECT_EMISSION(scene, "hr_ddgi_ray_trace", p->want_stats || kDivergenceBuild);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong
@@ -480,7 +407,14 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
     // one CUTOUT instantiation for the two classes the kernel fires; a class that is forced opaque gets a view without a table
     const bool       cut_gi = cutout_on(scene, HR_RAY_GI), cut_shadow = cutout_on(scene, HR_RAY_SHADOW), cutout = cut_gi || cut_shadow;
     const CutoutView cv_gi = cut_gi ? cutout_view_of(scene) : CutoutView(), cv_shadow = cut_shadow ? cutout_view_of(scene) : CutoutView();
-    if (scene->shared) hipLaunchKernelGGL((cutout ? k_ddgi_trace<false, true, true> : k_ddgi_trace<false, true>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow);
+    if (emission_live(scene))
+    {
+        // the EMISSIVE instantiations: picked iff the scene's emission is enabled and some material emits (hr_internal.h emission_live)
+        void (*const kernel[2][2])(DDGITraceArgs, CutoutView, CutoutView, EmissionView) = { { k_ddgi_trace_emissive<false, false>, k_ddgi_trace_emissive<false, true> },
+                                                                                             { k_ddgi_trace_emissive<true, false>, k_ddgi_trace_emissive<true, true> } };
+        hipLaunchKernelGGL(kernel[scene->shared ? 1 : 0][cutout ? 1 : 0], dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow, emission_view_of(scene));
+    }
+    else if (scene->shared) hipLaunchKernelGGL((cutout ? k_ddgi_trace<false, true, true> : k_ddgi_trace<false, true>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow);
     else hipLaunchKernelGGL((cutout ? k_ddgi_trace<false, false, true> : k_ddgi_trace<false, false>), dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow);
     p->prof.end(ev, st);
     HR_HIP(hipGetLastError());

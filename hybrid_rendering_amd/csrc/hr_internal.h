@@ -110,6 +110,10 @@ hr_status deformable_scene_refresh_bounds(const hr_scene* scene);
 // cutouts are enabled for the call's ray class, before anything is enqueued or any state of the pass changes; with every cutoff 0 they run as ever
 bool      reject_cutout_dev_switches(const hr_scene* s, int ray_class, const char* call, bool wanted);
 #define HR_REJECT_CUTOUT(scene, ray_class, call, wanted) do { if (::hr::reject_cutout_dev_switches(scene, ray_class, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
+// emission.hip.  HR_REJECT_EMISSION: the same for a scene whose emission is live (hr_scene_set_emission and some emitting material) — no EMISSIVE
+// instantiation of the instrumented and developer variants exists
+bool      reject_emission_dev_switches(const hr_scene* s, const char* call, bool wanted);
+#define HR_REJECT_EMISSION(scene, call, wanted) do { if (::hr::reject_emission_dev_switches(scene, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
 
 struct DevBuf
 {
@@ -392,6 +396,8 @@ struct hr_scene
         if (mask_stage) (void)hipHostFree(mask_stage);
         if (cutoff_copied) (void)hipEventDestroy(cutoff_copied);
         if (cutoff_stage) (void)hipHostFree(cutoff_stage);
+        if (em_copied) (void)hipEventDestroy(em_copied);
+        if (em_stage) (void)hipHostFree(em_stage);
     }
     int           max_rel_depth = 0;              // deepest node below an instance root (a fresh top level must leave room for it)
     std::vector<int32_t>  level_offsets;          // level_nodes[level_offsets[d] .. level_offsets[d + 1]): the nodes of depth d
@@ -445,6 +451,18 @@ struct hr_scene
     hr::DevBuf    cutoff_dev, cutout_tab;         // [n_materials] floats; per attribute index { albedo texture + 1 or 0, cutoff bits }; allocated by the first setter call
     float*        cutoff_stage = nullptr;         // pinned source of the copy into cutoff_dev; the next call waits for cutoff_copied before it rewrites it
     hipEvent_t    cutoff_copied = nullptr;
+    // ---- emissive materials (emission.hip, emission.h; DESIGN.md §7 "Emissive materials").  emission_enabled / emission_scale are host state, read when a pass or query
+    // enqueues: a hit-shading launch takes its EMISSIVE instantiation iff emission_live().  The tables are keyed on the material, so no update of
+    // the geometry touches them; allocated by the first setter call, never after
+    bool          emission_enabled = false;
+    float         emission_scale = 1.0f;
+    std::vector<float>    emissive_host;          // [n_materials][3] as the host last set them (initially materials[m][5..7]); empty: no setter call yet
+    std::vector<int32_t>  emissive_tex_host;      // [n_materials]: emissive texture, -1 none
+    bool          emissive_on_device = false;     // hr_scene_set_emissive_device ran since the last host form: the host does not know the constants
+    bool          emission_any = false;           // some material emits, as far as the host knows (emissive_on_device: assumed)
+    hr::DevBuf    em_rgb, em_tex, em_inst;        // the tables of EmissionView; instanced kinds: per instance { first_tri, mesh_tri_base } + a sentinel (hr_scene_emission)
+    float*        em_stage = nullptr;             // pinned source of the host forms' copies: [M][3] floats, then [M] int32; guarded by em_copied
+    hipEvent_t    em_copied = nullptr;
     // ---- deforming geometry (deform_refit.hip): trees built without spatial splits, refitted under new vertices through `deform` and node_box.
     // deform.hip: a flat scene (`deformable`); hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`.  instances_shared_deform.hip: the
     // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
@@ -465,5 +483,13 @@ namespace hr {
 inline uint32_t cull_of(const hr_scene* s, int ray_class) { return (s->cull_mask[ray_class] & 0xFFu) << kInstanceMaskShift; }
 // does a launch of `ray_class` over the scene take its CUTOUT instantiation?
 inline bool cutout_on(const hr_scene* s, int ray_class) { return s->cutout_enabled && !s->class_opaque[ray_class]; }
+// a -DHR_TRACE_DIVERGENCE build of the library (developer instrumentation, traverse.h)
+#ifdef HR_TRACE_DIVERGENCE
+constexpr bool kDivergenceBuild = true;
+#else
+constexpr bool kDivergenceBuild = false;
+#endif
+// does a hit-shading launch over the scene take its EMISSIVE instantiation?
+inline bool emission_live(const hr_scene* s) { return s->emission_enabled && s->emission_any; }
 inline Scene2 scene2_of(const hr_scene* s, int ray_class) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p, cull_of(s, ray_class) }; }
 } // namespace hr

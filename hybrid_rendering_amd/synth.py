@@ -38,6 +38,7 @@ class SceneData:
     material_textures: np.ndarray = None  # [m,6] int32: albedo, normal, roughness, metallic texture (-1 none), roughness channel, metallic channel
     textures: list = None                 # list of [h,w,4] uint8 (RGBA8 UNORM)
     alpha_cutoffs: np.ndarray = None      # [m] float32 for Scene.set_alpha_cutoffs (0: opaque); nothing applies it by itself
+    emissive_textures: np.ndarray = None  # [m] int32 for Scene.set_emissive_textures (-1: none); nothing applies it by itself
 
     @property
     def n_tris(self) -> int:
@@ -60,6 +61,7 @@ class InstancedSceneData:
     material_textures: np.ndarray = None
     textures: list = None
     alpha_cutoffs: np.ndarray = None      # [m] float32 for Scene.set_alpha_cutoffs (0: opaque); nothing applies it by itself
+    emissive_textures: np.ndarray = None  # [m] int32 for Scene.set_emissive_textures (-1: none); nothing applies it by itself
 
     def matrices(self) -> np.ndarray:
         return np.ascontiguousarray(np.stack([np.asarray(m, np.float32).reshape(16) for m, _, _ in self.instances]), np.float32)
@@ -93,7 +95,7 @@ class InstancedSceneData:
             U.append(me.uvs); T.append(me.tangents)
         cat = lambda xs: None if any(x is None for x in xs) else np.ascontiguousarray(np.concatenate(xs))
         return SceneData(verts=cat(V), normals=cat(Nn), tri_material=cat(M), tri_mesh_id=cat(I), materials=np.asarray(self.materials, np.float32), name=self.name + "_flat",
-                         uvs=cat(U), tangents=cat(T), material_textures=self.material_textures, textures=self.textures)
+                         uvs=cat(U), tangents=cat(T), material_textures=self.material_textures, textures=self.textures, emissive_textures=self.emissive_textures)
 
 
 def model_matrix(translate=(0.0, 0.0, 0.0), axis=(0.0, 1.0, 0.0), angle=0.0, scale=1.0) -> np.ndarray:
@@ -383,6 +385,42 @@ def with_leaf_cutout(sd: SceneData, material: int = FOLIAGE_MATERIAL, cutoff: fl
 
 
 # --------------------------------------------------------------------------- scenes
+
+def with_light_panel(sd: SceneData, rgb=(14.0, 12.5, 10.0), size: float = 0.3, drop: float = 0.15) -> SceneData:
+    """`sd` plus a horizontal emissive quad (`size` of the bounds' extent in x and z, `drop` of its height under the top, facing down) under a
+    material of its own, the last one: a light panel for Scene.set_emission (tools/render_frame.py --emissive)"""
+    import dataclasses
+    lo, hi = (np.asarray(b, np.float64) for b in sd.bounds())
+    c, e = 0.5 * (lo + hi), hi - lo
+    y = hi[1] - drop * e[1]
+    x0, x1, z0, z1 = c[0] - 0.5 * size * e[0], c[0] + 0.5 * size * e[0], c[2] - 0.5 * size * e[2], c[2] + 0.5 * size * e[2]
+    q = np.array([[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]], np.float32)
+    v = np.stack([q[[0, 1, 2]], q[[0, 2, 3]]])
+    n = np.broadcast_to(np.array([0.0, -1.0, 0.0], np.float32), v.shape).copy()
+    mats = np.concatenate([np.asarray(sd.materials, np.float32), np.array([[0.2, 0.2, 0.2, 0.0, 0.8, rgb[0], rgb[1], rgb[2]]], np.float32)])
+    m = len(mats) - 1
+    cat = lambda a, b: None if a is None else np.ascontiguousarray(np.concatenate([a, b]))
+    mt = None if sd.material_textures is None else np.concatenate([np.asarray(sd.material_textures, np.int32), np.array([[-1, -1, -1, -1, 1, 2]], np.int32)])
+    return dataclasses.replace(sd, verts=cat(sd.verts, v), normals=cat(sd.normals, n), tri_material=cat(np.asarray(sd.tri_material, np.uint32), np.full(2, m, np.uint32)),
+                               tri_mesh_id=cat(np.asarray(sd.tri_mesh_id, np.uint32), np.full(2, int(np.max(sd.tri_mesh_id)) + 1, np.uint32)), materials=mats,
+                               uvs=cat(sd.uvs, np.zeros((2, 3, 2), np.float32)), tangents=cat(sd.tangents, np.tile(np.array([1.0, 0.0, 0.0], np.float32), (2, 3, 1))),
+                               material_textures=mt, name=sd.name + "_panel")
+
+
+def with_emissive_twins(sd: SceneData, fraction: float, rgb=(2.0, 2.0, 2.0), seed: int = 3) -> SceneData:
+    """`sd` with every material twice — material m + M is m with the emissive constant `rgb` — and a random `fraction` of the triangles moved to their
+    material's twin: about that share of all hits then lands on an emitter (tools/emission_probe.py)"""
+    import dataclasses
+    M = len(sd.materials)
+    twin = np.asarray(sd.materials, np.float32).copy()
+    twin[:, 5:8] = rgb
+    pick = np.random.RandomState(seed).uniform(size=sd.n_tris) < fraction
+    tm = np.asarray(sd.tri_material, np.uint32).copy()
+    tm[pick] += M
+    mt = None if sd.material_textures is None else np.concatenate([np.asarray(sd.material_textures, np.int32)] * 2)
+    return dataclasses.replace(sd, tri_material=tm, materials=np.concatenate([np.asarray(sd.materials, np.float32), twin]), material_textures=mt,
+                               name=f"{sd.name}_emissive_{fraction:g}")
+
 
 def cornell32() -> SceneData:
     """32 triangles: 5 walls x2, two boxes x (5 faces x2), ceiling light quad x2."""

@@ -5,6 +5,9 @@ bench.py are numbers of.   python tools/render_frame.py [--width 960 --height 54
 # (the sky, SH9, the prefiltered chain and the BRDF LUT); without them the environment is synth_env's host-made gradient.
 # --probes [SCALE] draws the DDGI probe grid over the composite (DeferredShading::render_probes): one sphere of radius SCALE per probe, an eighth
 # of the smallest grid step by default, coloured with the probe's irradiance; the depth it writes is the depth TAA sees.
+# --emissive [SCALE] hangs a light panel into the scene (synth.with_light_panel), switches the directional light off and enables emission
+# (include/hr_emission.h): the room is lit by what the probe and reflection rays find on the panel, and the panel's own pixels come from
+# Scene.emissive_image through DeferredShading.add_emissive, after the composite and before TAA.
 import argparse, os, struct, sys, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,6 +32,7 @@ def main():
     src.add_argument("--hdr", metavar="FILE", help="a Radiance .hdr equirectangular map as the environment (hr_env_update_equirect)")
     src.add_argument("--sky", action="store_true", help="the analytic sky, its sun along the scene's light (hr_env_update_sky)")
     ap.add_argument("--probes", nargs="?", type=float, const=0.0, default=None, metavar="SCALE", help="visualise the DDGI probe grid; SCALE: the spheres' radius (default: min grid step / 8)")
+    ap.add_argument("--emissive", nargs="?", type=float, const=1.0, default=None, metavar="SCALE", help="a light panel as the only light; SCALE: hr_scene_set_emission's scale (default 1)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame.png"))
     a = ap.parse_args()
     import torch
@@ -37,9 +41,15 @@ def main():
     sd = synth.sponza_like(1.0)
     if a.textured:
         sd = synth.with_textures(sd)
+    if a.emissive is not None:
+        sd = synth.with_light_panel(sd)
     ctx = hr.Context(0)
     scene = hr.Scene(ctx, sd)
     light = synth.sponza_light()
+    if a.emissive is not None:
+        scene.set_emission(True, a.emissive)
+        light = light.copy()
+        light[3] = 0.0      # data0.w: the intensity
     sob, sr = synth.blue_noise_tables()
     sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
     lo, hi = sd.bounds()
@@ -84,6 +94,8 @@ def main():
             depth_out = torch.empty_like(cur["depth"])
             df.render_probes(fi, gi, radius=a.probes if a.probes > 0 else float(ddgi_u["grid_step"].min()) / 8.0, depth_out=depth_out)
             seen = dict(cur, depth=depth_out)
+        if a.emissive is not None:
+            df.add_emissive(scene.emissive_image(ubo, W, H))
         taa.update(f)
         taa.render(df.output(), seen, f & 1)
         prev = (cur, half)
