@@ -440,6 +440,25 @@ class Scene:
         from . import emission
         return emission.emissive_image(self.h, np_ubo, w, h, device, stream)
 
+    # ---- extra lights (include/hr_lights.h, lights.py): a per-scene list beside the UBO light, empty by default, every kind of scene
+    def set_lights(self, lights, stream=None):
+        """hr_scene_set_lights: up to HR_MAX_LIGHTS hr_light records (host float32 [n, 4, 4]; ``lights.light`` makes one) that the DDGI, reflection and
+        ground-truth hit shaders add to the UBO light, and that ``lights.Lights`` draws on the primary surfaces.  An empty list is off."""
+        from . import lights as _lights
+        _lights.set_lights(self.h, lights, stream)
+        return self
+
+    def set_lights_device(self, lights, stream=None):
+        """hr_scene_set_lights_device: the same count as the last ``set_lights``, from a cuda float32 tensor; one device copy, capturable, unchecked"""
+        from . import lights as _lights
+        _lights.set_lights_device(self.h, lights, stream)
+        return self
+
+    def get_lights(self):
+        """hr_scene_get_lights -> float32 [n, 4, 4], what the host last set"""
+        from . import lights as _lights
+        return _lights.get_lights(self.h)
+
 
 def _instanced_desc(isd):
     """(hr_instanced_scene_desc, the host arrays it points into) of a synth.InstancedSceneData"""

@@ -53,6 +53,11 @@ class DeferredShading:
         from . import emission
         emission.add_emissive(self.h, image, stream)
 
+    def add_lights(self, image, stream=None):
+        """The image of ``lights.Lights`` (include/hr_lights.h) added onto this pass's output: hr_deferred_add_emissive under the lights' name, after
+        ``render`` on the same stream and before TAA."""
+        self.add_emissive(image, stream)
+
     def output(self):
         v = hr_image_view()
         _check(lib().hr_deferred_output(self.h, C.byref(v)), "hr_deferred_output")

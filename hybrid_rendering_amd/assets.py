@@ -12,6 +12,7 @@ skinning.Skin (include/hr_skin.h).
 """
 from __future__ import annotations
 
+import math
 import os
 import struct
 import zlib
@@ -578,6 +579,58 @@ def load_gltf_instanced(path: str, scale: float = 1.0):
     by several nodes is stored once.  hr.InstancedScene(ctx, it) builds it; its flatten() gives the world-space triangles load_gltf() returns
     (up to the rounding of the pinned fp32 transform; normals through mat3(model), as transform_vertex does, not the inverse transpose)."""
     return load_gltf(path, scale, instanced=True)
+
+
+def load_gltf_lights(path: str, scale: float = 1.0) -> np.ndarray:
+    """The KHR_lights_punctual lights of a glTF 2.0 file -> hr_light records, float32 [n, 4, 4] (rows data0 .. data3; what ``Scene.set_lights`` takes),
+    one per node of the default scene that carries a light, in the order the hierarchy is visited.  Per record: data0.xyz the node's world +Z axis,
+    normalised (a glTF light shines along its node's -Z; data0 points TO the light), data0.w the light's ``intensity`` as written (no unit is
+    converted); data1.xyz the node's world translation (times ``scale``, as load_gltf scales positions), radius 0; data2.xyz the ``color``;
+    data3 = (0 directional / 1 point / 2 spot, cos(outerConeAngle), cos(innerConeAngle)) with glTF's defaults pi/4 and 0 for a spot and zeros for
+    the other types.  ``range`` is IGNORED: the library's lights have no range (include/hr_lights.h).  A file without the extension: [0, 4, 4]."""
+    doc, _ = _gltf_document(path)
+    defs = doc.get("extensions", {}).get("KHR_lights_punctual", {}).get("lights", [])
+    kinds = {"directional": 0.0, "point": 1.0, "spot": 2.0}
+    out = []
+
+    def visit(ni, parent):
+        node = doc["nodes"][ni]
+        if "matrix" in node:
+            local = np.asarray(node["matrix"], np.float64).reshape(4, 4).T
+        else:
+            local = np.eye(4)
+            local[:3, :3] = _quat_to_mat(node.get("rotation", [0, 0, 0, 1])) @ np.diag(node.get("scale", [1, 1, 1]))
+            local[:3, 3] = node.get("translation", [0, 0, 0])
+        M = parent @ local
+        ref = node.get("extensions", {}).get("KHR_lights_punctual")
+        if ref is not None:
+            li = int(ref["light"])
+            if not 0 <= li < len(defs):
+                raise ValueError(f"{path}: node {ni} names light {li}; the file defines {len(defs)}")
+            d = defs[li]
+            if d.get("type") not in kinds:
+                raise ValueError(f"{path}: light {li} has type {d.get('type')!r}; KHR_lights_punctual knows directional, point and spot")
+            z = M[:3, 2]
+            zl = float(np.linalg.norm(z))
+            if not zl > 0.0:
+                raise ValueError(f"{path}: node {ni} has a degenerate transform: its light has no direction")
+            rec = np.zeros((4, 4), np.float64)
+            rec[0, :3], rec[0, 3] = z / zl, float(d.get("intensity", 1.0))
+            rec[1, :3] = M[:3, 3] * scale
+            rec[2, :3] = d.get("color", [1.0, 1.0, 1.0])
+            rec[3, 0] = kinds[d["type"]]
+            if d["type"] == "spot":
+                spot = d.get("spot", {})
+                rec[3, 1], rec[3, 2] = math.cos(float(spot.get("outerConeAngle", math.pi / 4))), math.cos(float(spot.get("innerConeAngle", 0.0)))
+            out.append(rec.astype(np.float32))
+        for c in node.get("children", []):
+            visit(c, M)
+
+    scenes = doc.get("scenes", [])
+    roots = scenes[doc.get("scene", 0)].get("nodes", []) if scenes else range(len(doc.get("nodes", [])))
+    for r in roots:
+        visit(r, np.eye(4))
+    return np.stack(out) if out else np.zeros((0, 4, 4), np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ glTF 2.0: skins, morph targets, animations

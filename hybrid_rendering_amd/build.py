@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhybrid_rendering_amd.so")
 SOURCES = ["api.hip", "shadows.hip", "bvh_build.cpp"]
-OPTIONAL = ["denoise_fast_shadows.hip", "denoise_fast_ao.hip", "denoise_fast_reflections.hip", "denoise_fast_resolve.hip","ao.hip", "reflections.hip", "ddgi.hip", "deferred.hip", "ground_truth.hip", "taa.hip", "frame.hip", "instances.hip", "instances_shared.hip", "deform_refit.hip", "deform_redeal.hip", "deform.hip", "instances_shared_deform.hip", "instances_shared_update.hip", "instances_shared_rebuild.hip", "instances_shared_masks.hip", "cutout.hip", "selftest_shading.hip", "env.hip", "env_sources.hip", "probe_vis.hip", "skinning.hip", "emission.hip"]
+OPTIONAL = ["denoise_fast_shadows.hip", "denoise_fast_ao.hip", "denoise_fast_reflections.hip", "denoise_fast_resolve.hip","ao.hip", "reflections.hip", "ddgi.hip", "deferred.hip", "ground_truth.hip", "taa.hip", "frame.hip", "instances.hip", "instances_shared.hip", "deform_refit.hip", "deform_redeal.hip", "deform.hip", "instances_shared_deform.hip", "instances_shared_update.hip", "instances_shared_rebuild.hip", "instances_shared_masks.hip", "cutout.hip", "selftest_shading.hip", "env.hip", "env_sources.hip", "probe_vis.hip", "skinning.hip", "emission.hip", "lights.hip"]
 # -ffp-contract=off: every fp32 op is individually rounded; FMAs are explicit.
 # -fno-slp-vectorize: the SLP vectoriser pairs independent fp32 operations into v_pk_mul / v_pk_add / v_pk_fma_f32.  On gfx950 a packed
 # fp32 instruction issues at half rate, and pairing costs v_mov / v_pk_mov shuffles and hazard s_nops on top (kf_ddgi_sample: 305 packed
@@ -55,7 +55,7 @@ def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "hr_api.h"), os.path.join(HERE, "..", "include", "hr_api_stages.h"),
                                                            os.path.join(HERE, "..", "include", "hr_api_post.h"), os.path.join(HERE, "..", "include", "hr_env.h"),
                                                            os.path.join(HERE, "..", "include", "hr_env_sources.h"), os.path.join(HERE, "..", "include", "hr_probe_vis.h"),
-                                                           os.path.join(HERE, "..", "include", "hr_skin.h"), os.path.join(HERE, "..", "include", "hr_emission.h"), __file__]
+                                                           os.path.join(HERE, "..", "include", "hr_skin.h"), os.path.join(HERE, "..", "include", "hr_emission.h"), os.path.join(HERE, "..", "include", "hr_lights.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -76,7 +76,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = None) -> st
     obj_dir = os.path.join(HERE, "_obj", variant or "product")
     os.makedirs(obj_dir, exist_ok=True)
     cflags = [f for f in FLAGS if f != "-shared"] + extra
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", h) for h in ("hr_api.h", "hr_api_stages.h", "hr_api_post.h", "hr_env.h", "hr_env_sources.h", "hr_probe_vis.h", "hr_skin.h", "hr_emission.h")] + [__file__]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", h) for h in ("hr_api.h", "hr_api_stages.h", "hr_api_post.h", "hr_env.h", "hr_env_sources.h", "hr_probe_vis.h", "hr_skin.h", "hr_emission.h", "hr_lights.h")] + [__file__]
     hdr_t = max(os.path.getmtime(h) for h in headers)
     tag = hashlib.sha1(" ".join(cflags).encode()).hexdigest()[:10]
 

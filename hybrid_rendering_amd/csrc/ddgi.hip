@@ -7,6 +7,7 @@
 #include "shading.h"
 #include "cutout_host.h"
 #include "emission_host.h"
+#include "lights_host.h"
 #include "pass_args.h"
 
 using namespace hr;
@@ -74,14 +75,24 @@ extern "C" int hr_debug_divergence_ddgi(uint64_t* out, int reset)
 template <bool STATS, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, CUTOUT ? DDGI_TRACE_CUTOUT_EU : SHARED ? DDGI_TRACE_SHARED_EU : DDGI_TRACE_EU) void k_ddgi_trace(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow)
 {
-    constexpr bool     EMISSIVE = false;
+    constexpr bool     EMISSIVE = false, LIGHTS = false;
     [[maybe_unused]] const EmissionView em = EmissionView();   // never read
+    [[maybe_unused]] const LightsView   lt = LightsView();     // never read
 #include "ddgi_trace_body.h"
 }
 template <bool SHARED, bool CUTOUT>
 __global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_CUTOUT_EU) void k_ddgi_trace_emissive(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow, EmissionView em)
 {
-    constexpr bool STATS = false, EMISSIVE = true;
+    constexpr bool STATS = false, EMISSIVE = true, LIGHTS = false;
+    [[maybe_unused]] const LightsView lt = LightsView();   // never read
+#include "ddgi_trace_body.h"
+}
+// LIGHTS (lights.h; hr_scene_set_lights): Lo = direct_lighting(...) + X, the list's sum, before the infinite-bounce term.  One kernel with and without
+// live emission: without, `em` names no material and emission_at returns before it reads (lights_host.h emission_view_or_none).
+template <bool SHARED, bool CUTOUT>
+__global__ __launch_bounds__(64 * DDGI_TRACE_WAVES, DDGI_TRACE_CUTOUT_EU) void k_ddgi_trace_lights(DDGITraceArgs a, CutoutView cv_gi, CutoutView cv_shadow, EmissionView em, LightsView lt)
+{
+    constexpr bool STATS = false, EMISSIVE = true, LIGHTS = true;
 #include "ddgi_trace_body.h"
 }
 #undef HR_DDGI_TRACE_BODY
@@ -373,6 +384,7 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
     HR_REJECT_CUTOUT(scene, HR_RAY_GI, "hr_ddgi_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_ddgi_ray_trace", p->want_stats);
     HR_REJECT_EMISSION(scene, "hr_ddgi_ray_trace", p->want_stats || kDivergenceBuild);
+    HR_REJECT_LIGHTS(scene, "hr_ddgi_ray_trace", p->want_stats || kDivergenceBuild);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int rd = p->ping_pong ? 0 : 1; // read_idx = !m_ping_pong
@@ -407,7 +419,14 @@ hr_status hr_ddgi_ray_trace(hr_ddgi* p, const hr_scene* scene, const hr_frame_in
     // one CUTOUT instantiation for the two classes the kernel fires; a class that is forced opaque gets a view without a table
     const bool       cut_gi = cutout_on(scene, HR_RAY_GI), cut_shadow = cutout_on(scene, HR_RAY_SHADOW), cutout = cut_gi || cut_shadow;
     const CutoutView cv_gi = cut_gi ? cutout_view_of(scene) : CutoutView(), cv_shadow = cut_shadow ? cutout_view_of(scene) : CutoutView();
-    if (emission_live(scene))
+    if (lights_live(scene))
+    {
+        // the LIGHTS instantiations: picked iff the scene's light list is not empty (hr_internal.h lights_live)
+        void (*const kernel[2][2])(DDGITraceArgs, CutoutView, CutoutView, EmissionView, LightsView) = { { k_ddgi_trace_lights<false, false>, k_ddgi_trace_lights<false, true> },
+                                                                                                         { k_ddgi_trace_lights<true, false>, k_ddgi_trace_lights<true, true> } };
+        hipLaunchKernelGGL(kernel[scene->shared ? 1 : 0][cutout ? 1 : 0], dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, st, a, cv_gi, cv_shadow, emission_view_or_none(scene), lights_view_of(scene));
+    }
+    else if (emission_live(scene))
     {
         // the EMISSIVE instantiations: picked iff the scene's emission is enabled and some material emits (hr_internal.h emission_live)
         void (*const kernel[2][2])(DDGITraceArgs, CutoutView, CutoutView, EmissionView) = { { k_ddgi_trace_emissive<false, false>, k_ddgi_trace_emissive<false, true> },

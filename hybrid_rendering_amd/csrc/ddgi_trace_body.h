@@ -1,5 +1,5 @@
-// The body of the DDGI probe-trace kernels (ddgi.hip), one text for k_ddgi_trace<STATS, SHARED, CUTOUT> as it was and for k_ddgi_trace_emissive<SHARED, CUTOUT>:
-// included inside each kernel, which names STATS, SHARED, CUTOUT, EMISSIVE, a, cv_gi, cv_shadow and em.  Not a function: behind a call, however
+// The body of the DDGI probe-trace kernels (ddgi.hip), one text for k_ddgi_trace<STATS, SHARED, CUTOUT> as it was, for k_ddgi_trace_emissive<SHARED, CUTOUT>
+// and for k_ddgi_trace_lights<SHARED, CUTOUT>: included inside each kernel, which names STATS, SHARED, CUTOUT, EMISSIVE, LIGHTS, a, cv_gi, cv_shadow, em and lt.  Not a function: behind a call, however
 // inlined, the code of the kernels that exist moves (docs/EXPERIMENTS.md, "Emissive materials"); textual inclusion leaves them bit for bit.
 #ifndef HR_DDGI_TRACE_BODY
 #error "ddgi_trace_body.h is the text of a kernel body: only ddgi.hip includes it, between the braces of its two kernels"
@@ -62,6 +62,7 @@
             HR_DIV(if constexpr (!SHARED) tc.dv = &dvs;)
             f3 Lo = direct_lighting<STATS, CUTOUT>(tc, a.light, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), true, r2x, r2y, a.sky, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
+            if constexpr (LIGHTS) Lo = add3(Lo, extra_lights_hard<CUTOUT>(tc, lt, Wo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), rays));
 #ifndef HR_ABL_DDGI_NO_IRRADIANCE
             if (a.infinite_bounces == 1)
 #else

@@ -9,6 +9,7 @@
 #include "shading.h"
 #include "cutout_host.h"
 #include "emission_host.h"
+#include "lights_host.h"
 
 using namespace hr;
 
@@ -44,14 +45,24 @@ struct GTArgs
 template <bool INDIRECT, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64) void k_ground_truth(GTArgs a, CutoutView cv_primary, CutoutView cv_gi, CutoutView cv_shadow)
 {
-    constexpr bool     EMISSIVE = false;
+    constexpr bool     EMISSIVE = false, LIGHTS = false;
     [[maybe_unused]] const EmissionView em = EmissionView();   // never read
+    [[maybe_unused]] const LightsView   lt = LightsView();     // never read
 #include "ground_truth_body.h"
 }
 template <bool INDIRECT, bool SHARED, bool CUTOUT>
 __global__ __launch_bounds__(64) void k_ground_truth_emissive(GTArgs a, CutoutView cv_primary, CutoutView cv_gi, CutoutView cv_shadow, EmissionView em)
 {
-    constexpr bool EMISSIVE = true;
+    constexpr bool EMISSIVE = true, LIGHTS = false;
+    [[maybe_unused]] const LightsView lt = LightsView();   // never read
+#include "ground_truth_body.h"
+}
+// LIGHTS (lights.h; hr_scene_set_lights): Lo = Lo + X at every hit of the chain, after the sky block and before emission; the list's terms take the
+// hit's T and the two numbers the UBO light drew.  One kernel with and without live emission (lights_host.h emission_view_or_none).
+template <bool INDIRECT, bool SHARED, bool CUTOUT>
+__global__ __launch_bounds__(64) void k_ground_truth_lights(GTArgs a, CutoutView cv_primary, CutoutView cv_gi, CutoutView cv_shadow, EmissionView em, LightsView lt)
+{
+    constexpr bool EMISSIVE = true, LIGHTS = true;
 #include "ground_truth_body.h"
 }
 #undef HR_GROUND_TRUTH_BODY
@@ -148,7 +159,14 @@ hr_status hr_ground_truth_render(hr_ground_truth* p, const hr_scene* scene, cons
     void (*const emissive[2][2][2])(GTArgs, CutoutView, CutoutView, CutoutView, EmissionView) = {
         { { k_ground_truth_emissive<false, false, false>, k_ground_truth_emissive<false, false, true> }, { k_ground_truth_emissive<false, true, false>, k_ground_truth_emissive<false, true, true> } },
         { { k_ground_truth_emissive<true, false, false>, k_ground_truth_emissive<true, false, true> }, { k_ground_truth_emissive<true, true, false>, k_ground_truth_emissive<true, true, true> } } };
-    if (emission_live(scene))
+    // ... and the LIGHTS ones, picked iff the scene's light list is not empty (hr_internal.h lights_live)
+    void (*const lights[2][2][2])(GTArgs, CutoutView, CutoutView, CutoutView, EmissionView, LightsView) = {
+        { { k_ground_truth_lights<false, false, false>, k_ground_truth_lights<false, false, true> }, { k_ground_truth_lights<false, true, false>, k_ground_truth_lights<false, true, true> } },
+        { { k_ground_truth_lights<true, false, false>, k_ground_truth_lights<true, false, true> }, { k_ground_truth_lights<true, true, false>, k_ground_truth_lights<true, true, true> } } };
+    if (lights_live(scene))
+        hipLaunchKernelGGL(lights[a.trace_indirect ? 1 : 0][scene->shared ? 1 : 0][cut_primary || cut_gi || cut_shadow], dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a,
+                           cut_primary ? on : off, cut_gi ? on : off, cut_shadow ? on : off, emission_view_or_none(scene), lights_view_of(scene));
+    else if (emission_live(scene))
         hipLaunchKernelGGL(emissive[a.trace_indirect ? 1 : 0][scene->shared ? 1 : 0][cut_primary || cut_gi || cut_shadow], dim3(p->tiles_x * tiles_y), dim3(64), 0, st, a,
                            cut_primary ? on : off, cut_gi ? on : off, cut_shadow ? on : off, emission_view_of(scene));
     else

@@ -1,6 +1,6 @@
 // The body of the ground-truth path-trace kernels (ground_truth.hip), one text for k_ground_truth<INDIRECT, SHARED, CUTOUT> as it was and for
-// k_ground_truth_emissive<INDIRECT, SHARED, CUTOUT>: included inside each kernel, which names INDIRECT, SHARED, CUTOUT, EMISSIVE, a, cv_primary, cv_gi,
-// cv_shadow and em (see ddgi_trace_body.h for why this is not a function).
+// k_ground_truth_emissive<INDIRECT, SHARED, CUTOUT> and k_ground_truth_lights<INDIRECT, SHARED, CUTOUT>: included inside each kernel, which names INDIRECT,
+// SHARED, CUTOUT, EMISSIVE, LIGHTS, a, cv_primary, cv_gi, cv_shadow, em and lt (see ddgi_trace_body.h for why this is not a function).
 #ifndef HR_GROUND_TRUTH_BODY
 #error "ground_truth_body.h is the text of a kernel body: only ground_truth.hip includes it, between the braces of its two kernels"
 #endif
@@ -79,6 +79,7 @@
                 const f3 brdf = evaluate_uber_brdf(c_diffuse, roughness, s.N, F0, Wo, Wh, Wi);
                 Lo = add3(Lo, mul3(mul3(T, brdf), Li));
             }
+            if constexpr (LIGHTS) Lo = add3(Lo, extra_lights_soft<CUTOUT>(tc, lt, Wo, s.N, s.P, ray_origin, F0, c_diffuse, roughness, T, r1x, r1y, rays));
             if constexpr (EMISSIVE)
             {
                 f3 E;

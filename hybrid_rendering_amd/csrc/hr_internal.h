@@ -114,6 +114,9 @@ bool      reject_cutout_dev_switches(const hr_scene* s, int ray_class, const cha
 // instantiation of the instrumented and developer variants exists
 bool      reject_emission_dev_switches(const hr_scene* s, const char* call, bool wanted);
 #define HR_REJECT_EMISSION(scene, call, wanted) do { if (::hr::reject_emission_dev_switches(scene, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
+// lights.hip.  HR_REJECT_LIGHTS: the same for a scene with a non-empty light list (hr_scene_set_lights)
+bool      reject_lights_dev_switches(const hr_scene* s, const char* call, bool wanted);
+#define HR_REJECT_LIGHTS(scene, call, wanted) do { if (::hr::reject_lights_dev_switches(scene, call, wanted)) return HR_ERR_UNSUPPORTED; } while (0)
 
 struct DevBuf
 {
@@ -398,6 +401,8 @@ struct hr_scene
         if (cutoff_stage) (void)hipHostFree(cutoff_stage);
         if (em_copied) (void)hipEventDestroy(em_copied);
         if (em_stage) (void)hipHostFree(em_stage);
+        if (lights_copied) (void)hipEventDestroy(lights_copied);
+        if (lights_stage) (void)hipHostFree(lights_stage);
     }
     int           max_rel_depth = 0;              // deepest node below an instance root (a fresh top level must leave room for it)
     std::vector<int32_t>  level_offsets;          // level_nodes[level_offsets[d] .. level_offsets[d + 1]): the nodes of depth d
@@ -463,6 +468,12 @@ struct hr_scene
     hr::DevBuf    em_rgb, em_tex, em_inst;        // the tables of EmissionView; instanced kinds: per instance { first_tri, mesh_tri_base } + a sentinel (hr_scene_emission)
     float*        em_stage = nullptr;             // pinned source of the host forms' copies: [M][3] floats, then [M] int32; guarded by em_copied
     hipEvent_t    em_copied = nullptr;
+    // ---- extra lights (lights.hip, lights.h; include/hr_lights.h).  The list is host state, read when a pass enqueues: a hit-shading launch takes
+    // its LIGHTS instantiation iff lights_live().  The table of HR_MAX_LIGHTS records is allocated by the first setter call, never after
+    std::vector<hr_light> lights_host;            // the list as the host last set it; its size is the count every launch passes
+    hr::DevBuf    lights_dev;                     // [HR_MAX_LIGHTS] hr_light
+    hr_light*     lights_stage = nullptr;         // pinned source of the host form's copy; guarded by lights_copied
+    hipEvent_t    lights_copied = nullptr;
     // ---- deforming geometry (deform_refit.hip): trees built without spatial splits, refitted under new vertices through `deform` and node_box.
     // deform.hip: a flat scene (`deformable`); hr_scene_update_vertices rewrites `tris` / `positions` / `tri_normals`.  instances_shared_deform.hip: the
     // flagged meshes of a shared scene; hr_scene_update_meshes rewrites `tris` / `mesh_positions` / `mesh_normals`
@@ -491,5 +502,7 @@ constexpr bool kDivergenceBuild = false;
 #endif
 // does a hit-shading launch over the scene take its EMISSIVE instantiation?
 inline bool emission_live(const hr_scene* s) { return s->emission_enabled && s->emission_any; }
+// does a hit-shading launch over the scene take its LIGHTS instantiation?  n == 0 is off
+inline bool lights_live(const hr_scene* s) { return !s->lights_host.empty(); }
 inline Scene2 scene2_of(const hr_scene* s, int ray_class) { return Scene2 { (const Node8*)s->nodes.p, (const TriGPU*)s->tris.p, (const InstanceShared*)s->inst_shared.p, cull_of(s, ray_class) }; }
 } // namespace hr

@@ -1,5 +1,6 @@
 // The body of the reflection trace kernels (reflections.hip), one text for k_refl_trace<STATS, SHARED, CUTOUT> as it was and for
-// k_refl_trace_emissive<SHARED, CUTOUT>: included inside each kernel, which names STATS, SHARED, CUTOUT, EMISSIVE, a, cv_refl, cv_shadow and em
+// k_refl_trace_emissive<SHARED, CUTOUT> and k_refl_trace_lights<SHARED, CUTOUT>: included inside each kernel, which names STATS, SHARED, CUTOUT, EMISSIVE,
+// LIGHTS, a, cv_refl, cv_shadow, em and lt
 // (see ddgi_trace_body.h for why this is not a function).
 #ifndef HR_REFL_TRACE_BODY
 #error "refl_trace_body.h is the text of a kernel body: only reflections.hip includes it, between the braces of its two kernels"
@@ -87,6 +88,7 @@
             CubeMap  none { nullptr, 0 };
             hLo = direct_lighting<STATS, CUTOUT>(tc, a.light, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), false, 0.0f, 0.0f, none, rays);
             if (STATS) { st_n += tc.nn; st_t += tc.nt; }
+            if constexpr (LIGHTS) hLo = add3(hLo, extra_lights_hard<CUTOUT>(tc, lt, hWo, s.N, s.P, F0, c_diffuse, s.roughness, one3(), rays));
             if (a.sample_gi == 1)
             {
                 const f3    R   = reflect3(neg3(hWo), s.N);

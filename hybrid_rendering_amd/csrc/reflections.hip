@@ -11,6 +11,7 @@
 #include "shading.h"
 #include "cutout_host.h"
 #include "emission_host.h"
+#include "lights_host.h"
 #include "upsample.h"
 #include "pass_args.h"
 #include "tile_order.h"
@@ -88,14 +89,24 @@ extern "C" int hr_debug_divergence_refl(uint64_t* out, int reset)
 template <bool STATS, bool SHARED = false, bool CUTOUT = false>
 __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace(ReflTraceArgs a, CutoutView cv_refl, CutoutView cv_shadow)
 {
-    constexpr bool     EMISSIVE = false;
+    constexpr bool     EMISSIVE = false, LIGHTS = false;
     [[maybe_unused]] const EmissionView em = EmissionView();   // never read
+    [[maybe_unused]] const LightsView   lt = LightsView();     // never read
 #include "refl_trace_body.h"
 }
 template <bool SHARED, bool CUTOUT>
 __global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace_emissive(ReflTraceArgs a, CutoutView cv_refl, CutoutView cv_shadow, EmissionView em)
 {
-    constexpr bool STATS = false, EMISSIVE = true;
+    constexpr bool STATS = false, EMISSIVE = true, LIGHTS = false;
+    [[maybe_unused]] const LightsView lt = LightsView();   // never read
+#include "refl_trace_body.h"
+}
+// LIGHTS (lights.h; hr_scene_set_lights): hLo = direct_lighting(...) + X, the list's sum, at a hit.  One kernel with and without live emission
+// (lights_host.h emission_view_or_none).
+template <bool SHARED, bool CUTOUT>
+__global__ __launch_bounds__(64 * REFL_TRACE_WAVES, REFL_TRACE_EU) void k_refl_trace_lights(ReflTraceArgs a, CutoutView cv_refl, CutoutView cv_shadow, EmissionView em, LightsView lt)
+{
+    constexpr bool STATS = false, EMISSIVE = true, LIGHTS = true;
 #include "refl_trace_body.h"
 }
 #undef HR_REFL_TRACE_BODY
@@ -364,6 +375,7 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     HR_REJECT_CUTOUT(scene, HR_RAY_REFLECTION, "hr_reflections_ray_trace", p->want_stats);
     HR_REJECT_CUTOUT(scene, HR_RAY_SHADOW, "hr_reflections_ray_trace", p->want_stats);
     HR_REJECT_EMISSION(scene, "hr_reflections_ray_trace", p->want_stats || kDivergenceBuild);
+    HR_REJECT_LIGHTS(scene, "hr_reflections_ray_trace", p->want_stats || kDivergenceBuild);
     hipStream_t st = (hipStream_t)stream_;
     p->last_stream = st;
     const int pp = in->ping_pong ? 1 : 0;
@@ -416,7 +428,15 @@ hr_status hr_reflections_ray_trace(hr_reflections* p, const hr_scene* scene, con
     // one CUTOUT instantiation for the two classes the kernel fires; a class that is forced opaque gets a view without a table
     const bool       cut_refl = cutout_on(scene, HR_RAY_REFLECTION), cut_shadow = cutout_on(scene, HR_RAY_SHADOW), cutout = cut_refl || cut_shadow;
     const CutoutView cv_refl = cut_refl ? cutout_view_of(scene) : CutoutView(), cv_shadow = cut_shadow ? cutout_view_of(scene) : CutoutView();
-    if (emission_live(scene))
+    if (lights_live(scene))
+    {
+        // the LIGHTS instantiations: picked iff the scene's light list is not empty (hr_internal.h lights_live)
+        void (*const kernel[2][2])(ReflTraceArgs, CutoutView, CutoutView, EmissionView, LightsView) = { { k_refl_trace_lights<false, false>, k_refl_trace_lights<false, true> },
+                                                                                                         { k_refl_trace_lights<true, false>, k_refl_trace_lights<true, true> } };
+        hipLaunchKernelGGL(kernel[scene->shared ? 1 : 0][cutout ? 1 : 0], dim3(cdiv(a.tiles_x * a.tiles_y, REFL_TRACE_WAVES)), dim3(64 * REFL_TRACE_WAVES), 0, st, a, cv_refl, cv_shadow,
+                           emission_view_or_none(scene), lights_view_of(scene));
+    }
+    else if (emission_live(scene))
     {
         // the EMISSIVE instantiations: picked iff the scene's emission is enabled and some material emits (hr_internal.h emission_live)
         void (*const kernel[2][2])(ReflTraceArgs, CutoutView, CutoutView, EmissionView) = { { k_refl_trace_emissive<false, false>, k_refl_trace_emissive<false, true> },

@@ -20,6 +20,7 @@
 #pragma once
 #include "../hr_api.h"
 #include "../hr_probe_vis.h"
+#include "../hr_lights.h"
 #include <stdexcept>
 #include <string>
 
@@ -124,6 +125,9 @@ public:
     void     alpha_cutoffs(float* cutoffs_out) const { check(hr_scene_get_alpha_cutoffs(m_scene, cutoffs_out), "hr_scene_get_alpha_cutoffs"); }
     void     set_ray_class_opaque(hr_ray_class ray_class, bool force_opaque) { check(hr_scene_set_ray_class_opaque(m_scene, (int32_t)ray_class, force_opaque ? 1 : 0), "hr_scene_set_ray_class_opaque"); }
     bool     ray_class_opaque(hr_ray_class ray_class) const { int32_t v = 0; check(hr_scene_get_ray_class_opaque(m_scene, (int32_t)ray_class, &v), "hr_scene_get_ray_class_opaque"); return v != 0; }
+    // extra lights (hr_lights.h): up to HR_MAX_LIGHTS records beside the UBO light (host, copied before the call returns; n == 0 clears the list: off),
+    // added in the DDGI, reflection and ground-truth hit shaders and drawn on the primary surfaces by hr::Lights (lights.hpp)
+    void     set_lights(const hr_light* lights, int32_t n, Stream cmd_buf = nullptr) { check(hr_scene_set_lights(m_scene, lights, n, cmd_buf), "hr_scene_set_lights"); }
     int      instance_count() const { return hr_scene_instance_count(m_scene); }
     uint64_t id() const { return hr_scene_id(m_scene); }   // dw::Scene::id()
     ~Scene() { hr_scene_destroy(m_scene); }

@@ -8,6 +8,8 @@ bench.py are numbers of.   python tools/render_frame.py [--width 960 --height 54
 # --emissive [SCALE] hangs a light panel into the scene (synth.with_light_panel), switches the directional light off and enables emission
 # (include/hr_emission.h): the room is lit by what the probe and reflection rays find on the panel, and the panel's own pixels come from
 # Scene.emissive_image through DeferredShading.add_emissive, after the composite and before TAA.
+# --lights N places N deterministic point lights along the scene's long axis (Scene.set_lights, include/hr_lights.h): the probe and reflection rays
+# see them, and their light on the primary surfaces comes from lights.Lights through DeferredShading.add_lights, after the composite and before TAA.
 import argparse, os, struct, sys, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,6 +35,7 @@ def main():
     src.add_argument("--sky", action="store_true", help="the analytic sky, its sun along the scene's light (hr_env_update_sky)")
     ap.add_argument("--probes", nargs="?", type=float, const=0.0, default=None, metavar="SCALE", help="visualise the DDGI probe grid; SCALE: the spheres' radius (default: min grid step / 8)")
     ap.add_argument("--emissive", nargs="?", type=float, const=1.0, default=None, metavar="SCALE", help="a light panel as the only light; SCALE: hr_scene_set_emission's scale (default 1)")
+    ap.add_argument("--lights", type=int, default=0, metavar="N", help="N extra point lights in the scene's list (at most 256)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame.png"))
     a = ap.parse_args()
     import torch
@@ -53,6 +56,11 @@ def main():
     sob, sr = synth.blue_noise_tables()
     sob_d, sr_d = torch.from_numpy(sob).cuda(), torch.from_numpy(sr).cuda()
     lo, hi = sd.bounds()
+    lamps = None
+    if a.lights > 0:
+        from hybrid_rendering_amd import lights as lights_mod
+        scene.set_lights(lights_mod.placed_point_lights(lo, hi, a.lights))
+        lamps = lights_mod.Lights(ctx, W, H)
     ddgi_u = synth_env.ddgi_uniforms(lo, hi, probe_counts=(16, 8, 16), rays_per_probe=256, normal_bias=0.1)
     sky = synth_env.sky_cubemap(32)
     f16 = lambda x: torch.from_numpy(x).cuda().view(torch.float16)
@@ -96,6 +104,9 @@ def main():
             seen = dict(cur, depth=depth_out)
         if a.emissive is not None:
             df.add_emissive(scene.emissive_image(ubo, W, H))
+        if lamps is not None:
+            lamps.render(scene, fi)
+            df.add_lights(lamps.output())
         taa.update(f)
         taa.render(df.output(), seen, f & 1)
         prev = (cur, half)
